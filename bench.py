@@ -3,7 +3,15 @@
 circuit-level noise p = 0.003, (W,F) = (3,1) over 12 rounds -> 11 windows per shot, BP+OSD on the
 shortened window matrix (osd_window semantics), batch = 4096 shots per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step and the decode
+accounting of the last step).  `--full` adds everything else the line can carry, each measured after the timed region: the
+single-launch kernel timing behind `roofline`, the other OSD order, config.other_workloads and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed (the output buffers a caller of the timed path receives) as
+DIR/<name>.npy in float32 / float64, at most 64 MiB in all: an array too large for that keeps a fixed sample of its rows, whose
+indices are written as DIR/<name>_sample_rows.npy.  The inputs depend on the arguments only, so two builds can be compared output
+for output.
 
 With N > 1 and no WORLD_SIZE in the environment this process starts the N ranks itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...`, rendezvous on 127.0.0.1) and only relays
@@ -214,7 +222,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-stream", action="store_true", help="time one launch at a time instead of the two-lane streaming entry")
     ap.add_argument("--no-other-workloads", action="store_true",
                     help="skip config.other_workloads (N = 1, headline): a few launches each of bb288, gdg, gdg64, global144 and bp4 after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (single-launch kernel timing), the other OSD order, "
+                         "other workloads and the CPU baseline (the --no-* options above apply to this mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MiB in all)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.shots is None:
         args.shots = default_shots(args.workload)
     return args
@@ -260,6 +275,9 @@ class StubEngine:  # (launcher test only)
 
     def step(self, i):
         self.shot.copy_(self.torch.from_numpy(self.expected(self.lo, self.hi)))
+
+    def outputs(self):
+        return {"shot_result": self.shot}
 
     def sync(self):
         pass
@@ -308,6 +326,9 @@ class GpuEngine:
     @property
     def stats(self):
         return self.out[self.last]["stats"]
+
+    def outputs(self):  # the buffers the most recent step wrote: committed faults, per-window statistics, per-shot decisions
+        return dict(self.out[self.last])
 
     def step(self, i):
         if self.streaming:
@@ -398,6 +419,9 @@ class Bp4Engine:
     @property
     def shot(self):
         return self.stat[self.last][:, :2]
+
+    def outputs(self):  # the buffers the most recent step wrote: corrections (x and z) and per-decode statistics
+        return {"out": self.outs[self.last], "stats": self.stat[self.last]}
 
     def step(self, i):
         if self.streaming and not self.timing:
@@ -726,6 +750,38 @@ def measure_other_workload(workload, args, rank, local_rank, steps=5, shots=None
     return rec
 
 
+DUMP_BYTES = 60 << 20  # data of all dumped arrays together (the .npy headers stay well inside the 64 MiB of --dump-outputs)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <path>/<name>.npy, converted exactly (1- and 2-byte types to float32, wider ones to float64).
+    Smallest first; an array that does not fit what is left of DUMP_BYTES keeps a fixed seeded sample of its rows (axis 0), whose
+    indices go to <name>_sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    conv = {k: np.asarray(a).astype(np.float32 if np.asarray(a).dtype.itemsize <= 2 else np.float64) for k, a in arrays.items()}
+    left = DUMP_BYTES
+    for name in sorted(conv, key=lambda k: conv[k].nbytes):
+        a = conv[name]
+        if a.nbytes > left:
+            k = left // (a.nbytes // a.shape[0] + 8)
+            if k < 1:
+                raise SystemExit(f"--dump-outputs: no room left for a row of {name} {a.shape}")
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_sample_rows.npy"), rows.astype(np.float64))
+            left -= rows.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
+def write_outputs(args, engine, gathered, world):
+    """rank 0's output buffers of the last timed step (and, over several ranks, every rank's gathered decisions)"""
+    arrays = {k: v.cpu().numpy() for k, v in engine.outputs().items()}
+    if world > 1:
+        arrays["decisions_all_ranks"] = gathered.cpu().numpy()
+    dump_outputs(args.dump_outputs, arrays)
+
+
 def time_steps(engine, args, dist, world, total_shots):
     """W untimed steps, then exactly K timed steps + the gather of the decisions, bracketed by barriers and
     device synchronisation; returns (elapsed seconds = max over ranks, gathered decisions, per-rank record).
@@ -792,7 +848,7 @@ def main():
     # bp4_osd: four HIP streams handed to swd_bp4_decode_batch_dev in turn (a launch ends on the few decodes that run all max_iter iterations)
     streaming = not args.no_stream and not STUB
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not STUB and headline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not STUB and headline:
         cpu = cpu_baseline(args.osd_order)  # before the GPU is touched (spawned workers)
 
     import torch
@@ -853,6 +909,8 @@ def main():
                           "shots_this_rank": hi - lo, "shots_per_rank": per_rank, "gather_ok": bool(ok),
                           "collective_backend": backend, "collective_ranks": dist_ranks, "rank_times": rank_times}
         if rank == 0:
+            if args.dump_outputs:
+                write_outputs(args, engine, gathered, world)
             print(json.dumps(line))
         if dist.is_initialized():
             dist.destroy_process_group()
@@ -864,14 +922,10 @@ def main():
     # accounting data of the LAST timed step (copied before the timing loop below re-uses the first lane's buffers)
     st = engine.stats.cpu().numpy()
     sr = engine.shot.cpu().numpy()
-    # the single-launch kernel duration behind the roofline: HIP events around each launch on the launch stream, one launch at a
-    # time, after the timed region (streamed launches overlap, so their individual durations would not describe the kernel)
-    kt = max(3, min(args.steps, 20))
-    kern_ms, launches, single_wall = engine.kernel_timing(args.warmup + args.steps, kt)
-    engine.check_status()
+    if args.dump_outputs and rank == 0:
+        write_outputs(args, engine, gathered, world)
 
     # accounting (outside the timed region), on this rank's shard of the last step
-    avg_kernel_s = kern_ms / max(launches, 1) / 1e3
     cfg = {
         "workload": (wl["desc"] % args.osd_order if "%d" in wl["desc"] else wl["desc"]) + ", "
                     + ("".join(f"DIAGNOSTIC RUN {k}={DECODER_KW[k]}, " for k in ("pre_max_iter", "post_max_iter") if os.environ.get("SWD_BENCH_" + k.upper())))
@@ -880,31 +934,49 @@ def main():
         "parallelism": f"shots sharded over {world} GPU(s), no data-path collective; one all_gather of 8 B per shot",
         # what closed the timed region: the RCCL (backend nccl) all_gather over this many ranks, or nothing (plain one-process run)
         "collective_backend": backend, "collective_ranks": dist_ranks, "rank_times": rank_times,
-        "kernel_launches_timed": int(launches),
         "step_mode": (("four HIP streams in turn (swd_bp4_decode_batch_dev): consecutive steps overlap" if args.workload == "bp4" else
                        "two-lane stream (swd_pipeline_stream_push_dev): consecutive steps overlap") if streaming else "one launch at a time"),
-        "single_stream_windows_per_s": (hi - lo) * W * launches / single_wall if launches else None,
-        "single_stream_note": "this rank's shots, one launch at a time with HIP events and a host synchronisation per launch (the loop that times the kernel)",
     }
-    alg_bytes = lds_alg = irr = lds_note = None
     if args.workload == "bp4":
         cls = np.bincount((st[:, 0] & 0xFF).ravel(), minlength=7)
         cfg["exit_classes_bp_osd_rank0"] = [int(cls[0]), int(cls[2])]
         cfg["converged_fraction_rank0"] = float(((st[:, 0] & 0x100) != 0).mean())
-        kernel = "swd::bp4_kernel"
-        lds_alg = bp4_lds_algorithmic_bytes(engine.edges, st)
     else:
         last = (args.warmup + args.steps - 1) % engine.nb
         logical = (sr[:, 0].astype(np.int64) != engine.obs_true[last]) | (sr[:, 1] != 0)
         cls = np.bincount((st[..., 0] & 0xFF).ravel(), minlength=7)
         cfg.update({"exit_classes_pre_post_osd_rank0": [int(cls[0]), int(cls[1]), int(cls[2])], "sched_faults": int(cls[6]),
                     "logical_errors_last_step_rank0": int(logical.sum())})
-        kernel = "swd::pipeline_kernel"
-        irr = irreducible_hbm_bytes(plan, hi - lo)
         if osdw:
             cfg["bp_iterations_pre_post_rank0"] = [int(st[..., 2].sum()), int(st[..., 3].sum())]
             cfg["live_edge_iterations_pre_post_rank0"] = [int(sum(w.mat.nnz * st[:, i, 2].sum() for i, w in enumerate(plan.windows))),
                                                           int((st[..., 6].astype(np.int64) * st[..., 3]).sum())]
+    if not args.full:
+        if rank == 0:
+            line["config"] = cfg
+            print(json.dumps(line))
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+
+    # --full: the single-launch kernel duration behind the roofline: HIP events around each launch on the launch stream, one launch at a
+    # time, after the timed region (streamed launches overlap, so their individual durations would not describe the kernel)
+    kt = max(3, min(args.steps, 20))
+    kern_ms, launches, single_wall = engine.kernel_timing(args.warmup + args.steps, kt)
+    engine.check_status()
+    avg_kernel_s = kern_ms / max(launches, 1) / 1e3
+    cfg.update({"kernel_launches_timed": int(launches),
+                "single_stream_windows_per_s": (hi - lo) * W * launches / single_wall if launches else None,
+                "single_stream_note": "this rank's shots, one launch at a time with HIP events and a host synchronisation per launch (the loop "
+                                      "that times the kernel)"})
+    alg_bytes = lds_alg = irr = lds_note = None
+    if args.workload == "bp4":
+        kernel = "swd::bp4_kernel"
+        lds_alg = bp4_lds_algorithmic_bytes(engine.edges, st)
+    else:
+        kernel = "swd::pipeline_kernel"
+        irr = irreducible_hbm_bytes(plan, hi - lo)
+        if osdw:
             alg_bytes = algorithmic_bytes(plan, st, DECODER_KW["pre_max_iter"], post_in_lds=args.workload == "global144")
             lds_alg = lds_algorithmic_bytes(plan, st) if args.workload != "global144" else None  # (its messages are not in LDS)
         else:

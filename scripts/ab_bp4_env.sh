@@ -4,7 +4,7 @@ OUT=$1; SW=$2
 mkdir -p $OUT
 for rep in 1 2; do
   for mode in default "$SW"; do
-    env $( [ "$mode" = default ] && echo SWD_DUMMY=1 || echo $mode ) timeout 300 python bench.py --workload bp4 --steps 10 --warmup 2 2>/dev/null | python -c "
+    env $( [ "$mode" = default ] && echo SWD_DUMMY=1 || echo $mode ) timeout 300 python bench.py --full --workload bp4 --steps 10 --warmup 2 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.read())
 print('$mode', round(j['value']), round(j['ms_per_step'], 3), round(j['roofline']['avg_kernel_ms'], 3), j['config'].get('exit_classes_bp_osd_rank0'))" >> $OUT/ab.log

@@ -8,6 +8,6 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${TAG}_${WL}_stream
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --workload $WL --no-cpu-baseline --no-order0 --no-other-workloads --steps 60 --warmup 3 $* > $O/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --workload $WL --no-cpu-baseline --no-order0 --no-other-workloads --steps 60 --warmup 3 $* > $O/bench.log 2>&1
 find $O -name '*.db' -delete 2>/dev/null
 tail -1 $O/bench.log | cut -c1-300

@@ -174,3 +174,46 @@ def test_other_workloads_share_the_launcher():
     r, lines = run_bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--shots", "37", "--workload", "gdg")
     assert r.returncode == 0, r.stderr[-2000:]
     assert lines[0]["n_gpus"] == 2 and lines[0]["config"]["gather_ok"] is True and "bpgdg_decoder" in lines[0]["metric"]
+
+
+def test_dump_outputs_writes_the_last_steps_decisions(tmp_path):
+    """--dump-outputs DIR: the decisions the timed path returned, as float64 .npy (stub: a pure function of the shot number)"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    r, lines = run_bench("--steps", "2", "--warmup", "1", "--shots", "31", "--dump-outputs", str(tmp_path / "one"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    a = np.load(tmp_path / "one" / "shot_result.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, bench.StubEngine.expected(0, 31))
+    r, lines = run_bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--shots", "9", "--dump-outputs", str(tmp_path / "two"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert np.array_equal(np.load(tmp_path / "two" / "decisions_all_ranks.npy"), bench.StubEngine.expected(0, 18))
+    assert np.array_equal(np.load(tmp_path / "two" / "shot_result.npy"), bench.StubEngine.expected(0, 9))
+
+
+def test_dump_outputs_stays_within_64_mib_with_a_fixed_sample(tmp_path):
+    """an output larger than the budget keeps a seeded sample of its rows (the same rows every run); small outputs stay whole"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    total = (np.arange(4096 * 8784, dtype=np.int64).reshape(4096, 8784) % 251).astype(np.uint8)  # the headline's faults buffer
+    stats = np.arange(4096 * 11 * 8, dtype=np.int32).reshape(4096, 11, 8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"total": total, "stats": stats})
+    size = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    assert size <= 64 << 20
+    s = np.load(tmp_path / "a" / "stats.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, stats)
+    t, rows = np.load(tmp_path / "a" / "total.npy"), np.load(tmp_path / "a" / "total_sample_rows.npy")
+    assert t.dtype == np.float32 and 1000 < t.shape[0] < 4096 and np.array_equal(t, total[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "total_sample_rows.npy"))
+
+
+def test_full_is_off_by_default():
+    """a plain run measures the headline figure only; roofline, the other OSD order, other workloads and the CPU baseline need --full"""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    assert bench.parse_args([]).dump_outputs is None
+    r, lines = run_bench("--steps", "2", "--warmup", "1", "--shots", "10")
+    assert r.returncode == 0 and "roofline" not in lines[0] and "cpu_baseline" not in lines[0]

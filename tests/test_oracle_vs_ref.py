@@ -1,8 +1,11 @@
 """Oracle vs. the reference's own C/C++ objects (oracle/_ref/libswd_ref.so, built by `make -C oracle ref`
-from the sources where they lie under /root/reference; the .so travels, the sources do not).
+from the reference's sources, which are not part of this repository).
 Covers the parts of the path that exist as C/C++ in the reference: rank, index_sort, the sparse LU +
-solve behind OSD-0, and the BPGD worker class.  Skipped when the library has not been built."""
+solve behind OSD-0, and the BPGD worker class.  Where the library has not been built, every test replays the reference's answers
+recorded under tests/golden/ref_calls/ (tests/ref_replay.py: the oracle's inputs to each call must equal the recorded ones);
+SWD_RECORD_REF=1 with the library present records them again."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -11,30 +14,24 @@ import scipy.sparse as sp
 
 from oracle import oracle as O
 from tests import fixtures as fx
+from tests.ref_replay import GOLDEN, RefCalls
 
 REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libswd_ref.so")
 HAVE_REFERENCE = os.path.isdir("/root/reference/src/include")
-# Where the reference's sources exist (the build container) a missing library is a FAILURE -- the strongest pin of the oracle must
-# not disappear silently there; on a box without /root/reference (the GPU box) the library travels prebuilt, and if it is absent
-# too the skip says so loudly.
-if not os.path.exists(REF) and not HAVE_REFERENCE:
-    import warnings
-    warnings.warn("oracle/_ref/libswd_ref.so is absent and /root/reference does not exist here: the oracle-vs-reference pin "
-                  "(tests/test_oracle_vs_ref.py) is NOT checked in this run; the recorded fixtures still are")
-pytestmark = pytest.mark.skipif(not os.path.exists(REF) and not HAVE_REFERENCE,
-                                reason="ORACLE PIN NOT CHECKED: oracle/_ref/libswd_ref.so absent and no /root/reference to build it from")
 
 
 def test_ref_library_is_built():
-    """/root/reference present => `make -C oracle ref` (run by __graft_entry__.build()) must have produced the library"""
-    assert os.path.exists(REF), ("oracle/_ref/libswd_ref.so is missing although /root/reference exists: run "
-                                 "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C oracle ref`")
+    """reference sources present => `make -C oracle ref` (run by __graft_entry__.build()) must have produced the library;
+    without them the recorded calls stand in for it"""
+    if HAVE_REFERENCE:
+        assert os.path.exists(REF), ("oracle/_ref/libswd_ref.so is missing although /root/reference exists: run "
+                                     "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C oracle ref`")
+    else:
+        assert os.path.exists(REF) or len(os.listdir(GOLDEN)) >= 11
 
 
-
-@pytest.fixture(scope="module")
-def R():
-    assert os.path.exists(REF), "oracle/_ref/libswd_ref.so is missing although /root/reference exists (make -C oracle ref)"
+@functools.lru_cache(maxsize=None)
+def _lib():
     L = C.CDLL(REF)
     vp, i32 = C.c_void_p, C.c_int32
     L.ref_pcm_new.restype = vp
@@ -53,6 +50,14 @@ def R():
     L.ref_bpgd_get_pm.argtypes = [vp]
     L.ref_bpgd_error.argtypes = [vp, vp]
     return L
+
+
+@pytest.fixture
+def R(request):
+    """the reference library (live, recording with SWD_RECORD_REF=1) or the replay of its recorded calls for this test"""
+    rc = RefCalls(request.node.name, _lib() if os.path.exists(REF) else None, record=os.environ.get("SWD_RECORD_REF") == "1")
+    yield rc
+    rc.finish()
 
 
 class Pcm:
