@@ -175,6 +175,13 @@ swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, cons
                         const double *pz, const swd_bp4_params *p, int device); /* channel_probs of hx/hz ignored */
 void swd_bp4_destroy(swd_bp4 *d);
 int swd_bp4_info(const swd_bp4 *d, int32_t *mx, int32_t *mz, int32_t *n, int32_t *rank_x, int32_t *rank_z);
+/* The form of the BP kernel the handle's most recent launch took (diagnostics and tests; every pointer nullable):
+ * split 1 = two threads per qubit, lazy 1 = the two-half node update, fast 1 = the specialised instantiation (0: generic),
+ * wmax / dm = the instantiation's most waves per workgroup and column-weight bound, threads = the workgroup size, skew = the
+ * SWD_BP4_SKEW wave stagger (0 off, 1 even, 2 odd), overlapped 1 = taken as a launch with another one in flight.
+ * Returns -1 before the first launch. */
+int swd_bp4_last_form(const swd_bp4 *d, int32_t *split, int32_t *lazy, int32_t *fast, int32_t *wmax, int32_t *dm,
+                      int32_t *threads, int32_t *skew, int32_t *overlapped);
 /* sx [B*mx], sz [B*mz] -> out [B*2*n] (row 0: X string, row 1: Z string, like the (2, n) array decode()
  * returns); stats [B*SWD_STAT_WORDS] ([0] exit|converge, [1] bp_iteration); lpr [B*3*n] nullable posterior
  * LLRs laid out [shot][x|y|z][vn] (property log_prob_ratios transposed); osd0 [B*2*n] nullable;

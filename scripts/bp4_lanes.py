@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""bp4_osd decodes/s with K launches in flight on K streams (the handle has four launch slots): python scripts/bp4_lanes.py [decodes per launch]"""
+"""bp4_osd decodes/s with K launches in flight on K streams (the handle has four launch slots):
+python scripts/bp4_lanes.py [decodes per launch] [BB code length, default 144]"""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from slidingwindowdecoder_amd import bp4_osd
 from slidingwindowdecoder_amd.codes import bb_code
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
-c, _, _ = bb_code(144)
+c, _, _ = bb_code(int(sys.argv[2]) if len(sys.argv) > 2 else 144)
 hx, hz = np.asarray(c.hx), np.asarray(c.hz)
 n = hx.shape[1]; p = 0.02
 pr = np.full(n, p / 3)
@@ -30,4 +31,4 @@ for K in (1, 2, 3, 4):
         for k in range(48): dec.decode_batch_device(*data[k % 4], out=outs[k % K][0], stats=outs[k % K][1], stream=lanes[k % K])
         torch.cuda.synchronize()
         best = min(best, (time.perf_counter() - t0) / 48 * 1e3)
-    print(f"{K} launches in flight: {best:.3f} ms per launch of {B} decodes = {B / best / 1e3:.1f} M decodes/s")
+    print(f"[[{n}]] {K} launches in flight: {best:.3f} ms per launch of {B} decodes = {B / best / 1e3:.1f} M decodes/s; form {dec.last_form}")

@@ -35,6 +35,8 @@ struct Bp4 {
     hipEvent_t last_done = nullptr; // (under mu) end of the most recent decode launch and the stream it ran on
     hipStream_t last_stream = nullptr;
     bool overlapped = false;        // (under mu) the launch being prepared found the previous one still running on another stream
+    // (under mu) the form of bp4_kernel the most recent launch took (swd_bp4_last_form); threads == 0: no launch yet
+    struct Form { int split, lazy, fast, wmax, dm, threads, skew, overlapped; } form{};
     std::mutex mu;
     ~Bp4() { for (auto &sl : slot) if (sl.done) (void)hipEventDestroy(sl.done); }
     // the next slot, ordered behind its previous launch on `st` (call under mu)
@@ -52,6 +54,7 @@ template <int WMAX, int NTO, int DM, bool FAST, bool LAZY>
 static int bp4_launch(Bp4 *d, const SwdBp4Args &a0, hipStream_t st, int nt) {
     SwdBp4Args a = a0;
     a.split = (FAST && nt == d->nt_split) ? 1 : 0;
+    d->form = {a.split, LAZY ? 1 : 0, FAST ? 1 : 0, WMAX, DM, nt, a.skew, d->overlapped ? 1 : 0};
     static std::mutex fn_mu; // the attributes and occupancy answers belong to the functions, not to a handle
     std::lock_guard<std::mutex> fn_lock(fn_mu);
     static int lds_limit[64] = {0};
@@ -116,6 +119,15 @@ static int bp4_dispatch_nt(Bp4 *d, const SwdBp4Args &a, hipStream_t st, int nt) 
     if (nt <= 512) return bp4_dispatch_dm<8, 256, FAST>(d, a, st, nt); // (still six waves per SIMD: three workgroups of up to eight waves per CU)
     return d->nt_osd == 256 ? bp4_dispatch_dm<16, 256, FAST>(d, a, st, nt) : bp4_dispatch_dm<16, 1024, FAST>(d, a, st, nt);
 }
+// SWD_BP4_SKEW=even|odd (diagnostics): the waves of that index parity sleep before every node pass of a split launch that stores messages
+// (bp4_skew, swd_bp4_kernel.h) -- the two threads of a qubit must not depend on running in step
+static int bp4_skew_switch() {
+    static const int v = [] {
+        const char *e = getenv("SWD_BP4_SKEW");
+        return !e ? 0 : (!strcmp(e, "even") ? 1 : (!strcmp(e, "odd") ? 2 : 0));
+    }();
+    return v;
+}
 static int bp4_dispatch(Bp4 *d, const SwdBp4Args &a, hipStream_t st) {
     // the specialised instantiation: a thread per qubit and per check, no camel run (swd_bp4_kernel.h); two threads per qubit for
     // small codes (swd_bp4_create; SWD_BP4_NOSPLIT: the one-thread form)
@@ -171,8 +183,11 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
     if (d->gx.upload() || d->gz.upload()) { delete d; return nullptr; }
     d->gx.d.new_n = n; d->gz.d.new_n = n;
     // rank(Hx) > rank(Hz): the z-basis sweep walks the first kx = n - rank_x non-pivot columns like the reference's (not the n - rank_z
-    // that exist).  The sweep takes k = new_n - rank candidate columns among the first new_n sorted ones, and the first k non-pivot
-    // columns always lie among the first k + rank: new_n = kx + rank_z is the same set.
+    // that exist).  new_n bounds only the sweep's candidates (osd_sweep: the first k = new_n - rank non-pivot columns among the first
+    // new_n sorted ones); the elimination before it (osd_run) runs over all n sorted columns whatever new_n is, so the pivots are the
+    // reference's even when the first kx + rank_z sorted columns span less than rank_z.  At most rank_z of those kx + rank_z columns
+    // are pivots, so at least kx are not: the first kx non-pivot columns of the whole order always lie among them, whatever their rank
+    // (pinned by tests/golden/bp4_unequal_prefix.npz, where that prefix is rank-deficient on every OSD shot).
     if (d->p.osd_order > 0 && d->gx.rank > d->gz.rank) d->gz.d.new_n = n - d->gx.rank + d->gz.rank;
     make_layout_for_osd(d->gx, d->nt_osd, d->Lx);
     make_layout_for_osd(d->gz, d->nt_osd, d->Lz);
@@ -228,6 +243,24 @@ extern "C" int swd_bp4_info(const swd_bp4 *h, int32_t *mx, int32_t *mz, int32_t 
     return 0;
 }
 
+extern "C" int swd_bp4_last_form(const swd_bp4 *h, int32_t *split, int32_t *lazy, int32_t *fast, int32_t *wmax, int32_t *dm,
+                                 int32_t *threads, int32_t *skew, int32_t *overlapped) {
+    Bp4 *d = (Bp4 *)h;
+    if (!d) { set_error("null decoder"); return -1; }
+    std::lock_guard<std::mutex> lk(d->mu);
+    const Bp4::Form f = d->form;
+    if (!f.threads) { set_error("no decode launched yet"); return -1; }
+    if (split) *split = f.split;
+    if (lazy) *lazy = f.lazy;
+    if (fast) *fast = f.fast;
+    if (wmax) *wmax = f.wmax;
+    if (dm) *dm = f.dm;
+    if (threads) *threads = f.threads;
+    if (skew) *skew = f.skew;
+    if (overlapped) *overlapped = f.overlapped;
+    return 0;
+}
+
 extern "C" int swd_bp4_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8_t *sx, const uint8_t *sz, uint8_t *out,
                                         int32_t *stats, double *lpr, uint8_t *osd0, uint8_t *bp_dec, void *stream) {
     Bp4 *d = (Bp4 *)h;
@@ -252,6 +285,7 @@ extern "C" int swd_bp4_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8_t *sx
     a.max_iter = d->p.max_iter; a.osd_method = d->p.osd_method; a.osd_order = d->p.osd_order; a.alpha = d->p.ms_scaling_factor;
     a.B = B; a.sx = sx; a.sz = sz; a.out = out; a.osd0 = osd0; a.bp_dec = bp_dec; a.stats = stats; a.lpr = lpr;
     a.lpr_wanted = lpr_wanted ? 1 : 0;
+    a.skew = bp4_skew_switch();
     // [ OSD queue counter | ticket counter | - | - | OSD queue [B] | weights [B] | start order [B] ]
     for (auto &s2 : d->slot) if (s2.osd_q.reserve((size_t)B * 12 + 16)) return -1;
     a.osd_count = sl->osd_q.as<uint32_t>(); a.osd_list = sl->osd_q.as<int32_t>() + 4;
@@ -268,8 +302,11 @@ extern "C" int swd_bp4_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8_t *sx
         // ([[144]], two streams in turn: 55.4 -> 58.7 M decodes/s without them)
         static const bool by_weight = getenv("SWD_BP4_NO_ORDER") == nullptr;
         static const bool always = getenv("SWD_BP4_ORDER_ALWAYS") != nullptr;
-        bool overlapped = false;
-        if (!always && d->last_done && d->last_stream != st) {
+        // SWD_BP4_OVERLAPPED (diagnostics): every launch takes the path of a launch with another one in flight -- the two-half (LAZY)
+        // form for two threads per qubit, no start order -- so that the tests reach that form without depending on timing
+        static const bool force_overlap = getenv("SWD_BP4_OVERLAPPED") != nullptr;
+        bool overlapped = force_overlap;
+        if (!force_overlap && !always && d->last_done && d->last_stream != st) {
             overlapped = hipEventQuery(d->last_done) == hipErrorNotReady;
             (void)hipGetLastError(); // ("not ready" is an answer, not an error: it must not be what the launch checks below pick up)
         }
@@ -309,6 +346,8 @@ extern "C" int swd_bp4_camel_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8
     a.max_iter = d->p.max_iter; a.osd_method = d->p.osd_method; a.osd_order = d->p.osd_order; a.alpha = d->p.ms_scaling_factor;
     a.B = B; a.sx = sx; a.sz = sz; a.out = nullptr; a.osd0 = nullptr; a.stats = nullptr; a.lpr = sl->lpr.as<double>();
     a.camel = 1; a.camel_dec = sl->cdec.as<uint8_t>(); a.camel_pm = sl->cpm.as<double>(); a.camel_st = sl->cst.as<int32_t>();
+    a.skew = bp4_skew_switch();
+    d->overlapped = false;
     int rc;
     rc = bp4_dispatch(d, a, st);
     if (rc) return rc;

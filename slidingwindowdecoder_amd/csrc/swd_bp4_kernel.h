@@ -42,8 +42,10 @@ struct SwdBp4Args {
     // 60 % empty on average.  Both NULL: static shares (camel runs).
     uint32_t *ticket;        // zeroed before the launch
     const uint32_t *order;   // [B] decode numbers by decreasing syndrome weight (bp4_weight_kernel + shot_order_kernel)
-    int32_t split;           // FAST instantiation: two threads per qubit -- thread v the Hx edges of qubit v, thread n + v its Hz edges
+    int32_t split;           // FAST instantiation: two threads per qubit -- thread 2 v the Hx edges of qubit v, thread 2 v + 1 its Hz edges
     int32_t lpr_wanted;      // the caller reads lpr: every decode stores its posteriors (else only those the OSD kernel finishes)
+    int32_t skew;            // diagnostics (SWD_BP4_SKEW): 0 off; 1 / 2 the waves of even / odd index sleep before each node pass that
+                             // stores messages in a split launch
     uint8_t *camel_dec;      // [4B][2][n] decisions of every run
     double *camel_pm;        // [4B] cal_pm of the converged runs
     int32_t *camel_st;       // [4B][2] converged, iterations
@@ -81,6 +83,42 @@ __device__ __forceinline__ bool bp4_block_any(bool p, Lds &s, int nwaves) {
     int r = 0;
     for (int w = 0; w < nwaves; ++w) r |= s.flags[par * 16 + w];
     return __builtin_amdgcn_readfirstlane(r) != 0;
+}
+
+// One half of a variable node's edges in the node update (bp4_osd.pyx:571-589): the new bit-to-check messages of its Hx edges (hx) or
+// its Hz edges, with the parity flip of each edge when `flip` (Hx * z-string, Hz * x-string).  One loop body whichever the half: the
+// two lanes of a split pair (two threads per qubit) walk their halves side by side, and a thread that owns the whole node calls it for
+// Hx, then Hz -- the operations and their order of the reference's vn_update.
+template <int DM>
+__device__ __forceinline__ void bp4_split_edges(bool hx, const uint32_t (&ex)[DM], const uint32_t (&ez)[DM], int dx, int dz, double llrx_hx,
+                                                double llry_all, double llrz_hz, double *msgx, double *msgz, uint32_t *parx, uint32_t *parz,
+                                                int flip, const uint64_t *xt) {
+    const double num = bp4_log1pexp(-1. * (hx ? llrx_hx : llrz_hz), xt);
+    const double other = hx ? llrz_hz : llrx_hx;
+    double *const msg = hx ? msgx : msgz;
+    uint32_t *const par = hx ? parx : parz;
+    const int deg = hx ? dx : dz;
+#pragma unroll 1
+    for (int k = 0; k < deg; ++k) {
+        uint32_t e = hx ? ex[0] : ez[0];
+#pragma unroll
+        for (int j = 1; j < DM; ++j) e = (k == j) ? (hx ? ex[j] : ez[j]) : e;
+        const double c = msg[swd_edge_slot(e)];
+        const double aa = other - c, bb = llry_all - c;
+        msg[swd_edge_slot(e)] = num - bp4_logaddexp(-1. * aa, -1. * bb, xt);
+        if (flip) atomicXor(&par[swd_edge_lane(e)], 1u);
+    }
+}
+
+// SWD_BP4_SKEW (diagnostics): the waves of one parity fall ~65 k cycles behind the others before a node pass that stores messages, so
+// that a pass whose loads and stores are not ordered between the two threads of a qubit would show it.  Wave-uniform, bounded: eight
+// sleeps, no wait on anything.  Unset (skew == 0): one scalar compare and branch on a kernel argument per node pass.
+__device__ __forceinline__ void bp4_skew(int skew) {
+    if (skew == 0) return;
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    if ((w & 1) == skew - 1)
+#pragma unroll 1
+        for (int i = 0; i < 8; ++i) __builtin_amdgcn_s_sleep(127);
 }
 
 #ifndef SWD_BP4_OWN_CHECK
@@ -221,12 +259,17 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
     for (int j = tid; j <= gz.K; j += NT) jpz[j] = gz.jptr[j];
     const bool one = FAST || n <= NT;
     // Round 6: two threads per qubit (a.split; FAST launches with 2 n <= 1024).  Both compute the node's three posteriors from all of its
-    // messages (same operations in the same order), thread v then updates the Hx edges, thread n + v the Hz edges: the chain of eight
+    // messages (same operations in the same order), one then updates the Hx edges, the other the Hz edges: the chain of eight
     // dependent exp / log1p evaluations per node and iteration -- what a launch waits for once its units are ticket-scheduled: the
-    // decodes that run all max_iter iterations -- becomes two chains of four.
+    // decodes that run all max_iter iterations -- becomes two chains of four.  Each thread READS both halves of the node's messages
+    // and then OVERWRITES its own half in place, with no barrier in between: the two threads are neighbouring lanes of one wave
+    // (2 v, 2 v + 1), so every load of the pair is issued before either of its stores.  (Until this was found, thread n + v held the
+    // Hz half: from n > 32 on the pair sat in different waves, and a wave that ran ahead overwrote check-to-bit messages its partner
+    // had yet to read -- caught by SWD_BP4_SKEW, tests/test_gpu_bp4.py.)  The edge loops of a split thread walk its own half in one
+    // loop, so that the two halves of a pair run side by side, not one after the other (bp4_split_edges).
     const bool split = FAST && a.split != 0;
-    const int vt = (split && tid >= n) ? tid - n : tid;          // the thread's qubit
-    const int hsel = !split ? 3 : (tid < n ? 1 : 2);             // bit 0: the Hx edges are this thread's, bit 1: the Hz edges
+    const int vt = split ? tid >> 1 : tid;                       // the thread's qubit
+    const int hsel = !split ? 3 : ((tid & 1) ? 2 : 1);           // bit 0: the Hx edges are this thread's, bit 1: the Hz edges
     const bool mine = one && vt < n;
     int c_dx = 0, c_dz = 0;
     uint32_t c_ex[DM], c_ez[DM];
@@ -413,6 +456,7 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
 #endif
         if (!any) { conv = 1; iters = it + 1; break; }
         if (it + 1 >= a.max_iter) break; // (the messages of the last update feed no check pass)
+        if (split) bp4_skew(a.skew);
         for (int v = vt; v < n; v += NT) { // half B: the new bit-to-check messages (bp4_osd.pyx:571-589)
             if (v == fixed) { // decided: its bit-to-check messages stay the priors of bp_init; the CN pass has overwritten the shared
                               // slots with check-to-bit values, so put them back
@@ -429,26 +473,10 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
             // (the sums of half A again, from the check messages it left untouched: holding them across the test costs registers this
             // kernel does not have -- [[144]], 4 launches in flight: 73 -> 79 M decodes/s without them)
             node_sums(v, ex, ez, dx, dz, llrx_hx, llry_all, llrz_hz);
-            const double num_hx = (hsel & 1) ? bp4_log1pexp(-1. * llrx_hx, xt) : 0.0;
-            BP4T(4) // log1pexp
-#pragma unroll 1
-            for (int k = 0; k < ((hsel & 1) ? dx : 0); ++k) {
-                const uint32_t e = pick(ex, k);
-                const double c = msgx[swd_edge_slot(e)];
-                const double aa = llrz_hz - c, bb = llry_all - c;
-                msgx[swd_edge_slot(e)] = num_hx - bp4_logaddexp(-1. * aa, -1. * bb, xt);
-            }
-            BP4T(5) // Hx edges: logaddexp + store each
-            const double num_hz = (hsel & 2) ? bp4_log1pexp(-1. * llrz_hz, xt) : 0.0;
-            BP4T(4)
-#pragma unroll 1
-            for (int k = 0; k < ((hsel & 2) ? dz : 0); ++k) {
-                const uint32_t e = pick(ez, k);
-                const double c = msgz[swd_edge_slot(e)];
-                const double aa = llrx_hx - c, bb = llry_all - c;
-                msgz[swd_edge_slot(e)] = num_hz - bp4_logaddexp(-1. * aa, -1. * bb, xt);
-            }
-            BP4T(6) // Hz edges
+            // the node's edge halves: this thread's one (split) or both, Hx first (bp4_split_edges)
+            for (int h = (hsel & 1) ? 0 : 1; h <= ((hsel & 2) ? 1 : 0); ++h)
+                bp4_split_edges<DM>(h == 0, ex, ez, dx, dz, llrx_hx, llry_all, llrz_hz, msgx, msgz, parx, parz, 0, xt);
+            BP4T(6) // edges
         }
         __syncthreads();
             continue;
@@ -468,6 +496,7 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
         const bool any = bp4_block_any(unsat, s, NT >> 6);
         BP4T(2) // flags + barrier
         if (it > 0 && !any) { conv = 1; iters = it; break; }
+        if (split) bp4_skew(a.skew);
         for (int v = vt; v < n; v += NT) { // vn_update (bp4_osd.pyx:533-589)
             if (v == fixed) { // decided (bp4_osd.pyx:456-458): its bit-to-check messages stay the priors of bp_init; the
                               // CN pass has just overwritten the shared slots with check-to-bit values, so put them back
@@ -507,34 +536,12 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
             const int bx = idx & 1, bz = idx >> 1;
             if (hsel & 1) { decx[v] = (uint8_t)bx; decz[v] = (uint8_t)bz; }
             BP4T(3) // node: message loads, sums, posteriors, decision
-            const double num_hx = (hsel & 1) ? bp4_log1pexp(-1. * llrx_hx, xt) : 0.0;
-            BP4T(4) // log1pexp
-#if SWD_BP4_ROLLED // one body of the helper per basis instead of DM: the edge word is picked by a select chain, the message re-read from LDS
-            auto pick = [&](const uint32_t (&ev)[DM], int k) { uint32_t e = ev[0];
-#pragma unroll
-                for (int j = 1; j < DM; ++j) e = (k == j) ? ev[j] : e;
-                return e; };
-#pragma unroll 1
-            for (int k = 0; k < ((hsel & 1) ? dx : 0); ++k) {
-                const uint32_t e = pick(ex, k);
-                const double c = msgx[swd_edge_slot(e)];
-                const double aa = llrz_hz - c, bb = llry_all - c;
-                msgx[swd_edge_slot(e)] = num_hx - bp4_logaddexp(-1. * aa, -1. * bb, xt);
-                if (bz) atomicXor(&parx[swd_edge_lane(e)], 1u); // Hx * z-string
-            }
-            BP4T(5) // Hx edges: logaddexp + store + parity flip each
-            const double num_hz = (hsel & 2) ? bp4_log1pexp(-1. * llrz_hz, xt) : 0.0;
-            BP4T(4)
-#pragma unroll 1
-            for (int k = 0; k < ((hsel & 2) ? dz : 0); ++k) {
-                const uint32_t e = pick(ez, k);
-                const double c = msgz[swd_edge_slot(e)];
-                const double aa = llrx_hx - c, bb = llry_all - c;
-                msgz[swd_edge_slot(e)] = num_hz - bp4_logaddexp(-1. * aa, -1. * bb, xt);
-                if (bx) atomicXor(&parz[swd_edge_lane(e)], 1u); // Hz * x-string
-            }
-            BP4T(6) // Hz edges
+#if SWD_BP4_ROLLED // one body of the edge loop for both halves (bp4_split_edges): the edge word is picked by a select chain, the message re-read from LDS
+            for (int h = (hsel & 1) ? 0 : 1; h <= ((hsel & 2) ? 1 : 0); ++h)
+                bp4_split_edges<DM>(h == 0, ex, ez, dx, dz, llrx_hx, llry_all, llrz_hz, msgx, msgz, parx, parz, h == 0 ? bz : bx, xt);
+            BP4T(6) // edges: log1pexp, then logaddexp + store + parity flip each
 #else
+            const double num_hx = (hsel & 1) ? bp4_log1pexp(-1. * llrx_hx, xt) : 0.0;
 #pragma unroll
             for (int k = 0; k < DM; ++k)
                 if (k < dx && (hsel & 1)) {

@@ -470,6 +470,16 @@ class bp4_osd:
             raise RuntimeError(f"swd_bp4_decode_batch_dev failed: {_lib.last_error()}")
         return out, stats
 
+    @property
+    def last_form(self):
+        """The form of the BP kernel the most recent launch took (include/swd.h swd_bp4_last_form): dict with split, lazy, fast,
+        wmax, dm, threads, skew, overlapped; None before the first launch."""
+        keys = ("split", "lazy", "fast", "wmax", "dm", "threads", "skew", "overlapped")
+        v = [C.c_int32() for _ in keys]
+        if _lib.lib().swd_bp4_last_form(self._h, *[C.byref(x) for x in v]):
+            return None
+        return {k: x.value for k, x in zip(keys, v)}
+
     def decode(self, input_vector_x, input_vector_z):
         sx, sz = np.asarray(input_vector_x), np.asarray(input_vector_z)
         if sx.shape[0] != self.mx or sz.shape[0] != self.mz:

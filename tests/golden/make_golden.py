@@ -468,6 +468,52 @@ def gen_bp4_unequal_ranks(ref):
     save("bp4_unequal_ranks.npz", **arrs)
 
 
+def gen_bp4_unequal_prefix(ref):
+    """rank(Hx) > rank(Hz), built so that the first kx + rank_z columns of the z-basis order span LESS than rank_z: Hx has full
+    row rank n - kx (kx = 4); outside a set S every Hz column is the same single check (rank 1 together), Hz's other rank lies
+    on S, whose priors are far below the rest, so S sorts last.  The reference eliminates over all n sorted columns and takes the
+    first kx non-pivots (bp4_osd.pyx:297-366); few BP iterations, so that most shots reach the OSD."""
+    rng = np.random.default_rng(31415)
+    arrs = {}
+    n, kx, ns, mz = 44, 4, 12, 10
+    for tag, kw in [("cs4", dict(max_iter=3, ms_scaling_factor=0.8, osd_method="osd_cs", osd_order=4)),
+                    ("e3", dict(max_iter=2, ms_scaling_factor=1.0, osd_method="osd_e", osd_order=3))]:
+        mx = n - kx
+        S = rng.choice(n, size=ns, replace=False)
+        piv = rng.permutation(n)
+        Hx = np.zeros((mx, n), np.uint8)
+        for i in range(mx):  # upper triangular over the pivot columns: full row rank
+            Hx[i, piv[i]] = 1
+            if i > 0:
+                Hx[rng.choice(i, size=min(i, int(rng.integers(0, 3))), replace=False), piv[i]] = 1
+        for c in piv[mx:]:
+            Hx[rng.choice(mx, size=3, replace=False), c] = 1
+        Hz = np.zeros((mz, n), np.uint8)
+        Hz[0, :] = 1
+        Hz[:, S] = 0
+        for j, c in enumerate(S):
+            Hz[rng.choice(np.arange(1, mz), size=2, replace=False), c] = 1
+            Hz[1 + j % (mz - 1), c] = 1
+        lo = np.ones(n, bool)
+        lo[S] = False
+        px, py, pz = (np.where(lo, rng.uniform(0.02, 0.05, n), rng.uniform(1e-5, 1e-4, n)) for _ in range(3))
+        dec = ref.bp4_osd(Hx.astype(int), Hz.astype(int), channel_probs_x=px, channel_probs_y=py, channel_probs_z=pz, **kw)
+        sxs, szs, outs, o0, conv, its = [], [], [], [], [], []
+        for _ in range(250):
+            u = rng.random(n)
+            ex = (u < px + py).astype(np.uint8)
+            ez = ((u >= px) & (u < px + py + pz)).astype(np.uint8)
+            sx, sz = (Hx @ ez) % 2, (Hz @ ex) % 2
+            out = dec.decode(sx, sz)
+            sxs.append(sx); szs.append(sz); outs.append(np.asarray(out, np.uint8)); conv.append(int(dec.converge)); its.append(int(dec.bp_iteration))
+            o0.append(np.stack([dec.osd0_decoding_x, dec.osd0_decoding_z]).astype(np.uint8))
+        arrs.update({tag + "_hx": Hx, tag + "_hz": Hz, tag + "_px": px, tag + "_py": py, tag + "_pz": pz, tag + "_params": json.dumps(kw),
+                     tag + "_sx": pack(np.array(sxs)), tag + "_sz": pack(np.array(szs)), tag + "_out": pack(np.array(outs)),
+                     tag + "_osd0": pack(np.array(o0)), tag + "_converge": np.array(conv, np.uint8), tag + "_bp_iteration": np.array(its, np.int32)})
+        print(f"  bp4_unequal_prefix/{tag}: converge {sum(conv)}/250")
+    save("bp4_unequal_prefix.npz", **arrs)
+
+
 def gen_bp4_camel(ref):
     """bp4_osd.camel_decode (src/bp4_osd.pyx:223-247, used by Misc.ipynb): one reference object per case, calls in
     sequence (the returned vectors persist in the object when no run converges)."""
@@ -543,7 +589,7 @@ def gen_bp4_shyps(ref):
 def main():
     ensure_reference()
     import src as ref
-    which = sys.argv[1:] or ["bb72", "bb144", "bb288", "bb288_gdg", "kat288", "bp4", "camel", "bp4_shyps", "global144", "bp4_unequal"]
+    which = sys.argv[1:] or ["bb72", "bb144", "bb288", "bb288_gdg", "kat288", "bp4", "camel", "bp4_shyps", "global144", "bp4_unequal", "bp4_unequal_prefix"]
     if "bb72" in which:
         gen_bb72(ref)
     if "bb144" in which:
@@ -564,6 +610,8 @@ def main():
         gen_bp4_shyps(ref)
     if "bp4_unequal" in which:
         gen_bp4_unequal_ranks(ref)
+    if "bp4_unequal_prefix" in which:
+        gen_bp4_unequal_prefix(ref)
 
 
 if __name__ == "__main__":

@@ -49,3 +49,19 @@ def test_product_never_imports_oracle():
             if fn.endswith((".py", ".hip", ".h", ".cpp")):
                 txt = open(os.path.join(dp, fn)).read()
                 assert "swd_oracle" not in txt and "from oracle" not in txt and "import oracle" not in txt, fn
+
+
+def test_bp4_last_form_is_bound_and_refuses_a_null_handle():
+    """swd_bp4_last_form (the form of the BP kernel a handle's last launch took) answers without a GPU for a null handle: -1 and
+    a message, the out-parameters untouched; the Python surface reads it as ``bp4_osd.last_form``."""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libswd_hip.so not built")
+    import ctypes as C
+    from slidingwindowdecoder_amd import bp4_osd
+    L = _lib.lib()
+    v = [C.c_int32(-7) for _ in range(8)]
+    assert L.swd_bp4_last_form(None, *[C.byref(x) for x in v]) == -1
+    assert "null" in _lib.last_error()
+    assert all(x.value == -7 for x in v)
+    assert L.swd_bp4_last_form(None, *([None] * 8)) == -1
+    assert isinstance(bp4_osd.last_form, property)

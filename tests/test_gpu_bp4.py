@@ -3,6 +3,10 @@ algorithms of the C library the reference ran on (csrc/swd_libm.h, pinned by tes
 EVERY shot has to agree: error vectors, converge flags, iteration counts and OSD-0 solutions bit for bit; the
 posterior LLRs are held to the north star's 1e-5 relative tolerance and the number of them that is bit-identical
 is printed (all of them, when the goldens come from an FMA-capable glibc 2.35 host as committed)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -10,6 +14,7 @@ from tests import fixtures as fx
 from tests.test_oracle_bp4 import SHYPS_TAGS, TAGS, load_case, load_shyps
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _check_all_shots(dec, out, c, label):
@@ -174,3 +179,97 @@ def test_bp4_unequal_ranks_matches_reference(tag):
     assert np.array_equal(dec.last_iterations, f[tag + "_bp_iteration"])
     with pytest.raises((ValueError, RuntimeError), match="rank"):
         bp4_osd(Hz, Hx, **pr, **kw)  # rank(Hx) < rank(Hz)
+
+
+@pytest.mark.parametrize("tag", ["cs4", "e3"])
+def test_bp4_unequal_prefix_matches_reference(tag):
+    """rank(Hx) > rank(Hz) where the first kx + rank_z columns of the z-basis order span less than rank_z (make_golden.py
+    bp4_unequal_prefix; tests/test_oracle_bp4.py shows the recorded OSD shots reach that case).  The device shortens the z basis to
+    new_n = kx + rank_z for its candidate columns but eliminates over all n sorted columns, like the reference."""
+    from slidingwindowdecoder_amd import bp4_osd
+    from tests.test_oracle_bp4 import load_prefix
+    c = load_prefix(tag)
+    dec = bp4_osd(c["Hx"], c["Hz"], **c["pr"], **c["kw"])
+    assert dec.rank_x > dec.rank_z
+    out = dec.decode_batch(c["sx"], c["sz"])
+    bad = np.flatnonzero((out != c["out"]).any(axis=(1, 2)))
+    assert bad.size == 0, f"{bad.size} decodes differ: {bad[:8]}"
+    assert np.array_equal((dec.last_status & 0x100) != 0, c["converge"] != 0)
+    assert np.array_equal(dec.last_iterations, c["its"])
+    assert (dec.last_osd0 == c["osd0"]).all()
+    assert (np.bincount(dec.last_status & 0xFF, minlength=3)[2]) > 60  # the OSD ran
+
+
+def _bp4_env(**switches):
+    """The environment of a child process with exactly these SWD_BP4_* switches (the library reads them once per process)."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("SWD_BP4_")}
+    env.update(switches)
+    return env
+
+
+def _run_child(cmd, env, timeout=600):
+    """One child process at a time.  A child that dies of a signal, aborts or hangs may have left the device faulted: the session
+    stops there instead of starting the next child on it."""
+    try:
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
+    except subprocess.TimeoutExpired as ex:
+        pytest.exit(f"child timed out after {timeout} s: {cmd[-6:]}\n{(ex.stdout or b'')[-2000:]!r}", returncode=3)
+    if r.returncode < 0 or r.returncode >= 128:
+        pytest.exit(f"child ended with status {r.returncode}: {cmd[-6:]}\n{r.stdout[-2000:]}{r.stderr[-2000:]}", returncode=3)
+    print(r.stdout[-1500:])
+    return r
+
+
+# (form of tests/fuzz_bp4.py FORMS, SWD_BP4_SKEW): every form of bp4_kernel against the oracle, the split forms also with either
+# parity of waves held back before the node passes that store messages
+FORM_CELLS = [(f, None) for f in ("split", "split_lazy", "split8", "nosplit_lazy", "nosplit_fused", "generic")] + \
+             [(f, k) for f in ("split", "split_lazy", "split8") for k in ("even", "odd")]
+
+
+@pytest.mark.parametrize("form,skew", FORM_CELLS, ids=[f + ("-skew_" + k if k else "") for f, k in FORM_CELLS])
+def test_bp4_form_vs_oracle(form, skew):
+    """One form of the BP kernel, demanded through its switches in a fresh process and confirmed by bp4_osd.last_form, against the
+    oracle on every shot: vectors, converge flags, iteration counts, posteriors and camel_decode (tests/fuzz_bp4.py)."""
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "fuzz_bp4.py"), "--trials", "10", "--seed", "7", "--form", form]
+    if skew:
+        cmd += ["--skew", skew]
+    r = _run_child(cmd, _bp4_env())
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "; form {" in r.stdout
+
+
+def test_bp4_unequal_prefix_fuzz_vs_oracle():
+    """Adversarial codes for the unequal-rank shortcut (tests/fuzz_bp4.py --prefix): the script fails when no OSD shot reaches a
+    rank-deficient z prefix."""
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "fuzz_bp4.py"), "--trials", "12", "--seed", "3", "--prefix", "--form", "split"]
+    r = _run_child(cmd, _bp4_env())
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "rank-deficient z prefix" in r.stdout
+
+
+def _recorded_split_cases(skew, lazy):
+    """(run in a child process with SWD_BP4_SKEW, and SWD_BP4_OVERLAPPED for the two-half form) bb72_cs10 and the SHYPS cases --
+    both split launches -- under _check_all_shots"""
+    from slidingwindowdecoder_amd import bp4_osd, shyps
+    want = dict(split=1, lazy=int(lazy), fast=1, skew=1 if skew == "even" else 2)
+    cases = [("bb72_cs10", load_case("bb72_cs10"), None)] + [("shyps " + t, load_shyps(t), shyps.shyps_stabilizers(3)) for t in SHYPS_TAGS]
+    for label, c, mats in cases:
+        hx, hz = mats if mats is not None else (c["code"].hx, c["code"].hz)
+        dec = bp4_osd(hx, hz, channel_probs_x=c["pr"], channel_probs_y=c["pr"], channel_probs_z=c["pr"], **c["kw"])
+        out = dec.decode_batch(c["sx"], c["sz"])
+        form = dec.last_form
+        assert all(form[k] == v for k, v in want.items()), f"{label}: demanded {want}, the launch took {form}"
+        assert _check_all_shots(dec, out, c, label) == 1.0
+    print("recorded split cases ok")
+
+
+@pytest.mark.parametrize("skew", ["even", "odd"])
+@pytest.mark.parametrize("lazy", [False, True], ids=["fused", "lazy"])
+def test_bp4_recorded_cases_under_skew(lazy, skew):
+    """The recorded cases that run split (bb72_cs10, SHYPS r = 3) bit for bit with one parity of waves held back before every
+    message-storing node pass: the two threads of a qubit must not depend on running in step."""
+    env = _bp4_env(SWD_BP4_SKEW=skew, **({"SWD_BP4_OVERLAPPED": "1"} if lazy else {}))
+    code = f"from tests.test_gpu_bp4 import _recorded_split_cases; _recorded_split_cases({skew!r}, {lazy})"
+    r = _run_child([sys.executable, "-c", code], env)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "recorded split cases ok" in r.stdout

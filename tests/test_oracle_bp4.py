@@ -2,6 +2,9 @@
 (tests/golden/make_golden.py bp4).  Equality is exact here because oracle and reference call the same
 libm on the same machine; log/exp/log1p make BP4 results libm-dependent in general, which is why the
 GPU tests compare the posterior LLRs with a tolerance."""
+import math
+import sys
+
 import numpy as np
 import pytest
 
@@ -117,3 +120,73 @@ def test_bp4_unequal_ranks_oracle_matches_reference(tag):
         assert (got == out[k]).all(), f"decode {k}"
         assert dec.converge == f[tag + "_converge"][k] and dec.bp_iteration == f[tag + "_bp_iteration"][k]
     assert (f[tag + "_converge"] == 0).sum() > 100  # the sweeps really ran
+
+
+def _log1pexp(x):  # bpgd.cpp:399-406, as swd_oracle.c log1pexp_ (math calls the same libm)
+    return x + math.log1p(math.exp(-x)) if x > -math.log(sys.float_info.epsilon) else math.log1p(math.exp(x))
+
+
+def _logaddexp(x, y):  # bpgd.cpp:408-416, as swd_oracle.c logaddexp_
+    t = x - y
+    if x == y:
+        return x + math.log(2.0)
+    if t > 0:
+        return x + _log1pexp(-t)
+    if t <= 0:
+        return y + _log1pexp(t)
+    return t
+
+
+def z_basis_order(lpr):
+    """The column order of the oracle's z-basis OSD (swd_oracle.c bp4_osd_basis with is_x = 0): key log1pexp(-z) - logaddexp(-y, -x)
+    of the posteriors ``lpr`` [n, 3] (x, y, z), stable ascending (index_sort)."""
+    key = np.array([_log1pexp(-1. * lz) - _logaddexp(-1. * ly, -1. * lx) for lx, ly, lz in lpr])
+    return np.argsort(key, kind="stable")
+
+
+def z_prefix_deficient(lpr, Hz, kx, rank_z):
+    """True when the first kx + rank_z columns of the z-basis order span less than rank_z: the case where the device's shortened z
+    basis (swd_bp4_create: new_n = kx + rank_z) must still eliminate over all n columns to agree with the reference."""
+    from slidingwindowdecoder_amd import gf2
+    order = z_basis_order(lpr)
+    return gf2.rank(np.asarray(Hz)[:, order[:kx + rank_z]]) < rank_z
+
+
+PREFIX_TAGS = ["cs4", "e3"]
+
+
+def load_prefix(tag):
+    f = fx.load("bp4_unequal_prefix.npz")
+    Hx, Hz = f[tag + "_hx"], f[tag + "_hz"]
+    n = Hx.shape[1]
+    return dict(Hx=Hx, Hz=Hz, kw=fx.params(f, tag + "_params"),
+                pr=dict(channel_probs_x=f[tag + "_px"], channel_probs_y=f[tag + "_py"], channel_probs_z=f[tag + "_pz"]),
+                sx=fx.unpack(f[tag + "_sx"], Hx.shape[0]), sz=fx.unpack(f[tag + "_sz"], Hz.shape[0]), out=fx.unpack(f[tag + "_out"], n),
+                osd0=fx.unpack(f[tag + "_osd0"], n), converge=f[tag + "_converge"], its=f[tag + "_bp_iteration"])
+
+
+@pytest.mark.parametrize("tag", PREFIX_TAGS)
+def test_bp4_unequal_prefix_oracle_matches_reference(tag):
+    """rank(Hx) > rank(Hz) where the first kx + rank_z columns of the z-basis order are rank-deficient (make_golden.py
+    bp4_unequal_prefix): the oracle equals the recorded reference on every decode, and the case is not vacuous -- on at least
+    60 of the recorded OSD shots the prefix really spans less than rank_z."""
+    from slidingwindowdecoder_amd import gf2
+    c = load_prefix(tag)
+    Hx, Hz = c["Hx"], c["Hz"]
+    n, rank_x, rank_z = Hx.shape[1], gf2.rank(Hx), gf2.rank(Hz)
+    kx = n - rank_x
+    assert rank_x > rank_z and c["kw"]["osd_order"] > 0
+    dec = O.bp4_osd(Hx, Hz, **c["pr"], **c["kw"])
+    deficient = osd_shots = 0
+    for k in range(len(c["sx"])):
+        got = dec.decode(c["sx"][k], c["sz"][k])
+        assert (got == c["out"][k]).all(), f"decode {k}"
+        assert dec.converge == c["converge"][k] and dec.bp_iteration == c["its"][k], f"decode {k}"
+        assert (np.stack([dec.osd0_decoding_x, dec.osd0_decoding_z]) == c["osd0"][k]).all(), f"decode {k}"
+        if not dec.converge:
+            osd_shots += 1
+            lpr = dec.log_prob_ratios
+            assert np.isfinite(lpr).all()
+            deficient += z_prefix_deficient(lpr, Hz, kx, rank_z)
+    print(f"{tag}: {osd_shots} OSD shots, {deficient} with a rank-deficient z prefix (kx {kx}, rank_z {rank_z})")
+    assert deficient >= 60
