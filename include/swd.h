@@ -145,6 +145,13 @@ typedef struct swd_gdg_params {
 } swd_gdg_params;
 
 typedef struct swd_gdg swd_gdg;
+/* Graphs beyond every kernel variant (more than 1024 checks, 9216 columns, row weight 64, column weight 10, or new_n > 2048) take
+ * the general form (csrc/swd_huge_gdg.hip, one workgroup per shot, every array in HBM), as swd_osdw_create does; same results and
+ * statistics words.  Its bounds, each an error at construction: 4096 checks, 4194304 columns, 4096 snapshots per shot
+ * (max_guess, or S - D + 2 for the threaded ensemble); multi_thread = 2 is refused there; modes 0 and 1 refuse a check of weight
+ * >= 128 (the reference keeps check degrees in char, bpgd.hpp:23: they wrap, no answer is pinned), mode 2 takes it.
+ * Test hook of both constructors: with the environment variable SWD_FORCE_HUGE set, swd_osdw_create and swd_gdg_create build
+ * the general form on any graph.  swd_pipeline_create_gdg refuses windows beyond every pipeline kernel. */
 swd_gdg *swd_gdg_create(const swd_graph_desc *g, const swd_gdg_params *p, int device);
 void swd_gdg_destroy(swd_gdg *d);
 /* host pointers; hist [B*4*n] nullable as in swd_osdw_decode_batch (pre-processing BP history) */

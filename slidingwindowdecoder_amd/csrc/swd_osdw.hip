@@ -937,7 +937,12 @@ extern "C" swd_gdg *swd_gdg_create(const swd_graph_desc *g, const swd_gdg_params
     d->kind = gp->mode + 1;
     d->p.pre_max_iter = gp->max_iter; d->p.osd_order = -1; d->p.ms_scaling_factor = gp->ms_scaling_factor;
     std::map<std::string, std::shared_ptr<Graph>> cache;
-    if (d->add_window(g, 0, 0, 0, cache) || d->finalize(nullptr)) { delete d; return nullptr; }
+    if (getenv("SWD_FORCE_HUGE") /* tests: the general form on graphs a variant would take */ || d->add_window(g, 0, 0, 0, cache) || d->finalize(nullptr)) {
+        // no kernel variant takes this graph: the guessing decoders' general form, every array in HBM (swd_huge_gdg.hip)
+        d->wins.clear();
+        d->huge.reset(huge_gdg_create(g, gp, device));
+        if (!d->huge) { delete d; return nullptr; }
+    }
     return (swd_gdg *)d;
 }
 

@@ -86,6 +86,8 @@ struct HugeIface {
                            double *min_pm, double *hist, int32_t hist_is_state, uint8_t *osd0, uint8_t *bp_dec, void *stream) = 0;
 };
 HugeIface *huge_create(const swd_graph_desc *g, const swd_osdw_params *p, int device);
+// the guessing decoders' general form (swd_huge_gdg.hip): bpgdg_decoder / bpgd_decoder / bp_history_decoder on any such graph
+HugeIface *huge_gdg_create(const swd_graph_desc *g, const swd_gdg_params *p, int device);
 
 struct Plan {
     std::unique_ptr<HugeIface> huge;

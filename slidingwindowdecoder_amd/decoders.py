@@ -627,12 +627,15 @@ class SlidingWindowDecoder:
             msg = _lib.last_error()
             if "OSD order" in msg or "invalid" in msg:
                 raise ValueError(msg)
-            if decoder == "osd_window" and ("no kernel variant" in msg or "exceeds" in msg or "needs" in msg):
+            if "no kernel variant" in msg or "exceeds" in msg or "needs" in msg:
                 # windows beyond every kernel variant (e.g. the un-windowed [[288,12,18]] model, 2736 x 26 208): the window loop of
-                # /root/reference/osd.py:130-179 as the reference runs it -- one osd_window per window (device: the general form,
-                # csrc/swd_huge.hip), the residual syndrome det ^ chk @ total_e_hat between windows (osd.py:165, 178) on the host
-                self._loop = [osd_window(w.mat, channel_probs=w.prior, device=self.device,
-                                         **{k: v for k, v in kwargs.items() if k != "device"}) for w in plan.windows]
+                # /root/reference/osd.py:130-179 as the reference runs it -- one device decoder per window (the general forms,
+                # csrc/swd_huge.hip and csrc/swd_huge_gdg.hip), the residual syndrome det ^ chk @ total_e_hat between windows
+                # (osd.py:165, 178) on the host
+                cls = {"osd_window": osd_window, "bpgdg_decoder": bpgdg_decoder, "bpgd_decoder": bpgd_decoder,
+                       "bp_history_decoder": bp_history_decoder}[decoder]
+                self._loop = [cls(w.mat, channel_probs=w.prior, device=self.device,
+                                  **{k: v for k, v in kwargs.items() if k != "device"}) for w in plan.windows]
                 self._chk_t = sp.csr_matrix(plan.chk.T.astype(np.int32))
                 self.lds_bytes, self.threads = 0, 1024
                 self.num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
@@ -691,7 +694,7 @@ class SlidingWindowDecoder:
         return total
 
     def _decode_window_loop(self, d, packed):
-        """the window loop for plans no pipeline kernel takes: per window one batched osd_window decode on the device, commit, residual"""
+        """the window loop for plans no pipeline kernel takes: per window one batched device decode, commit, residual"""
         B = d.shape[0]
         total = np.zeros((B, self.num_col), np.uint8)
         st = np.zeros((B, self.W, _lib.STAT_WORDS), np.int32)
@@ -700,8 +703,10 @@ class SlidingWindowDecoder:
         for wi, (w, dec) in enumerate(zip(self.plan.windows, self._loop)):
             out = dec.decode_batch(np.ascontiguousarray(cur[:, w.row0:w.row1])) if B else np.zeros((0, w.mat.shape[1]), np.uint8)
             total[:, w.col0:w.col0 + w.commit] = out[:, :w.commit]
-            if B:
+            if B and self.decoder == "osd_window":
                 st[:, wi, 0], st[:, wi, 1], pm[:, wi] = dec.last_status, dec.last_iterations, dec.last_min_pm
+            elif B:  # the guessing decoders: every statistics word of the window decode (include/swd.h)
+                st[:, wi], pm[:, wi] = dec.last_stats, dec.last_min_pm
             cur = ((d.astype(np.int32) + (sp.csr_matrix(total) @ self._chk_t).toarray()) % 2).astype(np.uint8)  # osd.py:178
         self.last_stats, self.last_min_pm = st, pm
         self.last_flagged = cur.any(axis=1)
@@ -715,7 +720,7 @@ class SlidingWindowDecoder:
     def _no_loop(self, what):
         if self._loop is not None:
             raise RuntimeError(f"{what} needs the one-launch pipeline; this plan's windows are beyond every kernel variant and run as a "
-                               "window loop of osd_window decodes (use decode())")
+                               f"window loop of {self.decoder} decodes (use decode())")
 
     def stream(self, max_shots, packed=False, want_stats=True):
         """Streaming form for consecutive batches (``SlidingWindowStream``): two batches in flight on two lanes of this
