@@ -104,10 +104,9 @@ int make_layout(const Graph &g, int new_n, int nt, int kind, SwdLdsLayout &L, bo
             if (o + bytes <= lds_budget) { L.off_owide = o; L.owide_ring = ring; o += bytes; break; }
         }
     }
-    // experiment (SWD_POST_RENUM=1, tuned osd_window kernels of up to 256 threads): renumber the shortened graph's message cells
-    // one column per live variable node inside the scratch region; the old-slot -> cell table takes the staged column table's place
-    // (round 5, SWD_POST_SORTED: the production form of the tuned kernels' post phase whenever the renumbered cells fit in front of the
-    // staged column table, which becomes the old-slot -> cell table; SWD_NO_POST_SORTED=1 in the environment keeps the round-4 form)
+    // sorted form of the shortened graph (round 5): the production form of the tuned kernels' post phase whenever the renumbered cells
+    // fit in front of the staged column table, which becomes the old-slot -> cell table; SWD_NO_POST_SORTED=1 in the environment keeps
+    // the round-4 form
     // (diet kernels keep cell BYTE offsets in 16 bits, the 1024-thread osd_window kernels cell numbers)
     if (kind == 0 && !big && !getenv("SWD_NO_POST_SORTED") && L.off_lslot == 0 && (g.D * new_n + 1 + 2 * (nt / 64)) * 8 <= L.off_rc &&
         g.D * new_n + 1 + 2 * (nt / 64) <= (diet ? 8191 : 65535) && (diet || nt >= 512))

@@ -16,45 +16,35 @@
 
 #define SWD_DMAX 10 // largest column degree any kernel variant of this build supports
 
-// Translation units of the osd_window kernels (swd_kernels_k0 / k3) set SWD_OSDW_TUNED: their kernels of up to 256 threads
-// keep the BP register caches packed (VnCache / CnCache, P16) and -- variants with at most twelve groups of check
-// positions -- are built for three waves per SIMD (168 VGPRs); together with the LDS diet of the osd_window layout
-// (decided-node bits, 48-bit live masks, parity bytes, residual syndrome of the window's rows only; DIET below) three
-// workgroups of the <256, 7, 6, 9> kernel fit a CU (53 600 B of LDS each; the hardware's limit is 53 760, not the
-// 54 592 the occupancy API accepts: scripts/residency_check.py).
+// Build switches of this header -- every preprocessor conditional below tests one of these (DESIGN.md section 4 has the same table),
+// apart from five experiment switches whose folding changes the emitted code and which therefore stay for now, each where it is
+// used: SWD_POST_SORTED, SWD_POST_KGP (below), SWD_BIG_TBL, SWD_BIG_REC (in front of the OSD), SWD_QUAD_LAZY (osd0_quad).
+// Per translation unit (swd_kernels_k0 / k3 set them; the host reads SWD_TUNED_NT):
+//   SWD_OSDW_TUNED       the osd_window kernels of up to SWD_TUNED_NT threads keep the BP register caches packed (VnCache / CnCache,
+//                        P16) and -- variants with at most twelve groups of check positions -- are built for three waves per SIMD
+//                        (168 VGPRs); together with the LDS diet of the osd_window layout (decided-node bits, 48-bit live masks,
+//                        parity bytes, residual syndrome of the window's rows only; DIET below) three workgroups of the
+//                        <256, 7, 6, 9> kernel fit a CU (53 600 B of LDS each; the hardware's limit is 53 760, not the 54 592 the
+//                        occupancy API accepts: scripts/residency_check.py)
+//   SWD_TUNED_NT         largest workgroup of the tuned osd_window kernels (16-bit LDS offsets, LDS diet); the host uses the same bound
+//   SWD_POST_DEPTH2      the shortened graph's register cache of the [[288,12,18]] variants (swd_kernels_k0 / k3)
+// Development variant lists (swd_variants.h, scripts/devbuild.sh): SWD_HEADLINE_ONLY, SWD_BB288_ONLY, SWD_V7816_ONLY
+// Diagnostic builds (scripts/*_profile.py, *_timeline.py, gdg_debug.py, residency_check.py read what they record; SWD_OSDPROF and
+// SWD_GDG_CHECKS have no script of their own):
+//   SWD_BPPROF  SWD_OSDPROF  SWD_INITPROF  SWD_SHPROF  SWD_TSPROF  SWD_SELPROF  SWD_GDGPROF   cycle counters of a phase
+//   SWD_GDG_DEBUG  SWD_GDG_CHECKS   checksums / invariant checks of the guessing decoders
+//   SWD_RESIDENCY                   resident workgroups per launch
+// A/B builds of the structurizer flag (Makefile, STRUCT_FLAG; docs/history/DESIGN_rounds_1-5.md section 8):
+//   SWD_NO_SCALAR_ANY  SWD_NO_SCALAR_WMAX   block_any / the walk bound as vector values
 #ifndef SWD_OSDW_TUNED
 #define SWD_OSDW_TUNED 0
 #endif
-#ifndef SWD_TUNED_NT // largest workgroup of the tuned osd_window kernels (16-bit LDS offsets, LDS diet); the host uses the same bound
+#ifndef SWD_TUNED_NT
 #define SWD_TUNED_NT 256
 #endif
 #define SWD_P16(NT) (SWD_OSDW_TUNED && (NT) <= SWD_TUNED_NT)
-// experiment builds only (scripts/devbuild.sh -DSWD_POST_RENUM=1 + SWD_POST_RENUM=1 in the environment): the shortened graph's message
-// cells renumbered one column per live variable node in the tuned kernels too (the large-graph kernels always do it)
-#ifndef SWD_POST_RENUM
-#define SWD_POST_RENUM 0
-#endif
 #ifndef SWD_POST_DEPTH2
 #define SWD_POST_DEPTH2 0
-#endif
-#ifndef SWD_BP_HARD_DEFER
-#define SWD_BP_HARD_DEFER 1
-#endif
-#ifndef SWD_BP_PAR_INC
-#define SWD_BP_PAR_INC 1
-#endif
-// Round-5 experiments on the iteration loop's dependent LDS round trips (bp_run):
-//   SWD_BP_XARG_TRACK        1: the sign of a check's first-minimum position comes out of the sign shift registers (one compare-select
-//                               more per position) instead of a re-read of the message before the write phase
-//   SWD_BP_FLAG_MERGE_MAXVF  the convergence flags of block_any are read together with the first node's messages in caches of at
-//                            most this depth (0: never; deep caches pay for the twelve registers held across the exit test with spills)
-// Both measured on the headline (gpurun_out/r05f: 10.08 ms per launch without, 10.14 with the merge, 10.20 with the tracking, 10.17 with
-// both) and left off: the loops are bound by the CU's LDS pipeline, not by these round trips.
-#ifndef SWD_BP_XARG_TRACK
-#define SWD_BP_XARG_TRACK 0
-#endif
-#ifndef SWD_BP_FLAG_MERGE_MAXVF
-#define SWD_BP_FLAG_MERGE_MAXVF 0
 #endif
 // SWD_POST_SORTED (tuned osd_window kernels, round 5): the shortened graph's live nodes are listed by decreasing live degree, a node's
 // live edges are moved to the front of its cache, the message cells are renumbered one column per listed node (cell(k, i) = k x nlive + i)
@@ -65,29 +55,10 @@
 #ifndef SWD_POST_SORTED
 #define SWD_POST_SORTED 3
 #endif
-// SWD_FULL_SORTED (osd_window kernels, round 5): the full-graph phase serves its nodes in the graph's listed order (SwdGraphDev::vperm:
-// degree tiers of two, heaviest first) and its variable-node pass is tiered like the shortened graph's.
-// Measured on the headline (gpurun_out/r05l): bit-exact, 30 % fewer message positions in the full-graph variable-node pass (7296 of
-// 10368 per iteration of the [[144,12,12]] mid window) -- and 10.01 ms per launch against 9.80: the three bodies per cache row, the row
-// caps and the node numbers cost the check pass six more instructions per group of four.  Off.
-// (bit 1, the large-graph kernels, whose full-graph messages live in HBM: 40.1 against 33.9 us per iteration of the 936 x 8784 model --
-// the listed order scatters what were neighbouring 8-byte accesses; off too)
-#ifndef SWD_FULL_SORTED
-#define SWD_FULL_SORTED 0
-#endif
-// SWD_CN_HALF (round 5): the check pass of the SHORTENED graph walks its positions in groups of four whose second half is skipped when
-// no lane of the wave has a position there (cn_assign bounds a thread's walk by T = 3, 4, 6, 8, 12 ...: T = 6 costs 6 reads and writes
-// instead of 8).  Measured on the headline (gpurun_out/r05m): bit-exact and 10.45 ms per launch against 9.95 -- the scalar branch between
-// the two halves keeps the scheduler from issuing a group's four reads together; off.
-#ifndef SWD_CN_HALF
-#define SWD_CN_HALF 0
-#endif
-#ifndef SWD_TIER_STEP // positions per tier of the sorted form (tiers of one position -- six bodies of the pass per cache row, a second prefix sum for the order -- measured slower: 10.0 against 9.84 ms per headline launch)
-#define SWD_TIER_STEP(DM) 2
-#endif
 #ifndef SWD_POST_KGP // groups of four check positions in the shortened graph's register cache (0: as many as for the full graph)
 #define SWD_POST_KGP 0
 #endif
+constexpr int kTierStep = 2; // positions per tier of the sorted form (tiers of one position -- six bodies of the pass per cache row, a second prefix sum for the order -- measured slower: 10.0 against 9.84 ms per headline launch)
 
 struct SwdLdsLayout {
     int32_t off_livemask, off_par, off_lv, off_jptr, off_lslot, off_cnval, off_cndeg, off_cndeg0, off_vnval, off_hard,
@@ -399,11 +370,11 @@ __device__ __forceinline__ int swd_slot_zero(const SwdGraphDev &g) { return g.E 
 // whatever the caller does in between runs while the loads are in flight.
 template <int NT, int VF, int DM>
 struct VnRaw { uint32_t ev[VF][DM]; double llr[VF]; };
-template <int NT, int VF, int DM, bool SORTED = false> // SORTED: entry idx = the idx-th node of the graph's listed order (vperm)
+template <int NT, int VF, int DM>
 __device__ __forceinline__ void vn_cache_issue(const SwdGraphDev &g, const Lds &s, VnRaw<NT, VF, DM> &r) {
     const int n = g.n, D = g.D;
-    const uint32_t *et = SORTED ? g.vn_edge_s : g.vn_edge;
-    const double *lt = SORTED ? g.llr_s : g.llr;
+    const uint32_t *et = g.vn_edge;
+    const double *lt = g.llr;
 #pragma unroll
     for (int i = 0; i < VF; ++i) {
         const int idx = s.vtid + i * NT;
@@ -411,18 +382,6 @@ __device__ __forceinline__ void vn_cache_issue(const SwdGraphDev &g, const Lds &
         r.llr[i] = (n > 0) ? lt[v] : 0.0;
 #pragma unroll
         for (int k = 0; k < DM; ++k) r.ev[i][k] = (n > 0) ? et[max(min(k, D - 1), 0) * n + v] : SWD_PAD_EDGE;
-    }
-}
-// largest degree among the nodes this wave serves in cache row i (wave-uniform), from the raw edge words of the row
-template <int NT, int VF, int DM>
-__device__ __forceinline__ void vn_row_caps(const SwdGraphDev &g, const Lds &s, const uint32_t (&ev)[VF][DM], int (&kc)[VF]) {
-#pragma unroll
-    for (int i = 0; i < VF; ++i) {
-        const bool valid = s.vtid + i * NT < g.n;
-        int d = 0;
-#pragma unroll
-        for (int k = 0; k < DM; ++k) d += (valid && k < g.D && ev[i][k] != SWD_PAD_EDGE) ? 1 : 0;
-        kc[i] = __builtin_amdgcn_readfirstlane(wave_max(d));
     }
 }
 template <int NT, int VF, int DM, int SH, bool PB>
@@ -452,16 +411,14 @@ __device__ __forceinline__ void vn_cache_pack(const SwdGraphDev &g, const Lds &s
 }
 
 // ALLEDGES (with !FULL): the listed nodes with every edge of theirs, whatever the state of the checks.
-// SORTED (with FULL): entry idx = the idx-th node of the graph's listed order (vperm); kc (optional): the rows' degree caps (vn_row_caps)
 // JPACK: the halves of par[][] carry the edge's position inside its check's row in bits 10..15 (lane numbers need ten: bp_run<..., REC>)
-template <int NT, int VF, int DM, bool FULL, bool ALLEDGES = false, bool SORTED = false, bool JPACK = false, int SH, bool PB>
-__device__ __forceinline__ void vn_cache_load(const SwdGraphDev &g, Lds &s, int nlive, VnCacheP<VF, DM, SH, PB> &c, uint16_t *remap = nullptr, int (*kc)[VF] = nullptr) {
-    static_assert(!SORTED || FULL, "the listed order belongs to the full graph");
+template <int NT, int VF, int DM, bool FULL, bool ALLEDGES = false, bool JPACK = false, int SH, bool PB>
+__device__ __forceinline__ void vn_cache_load(const SwdGraphDev &g, Lds &s, int nlive, VnCacheP<VF, DM, SH, PB> &c, uint16_t *remap = nullptr) {
     const int n = g.n, cnt = FULL ? n : nlive;
     const uint32_t dead = (uint32_t)swd_slot_zero<NT>(g) << 3;
     const int D = g.D;
-    const uint32_t *et = SORTED ? g.vn_edge_s : g.vn_edge;
-    const double *lt = SORTED ? g.llr_s : g.llr;
+    const uint32_t *et = g.vn_edge;
+    const double *lt = g.llr;
     uint32_t ev[VF][DM];
 #pragma unroll
     for (int i = 0; i < VF; ++i) {
@@ -471,7 +428,6 @@ __device__ __forceinline__ void vn_cache_load(const SwdGraphDev &g, Lds &s, int 
 #pragma unroll
         for (int k = 0; k < DM; ++k) ev[i][k] = (n > 0) ? et[max(min(k, D - 1), 0) * n + v] : SWD_PAD_EDGE;
     }
-    if constexpr (SORTED) { if (kc) vn_row_caps<NT, VF, DM>(g, s, ev, *kc); }
 #pragma unroll
     for (int i = 0; i < VF; ++i) {
         const int idx = s.vtid + i * NT;
@@ -553,31 +509,22 @@ typedef uint32_t swd_u32x4r __attribute__((ext_vector_type(4)));
 // Hybrid store, explicit form: a FLAT access is worked through the texture addresser lane by lane whichever memory it ends in -- and the
 // scattered 8-byte accesses of the variable-node pass are bound by exactly that unit -- so the two memories get an instruction each
 // (ds_read / ds_write for the lanes in LDS, global_load / global_store for the rest, disjoint exec masks).
-#ifndef SWD_BIG_HYBRID_SPLIT
-#define SWD_BIG_HYBRID_SPLIT 1
-#endif
 #define SWD_AS3 __attribute__((address_space(3)))
 #define SWD_AS1 __attribute__((address_space(1)))
 template <bool HYB>
 __device__ __forceinline__ double swd_msg_ld(Lds &s, uint32_t ed) {
-    if constexpr (HYB && SWD_BIG_HYBRID_SPLIT) {
+    if constexpr (HYB) {
         double v;
         if (ed >= s.msg_lo) v = *(const SWD_AS3 double *)((SWD_AS3 char *)s.msg_alt + (ed - s.msg_lo));
         else v = *(const SWD_AS1 double *)((SWD_AS1 char *)s.msg + ed);
         return v;
-    } else if constexpr (HYB) {
-        const bool up = ed >= s.msg_lo;
-        return *(const double *)((up ? s.msg_alt : (char *)s.msg) + (up ? ed - s.msg_lo : ed));
     } else return *(const double *)((char *)s.msg + ed);
 }
 template <bool HYB>
 __device__ __forceinline__ void swd_msg_st(Lds &s, uint32_t ed, double v) {
-    if constexpr (HYB && SWD_BIG_HYBRID_SPLIT) {
+    if constexpr (HYB) {
         if (ed >= s.msg_lo) *(SWD_AS3 double *)((SWD_AS3 char *)s.msg_alt + (ed - s.msg_lo)) = v;
         else *(SWD_AS1 double *)((SWD_AS1 char *)s.msg + ed) = v;
-    } else if constexpr (HYB) {
-        const bool up = ed >= s.msg_lo;
-        *(double *)((up ? s.msg_alt : (char *)s.msg) + (up ? ed - s.msg_lo : ed)) = v;
     } else *(double *)((char *)s.msg + ed) = v;
 }
 template <bool HYB>
@@ -736,9 +683,6 @@ __device__ __forceinline__ void cn_assign(const SwdGraphDev &g, Lds &s, int *dhi
 #pragma unroll 1
             for (int ci = 0; ci < 8; ++ci) {
                 const int Tc = cand[ci];
-#ifdef SWD_CN_MIN_T // experiment: no walk bound below this (fewer, fuller waves in the check pass of the shortened graph)
-                if (Tc < SWD_CN_MIN_T) continue;
-#endif
                 int need = c0 * (d <= Tc ? 1 : (d <= 2 * Tc ? 2 : 4));
                 int q = (d > 2 * Tc) ? c0 : 0, pr = (d > Tc && d <= 2 * Tc) ? c0 : 0;
 #pragma unroll
@@ -821,12 +765,12 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
     swd_msg_st<HYB>(s, (uint32_t)zeroslot << 3, 0.0);
     char *const parb = (char *)s.par;
     // (shortened graph) the node a list entry names does not change during the run: read once, not once per iteration
-    // (full graph in tiers: the listed order of the graph, SwdGraphDev::vperm)
-    constexpr bool kNodeList = !FULL || TIER;
+    static_assert(!TIER || !FULL, "the tiered pass belongs to the shortened graph");
+    constexpr bool kNodeList = !FULL;
     [[maybe_unused]] int vnode[kNodeList ? VF : 1];
     if constexpr (kNodeList) {
 #pragma unroll
-        for (int i = 0; i < VF; ++i) { const int idx = s.vtid + i * NT; vnode[i] = (idx < vcnt) ? (FULL ? (int)g.vperm[idx] : (int)s.lv[idx]) : n; }
+        for (int i = 0; i < VF; ++i) { const int idx = s.vtid + i * NT; vnode[i] = (idx < vcnt) ? (int)s.lv[idx] : n; }
     }
 #ifdef SWD_BPPROF
     long long tc0, tc1, tc2, tc3;
@@ -853,9 +797,9 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
     };
     // Round 6: the hard decisions of a variable-node pass stay in a register (one bit per cache row) and go to LDS once, when the run
     // ends -- nothing reads s.hard while the iterations run (convergence is tested through the parity words), and the byte store per row
-    // and iteration was one LDS instruction in twenty-five of the loop (SWD_BP_HARD_DEFER=0: the store per row of rounds 1-5)
-    constexpr bool kHardDefer = SWD_BP_HARD_DEFER != 0 && VF <= 32 && !TBL;
-    constexpr bool kParInc = kHardDefer && SWD_BP_PAR_INC != 0;
+    // and iteration was one LDS instruction in twenty-five of the loop (rounds 1-5: a store per row)
+    constexpr bool kHardDefer = VF <= 32 && !TBL;
+    constexpr bool kParInc = kHardDefer;
     [[maybe_unused]] uint32_t hdbits = 0, hdprev = 0;
     [[maybe_unused]] auto hard_flush = [&]() {
         if constexpr (kHardDefer) {
@@ -894,41 +838,30 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
             // is slower with iterative-ilp, which overlaps the reads of the next group by itself.)
             double min1 = 1e308, min2 = 1e308;
             uint32_t argslot = (uint32_t)farslot << 3; // byte offset of the first position holding the minimum
-            uint32_t argk = 0;                          // ... and its position number: its sign comes out of the sign registers below
-                                                        // (round 4 re-read the message: one more dependent LDS round trip per iteration)
+            [[maybe_unused]] uint32_t argk = 0;         // ... and its position number (REC)
             uint32_t neg[NR];
 #pragma unroll
             for (int r = 0; r < NR; ++r) neg[r] = 0;
-            constexpr bool kHalf = SWD_CN_HALF != 0 && !FULL;
 #pragma unroll
             for (int gq = 0; gq < KG; ++gq) {
                 if (gq * 4 < wmax) { // wave-uniform
                     double xs[4];
                     uint32_t ad[4];
                     cn.group(gq, ad);
-                    const bool hi = !kHalf || gq * 4 + 2 < wmax; // (wave-uniform) does any lane walk the group's second half?
 #pragma unroll
-                    for (int u = 0; u < 2; ++u) xs[u] = swd_msg_ld<HYB>(s, ad[u]);
-                    if (hi) {
-#pragma unroll
-                        for (int u = 2; u < 4; ++u) xs[u] = swd_msg_ld<HYB>(s, ad[u]);
-                    }
+                    for (int u = 0; u < 4; ++u) xs[u] = swd_msg_ld<HYB>(s, ad[u]);
                     auto one = [&](auto u_tag) {
                         constexpr int u = decltype(u_tag)::value;
                         const int k = gq * 4 + u;
                         const double ax = vminabs64(xs[u], 50.0);
-                        if constexpr (SWD_BP_XARG_TRACK || REC) argk = (ax < min1) ? (uint32_t)k : argk;
+                        if constexpr (REC) argk = (ax < min1) ? (uint32_t)k : argk;
                         argslot = (ax < min1) ? ad[u] : argslot; // (as sign-of-difference mask + v_bfi instead of v_cmp + v_cndmask: 10.1 against 10.0 ms, round 4)
                         min2 = vmin64(min2, vmax64(min1, ax));
                         min1 = vmin64(min1, ax);
                         neg_shift_in(neg[k >> 5], xs[u]);
                     };
                     one(std::integral_constant<int, 0>{}); one(std::integral_constant<int, 1>{});
-                    if (hi) { one(std::integral_constant<int, 2>{}); one(std::integral_constant<int, 3>{}); }
-                    else {
-#pragma unroll
-                        for (int u = 2; u < 4; ++u) neg[(gq * 4 + u) >> 5] <<= 1;
-                    }
+                    one(std::integral_constant<int, 2>{}); one(std::integral_constant<int, 3>{});
                 } else {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) neg[(gq * 4 + u) >> 5] <<= 1; // keep position k at bit (31 - k % 32) ...
@@ -939,15 +872,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
             int npar = (cn.sub == 0) ? cv : 0;
 #pragma unroll
             for (int r = 0; r < NR; ++r) npar += __popc(neg[r]);
-            // "is negative" bit of the first-minimum position (position k sits at bit 31 - k % 32 of neg[k / 32]; no live position:
-            // position 0 = the far slot, positive)
-            uint32_t argneg = 0;
-            if constexpr (SWD_BP_XARG_TRACK) {
-                uint32_t wsel = neg[0];
-#pragma unroll
-                for (int r = 1; r < NR; ++r) wsel = ((argk >> 5) == (uint32_t)r) ? neg[r] : wsel;
-                argneg = (wsel << (argk & 31u)) >> 31;
-            }
+            uint32_t argneg = 0; // "is negative" bit of the first-minimum position
             if constexpr (!FULL || SF) {
                 // merge the partial results of the check's threads (butterfly inside the quad).  On a tie
                 // of the minima the second minimum equals the first, so which side's position is kept
@@ -955,10 +880,8 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
                 if (gmax >= 2) { // (scalar branch)
                     const double o1 = quad_xor<1>(min1), o2 = quad_xor<1>(min2);
                     const uint32_t oa = (uint32_t)quad_xor<1>((int)argslot); const int op = quad_xor<1>(npar);
-                    const uint32_t on = (uint32_t)quad_xor<1>((int)argneg);
                     if (cn.grp >= 2) {
                         npar += op;
-                        argneg = (o1 < min1) ? on : argneg;
                         argslot = (o1 < min1) ? oa : argslot;
                         min2 = vmin64(vmax64(min1, o1), vmin64(min2, o2));
                         min1 = vmin64(min1, o1);
@@ -967,10 +890,8 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
                 if (gmax == 4) {
                     const double o1 = quad_xor<2>(min1), o2 = quad_xor<2>(min2);
                     const uint32_t oa = (uint32_t)quad_xor<2>((int)argslot); const int op = quad_xor<2>(npar);
-                    const uint32_t on = (uint32_t)quad_xor<2>((int)argneg);
                     if (cn.grp == 4) {
                         npar += op;
-                        argneg = (o1 < min1) ? on : argneg;
                         argslot = (o1 < min1) ? oa : argslot;
                         min2 = vmin64(vmax64(min1, o1), vmin64(min2, o2));
                         min1 = vmin64(min1, o1);
@@ -979,7 +900,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
             }
             const uint32_t flip = (npar & 1) ? 0xFFFFFFFFu : 0u;
             // the first position holding the minimum gets the second minimum (ties: both equal); its own sign: argneg
-            if constexpr (!SWD_BP_XARG_TRACK && !REC) argneg = (swd_msg_ld<HYB>(s, argslot) <= 0) ? 1u : 0u; // (re-read before the slots are overwritten)
+            if constexpr (!REC) argneg = (swd_msg_ld<HYB>(s, argslot) <= 0) ? 1u : 0u; // (re-read before the slots are overwritten)
             if (cn.live == 1) min1 = min2 = 1e308; // minimum over no other edge (the far slot may have come first)
             const double p1 = min1 * alpha, p2 = min2 * alpha;
             const uint32_t p1lo = (uint32_t)__double_as_longlong(p1), p1hi = (uint32_t)(__double_as_longlong(p1) >> 32);
@@ -1007,7 +928,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
                         swd_msg_st<HYB>(s, ad[u], __longlong_as_double((long long)(((uint64_t)hi << 32) | p1lo)));
                     };
                     put(std::integral_constant<int, 0>{}); put(std::integral_constant<int, 1>{});
-                    if (!kHalf || gq * 4 + 2 < wmax) { put(std::integral_constant<int, 2>{}); put(std::integral_constant<int, 3>{}); }
+                    put(std::integral_constant<int, 2>{}); put(std::integral_constant<int, 3>{});
                 }
             }
             {
@@ -1019,9 +940,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
             } // (message form)
         }
         BPT(tc1);
-        // block_any, cut in two: the per-wave flags go out before the barrier; behind it they are read TOGETHER with the first
-        // node's messages -- one LDS round trip instead of two in front of the variable-node pass (a converged run has loaded
-        // those messages for nothing)
+        // block_any, inlined: the per-wave flags go out before the barrier and are read behind it
         int anyr = 0;
         {
             constexpr int NW = NT / 64;
@@ -1035,16 +954,6 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
             __syncthreads();
 #pragma unroll
             for (int w = 0; w < NW; ++w) anyr |= s.flags[fp_ * 16 + w];
-        }
-        constexpr bool kFlagMerge = VF <= SWD_BP_FLAG_MERGE_MAXVF;
-        [[maybe_unused]] double cc0[DM];
-        [[maybe_unused]] uint32_t ad0[DM];
-        if (kFlagMerge && nch > 0) { // (wave-uniform)
-            c.get_ed(0, ad0);
-#pragma unroll
-            for (int k = 0; k < DM; ++k) cc0[k] = swd_msg_ld<HYB>(s, ad0[k]);
-#pragma unroll
-            for (int k = 0; k < DM; ++k) asm volatile("" : "+v"(cc0[k])); // (loaded here, in front of the exit test)
         }
 #ifdef SWD_NO_SCALAR_ANY
         const bool any = anyr != 0;
@@ -1067,7 +976,6 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
         const bool record = record_all || it >= max_iter - 4;
         // VN pass (osd_window.pyx:442-471).  (Reading the next VN's messages before this one's are written
         // was tried and is slower.)
-        static_assert(!(TIER && kFlagMerge), "the tiered pass reads its own messages");
         // one node of the pass over its first KD positions (KD = DM unless TIER)
         auto vn_one = [&](auto kd_tag, auto i_tag) {
                 constexpr int KD = decltype(kd_tag)::value, i = decltype(i_tag)::value;
@@ -1078,10 +986,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
                 if constexpr (SPARSE) valid = v < n;
                 double cc[KD], pre[KD];
                 uint32_t ad[DM];
-                if (kFlagMerge && i == 0) {
-#pragma unroll
-                    for (int k = 0; k < KD; ++k) { ad[k] = ad0[k]; cc[k] = cc0[k]; }
-                } else if constexpr (TBL) {
+                if constexpr (TBL) {
                     // (the messages of row i + 1 asked for here as well, one row ahead: 41.6 -> 51.0 us per iteration -- the pass is bound by the
                     //  texture addresser's rate for scattered accesses, not by their latency)
                     if (i + 2 < nch) tb_load(i + 2, tbe[(i + 2) % 3], tbl[(i + 2) % 3]);      // (uniform) edge words, two rows ahead
@@ -1131,22 +1036,6 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
                     suf = suf + cc[k];
                 }
                 swd_msg_st<HYB>(s, (uint32_t)zeroslot << 3, 0.0); // re-arm
-#ifdef SWD_EXP_EXTRA_LDS // experiment: N more LDS reads per node and iteration (is the LDS pipeline what the iterations queue for?)
-                {
-                    double dx_[SWD_EXP_EXTRA_LDS];
-#pragma unroll
-                    for (int e_ = 0; e_ < SWD_EXP_EXTRA_LDS; ++e_) dx_[e_] = swd_msg_ld<HYB>(s, (uint32_t)farslot << 3);
-#pragma unroll
-                    for (int e_ = 0; e_ < SWD_EXP_EXTRA_LDS; ++e_) asm volatile("" :: "v"(dx_[e_]));
-                }
-#endif
-#ifdef SWD_EXP_EXTRA_VALU // experiment: N more vector instructions per node and iteration
-                {
-                    uint32_t vx_ = (uint32_t)v;
-#pragma unroll
-                    for (int e_ = 0; e_ < SWD_EXP_EXTRA_VALU; ++e_) asm volatile("v_add_u32 %0, %0, %0" : "+v"(vx_));
-                }
-#endif
                 if constexpr (TBL) {
                     if (hd) {
 #pragma unroll
@@ -1179,14 +1068,14 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
             if constexpr (KD >= DM) vn_one(std::integral_constant<int, DM>{}, i_tag);
             else {
                 if (kcv <= KD) vn_one(kd_tag, i_tag);
-                else self(self, std::integral_constant<int, KD + SWD_TIER_STEP(DM)>{}, i_tag, kcv);
+                else self(self, std::integral_constant<int, KD + kTierStep>{}, i_tag, kcv);
             }
         };
         auto vn_rows = [&](auto self, auto i_tag) -> void {
             constexpr int i = decltype(i_tag)::value;
             if constexpr (i < VF) {
                 if (i < nch) { // wave-uniform
-                    if constexpr (TIER) vn_tier(vn_tier, std::integral_constant<int, SWD_TIER_STEP(DM)>{}, i_tag, kcap[i]);
+                    if constexpr (TIER) vn_tier(vn_tier, std::integral_constant<int, kTierStep>{}, i_tag, kcap[i]);
                     else vn_one(std::integral_constant<int, DM>{}, i_tag);
                 }
                 self(self, std::integral_constant<int, i + 1>{});
@@ -1630,12 +1519,6 @@ __device__ __forceinline__ uint64_t wave_read64(uint64_t v, int srclane) { // sr
 // instructions per pivot -- overlaps the 9 x 40 of the update.  (osd0_block below: 3.4k cycles per pivot, wave 0
 // evaluating against T in LDS while 15 waves wait, then all threads rewriting T in LDS, two barriers per pivot.)
 #define SWD_LDS_AS __attribute__((address_space(3)))
-#ifndef SWD_OSD_QUAD
-#define SWD_OSD_QUAD 1 // m <= 256 on at least four waves: the elimination with the transform matrix on the other waves (osd0_quad)
-#endif
-#ifndef SWD_WIDE_EVAL_DS
-#define SWD_WIDE_EVAL_DS 0
-#endif
 #ifndef SWD_BIG_TBL
 #define SWD_BIG_TBL 0 // experiment (round 5, bit-exact): large-graph kernels, full-graph phase: the variable-node pass reads the graph's tables (one row
                       // ahead) instead of a register cache that does not fit: set-up 34 -> 24 us, 40.0 -> 41.6 us per iteration, 160 -> 163 k decodes/s: neutral, off
@@ -1646,23 +1529,7 @@ __device__ __forceinline__ uint64_t wave_read64(uint64_t v, int srclane) { // sr
                       // own instruction stream and its register spills, not by that traffic), and the shortened graph's iterations of the same
                       // kernel 3.38 -> 3.78 us: 160 -> 156 k decodes/s, off
 #endif
-#ifndef SWD_BIG_HYBRID
-#define SWD_BIG_HYBRID 1 // large-graph kernels: the top of the full graph's message array in the LDS region that idles during that phase
-#endif
-#ifndef SWD_OSD_WIDE
-#define SWD_OSD_WIDE 1 // large-graph kernels: the column-form elimination on fifteen column waves (osd0_colsw) instead of osd0_block
-#endif
-#ifndef SWD_SPEC_LOAD
-#define SWD_SPEC_LOAD 0 // experiment (round 5): the tuned osd_window kernels ask for the next unit's variable-node cache before they draw the
-                        // ticket -- the loads are in flight during the three round trips of ticket, counter and state record: 9.37 -> 9.44 ms per
-                        // launch, no gain (two other workgroups on the CU already run during a workgroup's waits)
-#endif
-#ifndef SWD_SERIAL_PRIO
-#define SWD_SERIAL_PRIO 0 // s_setprio of a wave the rest of its workgroup waits for (single-wave eliminations, the column form's resolver)
-#endif
-#ifndef SWD_OSD_RING
-#define SWD_OSD_RING 128 // row operations the column-form elimination can publish per round (ring entries in the exchange region)
-#endif
+#define SWD_OSD_RING 128 // row operations the column-form elimination can publish per round (ring entries in the exchange region; make_layout sizes it)
 // bit `rbit` of word `rw` (both wave-uniform) of a register-resident bit vector: a scalar branch per word instead of a select chain
 template <int WMC>
 __device__ __forceinline__ uint32_t osd_vec_bit(const uint64_t (&v)[WMC], int rw, int rbit) {
@@ -1688,211 +1555,8 @@ __device__ __forceinline__ void osd_vec_setbit(uint64_t (&v)[WMC], int rw, int r
     }
 }
 
-#ifdef SWD_OSD_COLS_V1 // round 2-4 form (one batch of 64 sorted columns per pair of barriers), kept for A/B builds
-template <int NT, int DM, int WMC>
-__device__ __forceinline__ int osd0_cols(const SwdGraphDev &g, Lds &s, const uint16_t *order, uint64_t *Tw, uint64_t *Sbuf,
-                                         uint16_t *piv_col, uint16_t *piv_row, const uint8_t *synd_b, const uint16_t *crows, int nst,
-                                         int *npiv_out, char *slotmem) {
-    constexpr int NBC = 64;
-    static_assert(NT >= 768 && WMC <= 16, "wave 0 resolves, nine of the waves 1..11 hold the columns");
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int m = g.m, n = g.n, wm = g.wm, rank = g.rank;
-    constexpr int ES = (WMC + 2) & ~1; // words per ring entry: S, then pivot row | column within the batch << 16 (16-byte multiples)
-    SWD_LDS_AS uint64_t *ringS = (SWD_LDS_AS uint64_t *)slotmem;                  // [NBC][ES] the batch's row operations
-    SWD_LDS_AS uint64_t *Pl = ringS + NBC * ES;                                   // [WMC] pivoted rows
-    SWD_LDS_AS int *ctl = (SWD_LDS_AS int *)(Pl + WMC + 1); // 0: published, 1: batch closed, 2: elimination finished, 3: pivots so far, 4: row additions
-    volatile SWD_LDS_AS int *vctl = ctl;
-    const bool colwave = (wave & 3) != 0 && wave < 12;
-    const int jc = colwave ? (wave - 1 - (wave >> 2)) * 64 + lane : m; // the column of T this thread keeps
-    uint64_t col[WMC];
-#pragma unroll
-    for (int x = 0; x < WMC; ++x) col[x] = (jc < m && x == (jc >> 6)) ? (1ull << (jc & 63)) : 0ull;
-    if (tid == 0) { ctl[0] = 0; ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; ctl[4] = 0; }
-    if (tid < WMC) Pl[tid] = 0ull;
-    __syncthreads();
-    // resolver state: lane x < WMC keeps word x of the pivoted-row mask and counts the unpivoted ones of the pivot columns there
-    // (a single wave issues one instruction of any kind per four cycles: the pivot search runs word-per-lane, not as scalar code)
-    uint64_t Pmine = 0;
-    int racc = 0;
-    int npiv = 0, p = 0;
-#ifdef SWD_OSDPROF // diagnostic build: cycles of the resolver (evaluation, pivots), of a column wave (applying, waiting) and between the barriers
-    long long q_eval = 0, q_res = 0, q_app = 0, q_wait = 0, q_sync = 0, q0_;
-    int q_batches = 0;
-#endif
-    for (;;) {
-        const int npiv0 = npiv, p0 = p;
-#ifdef SWD_OSDPROF
-        q0_ = clock64(); ++q_batches;
-#endif
-        if (wave == 0) {
-            const int pc = p + lane;
-            const bool cval = pc < n;
-            int rows[DM];
-            if (p + NBC <= nst) { // uniform: whole batch inside the staged prefix
-#pragma unroll
-                for (int kk = 0; kk < DM; ++kk) rows[kk] = crows[pc * DM + kk];
-            } else {
-                const int v = cval ? (int)order[pc] : 0;
-                const int deg = cval ? (int)g.col_deg[v] : 0;
-#pragma unroll
-                for (int kk = 0; kk < DM; ++kk) rows[kk] = (kk < deg) ? (int)g.vn_row[kk * n + v] : 0xFFFF;
-            }
-            uint64_t red[WMC];
-#pragma unroll
-            for (int x = 0; x < WMC; ++x) {
-                red[x] = 0ull;
-                if (x < wm) { // uniform
-#pragma unroll
-                    for (int kk = 0; kk < DM; ++kk) red[x] ^= (rows[kk] == 0xFFFF) ? 0ull : Tw[osd_tidx(rows[kk] == 0xFFFF ? 0 : rows[kk], x, m)];
-                }
-            }
-            bool alive = cval;
-            int nb = 0; // pivots of this batch
-#ifdef SWD_OSDPROF
-            q_eval += clock64() - q0_; q0_ = clock64();
-#endif
-            uint64_t pb[WMC]; // the pivoted-row mask, every word in every lane (read back after each pivot, ahead of its use)
-#pragma unroll
-            for (int x = 0; x < WMC; ++x) pb[x] = Pl[x];
-            while (npiv < rank) {
-                uint32_t nz = 0;
-#pragma unroll
-                for (int x = 0; x < WMC; ++x) {
-                    nz |= (uint32_t)red[x] & ~(uint32_t)pb[x];
-                    nz |= (uint32_t)(red[x] >> 32) & ~(uint32_t)(pb[x] >> 32);
-                }
-                const unsigned long long bal = __ballot(alive && nz != 0u);
-                if (bal == 0ull) break; // every remaining column of the batch is dependent
-                const int cs = __ffsll((long long)bal) - 1;
-                uint32_t lz = 0;
-                asm volatile("" : "+v"(lz)); // the lane number, recomputed here: kept across the loop it is spilled and reloaded per pivot
-                const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, lz));
-                SWD_LDS_AS uint64_t *ent = ringS + nb * ES;
-                if (ln == cs) { // the pivot column's lane publishes its reduced vector (LDS operations of a wave execute in order)
-#pragma unroll
-                    for (int x = 0; x < WMC; ++x) ent[x] = red[x];
-                }
-                asm volatile("" ::: "memory");
-                // one round trip: the vector a word per lane (pivot search) and every word in every lane (the update below)
-                const uint64_t wv = ent[ln < WMC ? ln : 0];
-                uint64_t S[WMC];
-#pragma unroll
-                for (int x = 0; x < WMC; ++x) S[x] = ent[x];
-                const uint64_t c = (ln < WMC) ? (wv & ~Pmine) : 0ull; // its ones in unpivoted rows
-                const unsigned long long balc = __ballot(c != 0ull);
-                const int fx = __ffsll((long long)balc) - 1;
-                const int bit = __builtin_amdgcn_readlane(__ffsll((long long)c) - 1, fx);
-                racc += __popcll(c); // row additions the reference's LU would apply: unpivoted rows with a one in this column (the pivot itself is taken off at the end)
-                if (ln == fx) {
-                    __hip_atomic_fetch_and(&ent[fx], ~(1ull << bit), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_or(&Pl[fx], 1ull << bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    Pmine |= 1ull << bit;
-                }
-                if (ln == 0) ent[WMC] = (uint64_t)(uint32_t)((fx * 64 + bit) | (cs << 16));
-                asm volatile("" ::: "memory"); // a wave's LDS operations execute in order: the count follows the entry
-                if (ln == 0) ctl[0] = nb + 1;
-#pragma unroll
-                for (int x = 0; x < WMC; ++x) pb[x] = Pl[x]; // for the next pivot
-                // the batch's later columns under the same row operation: y ^= S if y[r]; S here still has bit r, which y keeps
-                const uint32_t ybit = osd_vec_bit<WMC>(red, fx, bit);
-                if (ln <= cs) alive = false;
-                else if (alive && ybit) {
-#pragma unroll
-                    for (int x = 0; x < WMC; ++x) red[x] ^= S[x];
-                    osd_vec_setbit<WMC>(red, fx, bit);
-                }
-                ++npiv; ++nb;
-            }
-            p += NBC;
-#ifdef SWD_OSDPROF
-            q_res += clock64() - q0_; q0_ = clock64();
-#endif
-            int rsum = racc;
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) rsum += __shfl_xor(rsum, d, 64);
-            if (lane == 0) {
-                ctl[3] = npiv; ctl[4] = rsum - npiv;
-                ctl[2] = (p < n && npiv < rank) ? 0 : 1;
-            }
-            asm volatile("" ::: "memory");
-            if (lane == 0) ctl[1] = 1;
-        } else if (colwave) {
-            int done_ops = 0;
-            for (;;) {
-                const int closed = vctl[1]; // read before the count: a closed batch's count is final
-                const int avail = vctl[0];
-#ifdef SWD_OSDPROF
-                q_wait += clock64() - q0_; q0_ = clock64();
-#endif
-                while (done_ops < avail) {
-                    SWD_LDS_AS const uint64_t *ent = ringS + done_ops * ES;
-                    uint64_t S[WMC];
-#pragma unroll
-                    for (int x = 0; x < WMC; ++x) S[x] = ent[x];
-                    const int r = __builtin_amdgcn_readfirstlane((int)(uint32_t)ent[WMC]) & 0xFFFF;
-                    const int rw = r >> 6, rbit = r & 63;
-                    if (osd_vec_bit<WMC>(col, rw, rbit)) {
-#pragma unroll
-                        for (int x = 0; x < WMC; ++x) col[x] ^= S[x];
-                    }
-                    ++done_ops;
-                }
-#ifdef SWD_OSDPROF
-                q_app += clock64() - q0_; q0_ = clock64();
-#endif
-                if (closed) break;
-                __builtin_amdgcn_s_sleep(1);
-            }
-        }
-        __syncthreads(); // the batch's row operations are in every column; ctl[] is final
-        const int fin = ctl[2];
-        npiv = ctl[3];
-        p = p0 + NBC;
-        if (tid == 0) { ctl[0] = 0; ctl[1] = 0; } // nobody reads these two between the barriers
-        if (tid >= 64 && tid - 64 < npiv - npiv0) { // the batch's pivots (another wave than the resolver looks the columns up)
-            const int e = (int)(uint32_t)ringS[(tid - 64) * ES + WMC];
-            piv_col[npiv0 + tid - 64] = order[p0 + (e >> 16)];
-            piv_row[npiv0 + tid - 64] = (uint16_t)(e & 0xFFFF);
-        }
-        if (jc < m) {
-#pragma unroll
-            for (int x = 0; x < WMC; ++x)
-                if (x < wm) Tw[osd_tidx(jc, x, m)] = col[x]; // the mirror (after the last batch: what the higher-order sweep reads)
-        }
-        if (tid < wm) Sbuf[tid] = 0ull; // (used after the last batch)
-        __syncthreads();
-#ifdef SWD_OSDPROF
-        q_sync += clock64() - q0_;
-        if (fin && (tid == 0 || tid == 64) && (blockIdx.x & 63) == 0)
-            printf("osdprof cols thread %d: batches %d pivots %d | resolver: evaluation %lld resolve %lld | column wave: apply %lld wait %lld | rest of the batch %lld cycles\n",
-                   tid, q_batches, npiv, q_eval, q_res, q_app, q_wait, q_sync);
-#endif
-        if (fin) break;
-    }
-    // y = T * s (s in original row order)
-    const bool on = jc < m && synd_b[jc < m ? jc : 0] != 0;
-    if (colwave) {
-#pragma unroll
-        for (int x = 0; x < WMC; ++x) {
-            if (x < wm) { // uniform
-                uint64_t acc = on ? col[x] : 0ull;
-#pragma unroll
-                for (int d = 32; d > 0; d >>= 1) acc ^= __shfl_xor(acc, d, 64);
-                if (lane == 0 && acc) atomicXor((unsigned long long *)&Sbuf[x], (unsigned long long)acc);
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < npiv; i += NT) {
-        const int r = piv_row[i];
-        s.hard[piv_col[i]] = (uint8_t)((Sbuf[r >> 6] >> (r & 63)) & 1ull);
-    }
-    *npiv_out = npiv;
-    return ctl[4];
-}
-
-#else
-// Round 5: ROUNDS of up to four batches per pair of barriers.  What the instrumented build showed for the form above on the [[288,12,18]]
+// Round 5: ROUNDS of up to four batches per pair of barriers.  What the instrumented build showed for the round 2-4 form (one batch of
+// 64 sorted columns per pair of barriers; scripts/experiments/osd_cols_v1_and_noinline.patch) on the [[288,12,18]]
 // windows: of ~1.0 M cycles per elimination the resolver spends ~0.4 M evaluating its batches (54 LDS reads per lane whose
 // latencies the 128-VGPR allocation serialises) and another share in 47 x 2 workgroup barriers -- the scan walks ~3000 sorted columns
 // for its 576 pivots, and the ~2400 columns behind the first ~600 hold two or three pivots per batch.  Now three HELPER waves
@@ -1966,9 +1630,6 @@ __device__ __forceinline__ int osd0_cols(const SwdGraphDev &g, Lds &s, const uin
         q0_ = clock64(); ++q_rounds;
 #endif
         if (wave == 0) {
-#if SWD_SERIAL_PRIO
-            __builtin_amdgcn_s_setprio(SWD_SERIAL_PRIO);
-#endif
             int used = 0, nbatch = 0; // operations published this round, batches begun
             bool fin = false;
             for (;;) {
@@ -2056,9 +1717,6 @@ __device__ __forceinline__ int osd0_cols(const SwdGraphDev &g, Lds &s, const uin
             }
             asm volatile("" ::: "memory");
             if (lane == 0) ctl[1] = 1;
-#if SWD_SERIAL_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
         } else if (colwave) {
             int done_ops = 0;
             for (;;) {
@@ -2168,7 +1826,6 @@ __device__ __forceinline__ int osd0_cols(const SwdGraphDev &g, Lds &s, const uin
     *npiv_out = npiv;
     return ctl[4];
 }
-#endif // SWD_OSD_COLS_V1
 
 // Large-graph kernels (scratch region in HBM), 256 < m <= 960: the column form on ALL fifteen waves behind the resolver -- wave w holds
 // columns 64 (w - 1) .. 64 w - 1 of the transform matrix, one per lane, fifteen words each.  One batch of 64 sorted columns per pair
@@ -2233,17 +1890,7 @@ __device__ __forceinline__ int osd0_colsw(const SwdGraphDev &g, Lds &s, const ui
             }
             uint64_t (&red)[WMC] = col; // (the resolver keeps no column of T: its batch vectors take those registers -- a second array of
                                         //  thirty does not fit this kernel's 128 and sent both to scratch)
-            if (SWD_WIDE_EVAL_DS && lds_mirror) { // (uniform) ds_read instead of flat loads
-                SWD_LDS_AS const uint64_t *TwL = (SWD_LDS_AS const uint64_t *)Tw;
-#pragma unroll
-                for (int x = 0; x < WMC; ++x) {
-                    red[x] = 0ull;
-                    if (x < wm) { // uniform
-#pragma unroll
-                        for (int kk = 0; kk < DM; ++kk) red[x] ^= (rows[kk] == 0xFFFF) ? 0ull : TwL[osd_tidx(rows[kk] == 0xFFFF ? 0 : rows[kk], x, m)];
-                    }
-                }
-            } else {
+            {
 #pragma unroll
                 for (int x = 0; x < WMC; ++x) {
                     red[x] = 0ull;
@@ -2450,9 +2097,6 @@ __device__ __forceinline__ int osd0_wave_reg(const SwdGraphDev &g, Lds &s, const
         for (int x = 0; x < 4; ++x) t[q][x] = (x == q && q * 64 + lane < m) ? (1ull << lane) : 0ull;
     uint64_t Pw = 0;                    // word w of the pivoted-row mask (replicated per column group)
     int npiv = 0, rowadds = 0, p = 0;
-#if SWD_SERIAL_PRIO
-    __builtin_amdgcn_s_setprio(SWD_SERIAL_PRIO); // the workgroup's other waves wait for this one: ahead of the other workgroups' waves on its SIMD
-#endif
 #ifdef SWD_BPPROF
     long long acc_scan = 0, acc_upd = 0, acc_f1 = 0; int nscan = 0;
 #endif
@@ -2532,9 +2176,6 @@ __device__ __forceinline__ int osd0_wave_reg(const SwdGraphDev &g, Lds &s, const
     }
 #ifdef SWD_BPPROF
     if (lane == 0) { s.scal[20] = nscan; s.scal[21] = (int)(acc_scan >> 4); s.scal[22] = (int)(acc_upd >> 4); s.scal[23] = (int)(acc_f1 >> 4); }
-#endif
-#if SWD_SERIAL_PRIO
-    __builtin_amdgcn_s_setprio(0);
 #endif
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) rowadds += __shfl_xor(rowadds, d, 64);
@@ -3051,13 +2692,8 @@ __device__ __forceinline__ double osd_sweep(const SwdGraphDev &g, const SwdLdsLa
 // solution; the return value is its path metric (sum of g.llr over the solution in column order).
 // QUAD: the scratch region is LDS (osd0_quad addresses its ring there)
 // WIDE: large-graph kernel (osd0_colsw when the layout has its LDS block)
-#ifdef SWD_OSD_NOINLINE // experiment (round 6): the OSD of the shots that need one as a function of its own
-#define SWD_OSD_FN __device__ __attribute__((noinline))
-#else
-#define SWD_OSD_FN __device__ __forceinline__
-#endif
 template <int NT, int DM, bool COLFORM = false, bool QUAD = COLFORM, bool WIDE = false> // COLFORM: the caller's kernel can afford osd0_cols (osd_window kernels of 1024 threads)
-SWD_OSD_FN double osd_run(const SwdGraphDev &g, const SwdLdsLayout &L, const SwdDecodeParams &P, Lds &s,
+__device__ __forceinline__ double osd_run(const SwdGraphDev &g, const SwdLdsLayout &L, const SwdDecodeParams &P, Lds &s,
                                           const uint8_t *synd, uint8_t *osd0_b, int &rowadds, long long &t_sorted,
                                           long long &t_elim, bool presorted = false) {
     const int tid = threadIdx.x, m = g.m, n = g.n;
@@ -3090,7 +2726,7 @@ SWD_OSD_FN double osd_run(const SwdGraphDev &g, const SwdLdsLayout &L, const Swd
         for (int k = 0; k < DM; ++k) crows[p * DM + k] = (k < deg) ? g.vn_row[k * n + v] : (uint16_t)0xFFFF;
     }
     __syncthreads();
-    constexpr bool kQuad = QUAD && NT >= 256 && SWD_OSD_QUAD;
+    constexpr bool kQuad = QUAD && NT >= 256;
     bool quad = false;
     if constexpr (kQuad) quad = g.wm <= 4 && L.off_oring >= 0;
     if (quad) {
@@ -3111,7 +2747,7 @@ SWD_OSD_FN double osd_run(const SwdGraphDev &g, const SwdLdsLayout &L, const Swd
         if constexpr (kColForm) {
             if (cols) { ra = osd0_cols<NT, DM, 9>(g, s, idx, Tc, Sbuf, piv_col, piv_row, synd, crows, nst, &npiv, s.scratch + L.off_oslot); done = true; }
         }
-        if constexpr (WIDE && NT == 1024 && DM <= 8 && SWD_OSD_WIDE) {
+        if constexpr (WIDE && NT == 1024 && DM <= 8) {
             if (g.wm <= 15 && L.off_owide >= 0) {
                 ra = osd0_colsw<NT, DM, 15>(g, s, idx, Tc, Sbuf, piv_col, piv_row, synd, crows, nst, &npiv, (char *)s.hard - L.off_hard + L.off_owide, L.owide_ring, L.osd_lds != 0);
                 done = true;
@@ -3164,12 +2800,11 @@ __device__ __forceinline__ void lds_bind(Lds &s, char *smem, const SwdLdsLayout 
 
 // osd_window.decode (osd_window.pyx:158-199) for one syndrome `synd` (LDS bytes, original check
 // order).  On return s.hard[0..n) is the vector decode() returns.
-// vraw (kernels that split the cache load): where the raw edge words and priors of the variable nodes go; pre_valid: the caller has
-// issued the loads for this graph already
+// vraw (kernels that split the cache load): where the raw edge words and priors of the variable nodes go
 template <int NT, int VF, int DM, int KG, bool SF, bool HACC, bool BIG = false>
 __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLdsLayout &L, const SwdDecodeParams &P, Lds &s,
                               const uint8_t *synd, double *hist_b, uint8_t *osd0_b, uint8_t *bpdec_b, WinResult &R, const uint32_t *cn_map,
-                              VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> &vraw, bool pre_valid = false) {
+                              VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> &vraw) {
     constexpr bool DIET = SWD_P16(NT); // the tuned kernels' LDS forms (decided-node bits, 48-bit live masks, no copy of the check degrees)
     if constexpr (DIET) s.lm_m = (L.off_par - L.off_livemask < 8 * g.m) ? g.m : 0; // m if the masks are stored in the 48-bit form
     // Tuned kernels: the parity WORDS of the iterations lie over the live masks, which nothing reads while bp_run is running (the full-
@@ -3186,9 +2821,6 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     // kernels of up to 256 threads: the cache's loads are in flight during the reset loops (headline 9.95 -> 9.84 ms per launch at
     // order 0; the 1024-thread kernels lose by it -- [[288]] 63.2 -> 64.0 ms -- and load where they always did)
     constexpr bool kSplitLoad = NT <= SWD_TUNED_NT;
-    // the full-graph phase in the graph's listed order, tiered variable-node pass (bit 0: the LDS-resident kernels, bit 1: the large-graph ones)
-    constexpr bool kFullSorted = (SWD_FULL_SORTED & (BIG ? 2 : 1)) != 0;
-    [[maybe_unused]] int kcf[VF];
     // (memory loads return in order: what the reset loops need from the graph is asked for BEFORE the cache's 7 x DM + 7 loads, so
     // that the loops run while those are in flight instead of behind them)
     [[maybe_unused]] int d_first = 0, p_first = 0, j_first = 0;
@@ -3196,7 +2828,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
         if (tid < m) { d_first = g.row_deg[tid]; p_first = g.perm[tid]; }
         if (tid <= g.K) j_first = g.jptr[tid];
         __builtin_amdgcn_sched_barrier(0); // (issued here)
-        if (!pre_valid) vn_cache_issue<NT, VF, DM, kFullSorted>(g, s, vraw); // (uniform)
+        vn_cache_issue<NT, VF, DM>(g, s, vraw);
     }
     // reset (osd_window.pyx:288-303)
     for (int l = tid; l < m; l += NT) {
@@ -3217,17 +2849,16 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     const long long ip0 = wall_clock64();
 #endif
     // large graphs: check-to-bit messages as one record per check in LDS (bp_run<..., REC>) when the layout's LDS block has room for them
-    constexpr bool kTbl = BIG && SWD_BIG_TBL && !kFullSorted && !kSplitLoad; // the full graph's variable-node pass from the graph's tables (bp_run<..., TBL>)
-    constexpr bool kRec = BIG && SWD_BIG_REC && !kTbl && !kFullSorted && !kSplitLoad;
+    constexpr bool kTbl = BIG && SWD_BIG_TBL && !kSplitLoad; // the full graph's variable-node pass from the graph's tables (bp_run<..., TBL>)
+    constexpr bool kRec = BIG && SWD_BIG_REC && !kTbl && !kSplitLoad;
     bool rec_on = false;
     if constexpr (kRec) rec_on = L.off_pmsg >= 0 && m <= 1023 && L.pmsg_bytes >= (m + 1) * 32 + 4096;
     if constexpr (kSplitLoad) {
         vn_cache_pack<NT, VF, DM>(g, s, vraw, vc);
-        if constexpr (kFullSorted) vn_row_caps<NT, VF, DM>(g, s, vraw.ev, kcf);
     } else if constexpr (kTbl) { // (no cache)
     } else {
-        if (kRec && rec_on) { if constexpr (kRec) vn_cache_load<NT, VF, DM, true, false, false, true>(g, s, n, vc); }
-        else vn_cache_load<NT, VF, DM, true, false, kFullSorted>(g, s, n, vc, nullptr, kFullSorted ? &kcf : nullptr);
+        if (kRec && rec_on) { if constexpr (kRec) vn_cache_load<NT, VF, DM, true, false, true>(g, s, n, vc); }
+        else vn_cache_load<NT, VF, DM, true>(g, s, n, vc);
     }
 #ifdef SWD_INITPROF
     asm volatile("" : "+v"(vc.edp[VF - 1][0]), "+v"(vc.llr[0]));
@@ -3241,7 +2872,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
 #endif
     // large graphs: the LDS region that will hold the shortened graph's messages / the OSD arrays is idle in this phase -- the TOP of the
     // message array (the far and zero slots included) lives there, one select per access (flat addresses reach both memories)
-    constexpr bool kHyb = BIG && SWD_BIG_HYBRID;
+    constexpr bool kHyb = BIG;
     const int rec_b = (kRec && rec_on) ? (((m + 1) * 32 + 15) & ~15) : 0;
     if constexpr (kRec) {
         if (rec_on) {
@@ -3287,8 +2918,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     if (kRec && rec_on) {
         if constexpr (kRec) R.conv = bp_run<NT, VF, DM, KG, true, SF, HACC, false, false, kHyb, true>(g, P, s, P.pre_iter, n, vc, cn, hist_b, it, P.alpha, false, hs);
     } else
-    R.conv = bp_run<NT, VF, DM, KG, true, SF, HACC, false, kFullSorted, kHyb>(g, P, s, P.pre_iter, n, vc, cn, hist_b, it, P.alpha, false, hs, nullptr, false,
-                                                                        kFullSorted ? kcf : nullptr);
+    R.conv = bp_run<NT, VF, DM, KG, true, SF, HACC, false, false, kHyb>(g, P, s, P.pre_iter, n, vc, cn, hist_b, it, P.alpha, false, hs);
     R.pre_it = it;
     R.t[2] = wall_clock64();
     if (R.conv) {
@@ -3306,7 +2936,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
 #pragma unroll
         for (int i = 0; i < VF; ++i) { // the keys come straight from the accumulators of the owning thread
             const int li = s.vtid + i * NT;
-            if (li < n) { const int v = kFullSorted ? (int)g.vperm[li] : li; key[v] = f2key(hs[i]); idx[v] = (uint16_t)v; }
+            if (li < n) { const int v = li; key[v] = f2key(hs[i]); idx[v] = (uint16_t)v; }
         }
         for (int v = n + tid; v < L.npad; v += NT) { key[v] = ~0ull; idx[v] = 0xFFFF; }
     } else {
@@ -3494,9 +3124,9 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
             if (sorted) {
                 plain = false;
                 __syncthreads(); // the degrees are complete
-                // tiers of SWD_TIER_STEP(DM) positions: tier t = 1 .. NTIER holds the nodes whose live degree rounds up to t x step; the tier
+                // tiers of kTierStep positions: tier t = 1 .. NTIER holds the nodes whose live degree rounds up to t x step; the tier
                 // counts share prefix sums, FB bits each (a tier holds at most new_n <= 2 NT nodes), FPI of them per int
-                constexpr int TS = SWD_TIER_STEP(DM), NTIER = (DM + TS - 1) / TS;
+                constexpr int TS = kTierStep, NTIER = (DM + TS - 1) / TS;
                 constexpr int FB = (2 * NT < 1024) ? 10 : 12, FPI = (2 * NT < 1024) ? 3 : 2, FM = (1 << FB) - 1, NI = (NTIER + FPI - 1) / FPI;
                 const uint8_t *deg8 = (const uint8_t *)deg32;
                 auto tier_q = [&](int v) { const int d = deg8[v]; const int t = min(max((d + TS - 1) / TS, 1), NTIER); return NTIER - t; }; // 0 = the heaviest tier
@@ -3543,11 +3173,9 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     cn_assign<NT, KG>(g, s, dhist, cord, uselist, true, R.live_cn, clc, csub, cgrp);
     // BIG kernels: the shortened graph's messages move into LDS (layout flag post_lds), renumbered one column of cells per live
     // variable node; the staged column table of the shortening step (dead now) becomes the old-slot -> cell table
-    // (tuned kernels of up to 256 threads, experiment SWD_POST_RENUM: the same renumbering inside their LDS scratch region --
-    // the variable-node pass of the shortened graph then touches consecutive cells instead of scattered slots)
     SwdGraphDev gp = g;
     bool renum = false;
-    constexpr bool kRenum = BIG || (SWD_POST_RENUM && SWD_P16(NT));
+    constexpr bool kRenum = BIG; // (a local constant on purpose: run_post, a generic lambda, captures what it names, and its closure's layout decides two register numbers of the tuned kernels)
     if constexpr (kRenum) renum = L.post_lds != 0 && uselist;
     // the post phase proper, for a register cache of any depth: caches, (re)initialised messages, the iterations
     // (renum_tag: compile-time twin of `renum`, so that a BIG kernel's post-phase message pointer is an LDS pointer on every path
@@ -3758,8 +3386,8 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
 // On top of that thread 0 issues an agent-scope release fence before the counter store and an agent-scope acquire
 // fence after its poll, which makes the hand-over correct by the memory model alone (fence-fence synchronisation
 // through the relaxed counter, workgroup barriers on both sides, every state access an agent-scope atomic): measured
-// +0.4 % per launch (11.82 vs 11.78 ms).  -DSWD_HANDOFF_NOFENCE builds the variant that relies only on items 2-3
-// (gfx950's sc1 accesses; the guide lists "sc1 payload -> asm vmcnt(0) -> sc1 flag" as a valid form).
+// +0.4 % per launch (11.82 vs 11.78 ms) against a variant that relies only on items 2-3 (gfx950's sc1 accesses; "sc1 payload ->
+// asm vmcnt(0) -> sc1 flag" is a valid form on its own).
 // A wait that exceeds its 10 s bound sets bit 0 of *status, records exit class SWD_EXIT_SCHED_FAULT for the unit
 // and commits nothing for it: the caller sees the fault (swd_pipeline_status) instead of a plausible wrong answer.
 // BIG (large graphs, osd_window only): the scratch region of the window's layout -- fp64 messages, sort keys, OSD arrays --
@@ -3818,7 +3446,8 @@ __global__ void __launch_bounds__(NT) shot_order_kernel(const uint32_t *wt, int 
 }
 
 template <int NT, int VF, int DM, int KG, int KIND, bool SF = false, bool BIG = false, int VFP = VF>
-__global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : (NT == 640 ? 3 : ((SWD_OSDW_TUNED && NT == 512 && SWD_TUNED_NT >= 512 && (KIND == 0 || KIND == 3)) ? 6 : ((SWD_OSDW_TUNED && NT == 256 && KG <= 12 && (KIND == 0 || KIND == 3)) ? 3 : 2))))) pipeline_kernel(const SwdPipeArgs a) {
+__global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT == 256 && KG <= 12 && (KIND == 0 || KIND == 3)) ? 3 : 2))) pipeline_kernel(const SwdPipeArgs a) {
+    static_assert(NT == 64 || NT == 256 || NT == 1024, "workgroup sizes of swd_variants.h (the launch bounds and the sorted form know no other)");
     static_assert(!BIG || KIND == 0 || KIND == 3 || KIND == 1 || KIND == 7, "the HBM-resident scratch region exists for the osd_window kernels and for the guessing decoders' serial walk / ticket-scheduled ensemble");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -3846,23 +3475,9 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : (NT == 640 ? 3 : ((SWD_O
     // parallel form: every shot is admitted through the counter a.sched[0] -- by a workgroup that finds nothing unclaimed in the
     // ring, or by the one that finishes a shot -- so progress never depends on a workgroup that is not resident yet
     constexpr uint32_t shots0 = 0;
-    // The tuned osd_window kernels ask for the next unit's variable-node cache (7 x DM edge words + the priors per thread, from the
-    // graph's tables in L2) BEFORE they draw the ticket: consecutive tickets name the same window -- or a window that shares its
-    // graph -- nearly always, and the ticket, the predecessor's counter and the state record are three more dependent round trips to
-    // memory during which those loads can be in flight.  A unit of another graph asks again (decode_window).
-    constexpr bool kSpecLoad = SWD_SPEC_LOAD && (KIND == 0 || KIND == 3) && !BIG && NT <= SWD_TUNED_NT && !((SWD_FULL_SORTED & 1) != 0);
-    [[maybe_unused]] VnRaw<NT, kSpecLoad ? VF : 1, DM> vspec;
-    [[maybe_unused]] int wi_spec = 0;
-    [[maybe_unused]] const uint32_t *spec_tab = nullptr;
     for (;;) {
     const long long t_unit0 = wall_clock64();
     int wi, b, final_ctx = -1;
-    if constexpr (kSpecLoad) {
-        const SwdGraphDev &gs = a.wins[wi_spec].g;
-        vn_cache_issue<NT, VF, DM, false>(gs, s, vspec);
-        spec_tab = gs.vn_edge;
-        __builtin_amdgcn_sched_barrier(0);
-    }
     [[maybe_unused]] bool ens_task = false;      // kind 7: this turn runs a tree thread of a parked ensemble, not a unit
     [[maybe_unused]] uint32_t ens_item = 0;
 #ifdef SWD_GDG_DEBUG
@@ -3961,9 +3576,7 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : (NT == 640 ? 3 : ((SWD_O
                 // from hanging the device: flag the launch and go on (wall_clock64 ticks at 100 MHz -> 10 s)
                 if (wall_clock64() - t_wait0 > 1000000000ll) { atomicOr(a.status, 1u); atomicOr(&a.sched[a.B + 1], 1u); acc[3] = 1u; break; } // (the decoder's sticky word and this launch's own)
             }
-#ifndef SWD_HANDOFF_NOFENCE
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
         }
         __syncthreads();
         const uint32_t *st32 = (const uint32_t *)state_b;
@@ -4009,16 +3622,9 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : (NT == 640 ? 3 : ((SWD_O
             R.exit_class = SWD_EXIT_SCHED_FAULT;
         } else if constexpr (KIND == 0 || KIND == 3) // 3: osd_window with the posterior history accumulated in registers (bp_run, ACC)
         {
-            if constexpr (kSpecLoad) {
-                const bool hit = g.vn_edge == spec_tab && g.llr == a.wins[wi_spec].g.llr && g.n == a.wins[wi_spec].g.n;
-                wi_spec = wi;
-                decode_window<NT, VF, DM, KG, SF, KIND == 3, BIG>(g, L, a.P, s, sdet + (w.row0 - dbase), hist_b, a.osd0 ? a.osd0 + (int64_t)b * g.n : nullptr,
-                                                             a.bp_dec ? a.bp_dec + (int64_t)b * g.n : nullptr, R, w.cn_map, vspec, hit);
-            } else {
-                VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> vraw;
-                decode_window<NT, VF, DM, KG, SF, KIND == 3, BIG>(g, L, a.P, s, sdet + (w.row0 - dbase), hist_b, a.osd0 ? a.osd0 + (int64_t)b * g.n : nullptr,
-                                                             a.bp_dec ? a.bp_dec + (int64_t)b * g.n : nullptr, R, w.cn_map, vraw);
-            }
+            VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> vraw;
+            decode_window<NT, VF, DM, KG, SF, KIND == 3, BIG>(g, L, a.P, s, sdet + (w.row0 - dbase), hist_b, a.osd0 ? a.osd0 + (int64_t)b * g.n : nullptr,
+                                                         a.bp_dec ? a.bp_dec + (int64_t)b * g.n : nullptr, R, w.cn_map, vraw);
         }
         else {
             uint8_t *snap_b = a.snap + (int64_t)sidx * a.snap_stride;
@@ -4240,12 +3846,10 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : (NT == 640 ? 3 : ((SWD_O
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the state stores are acknowledged ...
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __syncthreads();                                  // ... by every wave, before the counter moves
-#ifndef SWD_HANDOFF_NOFENCE
             if (tid == 0) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
-#endif
             if (tid == 0) {
                 __hip_atomic_store(&a.sched[1 + b], (uint32_t)(wi + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if constexpr (kQueue) { if (queued) ring_push(a.gdgp.q, a.gdgp.qmask, item_unit(b, wi + 1)); } // the shot's next window is ready
