@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B of development builds (scripts/devbuild.sh) in one gpurun call: scripts/ab_dev.sh <out dir> <lib suffixes ...>; every build is timed
-# twice at OSD order 10 (the headline), interleaved; the first suffix also runs the recorded-run parity tests
+# twice at OSD order 10 (the headline), interleaved; the first suffix also runs the recorded-run parity tests.  The environment reaches
+# scripts/ab_time.py: SWD_NO_PM=1 scripts/ab_dev.sh ... times launches without a min_pm destination (what the streamed benchmark passes)
 OUT=$1; shift
 mkdir -p $OUT
 cd ${GRAFT_REPO_ROOT:-$(pwd)}

@@ -2801,10 +2801,12 @@ __device__ __forceinline__ void lds_bind(Lds &s, char *smem, const SwdLdsLayout 
 // osd_window.decode (osd_window.pyx:158-199) for one syndrome `synd` (LDS bytes, original check
 // order).  On return s.hard[0..n) is the vector decode() returns.
 // vraw (kernels that split the cache load): where the raw edge words and priors of the variable nodes go
+// want_pm (uniform over the launch): the caller gave min_pm a destination.  Without one the PRE and POST exits leave R.pm at 0 and skip
+// ordered_pm -- a scan, three barriers and a serial sum on one wave that nothing reads; the OSD exit needs the metric itself.
 template <int NT, int VF, int DM, int KG, bool SF, bool HACC, bool BIG = false>
 __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLdsLayout &L, const SwdDecodeParams &P, Lds &s,
                               const uint8_t *synd, double *hist_b, uint8_t *osd0_b, uint8_t *bpdec_b, WinResult &R, const uint32_t *cn_map,
-                              VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> &vraw) {
+                              VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> &vraw, const bool want_pm) {
     constexpr bool DIET = SWD_P16(NT); // the tuned kernels' LDS forms (decided-node bits, 48-bit live masks, no copy of the check degrees)
     if constexpr (DIET) s.lm_m = (L.off_par - L.off_livemask < 8 * g.m) ? g.m : 0; // m if the masks are stored in the 48-bit form
     // Tuned kernels: the parity WORDS of the iterations lie over the live masks, which nothing reads while bp_run is running (the full-
@@ -2923,7 +2925,13 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     R.t[2] = wall_clock64();
     if (R.conv) {
         R.exit_class = SWD_EXIT_PRE;
-        R.pm = ordered_pm<NT>(g, s, list0);
+#ifdef SWD_INITPROF
+        const long long pm0 = wall_clock64();
+#endif
+        if (want_pm) R.pm = ordered_pm<NT>(g, s, list0);
+#ifdef SWD_INITPROF
+        if (tid == 0) s.scal[25] = (int)(wall_clock64() - pm0);
+#endif
         R.total_it = R.pre_it;
         return;
     }
@@ -3279,7 +3287,13 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     R.total_it = R.pre_it + R.post_it;
     if (R.conv) {
         R.exit_class = SWD_EXIT_POST;
-        R.pm = ordered_pm<NT>(g, s, list0);
+#ifdef SWD_INITPROF
+        const long long pm0 = wall_clock64();
+#endif
+        if (want_pm) R.pm = ordered_pm<NT>(g, s, list0);
+#ifdef SWD_INITPROF
+        if (tid == 0) s.scal[25] = (int)(wall_clock64() - pm0);
+#endif
         return;
     }
     if (P.osd_order < 0) { R.exit_class = SWD_EXIT_NO_OSD; return; }
@@ -3624,7 +3638,7 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
         {
             VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> vraw;
             decode_window<NT, VF, DM, KG, SF, KIND == 3, BIG>(g, L, a.P, s, sdet + (w.row0 - dbase), hist_b, a.osd0 ? a.osd0 + (int64_t)b * g.n : nullptr,
-                                                         a.bp_dec ? a.bp_dec + (int64_t)b * g.n : nullptr, R, w.cn_map, vraw);
+                                                         a.bp_dec ? a.bp_dec + (int64_t)b * g.n : nullptr, R, w.cn_map, vraw, a.min_pm != nullptr);
         }
         else {
             uint8_t *snap_b = a.snap + (int64_t)sidx * a.snap_stride;
@@ -3819,7 +3833,7 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
 #endif
 #ifdef SWD_INITPROF
                 pr[0] = R.t[0] - t_unit0; pr[1] = s.scal[20]; pr[2] = s.scal[21]; pr[3] = s.scal[22]; pr[4] = s.scal[23]; pr[5] = s.scal[24];
-                pr[6] = tend - R.t[1]; pr[7] = tend - (R.t[7] ? R.t[7] : tend);
+                pr[6] = tend - R.t[1]; pr[7] = (R.exit_class == SWD_EXIT_PRE || R.exit_class == SWD_EXIT_POST) ? s.scal[25] : 0; // ordered_pm of the BP exits
 #endif
 #ifdef SWD_SELPROF
                 for (int k = 0; k < 8; ++k) { pr[k] = s.scal[20 + k]; s.scal[20 + k] = 0; }

@@ -752,10 +752,13 @@ class SlidingWindowDecoder:
                 st.close()
 
     def decode_device(self, det, total=None, stats=None, min_pm=None, shot_result=None, stream=None,
-                      want_stats=True):
+                      want_stats=True, want_min_pm=True):
         """torch uint8 CUDA tensor [B, num_det] -> (total [B, num_col], stats [B, W, 8], min_pm [B, W]);
         asynchronous on the current torch stream.  ``shot_result`` (int32 [B, 2] CUDA tensor, optional)
-        receives the predicted observable-flip mask and the flagged bit of every shot."""
+        receives the predicted observable-flip mask and the flagged bit of every shot.
+        ``min_pm=None`` alone does NOT mean "no path metrics" here (unlike ``push_device``): with ``want_stats`` a
+        buffer is allocated and returned, as it always was.  ``want_min_pm=False`` (and no ``min_pm`` tensor) gives the
+        launch no destination: None is returned in its place, and the windows that leave through BP do not compute one."""
         import torch
         self._no_loop("decode_device()")
         if det.dtype != torch.uint8 or det.dim() != 2 or det.shape[1] != self.num_det or det.stride(1) != 1:
@@ -768,7 +771,8 @@ class SlidingWindowDecoder:
         total = torch.empty((B, self.num_col), dtype=torch.uint8, device=dev) if total is None else total
         if want_stats:
             stats = torch.empty((B, self.W, _lib.STAT_WORDS), dtype=torch.int32, device=dev) if stats is None else stats
-            min_pm = torch.empty((B, self.W), dtype=torch.float64, device=dev) if min_pm is None else min_pm
+            if want_min_pm:
+                min_pm = torch.empty((B, self.W), dtype=torch.float64, device=dev) if min_pm is None else min_pm
         st = torch.cuda.current_stream(dev) if stream is None else stream
         rc = _lib.lib().swd_pipeline_decode_dev(self._h, B, det.data_ptr(), det.stride(0), total.data_ptr(),
                                                 total.stride(0), stats.data_ptr() if stats is not None else None,
