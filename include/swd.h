@@ -317,6 +317,43 @@ int swd_pipeline_stream_push_dev(swd_stream *s, int32_t B, const uint8_t *det, i
                                  int64_t total_stride, int32_t *stats, double *min_pm, int32_t *shot_result, void *after);
 int swd_pipeline_stream_wait(swd_stream *s, void *stream);
 
+/* ---- online sessions: the window loop driven by the arrival of detector rows --------------------
+ * The (W, F) scheme exists so that corrections are committed while the experiment still runs; the loop of the reference harness
+ * (/root/reference/osd.py:130-179) is causal -- window t reads only rows < row1 of det ^ chk @ total_e_hat.  A session owns the state
+ * of ONE batch of shots on the device: the residual syndrome (zero at the start), total_e_hat, the observable accumulators and the
+ * per-window records.  push hands over the next nrows detector rows of every shot, in row order, in pieces of any size (0 included):
+ * they are XORed into the residual syndrome, and every window whose last row has now arrived (the last window: every row of the
+ * experiment) is decoded at once -- the pipeline's own kernel, launched for that window alone -- and committed: its first `commit`
+ * columns go into total_e_hat, their columns of chk are XORed into the residual syndrome, rows that have NOT arrived yet included
+ * (osd.py:170-178).  Every result is bit-identical to swd_pipeline_decode of the whole experiment, whatever the chunking (guessing
+ * decoders: statistics word 7 aside, as ever).
+ *   begin       zeroes the state for a batch of B <= max_shots shots; also restarts a used session (osd.py:130-131)
+ *   push        det_rows [B*nrows] host bytes, row-major per shot; returns after the windows it made ready have been committed:
+ *               *first / *count = those windows (both nullable).  Errors: before begin, after the last window has been committed,
+ *               more rows than the experiment has.                                                        (osd.py:165-178)
+ *   push_dev    the same with a device pointer (stride = bytes between consecutive shots, 0 = nrows), asynchronous on `stream`:
+ *               merge, decode and commit are queued there in that order.  Calls on different streams are ordered by the session.
+ *   window      committed part of window t (t < windows committed): faults [B*commit] = total_e_hat[:, col0 : col0 + commit],
+ *               stats [B*SWD_STAT_WORDS], min_pm [B]; host pointers, all nullable; waits for the work queued so far   (osd.py:166-173)
+ *   finish      after the last window: total [B*num_col], stats [B*W*SWD_STAT_WORDS], min_pm [B*W], shot_result [B*2] as
+ *               swd_pipeline_decode returns them (host pointers, all nullable); before the last window it fails, and the message
+ *               names the detector rows still missing.  The state stays readable until the next begin.     (osd.py:184-187)
+ *   buffers     device view for the push_dev caller: total_e_hat (columns committed so far, the others zero), its stride, progress
+ * Lifetime and threading as for the stream objects: several sessions of one pipeline may be alive and interleaved, each owns its
+ * state; their launches are serialised on the host like all launches of the pipeline handle.  Destroy the sessions before the
+ * pipeline; the other order is tolerated in the same way (every later call fails with a message, destroy still frees). */
+typedef struct swd_session swd_session;
+swd_session *swd_pipeline_session_create(swd_pipeline *pl, int32_t max_shots);
+void swd_pipeline_session_destroy(swd_session *s);
+int swd_pipeline_session_begin(swd_session *s, int32_t B);
+int swd_pipeline_session_push(swd_session *s, int32_t nrows, const uint8_t *det_rows, int32_t *first, int32_t *count);
+int swd_pipeline_session_push_dev(swd_session *s, int32_t nrows, const uint8_t *det_rows, int64_t stride, int32_t *first,
+                                  int32_t *count, void *stream);
+int swd_pipeline_session_window(swd_session *s, int32_t t, uint8_t *faults, int32_t *stats, double *min_pm);
+int swd_pipeline_session_finish(swd_session *s, uint8_t *total, int32_t *stats, double *min_pm, int32_t *shot_result);
+int swd_pipeline_session_buffers(swd_session *s, uint8_t **total, int64_t *total_stride, int32_t *rows_received,
+                                 int32_t *windows_done);
+
 /* Threading and streams: every entry point may be called from any host thread.  Launches of ONE decoder /
  * pipeline handle are serialised on the host while they are prepared; on the device, launches on different streams
  * run concurrently -- each launch takes its scheduling scratch from a ring of four launch slots, and a fifth launch

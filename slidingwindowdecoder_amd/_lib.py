@@ -83,6 +83,14 @@ SYMBOLS = [
     ("swd_pipeline_stream_pending", C.c_int, [_vp]),
     ("swd_pipeline_stream_push_dev", C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     ("swd_pipeline_stream_wait", C.c_int, [_vp, _vp]),
+    ("swd_pipeline_session_create", _vp, [_vp, _i32]),
+    ("swd_pipeline_session_destroy", None, [_vp]),
+    ("swd_pipeline_session_begin", C.c_int, [_vp, _i32]),
+    ("swd_pipeline_session_push", C.c_int, [_vp, _i32, _vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    ("swd_pipeline_session_push_dev", C.c_int, [_vp, _i32, _vp, _i64, C.POINTER(_i32), C.POINTER(_i32), _vp]),
+    ("swd_pipeline_session_window", C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    ("swd_pipeline_session_finish", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("swd_pipeline_session_buffers", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
     ("swd_pipeline_status", C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     ("swd_pipeline_set_profiling", C.c_int, [_vp, _i32]),
     ("swd_pipeline_get_profile", C.c_int, [_vp, _i32, _vp]),

@@ -208,7 +208,7 @@ const Variant *select_variant(const std::vector<WindowHost> &wins, int mmax, int
     return nullptr;
 }
 
-static int launch(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
+int launch(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
     // work-unit scheduling state: ticket counter + per-shot progress (zeroed per launch), hand-over buffer
     SwdPipeArgs a = a0;
     std::lock_guard<std::recursive_mutex> lk(d->mu);
@@ -285,7 +285,7 @@ static int check_params(swd_osdw_params &p) {
     return 0;
 }
 
-static void fill_params(const Plan *d, SwdDecodeParams &P, bool hist_is_state, bool hist_is_output) {
+void fill_params(const Plan *d, SwdDecodeParams &P, bool hist_is_state, bool hist_is_output) {
     P.pre_iter = d->p.pre_max_iter; P.post_iter = d->p.post_max_iter;
     P.osd_method = d->p.osd_method; P.osd_order = d->p.osd_order; P.alpha = d->p.ms_scaling_factor;
     P.hist_is_state = hist_is_state ? 1 : 0;

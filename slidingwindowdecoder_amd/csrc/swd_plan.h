@@ -60,6 +60,31 @@ struct HostStream {
         }
     }
 };
+// Online session of a pipeline (include/swd.h: swd_pipeline_session_*; swd_session.hip): the per-shot state of ONE batch -- residual
+// syndrome, total_e_hat, observable accumulators, per-window records -- kept on the device between calls, so that a window is
+// decoded as soon as its last detector row has arrived.
+struct Session {
+    Plan *plan = nullptr;    // nulled by ~Plan when the pipeline is destroyed first: every later call on the session fails cleanly
+    int device = 0, max_shots = 0;
+    int B = 0;               // shots of the batch under way (0: swd_pipeline_session_begin has not been called)
+    int rows = 0, done = 0;  // detector rows received, windows committed
+    int W = 0, num_det = 0, num_col = 0, est_stride = 0;
+    int64_t res_stride = 0;  // bytes per shot of the residual syndrome (whole words)
+    DevBuf dev;              // [ resid | total | window estimate | accumulators | stats [W][max] | min_pm [W][max] | finish block | rows in ]
+    size_t o_total = 0, o_est = 0, o_acc = 0, o_stats = 0, o_pm = 0, o_fin = 0, o_in = 0;
+    size_t f_pm = 0, f_shot = 0, fin_bytes = 0; // finish block: stats [B][W][8] | min_pm [B][W] | shot_result [B][2]
+    PinnedBuf hin, hout;
+    hipStream_t st = nullptr;      // the host-buffer entry points' own stream
+    hipStream_t last = nullptr;    // stream of the most recent work on the state; `ev` marks its end
+    hipEvent_t ev = nullptr;
+    bool ev_set = false;
+    std::mutex mu;
+    ~Session() {
+        (void)hipSetDevice(device);
+        if (ev) { if (ev_set) (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+    }
+};
 // Kernel variants: threads per shot, VNs per thread, column-degree bound, groups of four row positions.
 // A plan uses the first variant with NT >= m, NT*VF >= n, DM >= D, 4*KG >= K over all its windows.
 struct Variant {
@@ -144,6 +169,7 @@ struct Plan {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::unique_ptr<HostStream> hstream; // the host-buffer entry point swd_pipeline_decode runs on its own two-lane stream object
     std::vector<HostStream *> streams;   // live stream objects of the caller (swd_pipeline_stream_create), under mu
+    std::vector<Session *> sessions;     // live online sessions (swd_pipeline_session_create), under mu
 
     ~Plan() {
         (void)hipSetDevice(device);
@@ -161,6 +187,17 @@ struct Plan {
             for (auto &l : hs->lane) { if (l.st) (void)hipStreamSynchronize(l.st); l.busy = false; }
             hs->npop = hs->npush;
             hs->plan = nullptr;
+        }
+        // online sessions that outlive their pipeline, likewise: their launches read this plan's graphs
+        std::vector<Session *> live_s;
+        {
+            std::lock_guard<std::recursive_mutex> lkp(mu);
+            live_s.swap(sessions);
+        }
+        for (Session *ss : live_s) {
+            std::lock_guard<std::mutex> lk(ss->mu);
+            if (ss->ev_set) (void)hipEventSynchronize(ss->ev);
+            ss->plan = nullptr;
         }
         if (ev0) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); }
         for (auto &sl : slot) if (sl.done) (void)hipEventDestroy(sl.done);
@@ -515,6 +552,10 @@ int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
     SWD_HIP(hipGetLastError());
     return 0;
 }
+
+// swd_osdw.hip: one launch of the plan's kernel on a launch slot of its own; the decoder parameters of the plan's kind
+int launch(Plan *d, const SwdPipeArgs &a0, hipStream_t st);
+void fill_params(const Plan *d, SwdDecodeParams &P, bool hist_is_state, bool hist_is_output);
 
 // one launcher per kernel instantiation, defined in swd_kernels_*.hip
 #define SWD_LAUNCHER_NAME(kind, nt, vf, dm, kg, sf) swd_launch_k##kind##_##nt##_##vf##_##dm##_##kg##_##sf

@@ -728,6 +728,12 @@ class SlidingWindowDecoder:
         self._no_loop("stream()")
         return SlidingWindowStream(self, max_shots, packed=packed, want_stats=want_stats)
 
+    def session(self, max_shots):
+        """Online form (``SlidingWindowSession``): the detector rows of a batch arrive in pieces, every window is decoded and
+        committed as soon as its last row is there; results equal ``decode`` of the whole experiment."""
+        self._no_loop("session()")
+        return SlidingWindowSession(self, max_shots)
+
     def decode_stream(self, batches, packed=False, want_stats=True):
         """Generator over an iterable of host batches [B_k, num_det]: yields (total_e_hat, stats, min_pm, obs_flips, flagged) per
         batch, in order, keeping two batches in flight (the deployment form of the shots loop of /root/reference/osd.py:130-191)."""
@@ -888,6 +894,122 @@ class SlidingWindowStream:
         """stream=None: the host waits for both lanes; a torch stream: that stream waits (device-side)."""
         if _lib.lib().swd_pipeline_stream_wait(self._h, stream.cuda_stream if stream is not None else None):
             raise RuntimeError(f"swd_pipeline_stream_wait failed: {_lib.last_error()}")
+
+
+class SlidingWindowSession:
+    """Online session of a ``SlidingWindowDecoder`` (C ABI: swd_pipeline_session_*): the window loop of
+    /root/reference/osd.py:130-179 driven by the arrival of detector rows.  The session keeps the residual syndrome,
+    total_e_hat and the observable accumulators of one batch on the device; ``push`` takes the next rows of every shot (any
+    number, in row order) and returns the windows they completed, each decoded on the rows received so far and committed --
+    bit-identical to ``decode`` of the whole experiment, whatever the chunking."""
+
+    def __init__(self, dec, max_shots):
+        self.dec, self.max_shots, self.B = dec, int(max_shots), 0
+        self._h = _lib.lib().swd_pipeline_session_create(dec._h, self.max_shots)
+        if not self._h:
+            raise RuntimeError(f"swd_pipeline_session_create failed: {_lib.last_error()}")
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                _lib.lib().swd_pipeline_session_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    __del__ = close
+
+    def begin(self, B):
+        """Zero state for a batch of ``B <= max_shots`` shots; also restarts a session that has been used."""
+        if _lib.lib().swd_pipeline_session_begin(self._h, int(B)):
+            raise RuntimeError(f"swd_pipeline_session_begin failed: {_lib.last_error()}")
+        self.B = int(B)
+
+    def _progress(self):
+        rows, done = C.c_int32(), C.c_int32()
+        if _lib.lib().swd_pipeline_session_buffers(self._h, None, None, C.byref(rows), C.byref(done)):
+            raise RuntimeError(f"swd_pipeline_session_buffers failed: {_lib.last_error()}")
+        return rows.value, done.value
+
+    @property
+    def rows_received(self):
+        return self._progress()[0]
+
+    @property
+    def windows_done(self):
+        return self._progress()[1]
+
+    @property
+    def rows_needed(self):
+        """Detector rows that must have arrived before the next window is decoded (``windows[next].row1``); None after the last."""
+        done = self.windows_done
+        return int(self.dec.plan.windows[done].row1) if done < self.dec.W else None
+
+    def window(self, t):
+        """(t, col0, faults [B, commit], stats [B, 8], min_pm [B]) of a committed window."""
+        w, B = self.dec.plan.windows[t], self.B
+        faults = np.empty((B, int(w.commit)), np.uint8)
+        st, pm = np.empty((B, _lib.STAT_WORDS), np.int32), np.empty(B, np.float64)
+        if _lib.lib().swd_pipeline_session_window(self._h, int(t), faults.ctypes.data, st.ctypes.data, pm.ctypes.data):
+            raise RuntimeError(f"swd_pipeline_session_window failed: {_lib.last_error()}")
+        return int(t), int(w.col0), faults, st, pm
+
+    def push(self, det_rows):
+        """det_rows [B, k] (host): the next k detector rows of every shot.  Returns the windows this call committed, in order, as
+        ``(t, col0, faults [B, commit], stats [B, 8], min_pm [B])`` -- ``faults`` is ``total_e_hat[:, col0:col0 + commit]``."""
+        d = np.asarray(det_rows)
+        if d.ndim != 2 or d.shape[0] != self.B:
+            raise ValueError(f"det_rows must have shape [{self.B}, k]")
+        if d.dtype != np.uint8 or not d.flags.c_contiguous:
+            d = np.ascontiguousarray((d.astype(np.int64) & 0xFF).astype(np.uint8))
+        first, count = C.c_int32(), C.c_int32()
+        if _lib.lib().swd_pipeline_session_push(self._h, d.shape[1], d.ctypes.data, C.byref(first), C.byref(count)):
+            raise RuntimeError(f"swd_pipeline_session_push failed: {_lib.last_error()}")
+        return [self.window(t) for t in range(first.value, first.value + count.value)]
+
+    def push_device(self, det_rows, stream=None):
+        """torch uint8 CUDA tensor [B, k] with unit column stride (a column slice of a [B, num_det] tensor fits); merge, decode and
+        commit are queued on ``stream`` (default: the current torch stream).  Returns (first, count) of the windows queued."""
+        import torch
+        if det_rows.dtype != torch.uint8 or det_rows.dim() != 2 or det_rows.shape[0] != self.B or not det_rows.is_cuda or \
+                (det_rows.shape[1] > 1 and det_rows.stride(1) != 1):
+            raise ValueError(f"det_rows must be a uint8 CUDA tensor [{self.B}, k] with unit column stride")
+        if det_rows.device.index != self.dec.device:
+            raise ValueError(f"det_rows lives on {det_rows.device}, the pipeline on cuda:{self.dec.device}")
+        st = torch.cuda.current_stream(det_rows.device) if stream is None else stream
+        first, count = C.c_int32(), C.c_int32()
+        k = det_rows.shape[1]
+        if _lib.lib().swd_pipeline_session_push_dev(self._h, k, det_rows.data_ptr() if k else None, det_rows.stride(0) if k else 0,
+                                                    C.byref(first), C.byref(count), st.cuda_stream):
+            raise RuntimeError(f"swd_pipeline_session_push_dev failed: {_lib.last_error()}")
+        return first.value, count.value
+
+    def finish(self):
+        """After the last window: (total_e_hat [B, num_col], stats [B, W, 8], min_pm [B, W], obs_flips [B], flagged [B]) as
+        ``decode`` leaves them.  Before it: RuntimeError naming the rows still missing."""
+        dec, B = self.dec, self.B
+        total = np.empty((B, dec.num_col), np.uint8)
+        st, pm = np.empty((B, dec.W, _lib.STAT_WORDS), np.int32), np.empty((B, dec.W), np.float64)
+        shot = np.empty((B, 2), np.int32)
+        if _lib.lib().swd_pipeline_session_finish(self._h, total.ctypes.data, st.ctypes.data, pm.ctypes.data, shot.ctypes.data):
+            raise RuntimeError(f"swd_pipeline_session_finish failed: {_lib.last_error()}")
+        return total, st, pm, shot[:, 0].astype(np.uint32), shot[:, 1].astype(bool)
+
+    def total_device(self):
+        """total_e_hat [B, num_col] of the batch as a torch CUDA tensor that ALIASES the session's buffer (columns committed so far,
+        zeros elsewhere): for ``push_device`` callers, who order their reads after the stream they pushed on."""
+        import torch
+        ptr, stride = C.c_void_p(), C.c_int64()
+        if _lib.lib().swd_pipeline_session_buffers(self._h, C.byref(ptr), C.byref(stride), None, None):
+            raise RuntimeError(f"swd_pipeline_session_buffers failed: {_lib.last_error()}")
+
+        class _View:
+            pass
+        v = _View()
+        v.__cuda_array_interface__ = {"shape": (self.B, self.dec.num_col), "typestr": "|u1", "data": (ptr.value, False), "version": 2,
+                                      "strides": (stride.value, 1)}
+        return torch.as_tensor(v, device=f"cuda:{self.dec.device}")
 
 
 class DemSampler:

@@ -190,6 +190,44 @@ def sliding_window_decode_host(plan: WindowPlan, det_data: np.ndarray, decoder_f
     return total, flagged
 
 
+def sliding_window_decode_online_host(plan: WindowPlan, chunks, decoder_factory):
+    """The same loop driven by the ARRIVAL of detector rows -- the executable specification of the online sessions
+    (``SlidingWindowDecoder.session``).  ``chunks``: arrays [shots, k] (k >= 0), the detector rows in row order.  The residual
+    syndrome starts as zero; arriving rows are XORed into it; window t is decoded once ``rows received >= row1`` and window
+    t - 1 has committed; every committed fault XORs its column of ``chk`` into the residual syndrome, rows that have not
+    arrived yet included.  The loop of osd.py:130-179 is causal (window t reads rows < row1 of det ^ chk @ total_e_hat), so the
+    result is that of ``sliding_window_decode_host`` whatever the chunking.
+    Returns (total_e_hat, events, resid): ``events`` = per chunk the list of ``(t, col0, faults[shots, commit])`` it committed;
+    ``resid`` = det ^ chk @ total_e_hat (flagged = ``resid.any(axis=1)``, osd.py:184-187)."""
+    chk_c = sp.csc_matrix(plan.chk)
+    num_det, num_col = chk_c.shape
+    decs = {}
+    total = resid = None
+    rows, nxt, events = 0, 0, []
+    for ch in chunks:
+        ch = np.asarray(ch, dtype=np.uint8)
+        if total is None:
+            total = np.zeros((ch.shape[0], num_col), np.uint8)
+            resid = np.zeros((ch.shape[0], num_det), np.uint8)
+        if nxt == len(plan.windows) or rows + ch.shape[1] > num_det:
+            raise ValueError("rows pushed after the last window / beyond the experiment")
+        resid[:, rows:rows + ch.shape[1]] ^= ch & 1
+        rows += ch.shape[1]
+        ready = []
+        while nxt < len(plan.windows) and rows >= plan.windows[nxt].row1:
+            w = plan.windows[nxt]
+            dec = decs.setdefault(nxt, decoder_factory(w))
+            for j in range(total.shape[0]):
+                e_hat = np.asarray(dec.decode(resid[j, w.row0:w.row1].copy()))[:w.commit].astype(np.uint8)
+                total[j, w.col0:w.col0 + w.commit] = e_hat
+                for c in np.flatnonzero(e_hat):
+                    resid[j, chk_c.indices[chk_c.indptr[w.col0 + c]:chk_c.indptr[w.col0 + c + 1]]] ^= 1
+            ready.append((nxt, w.col0, total[:, w.col0:w.col0 + w.commit].copy()))
+            nxt += 1
+        events.append(ready)
+    return total, events, resid
+
+
 def logical_error_stats(plan: WindowPlan, det_data, obs_data, total_e_hat):
     """osd.py:184-191: flagged = residual syndrome non-zero; logical = any observable wrong."""
     t = sp.csr_matrix(total_e_hat)
