@@ -354,6 +354,56 @@ int swd_pipeline_session_finish(swd_session *s, uint8_t *total, int32_t *stats, 
 int swd_pipeline_session_buffers(swd_session *s, uint8_t **total, int64_t *total_stride, int32_t *rows_received,
                                  int32_t *windows_done);
 
+/* ---- rolling sessions: experiments of any length on a frame of residual rows ------------------------
+ * An online session is tied to the number of rounds its plan was built for.  For a memory experiment every window between the first
+ * and the last is a translate of ONE window, so a pipeline built for R0 rounds serves as a TEMPLATE: head = window 0, body = window 1,
+ * tail = last window, F * h = row stride between windows.  A rolling session decodes experiments of every length R = R0 (mod F),
+ * known only when they end, bit-identical to swd_pipeline_decode of a pipeline built for R rounds; its device memory does not depend
+ * on R.  Per shot it keeps a FRAME of residual rows whose row 0 is the first row of the window decoded next, the observable
+ * accumulator and a sticky flagged bit.  Arriving rows are XORed into the frame; as soon as the frame holds the next window's rows it
+ * is decoded (the pipeline's own kernel, launched for that window alone) and committed: the first `commit` columns are written to the
+ * step's output, their columns of chk are XORed into the frame, their observable masks into the accumulator, the F * h rows that
+ * scroll out are ORed into the flagged bit and the frame moves down by F * h rows.
+ *   create      checks the template: at least a first, one body and a last window; body windows share one matrix, commit and stride;
+ *               their committed columns of chk and observable masks are translates; no committed column touches a row before its
+ *               window.  NOT checked here: the priors (a body window with other priors than window 1 is caught only as a
+ *               different window graph, a template with ONE body window not at all), and the periodicity of chk / obs when there
+ *               is one body window only.  windows.rolling_template is the full check -- priors, chk and obs per body ROUND -- and
+ *               the Python layer runs it before create; a caller of the C ABI answers for the periodicity of its own template.
+ *   begin       zero state for a batch of B <= max_shots shots; also restarts a used session
+ *   push        the next nrows detector rows of every shot (host bytes [B*nrows], any number, 0 included).  EVERY row handed to push
+ *               counts as a row of a syndrome round: the final data-measurement block must go to finish, push cannot tell the
+ *               difference and a whole final block would complete a body window.  Windows completed by the call: *count of them,
+ *               numbered *first .. (from 0, without bound); window k of the call writes faults [k][B][commit_max] (its first
+ *               `commit` columns of each row; commit_max = max of the head's and the body's commit, info[7]), stats
+ *               [k][B][SWD_STAT_WORDS], min_pm [k][B]; all nullable.  The call fails before it does anything if it would complete
+ *               more than max_windows windows (the capacity of those arrays).  Nothing of a window is kept after the call.
+ *   push_dev    the same with device pointers (stride = bytes between consecutive shots, 0 = nrows), asynchronous on `stream`
+ *   finish      the remaining nrows >= 1 rows, the final block among them, then the tail window, committed whole: faults
+ *               [B][tail commit], stats [B][SWD_STAT_WORDS], min_pm [B], shot_result [B][2] = observable flips of every fault
+ *               committed since begin, flagged (the sticky bit OR the rows left in the frame) as swd_pipeline_decode returns them.
+ *               Fails, leaving the state as it was, if the rows do not make an experiment the template serves (R = R0 (mod F) rounds
+ *               with a head and a tail window); the message names the lengths served.  After finish: begin.
+ *   finish_dev  the same with device pointers, asynchronous on `stream`
+ *   state       rows received and windows committed since begin, rows in the frame, info[8] = { frame rows, rows the next window
+ *               waits for in the frame, row stride, tail rows, head commit, body commit, tail commit, commit_max }, bytes of
+ *               device memory the session owns (a function of max_shots and the template alone); all nullable
+ * Stream ordering, lifetime and threading as for the online sessions. */
+typedef struct swd_rolling swd_rolling;
+swd_rolling *swd_pipeline_rolling_create(swd_pipeline *pl, int32_t max_shots);
+void swd_pipeline_rolling_destroy(swd_rolling *s);
+int swd_pipeline_rolling_begin(swd_rolling *s, int32_t B);
+int swd_pipeline_rolling_push(swd_rolling *s, int32_t nrows, const uint8_t *det_rows, int32_t max_windows, uint8_t *faults,
+                              int32_t *stats, double *min_pm, int64_t *first, int32_t *count);
+int swd_pipeline_rolling_push_dev(swd_rolling *s, int32_t nrows, const uint8_t *det_rows, int64_t stride, int32_t max_windows,
+                                  uint8_t *faults, int32_t *stats, double *min_pm, int64_t *first, int32_t *count, void *stream);
+int swd_pipeline_rolling_finish(swd_rolling *s, int32_t nrows, const uint8_t *final_rows, uint8_t *faults, int32_t *stats,
+                                double *min_pm, int32_t *shot_result);
+int swd_pipeline_rolling_finish_dev(swd_rolling *s, int32_t nrows, const uint8_t *final_rows, int64_t stride, uint8_t *faults,
+                                    int32_t *stats, double *min_pm, int32_t *shot_result, void *stream);
+int swd_pipeline_rolling_state(swd_rolling *s, int64_t *rows_received, int64_t *windows_done, int32_t *frame_fill, int32_t *info,
+                               int64_t *device_bytes);
+
 /* Threading and streams: every entry point may be called from any host thread.  Launches of ONE decoder /
  * pipeline handle are serialised on the host while they are prepared; on the device, launches on different streams
  * run concurrently -- each launch takes its scheduling scratch from a ring of four launch slots, and a fifth launch

@@ -91,6 +91,14 @@ SYMBOLS = [
     ("swd_pipeline_session_window", C.c_int, [_vp, _i32, _vp, _vp, _vp]),
     ("swd_pipeline_session_finish", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("swd_pipeline_session_buffers", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
+    ("swd_pipeline_rolling_create", _vp, [_vp, _i32]),
+    ("swd_pipeline_rolling_destroy", None, [_vp]),
+    ("swd_pipeline_rolling_begin", C.c_int, [_vp, _i32]),
+    ("swd_pipeline_rolling_push", C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i32)]),
+    ("swd_pipeline_rolling_push_dev", C.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i32), _vp]),
+    ("swd_pipeline_rolling_finish", C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    ("swd_pipeline_rolling_finish_dev", C.c_int, [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    ("swd_pipeline_rolling_state", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)]),
     ("swd_pipeline_status", C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     ("swd_pipeline_set_profiling", C.c_int, [_vp, _i32]),
     ("swd_pipeline_get_profile", C.c_int, [_vp, _i32, _vp]),

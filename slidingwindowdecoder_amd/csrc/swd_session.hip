@@ -349,3 +349,428 @@ extern "C" int swd_pipeline_session_buffers(swd_session *h, uint8_t **total, int
     if (windows_done) *windows_done = s->done;
     return 0;
 }
+
+// ---- rolling sessions (include/swd.h: swd_pipeline_rolling_*) ------------------------------------------------------------------------
+// The plan of R0 rounds is a template: head = window 0, body = window 1, tail = last window.  Per shot the session keeps a FRAME of
+// residual rows whose row 0 is the first row of the window decoded next (so all three windows sit at frame row 0), the observable
+// accumulator and a sticky flagged word -- nothing that grows with the experiment:
+//   arrival of k rows:      frame[:, fill : fill + k] ^= rows                                           (session_merge_kernel)
+//   frame holds a window:   decode it on frame[:, 0 : m] -- the plan's kernel as a pipeline of length 1 on a descriptor whose row0 is 0 --
+//                           commit, fold chk, accumulate observables, flag and drop the F * h rows that leave   (rolling_commit_kernel)
+//   finish:                 the last rows, the tail window, committed whole; every row left in the frame goes into the flag
+// The global check matrix of the template serves every window: body window t of a long experiment commits the columns of the
+// template's window 1, and its rows are those of window 1 moved down -- in frame rows both are `row - row0 of window 1`.
+namespace swd {
+
+struct RollingCommitArgs {
+    uint8_t *frame; int64_t frame_stride;
+    const uint8_t *est; int64_t est_stride;   // the window's full estimate (win_out of the decode launch)
+    uint8_t *out; int64_t out_stride;         // [B][out_stride]: the committed faults of this step
+    uint32_t *acc, *flag;                     // [B] observable accumulators, sticky flagged words
+    const uint32_t *chk_colptr; const uint16_t *chk_rows; const uint32_t *obs_mask;
+    int32_t *shot_result;                     // nullable [B][2]: written by the step that closes the experiment
+    int32_t frame_rows, col0, commit, row_off; // committed columns [col0, col0 + commit) of the template's chk; frame row = row - row_off
+    int32_t shift;                            // rows that leave the frame after this step
+};
+
+// one workgroup per shot: the frame staged in LDS (one byte per bit inside 32-bit words), the committed faults' columns folded in
+// with LDS atomics, the `shift` outgoing rows ORed into the flagged word, the frame written back moved down by `shift` rows (any
+// number: the bytes are gathered one by one) with zeros behind
+__global__ void __launch_bounds__(256) rolling_commit_kernel(const RollingCommitArgs a) {
+    extern __shared__ uint32_t sres[];
+    __shared__ uint32_t sacc;
+    const int tid = threadIdx.x, b = blockIdx.x, nw = (a.frame_rows + 3) >> 2;
+    uint32_t *fr32 = (uint32_t *)(a.frame + (int64_t)b * a.frame_stride);
+    for (int q = tid; q < nw; q += 256) sres[q] = fr32[q];
+    if (tid == 0) sacc = 0;
+    __syncthreads();
+    const uint8_t *est_b = a.est + (int64_t)b * a.est_stride;
+    uint8_t *out_b = a.out + (int64_t)b * a.out_stride;
+    for (int i = tid; i < a.commit; i += 256) {
+        const uint8_t hv = est_b[i];
+        out_b[i] = hv;
+        if (hv) {
+            const int c = a.col0 + i;
+            if (a.obs_mask) { const uint32_t om = a.obs_mask[c]; if (om) atomicXor(&sacc, om); }
+            for (uint32_t e = a.chk_colptr[c]; e < a.chk_colptr[c + 1]; ++e) {
+                const int r = (int)a.chk_rows[e] - a.row_off;
+                if ((unsigned)r < (unsigned)a.frame_rows) atomicXor(&sres[r >> 2], 1u << ((r & 3) * 8)); // (always: checked at creation)
+            }
+        }
+    }
+    __syncthreads();
+    const uint8_t *sb = (const uint8_t *)sres;
+    int nz = 0;
+    for (int r = tid; r < a.shift; r += 256) nz |= sb[r];
+    const int any = __syncthreads_or(nz);
+    for (int q = tid; q < nw; q += 256) {
+        uint32_t x = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int src = 4 * q + j + a.shift;
+            if (src < a.frame_rows && sb[src]) x |= 1u << (8 * j);
+        }
+        fr32[q] = x;
+    }
+    if (tid == 0) {
+        const uint32_t ac = a.acc[b] ^ sacc, fl = a.flag[b] | (any ? 1u : 0u);
+        a.acc[b] = ac; a.flag[b] = fl;
+        if (a.shot_result) { a.shot_result[2 * b] = (int32_t)ac; a.shot_result[2 * b + 1] = fl ? 1 : 0; }
+    }
+}
+
+// A rolling session IS a session for the plan's book-keeping (Plan::sessions: detached when the pipeline goes first) and for the
+// stream ordering; it has its own state layout.
+struct Rolling : Session {
+    enum { HEAD = 0, BODY = 1, TAIL = 2 };
+    struct Kind { int col0, commit, row_off, rows; } kd[3]{};
+    int frame_rows = 0, row_stride = 0, cmax = 0, call = 0; // cmax: head / body commits; call: the tail's too
+    int64_t frame_stride = 0;
+    int fill = 0;                 // rows in the frame
+    long long rows64 = 0, done64 = 0;
+    bool closed = false;          // finish has run: begin first
+    DevBuf wins3;                 // head, body, tail descriptors with row0 = 0
+    // dev: [ frame | flag | acc | window estimate | step output: faults [B][call] | stats | min_pm | shot_result ] [ rows in ]
+    size_t o_flag = 0, o_acc = 0, o_est = 0, o_out = 0, s_stats = 0, s_pm = 0, s_shot = 0, out_bytes = 0, o_in = 0, dev_bytes = 0;
+};
+
+// where the results of the windows of one call go: device arrays of the caller (window k at its offset), or the session's one-step
+// block -- then copied to the caller's HOST arrays after every window
+struct RollingOut {
+    uint8_t *faults = nullptr; int32_t *stats = nullptr; double *min_pm = nullptr; int32_t *shot_result = nullptr;
+    bool host = false;
+    bool decode_windows = true; // false (finish): the rows complete no head / body window, the tail follows
+    int max_windows = 0, count = 0;
+};
+
+static const char *rolling_lengths(const Rolling *r, char *buf, size_t n) {
+    // the rows of an experiment served: tail rows + one stride per window before the tail, at least one (the head)
+    snprintf(buf, n, "%d + %d k detector rows, k >= 1 (the final block included)", r->kd[Rolling::TAIL].rows, r->row_stride);
+    return buf;
+}
+
+// decode + commit the window the frame holds (kind: head / body / tail); results to `o` slot k
+static int rolling_step(Rolling *r, Plan *d, int kind, RollingOut &o, hipStream_t st) {
+    char *dv = (char *)r->dev.p;
+    const int B = r->B, k = o.count;
+    const Rolling::Kind &K = r->kd[kind];
+    const int64_t fstride = kind == Rolling::TAIL ? K.commit : r->cmax;
+    // the caller's device array (slot k of this call) or the session's one-step block
+    auto dest = [&](auto *caller, size_t slot_elems, size_t own_off) {
+        return (!o.host && caller) ? caller + (size_t)k * slot_elems : (decltype(caller))(dv + r->o_out + own_off);
+    };
+    uint8_t *faults = dest(o.faults, (size_t)B * fstride, 0);
+    int32_t *stats = dest(o.stats, (size_t)B * SWD_STAT_WORDS, r->s_stats);
+    double *pm = dest(o.min_pm, (size_t)B, r->s_pm);
+    int32_t *shot = kind == Rolling::TAIL ? dest(o.shot_result, 0, r->s_shot) : nullptr;
+    SwdPipeArgs a{};
+    a.wins = r->wins3.as<SwdWindowDev>() + kind; a.W = 1; a.B = B;
+    a.slot_scratch = 1;
+    fill_params(d, a.P, false, false);
+    a.det = (const uint8_t *)dv; a.det_stride = r->frame_stride; a.num_det = r->frame_rows; a.off_det = d->off_det;
+    a.total = nullptr; a.win_out = (uint8_t *)(dv + r->o_est); a.win_out_stride = r->est_stride;
+    a.stats = stats; a.min_pm = pm;
+    a.hist = nullptr; a.hist_stride = 4 * (int64_t)d->nmax;
+    if (launch(d, a, st)) return -1;
+    RollingCommitArgs c{};
+    c.frame = (uint8_t *)dv; c.frame_stride = r->frame_stride; c.frame_rows = r->frame_rows;
+    c.est = (const uint8_t *)(dv + r->o_est); c.est_stride = r->est_stride;
+    c.out = faults; c.out_stride = fstride;
+    c.acc = (uint32_t *)(dv + r->o_acc); c.flag = (uint32_t *)(dv + r->o_flag);
+    c.chk_colptr = d->d_colptr; c.chk_rows = d->d_rows; c.obs_mask = d->d_obs.p ? d->d_obs.as<uint32_t>() : nullptr;
+    c.shot_result = shot;
+    c.col0 = K.col0; c.commit = K.commit; c.row_off = K.row_off;
+    c.shift = kind == Rolling::TAIL ? r->frame_rows : r->row_stride;
+    hipLaunchKernelGGL(rolling_commit_kernel, dim3(B), dim3(256), (size_t)((r->frame_rows + 3) / 4) * 4, st, c);
+    SWD_HIP(hipGetLastError());
+    if (o.host) { // the one-step block -> the caller's host arrays, before the next window overwrites it
+        if (r->hout.reserve(std::max(r->out_bytes, (size_t)4096))) return -1;
+        SWD_HIP(hipMemcpyAsync(r->hout.p, dv + r->o_out, r->out_bytes, hipMemcpyDeviceToHost, st));
+        SWD_HIP(hipStreamSynchronize(st));
+        const char *ho = (const char *)r->hout.p;
+        if (o.faults) { // (staged rows: [B][fstride])
+            for (int b = 0; b < B; ++b) memcpy(o.faults + ((size_t)k * B + b) * fstride, ho + (size_t)b * fstride, (size_t)K.commit);
+        }
+        if (o.stats) memcpy(o.stats + (size_t)k * B * SWD_STAT_WORDS, ho + r->s_stats, (size_t)B * SWD_STAT_WORDS * 4);
+        if (o.min_pm) memcpy(o.min_pm + (size_t)k * B, ho + r->s_pm, (size_t)B * 8);
+        if (o.shot_result && kind == Rolling::TAIL) memcpy(o.shot_result, ho + r->s_shot, (size_t)B * 8);
+    }
+    o.count++;
+    return 0;
+}
+
+// windows that nrows more rows complete
+static long long rolling_windows_for(const Rolling *r, long long nrows) {
+    const long long have = r->fill + nrows, need = r->kd[Rolling::HEAD].rows;
+    return have < need ? 0 : (have - need) / r->row_stride + 1;
+}
+
+// XOR rows [0, nrows) of `rows` (device, or host when o.host) into the frame piece by piece, decoding every window that completes
+static int rolling_rows(Rolling *r, Plan *d, int nrows, const uint8_t *rows, int64_t stride, RollingOut &o, hipStream_t st) {
+    char *dv = (char *)r->dev.p;
+    const int B = r->B;
+    if (!stride) stride = nrows;
+    int done = 0;
+    while (done < nrows) {
+        const int k = std::min(nrows - done, r->frame_rows - r->fill); // (> 0: a frame that holds a window has been decoded)
+        const uint8_t *src = rows + done;
+        int64_t sstride = stride;
+        if (o.host) { // the piece through the page-locked block (free here: every step of a host call ends synchronised)
+            if (r->hin.reserve(std::max((size_t)B * r->frame_rows, (size_t)4096))) return -1;
+            for (int b = 0; b < B; ++b) memcpy((char *)r->hin.p + (size_t)b * k, rows + (size_t)b * stride + done, (size_t)k);
+            SWD_HIP(hipMemcpyAsync(dv + r->o_in, r->hin.p, (size_t)B * k, hipMemcpyHostToDevice, st));
+            src = (const uint8_t *)(dv + r->o_in); sstride = k;
+        }
+        const long long nthr = (long long)B * (((r->fill + k - 1) >> 2) - (r->fill >> 2) + 1);
+        hipLaunchKernelGGL(session_merge_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, (uint8_t *)dv, r->frame_stride, src,
+                           sstride, B, r->fill, k);
+        SWD_HIP(hipGetLastError());
+        r->fill += k; r->rows64 += k; done += k;
+        if (o.host) SWD_HIP(hipStreamSynchronize(st)); // (hin is reused by the next piece)
+        while (o.decode_windows && r->fill >= r->kd[Rolling::HEAD].rows) {
+            if (rolling_step(r, d, r->done64 == 0 ? Rolling::HEAD : Rolling::BODY, o, st)) return -1;
+            r->fill -= r->row_stride; r->done64++;
+        }
+    }
+    return 0;
+}
+
+static int rolling_push(Rolling *r, int32_t nrows, const uint8_t *rows, int64_t stride, RollingOut &o, int64_t *first, int32_t *count,
+                        hipStream_t st) {
+    Plan *d = session_plan(r);
+    if (!d) return -1;
+    if (!r->B) { set_error("rolling push: call swd_pipeline_rolling_begin first"); return -1; }
+    if (r->closed) { set_error("rolling push: the experiment has been finished; begin a new batch"); return -1; }
+    if (nrows < 0 || (nrows > 0 && !rows)) { set_error(nrows < 0 ? "rolling push: negative row count" : "null input pointer"); return -1; }
+    const long long nwin = rolling_windows_for(r, nrows);
+    if (nwin > o.max_windows) {
+        set_error("rolling push: %d rows complete %lld windows, the output arrays hold %d", nrows, nwin, o.max_windows);
+        return -1;
+    }
+    SWD_HIP(hipSetDevice(d->device));
+    if (session_enter(r, st)) return -1;
+    const long long first_w = r->done64;
+    const int rc = rolling_rows(r, d, nrows, rows, stride, o, st);
+    if (session_leave(r, st)) return -1;
+    if (first) *first = first_w;
+    if (count) *count = o.count;
+    return rc;
+}
+
+static int rolling_finish(Rolling *r, int32_t nrows, const uint8_t *rows, int64_t stride, RollingOut &o, hipStream_t st) {
+    Plan *d = session_plan(r);
+    if (!d) return -1;
+    if (!r->B) { set_error("rolling finish: call swd_pipeline_rolling_begin first"); return -1; }
+    if (r->closed) { set_error("rolling finish: the experiment has been finished; begin a new batch"); return -1; }
+    if (nrows < 0 || (nrows > 0 && !rows)) { set_error(nrows < 0 ? "rolling finish: negative row count" : "null input pointer"); return -1; }
+    char buf[160];
+    const long long total = r->rows64 + nrows;
+    if (nrows == 0) {
+        set_error("rolling finish: no final rows -- the final block must go to finish, not to push (%lld rows pushed; this template serves %s)",
+                  r->rows64, rolling_lengths(r, buf, sizeof buf));
+        return -1;
+    }
+    if (r->done64 == 0) {
+        set_error("rolling finish: %lld detector rows are fewer than the first and the last window need; this template serves %s", total,
+                  rolling_lengths(r, buf, sizeof buf));
+        return -1;
+    }
+    if (r->fill + (long long)nrows != r->kd[Rolling::TAIL].rows) {
+        set_error("rolling finish: %lld detector rows (%lld pushed, %d final) do not make an experiment this template serves: %s", total,
+                  r->rows64, nrows, rolling_lengths(r, buf, sizeof buf));
+        return -1;
+    }
+    SWD_HIP(hipSetDevice(d->device));
+    if (session_enter(r, st)) return -1;
+    o.decode_windows = false; // (the frame holds the tail's rows)
+    int rc = rolling_rows(r, d, nrows, rows, stride, o, st);
+    if (!rc) rc = rolling_step(r, d, Rolling::TAIL, o, st);
+    if (!rc) { r->fill = 0; r->done64++; r->closed = true; }
+    if (session_leave(r, st)) return -1;
+    return rc;
+}
+
+} // namespace swd
+
+extern "C" swd_rolling *swd_pipeline_rolling_create(swd_pipeline *h, int32_t max_shots) {
+    Plan *d = (Plan *)h;
+    if (!d) { set_error("null pipeline"); return nullptr; }
+    if (d->wins.empty() || d->num_col <= 0) { set_error("a rolling session needs a sliding-window pipeline"); return nullptr; }
+    if (max_shots <= 0) { set_error("max_shots must be positive"); return nullptr; }
+    const int n = (int)d->wins.size();
+    if (n < 3) { set_error("rolling template: %d windows, a first, a body and a last window are needed", n); return nullptr; }
+    if (hipSetDevice(d->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", d->device); return nullptr; }
+    const WindowHost &w0 = d->wins[0], &w1 = d->wins[1], &wl = d->wins[n - 1];
+    const int rs = d->wins[2].row0 - w1.row0, cs = d->wins[2].col0 - w1.col0;
+    if (rs <= 0 || cs <= 0 || w0.row0 != 0 || w0.col0 != 0 || w1.row0 != rs || w1.g->m != w0.g->m || w1.commit != cs || w0.commit != w1.col0 ||
+        wl.row0 + wl.g->m != d->num_det || wl.col0 + wl.commit != d->num_col) {
+        set_error("rolling template: windows are not periodic (placement of the first, second and last window)");
+        return nullptr;
+    }
+    for (int k = 2; k < n; ++k) {
+        const WindowHost &w = d->wins[k];
+        if (w.row0 - d->wins[k - 1].row0 != rs || w.col0 - d->wins[k - 1].col0 != cs) { set_error("rolling template: window %d is not placed one stride after window %d", k, k - 1); return nullptr; }
+        if (k < n - 1 && (w.g != w1.g || w.commit != w1.commit || w.new_n != w1.new_n)) { set_error("rolling template: window %d is not periodic (matrix, priors or commit differ from window 1)", k); return nullptr; }
+    }
+    // host copy of the CSC of chk and the observable masks: periodicity of the committed columns, and the rows they reach
+    std::vector<uint32_t> cp((size_t)d->num_col + 1);
+    if (hipMemcpy(cp.data(), d->d_colptr, cp.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_error("rolling template: reading chk failed"); return nullptr; }
+    std::vector<uint16_t> rows(cp.back());
+    if (!rows.empty() && hipMemcpy(rows.data(), d->d_rows, rows.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) { set_error("rolling template: reading chk failed"); return nullptr; }
+    std::vector<uint32_t> om;
+    if (d->d_obs.p) {
+        om.resize(d->num_col);
+        if (hipMemcpy(om.data(), d->d_obs.p, om.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_error("rolling template: reading obs failed"); return nullptr; }
+    }
+    for (int k = 2; k < n - 1; ++k)
+        for (int i = 0; i < cs; ++i) {
+            const int ca = w1.col0 + i, cb = d->wins[k].col0 + i;
+            bool same = cp[ca + 1] - cp[ca] == cp[cb + 1] - cp[cb] && (om.empty() || om[ca] == om[cb]);
+            for (uint32_t e = 0; same && e < cp[ca + 1] - cp[ca]; ++e) same = rows[cp[ca] + e] + (k - 1) * rs == rows[cp[cb] + e];
+            if (!same) { set_error("rolling template: chk / obs are not periodic (column %d of window %d against window 1)", i, k); return nullptr; }
+        }
+    Rolling *r = new Rolling();
+    const WindowHost *kw[3] = {&w0, &w1, &wl};
+    int frame = 0;
+    for (int j = 0; j < 3; ++j) {
+        const WindowHost &w = *kw[j];
+        r->kd[j] = {w.col0, w.commit, w.row0, w.g->m};
+        frame = std::max(frame, w.g->m);
+        for (uint32_t e = cp[w.col0]; e < cp[w.col0 + w.commit]; ++e) {
+            if (rows[e] < w.row0) { set_error("rolling template: a committed column of window %d touches row %d, before the window", j == 2 ? n - 1 : j, (int)rows[e]); delete r; return nullptr; }
+            frame = std::max(frame, (int)rows[e] - w.row0 + 1);
+        }
+    }
+    if (frame > d->num_det) { set_error("rolling template: the frame (%d rows) exceeds the template's %d detector rows", frame, d->num_det); delete r; return nullptr; }
+    r->plan = d; r->device = d->device; r->max_shots = max_shots;
+    r->frame_rows = frame; r->row_stride = rs;
+    r->cmax = std::max(w0.commit, w1.commit); r->call = std::max(r->cmax, wl.commit);
+    r->est_stride = align_up(d->nmax, 16);
+    r->frame_stride = align_up(frame, 16);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t B = (size_t)max_shots;
+    r->o_flag = al(B * r->frame_stride);
+    r->o_acc = r->o_flag + al(B * 4);
+    r->o_est = r->o_acc + al(B * 4);
+    r->o_out = r->o_est + al(B * r->est_stride);
+    r->s_stats = al(B * r->call);
+    r->s_pm = r->s_stats + al(B * SWD_STAT_WORDS * 4);
+    r->s_shot = r->s_pm + al(B * 8);
+    r->out_bytes = r->s_shot + al(B * 8);
+    r->o_in = r->o_out + r->out_bytes;
+    r->dev_bytes = r->o_in + al(B * (size_t)frame);
+    // the three descriptors: the plan's own, at frame row 0
+    std::vector<SwdWindowDev> hw(3);
+    const int idx[3] = {0, 1, n - 1};
+    bool ok = hipMemcpy(hw.data(), d->d_wins.as<SwdWindowDev>(), sizeof(SwdWindowDev), hipMemcpyDeviceToHost) == hipSuccess;
+    for (int j = 1; ok && j < 3; ++j)
+        ok = hipMemcpy(&hw[j], d->d_wins.as<SwdWindowDev>() + idx[j], sizeof(SwdWindowDev), hipMemcpyDeviceToHost) == hipSuccess;
+    for (auto &w : hw) w.row0 = 0;
+    if (!ok || r->dev.reserve(r->dev_bytes) || r->wins3.reserve(3 * sizeof(SwdWindowDev)) ||
+        hipMemcpy(r->wins3.p, hw.data(), 3 * sizeof(SwdWindowDev), hipMemcpyHostToDevice) != hipSuccess ||
+        hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&r->ev, hipEventDisableTiming) != hipSuccess) {
+        if (!ok || r->dev.p) set_error("rolling session: descriptor copy / stream / event creation failed");
+        delete r;
+        return nullptr;
+    }
+    r->dev_bytes = r->dev.cap + r->wins3.cap;
+    // (frame_rows <= num_det <= 65 535: the dynamic LDS of rolling_commit_kernel stays below the default limit's 64 KB only up to
+    // 16 384 words -- raise it as session_commit_kernel does)
+    static std::mutex attr_mu;
+    {
+        std::lock_guard<std::mutex> lk(attr_mu);
+        (void)hipFuncSetAttribute((const void *)rolling_commit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    }
+    { std::lock_guard<std::recursive_mutex> lk(d->mu); d->sessions.push_back(r); }
+    return (swd_rolling *)r;
+}
+
+extern "C" void swd_pipeline_rolling_destroy(swd_rolling *h) {
+    Rolling *r = (Rolling *)h;
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    if (Plan *d = r->plan) {
+        std::lock_guard<std::recursive_mutex> lk(d->mu);
+        d->sessions.erase(std::remove(d->sessions.begin(), d->sessions.end(), (Session *)r), d->sessions.end());
+    }
+    delete r;
+}
+
+extern "C" int swd_pipeline_rolling_begin(swd_rolling *h, int32_t B) {
+    Rolling *r = (Rolling *)h;
+    if (!r) { set_error("null session"); return -1; }
+    std::lock_guard<std::mutex> lk(r->mu);
+    Plan *d = session_plan(r);
+    if (!d) return -1;
+    if (B <= 0 || B > r->max_shots) { set_error("rolling begin: %d shots, the session was created for 1..%d", B, r->max_shots); return -1; }
+    SWD_HIP(hipSetDevice(d->device));
+    if (session_enter(r, r->st)) return -1;
+    // zero frames, flagged words and accumulators of the batch's shots
+    SWD_HIP(hipMemsetAsync(r->dev.p, 0, (size_t)B * r->frame_stride, r->st));
+    SWD_HIP(hipMemsetAsync((char *)r->dev.p + r->o_flag, 0, (size_t)B * 4, r->st));
+    SWD_HIP(hipMemsetAsync((char *)r->dev.p + r->o_acc, 0, (size_t)B * 4, r->st));
+    r->B = B; r->fill = 0; r->rows64 = 0; r->done64 = 0; r->closed = false;
+    return session_leave(r, r->st);
+}
+
+extern "C" int swd_pipeline_rolling_push_dev(swd_rolling *h, int32_t nrows, const uint8_t *det_rows, int64_t stride, int32_t max_windows,
+                                             uint8_t *faults, int32_t *stats, double *min_pm, int64_t *first, int32_t *count, void *stream) {
+    Rolling *r = (Rolling *)h;
+    if (!r) { set_error("null session"); return -1; }
+    std::lock_guard<std::mutex> lk(r->mu);
+    RollingOut o;
+    o.faults = faults; o.stats = stats; o.min_pm = min_pm; o.max_windows = std::max(max_windows, 0);
+    return rolling_push(r, nrows, det_rows, stride, o, first, count, (hipStream_t)stream);
+}
+
+extern "C" int swd_pipeline_rolling_push(swd_rolling *h, int32_t nrows, const uint8_t *det_rows, int32_t max_windows, uint8_t *faults,
+                                         int32_t *stats, double *min_pm, int64_t *first, int32_t *count) {
+    Rolling *r = (Rolling *)h;
+    if (!r) { set_error("null session"); return -1; }
+    std::lock_guard<std::mutex> lk(r->mu);
+    RollingOut o;
+    o.faults = faults; o.stats = stats; o.min_pm = min_pm; o.max_windows = std::max(max_windows, 0); o.host = true;
+    if (rolling_push(r, nrows, det_rows, 0, o, first, count, r->st)) return -1;
+    SWD_HIP(hipStreamSynchronize(r->st));
+    return 0;
+}
+
+extern "C" int swd_pipeline_rolling_finish_dev(swd_rolling *h, int32_t nrows, const uint8_t *final_rows, int64_t stride, uint8_t *faults,
+                                               int32_t *stats, double *min_pm, int32_t *shot_result, void *stream) {
+    Rolling *r = (Rolling *)h;
+    if (!r) { set_error("null session"); return -1; }
+    std::lock_guard<std::mutex> lk(r->mu);
+    RollingOut o;
+    o.faults = faults; o.stats = stats; o.min_pm = min_pm; o.shot_result = shot_result;
+    return rolling_finish(r, nrows, final_rows, stride, o, (hipStream_t)stream);
+}
+
+extern "C" int swd_pipeline_rolling_finish(swd_rolling *h, int32_t nrows, const uint8_t *final_rows, uint8_t *faults, int32_t *stats,
+                                           double *min_pm, int32_t *shot_result) {
+    Rolling *r = (Rolling *)h;
+    if (!r) { set_error("null session"); return -1; }
+    std::lock_guard<std::mutex> lk(r->mu);
+    RollingOut o;
+    o.faults = faults; o.stats = stats; o.min_pm = min_pm; o.shot_result = shot_result; o.host = true;
+    if (rolling_finish(r, nrows, final_rows, 0, o, r->st)) return -1;
+    SWD_HIP(hipStreamSynchronize(r->st));
+    return 0;
+}
+
+extern "C" int swd_pipeline_rolling_state(swd_rolling *h, int64_t *rows_received, int64_t *windows_done, int32_t *frame_fill, int32_t *info,
+                                          int64_t *device_bytes) {
+    Rolling *r = (Rolling *)h;
+    if (!r) { set_error("null session"); return -1; }
+    std::lock_guard<std::mutex> lk(r->mu);
+    if (!session_plan(r)) return -1;
+    if (rows_received) *rows_received = r->rows64;
+    if (windows_done) *windows_done = r->done64;
+    if (frame_fill) *frame_fill = r->fill;
+    if (info) {
+        const int v[8] = {r->frame_rows, r->kd[Rolling::HEAD].rows, r->row_stride, r->kd[Rolling::TAIL].rows, r->kd[Rolling::HEAD].commit,
+                          r->kd[Rolling::BODY].commit, r->kd[Rolling::TAIL].commit, r->cmax};
+        for (int i = 0; i < 8; ++i) info[i] = v[i];
+    }
+    if (device_bytes) *device_bytes = (int64_t)r->dev_bytes;
+    return 0;
+}

@@ -734,6 +734,14 @@ class SlidingWindowDecoder:
         self._no_loop("session()")
         return SlidingWindowSession(self, max_shots)
 
+    def rolling_session(self, max_shots):
+        """Rolling form (``RollingSession``): this decoder's plan of R0 rounds serves as a template (first, body and last window)
+        for experiments of every length ``R = R0 (mod F)``, known only when they end; per-shot device state is one frame of
+        residual rows, whatever R.  Results equal ``SlidingWindowDecoder(plan_windows(R)).decode``.  ValueError if the plan is
+        not periodic between its first and its last window (``windows.rolling_template``)."""
+        self._no_loop("rolling_session()")
+        return RollingSession(self, max_shots)
+
     def decode_stream(self, batches, packed=False, want_stats=True):
         """Generator over an iterable of host batches [B_k, num_det]: yields (total_e_hat, stats, min_pm, obs_flips, flagged) per
         batch, in order, keeping two batches in flight (the deployment form of the shots loop of /root/reference/osd.py:130-191)."""
@@ -1010,6 +1018,193 @@ class SlidingWindowSession:
         v.__cuda_array_interface__ = {"shape": (self.B, self.dec.num_col), "typestr": "|u1", "data": (ptr.value, False), "version": 2,
                                       "strides": (stride.value, 1)}
         return torch.as_tensor(v, device=f"cuda:{self.dec.device}")
+
+
+class RollingSession:
+    """Rolling session of a ``SlidingWindowDecoder`` (C ABI: swd_pipeline_rolling_*) whose plan of R0 rounds is the template: head =
+    window 0, body = window 1, tail = last window.  It decodes experiments of any length ``R = R0 (mod F)`` rounds, known only when
+    they end, with device memory that does not depend on R: per shot a frame of residual rows (``template.frame_rows``), an
+    observable accumulator and a sticky flagged bit.  ``push`` takes the next detector rows of the SYNDROME rounds in pieces of any
+    size and returns every window they completed; ``finish`` takes the rest and closes the experiment with the tail window.
+
+    The final data-measurement block must go to ``finish``: ``push`` treats every block as a syndrome round and cannot tell the
+    difference (a final block handed to ``push`` may complete a body window that the experiment does not have).
+
+    Every result is bit-identical to ``SlidingWindowDecoder(plan_windows(R)).decode`` (windows.sliding_window_decode_rolling_host is
+    the executable specification).  Per-window ``stats`` / ``min_pm`` come back with each step and are not retained.
+
+    One thread at a time per session at this layer: ``push`` sizes its output arrays from a state query made before the call, so
+    two threads pushing on one session would size them for the wrong state (the library then refuses the call, it does not
+    overrun).  The C ABI itself may be called from any thread."""
+
+    def __init__(self, dec, max_shots):
+        from .windows import rolling_template
+        self.template = rolling_template(dec.plan)  # ValueError names what is not periodic
+        self.dec, self.max_shots, self.B = dec, int(max_shots), 0
+        self._h = _lib.lib().swd_pipeline_rolling_create(dec._h, self.max_shots)
+        if not self._h:
+            raise RuntimeError(f"swd_pipeline_rolling_create failed: {_lib.last_error()}")
+        info = (C.c_int32 * 8)()
+        if _lib.lib().swd_pipeline_rolling_state(self._h, None, None, None, info, None):
+            raise RuntimeError(f"swd_pipeline_rolling_state failed: {_lib.last_error()}")
+        T = self.template
+        self._need, self._cmax = int(info[1]), int(info[7])
+        want = [T.frame_rows, T.head.row1, T.row_stride, T.tail.row1 - T.tail.row0, T.head.commit, T.body.commit, T.tail.commit,
+                max(T.head.commit, T.body.commit)]
+        if list(info) != [int(x) for x in want]:
+            raise RuntimeError(f"rolling template: the library extracted {list(info)}, windows.rolling_template {want}")
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                _lib.lib().swd_pipeline_rolling_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    __del__ = close
+
+    def begin(self, B):
+        """Zero state for a batch of ``B <= max_shots`` shots; also restarts a session that has been used."""
+        if _lib.lib().swd_pipeline_rolling_begin(self._h, int(B)):
+            raise RuntimeError(f"swd_pipeline_rolling_begin failed: {_lib.last_error()}")
+        self.B = int(B)
+
+    def _state(self):
+        rows, done, fill, nbytes = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
+        if _lib.lib().swd_pipeline_rolling_state(self._h, C.byref(rows), C.byref(done), C.byref(fill), None, C.byref(nbytes)):
+            raise RuntimeError(f"swd_pipeline_rolling_state failed: {_lib.last_error()}")
+        return rows.value, done.value, fill.value, nbytes.value
+
+    @property
+    def rows_received(self):
+        return self._state()[0]
+
+    @property
+    def rounds_received(self):
+        """whole blocks of ``n_half`` rows received since ``begin``"""
+        return self._state()[0] // self.template.n_half
+
+    @property
+    def windows_done(self):
+        return self._state()[1]
+
+    @property
+    def rows_needed(self):
+        """Rows still missing in the frame before ``push`` decodes the next head / body window."""
+        return max(self._need - self._state()[2], 0)
+
+    @property
+    def device_bytes(self):
+        """Bytes of device memory the session owns: a function of ``max_shots`` and the template, not of the rows received."""
+        return self._state()[3]
+
+    def _windows_for(self, k):
+        have = self._state()[2] + int(k)
+        return 0 if have < self._need else (have - self._need) // self.template.row_stride + 1
+
+    def _commit(self, t):
+        return int(self.template.head.commit if t == 0 else self.template.body.commit)
+
+    def push(self, det_rows):
+        """det_rows [B, k] (host): the next k rows of the syndrome rounds of every shot.  Returns the windows this call completed, in
+        order, as ``(t, faults [B, commit_t], stats [B, 8], min_pm [B])``; ``t`` counts from 0 without bound."""
+        d = np.asarray(det_rows)
+        if d.ndim != 2 or d.shape[0] != self.B:
+            raise ValueError(f"det_rows must have shape [{self.B}, k]")
+        if d.dtype != np.uint8 or not d.flags.c_contiguous:
+            d = np.ascontiguousarray((d.astype(np.int64) & 0xFF).astype(np.uint8))
+        n, B = self._windows_for(d.shape[1]) if self.B else 0, self.B
+        faults = np.zeros((n, B, self._cmax), np.uint8)
+        st, pm = np.empty((n, B, _lib.STAT_WORDS), np.int32), np.empty((n, B), np.float64)
+        first, count = C.c_int64(), C.c_int32()
+        if _lib.lib().swd_pipeline_rolling_push(self._h, d.shape[1], d.ctypes.data, n, faults.ctypes.data, st.ctypes.data, pm.ctypes.data,
+                                                C.byref(first), C.byref(count)):
+            raise RuntimeError(f"swd_pipeline_rolling_push failed: {_lib.last_error()}")
+        return [(first.value + k, faults[k, :, :self._commit(first.value + k)], st[k], pm[k]) for k in range(count.value)]
+
+    def _check_device_rows(self, det_rows):
+        import torch
+        if det_rows.dtype != torch.uint8 or det_rows.dim() != 2 or det_rows.shape[0] != self.B or not det_rows.is_cuda or \
+                (det_rows.shape[1] > 1 and det_rows.stride(1) != 1):
+            raise ValueError(f"det_rows must be a uint8 CUDA tensor [{self.B}, k] with unit column stride")
+        if det_rows.device.index != self.dec.device:
+            raise ValueError(f"det_rows lives on {det_rows.device}, the pipeline on cuda:{self.dec.device}")
+
+    def push_device(self, det_rows, faults_out=None, stream=None):
+        """torch uint8 CUDA tensor [B, k] with unit column stride; merge, decode and commit are queued on ``stream`` (default: the
+        current torch stream).  ``faults_out``: optional contiguous uint8 CUDA tensor [n, B, commit_max] of the caller's, n >= the
+        windows this call completes (``commit_max = max(head.commit, body.commit)``); window k of the call writes the first
+        ``commit_t`` columns of ``faults_out[k]``.  Returns ``(t, faults, stats, min_pm)`` per window as CUDA tensors (views of
+        ``faults_out``), valid once ``stream`` has reached them."""
+        import torch
+        self._check_device_rows(det_rows)
+        st = torch.cuda.current_stream(det_rows.device) if stream is None else stream
+        k, B, dev = det_rows.shape[1], self.B, det_rows.device
+        n = self._windows_for(k) if self.B else 0
+        with torch.cuda.stream(st):
+            if faults_out is None:
+                faults_out = torch.zeros((n, B, self._cmax), dtype=torch.uint8, device=dev)
+            elif faults_out.dtype != torch.uint8 or faults_out.dim() != 3 or faults_out.shape[0] < n or not faults_out.is_contiguous() or \
+                    tuple(faults_out.shape[1:]) != (B, self._cmax) or faults_out.device != dev:
+                raise ValueError(f"faults_out must be a contiguous uint8 CUDA tensor [n >= {n}, {B}, {self._cmax}] on {dev}")
+            stats = torch.empty((n, B, _lib.STAT_WORDS), dtype=torch.int32, device=dev)
+            pm = torch.empty((n, B), dtype=torch.float64, device=dev)
+        first, count = C.c_int64(), C.c_int32()
+        if _lib.lib().swd_pipeline_rolling_push_dev(self._h, k, det_rows.data_ptr() if k else None, det_rows.stride(0) if k else 0, n,
+                                                    faults_out.data_ptr() if n else None, stats.data_ptr() if n else None,
+                                                    pm.data_ptr() if n else None, C.byref(first), C.byref(count), st.cuda_stream):
+            raise RuntimeError(f"swd_pipeline_rolling_push_dev failed: {_lib.last_error()}")
+        return [(first.value + j, faults_out[j, :, :self._commit(first.value + j)], stats[j], pm[j]) for j in range(count.value)]
+
+    def _check_finish(self, k):
+        """ValueError unless the rows received plus ``k`` final rows make an experiment the template serves"""
+        T = self.template
+        rows, done, fill, _ = self._state()
+        total, tail_rows = rows + k, T.tail.row1 - T.tail.row0
+        if self.B and (k == 0 or done == 0 or fill + k != tail_rows):
+            what = f"{total // T.n_half - 1} syndrome rounds" if total % T.n_half == 0 else "no whole number of rounds"
+            why = "the final block must go to finish, not to push" if k == 0 else \
+                ("fewer rows than the first and the last window need" if done == 0 else "not a length this template serves")
+            raise ValueError(f"{total} detector rows ({rows} pushed, {k} final) make {what}: {why}; this template serves {T.lengths()}")
+
+    def finish(self, final_rows):
+        """final_rows [B, k] (host), k >= 1: the rest of the experiment, the final data-measurement block included.  The tail window
+        is decoded and committed whole.  Returns ``(t, tail_faults [B, tail commit], stats [B, 8], min_pm [B], obs_flips [B],
+        flagged [B])`` -- the last two as ``decode`` leaves ``last_obs_flips`` / ``last_flagged``.  ValueError, with the state
+        untouched, if the rows do not make an experiment of ``R = R0 (mod F)`` rounds or are fewer than head and tail need."""
+        d = np.asarray(final_rows)
+        if d.ndim != 2 or d.shape[0] != self.B:
+            raise ValueError(f"final_rows must have shape [{self.B}, k]")
+        if d.dtype != np.uint8 or not d.flags.c_contiguous:
+            d = np.ascontiguousarray((d.astype(np.int64) & 0xFF).astype(np.uint8))
+        self._check_finish(d.shape[1])
+        B, t = self.B, self._state()[1]
+        faults = np.empty((B, int(self.template.tail.commit)), np.uint8)
+        st, pm, shot = np.empty((B, _lib.STAT_WORDS), np.int32), np.empty(B, np.float64), np.empty((B, 2), np.int32)
+        if _lib.lib().swd_pipeline_rolling_finish(self._h, d.shape[1], d.ctypes.data, faults.ctypes.data, st.ctypes.data, pm.ctypes.data,
+                                                  shot.ctypes.data):
+            raise RuntimeError(f"swd_pipeline_rolling_finish failed: {_lib.last_error()}")
+        return t, faults, st, pm, shot[:, 0].astype(np.uint32), shot[:, 1].astype(bool)
+
+    def finish_device(self, final_rows, stream=None):
+        """``finish`` with a CUDA tensor, queued on ``stream``: returns ``(t, tail_faults, stats, min_pm, obs_flips, flagged)`` as
+        ``finish`` does, as CUDA tensors; ``obs_flips`` / ``flagged`` are the int32 columns of one [B, 2] tensor (bit mask; 0 or 1)."""
+        import torch
+        self._check_device_rows(final_rows)
+        self._check_finish(final_rows.shape[1])
+        st = torch.cuda.current_stream(final_rows.device) if stream is None else stream
+        B, dev, t = self.B, final_rows.device, self._state()[1]
+        with torch.cuda.stream(st):
+            faults = torch.empty((B, int(self.template.tail.commit)), dtype=torch.uint8, device=dev)
+            stats = torch.empty((B, _lib.STAT_WORDS), dtype=torch.int32, device=dev)
+            pm = torch.empty(B, dtype=torch.float64, device=dev)
+            shot = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        if _lib.lib().swd_pipeline_rolling_finish_dev(self._h, final_rows.shape[1], final_rows.data_ptr(), final_rows.stride(0),
+                                                      faults.data_ptr(), stats.data_ptr(), pm.data_ptr(), shot.data_ptr(), st.cuda_stream):
+            raise RuntimeError(f"swd_pipeline_rolling_finish_dev failed: {_lib.last_error()}")
+        return t, faults, stats, pm, shot[:, 0], shot[:, 1]
 
 
 class DemSampler:

@@ -235,3 +235,197 @@ def logical_error_stats(plan: WindowPlan, det_data, obs_data, total_e_hat):
     flagged = resid.any(axis=1)
     logical = ((obs_data + (t @ plan.obs.T.astype(np.int32)).toarray()) % 2).any(axis=1)
     return flagged, np.logical_or(flagged, logical)
+
+
+@dataclass
+class RollingTemplate:
+    """What a rolling session keeps of a template ``WindowPlan`` of R0 rounds (``rolling_template``): the head, body and tail
+    windows, the strides between body windows and the committed columns of ``chk`` / ``obs`` in FRAME rows (row 0 = first row of
+    the window that is decoded next).  It serves every experiment of ``R = R0 (mod F)`` rounds with ``R >= min_rounds``."""
+    plan: WindowPlan
+    head: Window
+    body: Window
+    tail: Window
+    n_half: int
+    W: int               # row blocks per window
+    F: int               # row blocks the frame moves per window
+    R0: int              # syndrome rounds of the template (its detector rows: (R0 + 1) * n_half)
+    min_rounds: int      # the shortest experiment with a head and a tail window
+    row_stride: int      # F * n_half
+    col_stride: int
+    frame_rows: int      # rows of residual syndrome kept per shot
+    head_chk: sp.csc_matrix   # frame_rows x commit, per kind of window
+    body_chk: sp.csc_matrix
+    tail_chk: sp.csc_matrix
+    head_obs: sp.csc_matrix   # num_obs x commit
+    body_obs: sp.csc_matrix
+    tail_obs: sp.csc_matrix
+
+    def serves(self, rounds: int) -> bool:
+        return rounds >= self.min_rounds and (rounds - self.R0) % self.F == 0
+
+    def lengths(self) -> str:
+        return (f"R = {self.R0} (mod {self.F}) syndrome rounds, R >= {self.min_rounds}: {self.min_rounds}, "
+                f"{self.min_rounds + self.F}, {self.min_rounds + 2 * self.F}, ... (plus the final block of {self.n_half} rows)")
+
+
+def _same_matrix(a, b):
+    a, b = sp.csr_matrix(a), sp.csr_matrix(b)
+    a.sort_indices()
+    b.sort_indices()
+    return a.shape == b.shape and np.array_equal(a.indptr, b.indptr) and np.array_equal(a.indices, b.indices) and \
+        np.array_equal(a.data != 0, b.data != 0)
+
+
+def rolling_template(plan: WindowPlan) -> RollingTemplate:
+    """Checks that ``plan`` is periodic between its first and its last window -- every body window a translate of window 1,
+    ``chk``, ``obs`` and ``priors`` periodic over the body column blocks -- and extracts head (window 0), body (window 1) and tail
+    (last window) for a rolling session.  Raises ValueError naming what is not periodic."""
+    wins = plan.windows
+    h = int(plan.n_half)
+    if len(wins) < 3:
+        raise ValueError(f"a rolling template needs a first, a body and a last window; this plan has {len(wins)} windows (build it "
+                         f"for more rounds)")
+    head, body, tail = wins[0], wins[1], wins[-1]
+    if not tail.is_last or any(w.is_last for w in wins[:-1]):
+        raise ValueError("the last window of the plan, and only the last, must be marked is_last")
+    num_det, num_col = plan.chk.shape
+    if num_det % h or any(w.row0 % h or (w.row1 - w.row0) % h for w in wins):
+        raise ValueError(f"detector rows and window rows must come in blocks of n_half = {h}")
+    row_stride, col_stride = wins[2].row0 - body.row0, wins[2].col0 - body.col0
+    W, F = (head.row1 - head.row0) // h, row_stride // h
+    if row_stride <= 0 or col_stride <= 0 or head.row0 != 0 or head.col0 != 0 or body.row0 != row_stride:
+        raise ValueError(f"windows do not advance by a constant positive stride from row 0 (rows {[w.row0 for w in wins]})")
+    if body.row1 - body.row0 != W * h:
+        raise ValueError("the first window and window 1 differ in their number of rows")
+    for k in range(2, len(wins)):
+        w, last = wins[k], k == len(wins) - 1
+        if w.row0 - wins[k - 1].row0 != row_stride or w.col0 - wins[k - 1].col0 != col_stride:
+            raise ValueError(f"window {k} is not placed one stride ({row_stride} rows, {col_stride} columns) after window {k - 1}")
+        if last:
+            break
+        if w.commit != body.commit or w.ncols_global != body.ncols_global:
+            raise ValueError(f"window {k} commits {w.commit} of {w.ncols_global} columns, window 1 commits {body.commit} of {body.ncols_global}")
+        if not _same_matrix(w.mat, body.mat):
+            raise ValueError(f"the matrix of window {k} is not periodic: it differs from that of window 1")
+        if not np.array_equal(np.asarray(w.prior), np.asarray(body.prior)):
+            j = np.flatnonzero(np.asarray(w.prior) != np.asarray(body.prior))
+            raise ValueError(f"the priors of window {k} are not periodic: {len(j)} differ from those of window 1, the first at its column {int(j[0])}")
+    if body.commit != col_stride:
+        raise ValueError(f"body windows commit {body.commit} columns and advance by {col_stride}")
+    if head.col0 + head.commit != body.col0:
+        raise ValueError("the first window does not commit up to the first column of window 1")
+    if tail.col0 + tail.commit != num_col or tail.row1 != num_det:
+        raise ValueError("the last window does not close the experiment (rows and columns up to the end)")
+    # chk, obs and priors over the body column blocks: the per-round blocks of plan.anchors that the body windows commit.  At least
+    # two of them, or nothing shows that they are translates of one another: two body windows, or one that commits F >= 2 rounds
+    anchors = [tuple(int(x) for x in a) for a in plan.anchors]
+    col_at = {a[1]: i for i, a in enumerate(anchors)}
+    if body.col0 not in col_at or tail.col0 not in col_at:
+        raise ValueError("window columns do not start at the plan's anchors")
+    j0, j1 = col_at[body.col0], col_at[tail.col0]
+    if j1 - j0 < 2:
+        raise ValueError(f"a rolling template needs at least two body windows (or one that commits two rounds or more) for its "
+                         f"periodicity to be checked; this plan has {len(wins) - 2} body window(s) committing {j1 - j0} round(s): build it "
+                         f"for more rounds")
+    chk_c, obs_c, priors = sp.csc_matrix(plan.chk), sp.csc_matrix(plan.obs), np.asarray(plan.priors)
+    chk_c.sort_indices()
+    obs_c.sort_indices()
+
+    def block(m, j, shift):
+        c = m[:, anchors[j][1]:anchors[j + 1][1]]
+        return c.indptr, c.indices - shift * (j - j0), c.data != 0
+
+    for j in range(j0 + 1, j1):
+        if anchors[j][0] - anchors[j - 1][0] != h:
+            raise ValueError(f"anchors are not periodic: round {j} starts {anchors[j][0] - anchors[j - 1][0]} rows after round {j - 1}")
+        for name, m, shift in (("chk", chk_c, h), ("obs", obs_c, 0)):
+            a, b = block(m, j0, shift), block(m, j, shift)
+            if not (len(a[0]) == len(b[0]) and all(np.array_equal(x, y) for x, y in zip(a, b))):
+                raise ValueError(f"{name} is not periodic: the columns of round {j} are no translate of those of round {j0}")
+        pa, pb = priors[anchors[j0][1]:anchors[j0 + 1][1]], priors[anchors[j][1]:anchors[j + 1][1]]
+        if not np.array_equal(pa, pb):
+            d = np.flatnonzero(pa != pb)
+            raise ValueError(f"priors are not periodic: {len(d)} of the columns of round {j} differ from those of round {j0}, the first "
+                             f"at global column {int(anchors[j][1] + d[0])}")
+    # committed columns in frame rows; the frame covers every row a window reads or a committed column can touch
+    frame_rows, parts = 0, {}
+    for name, w in (("head", head), ("body", body), ("tail", tail)):
+        cols = chk_c[:, w.col0:w.col0 + w.commit]
+        if cols.nnz and cols.indices.min() < w.row0:
+            raise ValueError(f"the {name} window commits columns that touch rows before its first row: they would have left the frame")
+        frame_rows = max(frame_rows, w.row1 - w.row0, int(cols.indices.max()) + 1 - w.row0 if cols.nnz else 0)
+        parts[name] = (cols, obs_c[:, w.col0:w.col0 + w.commit], w.row0)
+    if frame_rows > num_det:
+        raise ValueError("the committed columns do not fit the frame")
+
+    def in_frame(cols, row0):
+        c = sp.csc_matrix((np.ones(cols.nnz, np.uint8), cols.indices - row0, cols.indptr), shape=(frame_rows, cols.shape[1]))
+        return c
+
+    R0 = num_det // h - 1
+    n0 = len(wins) - 1                                   # non-last windows of the template: ceil((R0 + 1 - W) / F)
+    min_rounds = R0 - (n0 - 1) * F                       # the same residue with one non-last window (the head)
+    return RollingTemplate(plan, head, body, tail, h, W, F, R0, min_rounds, row_stride, col_stride, frame_rows,
+                           *[in_frame(parts[k][0], parts[k][2]) for k in ("head", "body", "tail")],
+                           *[sp.csc_matrix(parts[k][1]) for k in ("head", "body", "tail")])
+
+
+def sliding_window_decode_rolling_host(template_plan, chunks, final_rows, decoder_factory):
+    """The window loop on a FRAME of residual rows -- the executable specification of the rolling sessions
+    (``SlidingWindowDecoder.rolling_session``).  ``template_plan``: a ``WindowPlan`` (or its ``RollingTemplate``) of R0 rounds;
+    ``chunks``: arrays [shots, k] (k >= 0), the rows of the SYNDROME rounds in row order, as many rounds as the experiment has;
+    ``final_rows`` [shots, k]: the rest, which must hold the final data-measurement block (a piece of it would do, as long as
+    it is not empty: ``chunks`` are taken for syndrome rounds, a whole block among them completes a window).
+    Per shot: a frame of ``frame_rows`` residual rows, row 0 = first row of the next window.  Arriving rows are XORed in; when
+    the frame holds the next window's rows it is decoded (head, then bodies), its first ``commit`` columns are committed and
+    their ``chk`` columns folded into the frame; the ``F * n_half`` rows that scroll out are ORed into the sticky ``flagged`` bit
+    (committed columns of window t only touch row blocks >= t, arrivals come later still), and the frame moves on.  ``final_rows``
+    closes the experiment: the tail window is decoded and committed whole.  The result is that of ``sliding_window_decode_host``
+    on ``plan_windows`` of the experiment's own length R, for every ``R = R0 (mod F)``.
+    Returns (events, obs_flips [shots, num_obs], flagged [shots]); ``events`` = ``(t, faults [shots, commit_t])`` per window."""
+    T = template_plan if isinstance(template_plan, RollingTemplate) else rolling_template(template_plan)
+    final_rows = np.asarray(final_rows, dtype=np.uint8)
+    B = final_rows.shape[0]
+    frame = np.zeros((B, T.frame_rows), np.uint8)
+    flagged = np.zeros(B, bool)
+    obs_flips = np.zeros((B, T.head_obs.shape[0]), np.uint8)
+    decs, events = {}, []
+    fill, t, received = 0, 0, 0
+    need = T.head.row1 - T.head.row0
+
+    def step(kind, w, chk_f, obs_f, shift):
+        dec = decs.setdefault(kind, decoder_factory(w))
+        faults = np.zeros((B, w.commit), np.uint8)
+        for j in range(B):
+            e_hat = np.asarray(dec.decode(frame[j, :w.row1 - w.row0].copy()))[:w.commit].astype(np.uint8)
+            faults[j] = e_hat
+            for c in np.flatnonzero(e_hat):
+                frame[j, chk_f.indices[chk_f.indptr[c]:chk_f.indptr[c + 1]]] ^= 1
+                obs_flips[j, obs_f.indices[obs_f.indptr[c]:obs_f.indptr[c + 1]]] ^= 1
+        events.append((t, faults))
+        flagged[:] |= frame[:, :shift].any(axis=1)
+        frame[:, :T.frame_rows - shift] = frame[:, shift:].copy()
+        frame[:, T.frame_rows - shift:] = 0
+
+    for ch in chunks:
+        ch = np.asarray(ch, dtype=np.uint8)
+        r = 0
+        while r < ch.shape[1]:
+            k = min(ch.shape[1] - r, T.frame_rows - fill)
+            frame[:, fill:fill + k] ^= ch[:, r:r + k] & 1
+            fill, r, received = fill + k, r + k, received + k
+            while fill >= need:
+                step("head" if t == 0 else "body", T.head if t == 0 else T.body, T.head_chk if t == 0 else T.body_chk,
+                     T.head_obs if t == 0 else T.body_obs, T.row_stride)
+                fill, t = fill - T.row_stride, t + 1
+    k = final_rows.shape[1]
+    tail_rows = T.tail.row1 - T.tail.row0
+    total = received + k
+    if t == 0 or k == 0 or fill + k != tail_rows:
+        rounds = f"{total // T.n_half - 1} syndrome rounds" if total % T.n_half == 0 else "no whole number of rounds"
+        raise ValueError(f"{total} detector rows ({received} pushed, {k} final) make {rounds}; this template serves {T.lengths()}"
+                         + ("; the final block must go to the closing call, not to a push" if k == 0 else ""))
+    frame[:, fill:fill + k] ^= final_rows & 1
+    step("tail", T.tail, T.tail_chk, T.tail_obs, T.frame_rows)
+    return events, obs_flips, flagged
