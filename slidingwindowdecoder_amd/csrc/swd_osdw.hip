@@ -517,6 +517,7 @@ extern "C" int swd_pipeline_set_observables(swd_pipeline *h, const swd_graph_des
         }
     if (d->d_obs.reserve(mask.size() * 4)) return -1;
     SWD_HIP(hipMemcpy(d->d_obs.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice));
+    d->h_obs = std::move(mask);
     return 0;
 }
 

@@ -60,30 +60,36 @@ struct HostStream {
         }
     }
 };
-// Online session of a pipeline (include/swd.h: swd_pipeline_session_*; swd_session.hip): the per-shot state of ONE batch -- residual
-// syndrome, total_e_hat, observable accumulators, per-window records -- kept on the device between calls, so that a window is
-// decoded as soon as its last detector row has arrived.
-struct Session {
+// What the online and the rolling sessions of a pipeline (swd_session.hip) share: the plan's book-keeping (Plan::sessions: detached
+// when the pipeline goes first), one device block, page-locked staging and the stream ordering.  Each form adds its own layout.
+struct SessionBase {
     Plan *plan = nullptr;    // nulled by ~Plan when the pipeline is destroyed first: every later call on the session fails cleanly
     int device = 0, max_shots = 0;
-    int B = 0;               // shots of the batch under way (0: swd_pipeline_session_begin has not been called)
-    int rows = 0, done = 0;  // detector rows received, windows committed
-    int W = 0, num_det = 0, num_col = 0, est_stride = 0;
-    int64_t res_stride = 0;  // bytes per shot of the residual syndrome (whole words)
-    DevBuf dev;              // [ resid | total | window estimate | accumulators | stats [W][max] | min_pm [W][max] | finish block | rows in ]
-    size_t o_total = 0, o_est = 0, o_acc = 0, o_stats = 0, o_pm = 0, o_fin = 0, o_in = 0;
-    size_t f_pm = 0, f_shot = 0, fin_bytes = 0; // finish block: stats [B][W][8] | min_pm [B][W] | shot_result [B][2]
+    int B = 0;               // shots of the batch under way (0: begin has not been called)
+    int est_stride = 0;      // bytes per shot of the window estimate
+    DevBuf dev;
     PinnedBuf hin, hout;
     hipStream_t st = nullptr;      // the host-buffer entry points' own stream
     hipStream_t last = nullptr;    // stream of the most recent work on the state; `ev` marks its end
     hipEvent_t ev = nullptr;
     bool ev_set = false;
     std::mutex mu;
-    ~Session() {
+    virtual ~SessionBase() {
         (void)hipSetDevice(device);
         if (ev) { if (ev_set) (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
         if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     }
+};
+// Online session (include/swd.h: swd_pipeline_session_*): the per-shot state of ONE batch -- residual syndrome, total_e_hat,
+// observable accumulators, per-window records -- kept on the device between calls, so that a window is decoded as soon as its last
+// detector row has arrived.
+struct Session : SessionBase {
+    int rows = 0, done = 0;  // detector rows received, windows committed
+    int W = 0, num_det = 0, num_col = 0;
+    int64_t res_stride = 0;  // bytes per shot of the residual syndrome (whole words)
+    // dev: [ resid | total | window estimate | accumulators | stats [W][max] | min_pm [W][max] | finish block | rows in ]
+    size_t o_total = 0, o_est = 0, o_acc = 0, o_stats = 0, o_pm = 0, o_fin = 0, o_in = 0;
+    size_t f_pm = 0, f_shot = 0, fin_bytes = 0; // finish block: stats [B][W][8] | min_pm [B][W] | shot_result [B][2]
 };
 // Kernel variants: threads per shot, VNs per thread, column-degree bound, groups of four row positions.
 // A plan uses the first variant with NT >= m, NT*VF >= n, DM >= D, 4*KG >= K over all its windows.
@@ -169,7 +175,12 @@ struct Plan {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::unique_ptr<HostStream> hstream; // the host-buffer entry point swd_pipeline_decode runs on its own two-lane stream object
     std::vector<HostStream *> streams;   // live stream objects of the caller (swd_pipeline_stream_create), under mu
-    std::vector<Session *> sessions;     // live online sessions (swd_pipeline_session_create), under mu
+    std::vector<SessionBase *> sessions; // live online and rolling sessions (swd_pipeline_session_create / _rolling_create), under mu
+    // host copies of what finalize / swd_pipeline_set_observables upload (d_wins, d_colptr, d_rows, d_obs): a rolling session is
+    // checked and sized from them
+    std::vector<SwdWindowDev> h_wins;
+    std::vector<uint32_t> h_colptr, h_obs;
+    std::vector<uint16_t> h_rows;
 
     ~Plan() {
         (void)hipSetDevice(device);
@@ -189,12 +200,12 @@ struct Plan {
             hs->plan = nullptr;
         }
         // online sessions that outlive their pipeline, likewise: their launches read this plan's graphs
-        std::vector<Session *> live_s;
+        std::vector<SessionBase *> live_s;
         {
             std::lock_guard<std::recursive_mutex> lkp(mu);
             live_s.swap(sessions);
         }
-        for (Session *ss : live_s) {
+        for (SessionBase *ss : live_s) {
             std::lock_guard<std::mutex> lk(ss->mu);
             if (ss->ev_set) (void)hipEventSynchronize(ss->ev);
             ss->plan = nullptr;
@@ -355,6 +366,7 @@ struct Plan {
         }
         if (d_wins.reserve(hw.size() * sizeof(SwdWindowDev))) return -1;
         SWD_HIP(hipMemcpy(d_wins.p, hw.data(), hw.size() * sizeof(SwdWindowDev), hipMemcpyHostToDevice));
+        h_wins = std::move(hw);
         if (chk) {
             // CSC of the global check matrix for the residual-syndrome update (osd.py:178)
             if (chk->m > 65535) { set_error("more than 65535 detectors"); return -1; }
@@ -374,6 +386,7 @@ struct Plan {
             SWD_HIP(hipMemcpy((char *)d_chk.p + o_rows, rows.data(), rows.size() * 2, hipMemcpyHostToDevice));
             d_colptr = (const uint32_t *)d_chk.p;
             d_rows = (const uint16_t *)((char *)d_chk.p + o_rows);
+            h_colptr = std::move(cp); h_rows = std::move(rows);
             for (auto &w : wins)
                 if (w.col0 + w.commit > num_col) { set_error("commit range exceeds the global column count"); return -1; }
             for (auto &w : wins)

@@ -5,7 +5,7 @@
 //   window t ready (rows received >= its last row, window t - 1 committed):
 //       decode it on resid[:, row0 : row1]     -- the plan's own pipeline kernel, launched for window t alone as a pipeline of length 1
 //       commit the first `commit` columns, XOR their columns of the global check matrix into resid -- rows that have not arrived
-//       yet included -- and their observable masks into the accumulator                        (session_commit_kernel)
+//       yet included -- and their observable masks into the accumulator                        (window_commit_kernel, shift 0)
 //   after the last window: flagged = resid != 0, records transposed to [shot][window]          (session_finish_kernel)
 // The window loop is causal (window t reads rows < row1 of det ^ chk @ total_e_hat only) and XOR commutes, so every result equals the
 // one-launch decode's whatever the chunking.  The residual syndrome is one byte per bit inside 32-bit words, as in the decode
@@ -33,42 +33,70 @@ __global__ void __launch_bounds__(256) session_merge_kernel(uint8_t *resid, int6
     if (x) ((uint32_t *)(resid + (int64_t)b * res_stride))[q] ^= x;
 }
 
-struct SessionCommitArgs {
-    uint8_t *resid; int64_t res_stride;
+struct WindowCommitArgs {
+    uint8_t *rows; int64_t rows_stride;       // the staged rows of a shot: the fixed session's residual syndrome, the rolling session's frame
     const uint8_t *est; int64_t est_stride;   // the window's full estimate (win_out of the decode launch)
-    uint8_t *total; int64_t total_stride;
-    uint32_t *acc;                            // [B] observable accumulators
+    uint8_t *out; int64_t out_stride;         // [B][out_stride]: the committed faults of this step
+    uint32_t *acc, *flag;                     // [B] observable accumulators; sticky flagged words (nullable: the fixed session has none)
     const uint32_t *chk_colptr; const uint16_t *chk_rows; const uint32_t *obs_mask;
-    int32_t num_det, col0, commit;
+    int32_t *shot_result;                     // nullable [B][2]: written by the step that closes a rolling experiment
+    int32_t nrows, col0, commit, row_off;     // committed columns [col0, col0 + commit) of chk; staged row = row - row_off
+    int32_t shift;                            // rows that leave after this step (0, the fixed session: none)
 };
 
-// one workgroup per shot: the shot's residual words staged in LDS, the committed faults' columns of the global check matrix folded in
-// with LDS atomics (as the epilogue of pipeline_kernel does), written back whole (osd.py:170-178)
-__global__ void __launch_bounds__(256) session_commit_kernel(const SessionCommitArgs a) {
+// one workgroup per shot: the shot's rows staged in LDS (one byte per bit inside 32-bit words), the committed faults written out, their
+// columns of the global check matrix folded in with LDS atomics (as the epilogue of pipeline_kernel does; osd.py:170-178), their
+// observable masks XORed into the accumulator.  shift == 0: the words are written back as they are.  shift > 0: the outgoing rows are
+// ORed into the flagged word and the rest is written back moved down by `shift` rows (any number: the bytes, 0 or 1 each, are gathered
+// one by one) with zeros behind.
+__global__ void __launch_bounds__(256) window_commit_kernel(const WindowCommitArgs a) {
     extern __shared__ uint32_t sres[];
     __shared__ uint32_t sacc;
-    const int tid = threadIdx.x, b = blockIdx.x, nw = (a.num_det + 3) >> 2;
-    uint32_t *res32 = (uint32_t *)(a.resid + (int64_t)b * a.res_stride);
-    for (int q = tid; q < nw; q += 256) sres[q] = res32[q];
+    const int tid = threadIdx.x, b = blockIdx.x, nw = (a.nrows + 3) >> 2;
+    uint32_t *row32 = (uint32_t *)(a.rows + (int64_t)b * a.rows_stride);
+    for (int q = tid; q < nw; q += 256) sres[q] = row32[q];
     if (tid == 0) sacc = 0;
     __syncthreads();
     const uint8_t *est_b = a.est + (int64_t)b * a.est_stride;
-    uint8_t *tot_b = a.total + (int64_t)b * a.total_stride + a.col0;
+    uint8_t *out_b = a.out + (int64_t)b * a.out_stride;
     for (int i = tid; i < a.commit; i += 256) {
         const uint8_t hv = est_b[i];
-        tot_b[i] = hv;
+        out_b[i] = hv;
         if (hv) {
             const int c = a.col0 + i;
             if (a.obs_mask) { const uint32_t om = a.obs_mask[c]; if (om) atomicXor(&sacc, om); }
             for (uint32_t e = a.chk_colptr[c]; e < a.chk_colptr[c + 1]; ++e) {
-                const int r = a.chk_rows[e];
-                atomicXor(&sres[r >> 2], 1u << ((r & 3) * 8));
+                const int r = (int)a.chk_rows[e] - a.row_off;
+                if ((unsigned)r < (unsigned)a.nrows) atomicXor(&sres[r >> 2], 1u << ((r & 3) * 8)); // (always: row_off 0, or checked at creation)
             }
         }
     }
     __syncthreads();
-    for (int q = tid; q < nw; q += 256) res32[q] = sres[q];
-    if (tid == 0 && sacc) a.acc[b] ^= sacc;
+    int any = 0;
+    if (a.shift == 0) {
+        for (int q = tid; q < nw; q += 256) row32[q] = sres[q];
+    } else {
+        const uint8_t *sb = (const uint8_t *)sres;
+        int nz = 0;
+        for (int r = tid; r < a.shift; r += 256) nz |= sb[r];
+        any = __syncthreads_or(nz);
+        for (int q = tid; q < nw; q += 256) {
+            uint32_t x = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int src = 4 * q + j + a.shift;
+                if (src < a.nrows && sb[src]) x |= 1u << (8 * j);
+            }
+            row32[q] = x;
+        }
+    }
+    if (tid == 0) {
+        const uint32_t ac = a.acc[b] ^ sacc;
+        uint32_t fl = 0;
+        a.acc[b] = ac;
+        if (a.flag) { fl = a.flag[b] | (any ? 1u : 0u); a.flag[b] = fl; }
+        if (a.shot_result) { a.shot_result[2 * b] = (int32_t)ac; a.shot_result[2 * b + 1] = fl ? 1 : 0; }
+    }
 }
 
 // one workgroup per shot: shot_result as swd_pipeline_decode returns it (osd.py:184-187), the per-window records [t][shot] -> [shot][t]
@@ -89,10 +117,18 @@ __global__ void __launch_bounds__(256) session_finish_kernel(const uint8_t *resi
 }
 
 // the plan a session call works on; NULL (with a message) once the pipeline has been destroyed
-static Plan *session_plan(Session *s) {
+static Plan *session_plan(SessionBase *s) {
     if (!s->plan) set_error("the pipeline of this session has been destroyed");
     return s->plan;
 }
+
+// the prologue of every entry point after create: null handle -> message, the session's lock, its plan `d` or the message that it is gone
+#define SWD_SESSION_PROLOGUE(T, s, h)                 \
+    T *s = (T *)(h);                                  \
+    if (!s) { set_error("null session"); return -1; } \
+    std::lock_guard<std::mutex> lk(s->mu);            \
+    Plan *d = session_plan(s);                        \
+    if (!d) return -1
 
 // rows that must have arrived before window t is decoded: its last row; the last window closes the experiment and waits for every row
 static int session_need(const Plan *d, int t) {
@@ -100,19 +136,90 @@ static int session_need(const Plan *d, int t) {
 }
 
 // work on the state is ordered by one event: a call on another stream than the previous one waits for it first
-static int session_enter(Session *s, hipStream_t st) {
+static int session_enter(SessionBase *s, hipStream_t st) {
     if (s->ev_set && s->last != st) SWD_HIP(hipStreamWaitEvent(st, s->ev, 0));
     return 0;
 }
-static int session_leave(Session *s, hipStream_t st) {
+static int session_leave(SessionBase *s, hipStream_t st) {
     SWD_HIP(hipEventRecord(s->ev, st));
     s->ev_set = true; s->last = st;
     return 0;
 }
 
-static int session_push_dev(Session *s, int32_t nrows, const uint8_t *det_rows, int64_t stride, int32_t *first, int32_t *count, hipStream_t st) {
-    Plan *d = session_plan(s);
-    if (!d) return -1;
+// the tail of both creates: the LDS limit of the commit kernel (the attribute belongs to the function: up to 65 535 staged rows, one
+// word per four, against the default limit's 16 384 words) and the plan's list of live sessions
+static void session_attach(SessionBase *s, Plan *d) {
+    static std::mutex attr_mu;
+    {
+        std::lock_guard<std::mutex> lk(attr_mu);
+        (void)hipFuncSetAttribute((const void *)window_commit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    }
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    d->sessions.push_back(s);
+}
+
+static void session_destroy(SessionBase *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    if (Plan *d = s->plan) { // (a session whose pipeline went first was detached by ~Plan and only frees its own buffers)
+        std::lock_guard<std::recursive_mutex> lk(d->mu);
+        d->sessions.erase(std::remove(d->sessions.begin(), d->sessions.end(), s), d->sessions.end());
+    }
+    delete s;
+}
+
+// begin of both forms: the batch's shots zeroed in the given ranges of `dev` ({offset, bytes per shot}); the caller resets its counters
+static int session_begin(SessionBase *s, Plan *d, int32_t B, const char *form, std::initializer_list<std::pair<size_t, size_t>> zero) {
+    if (B <= 0 || B > s->max_shots) { set_error("%s begin: %d shots, the session was created for 1..%d", form, B, s->max_shots); return -1; }
+    SWD_HIP(hipSetDevice(d->device));
+    if (session_enter(s, s->st)) return -1;
+    for (const auto &z : zero) SWD_HIP(hipMemsetAsync((char *)s->dev.p + z.first, 0, (size_t)B * z.second, s->st));
+    s->B = B;
+    return session_leave(s, s->st);
+}
+
+// host rows [B][k] (row stride `stride`) through the page-locked block -- free here: every step of a host call ends synchronised --
+// to dev + o_in, packed [B][k]; `room`: bytes the block is sized for
+static int session_stage(SessionBase *s, size_t o_in, int k, const uint8_t *rows, int64_t stride, size_t room, hipStream_t st) {
+    if (s->hin.reserve(room)) return -1;
+    for (int b = 0; b < s->B; ++b) memcpy((char *)s->hin.p + (size_t)b * k, rows + (size_t)b * stride, (size_t)k);
+    SWD_HIP(hipMemcpyAsync((char *)s->dev.p + o_in, s->hin.p, (size_t)s->B * k, hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// rows [r, r + k) of the staged rows ^= the arriving rows
+static int launch_merge(uint8_t *rows, int64_t rows_stride, const uint8_t *in, int64_t in_stride, int B, int r, int k, hipStream_t st) {
+    const long long nthr = (long long)B * (((r + k - 1) >> 2) - (r >> 2) + 1);
+    hipLaunchKernelGGL(session_merge_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, rows, rows_stride, in, in_stride, B, r, k);
+    SWD_HIP(hipGetLastError());
+    return 0;
+}
+
+// the window decode: the plan's kernel on one window alone -- a pipeline of length 1 whose `det` is the staged rows (the kernel's
+// window-0 path reads absolute rows row0..), the full estimate through win_out, nothing committed by the kernel
+static int launch_window(Plan *d, const SwdWindowDev *win, int B, const uint8_t *rows, int64_t rows_stride, int nrows, uint8_t *est,
+                         int64_t est_stride, int32_t *stats, double *min_pm, hipStream_t st) {
+    SwdPipeArgs a{};
+    a.wins = win; a.W = 1; a.B = B;
+    a.slot_scratch = 1;
+    fill_params(d, a.P, false, false);
+    a.det = rows; a.det_stride = rows_stride; a.num_det = nrows; a.off_det = d->off_det;
+    a.total = nullptr; a.win_out = est; a.win_out_stride = est_stride;
+    a.stats = stats; a.min_pm = min_pm;
+    a.hist = nullptr; a.hist_stride = 4 * (int64_t)d->nmax;
+    return launch(d, a, st);
+}
+
+// ... and its commit, on the rows and the estimate of that launch: the plan's chk / obs are filled in here, the rest is the caller's
+static int launch_commit(Plan *d, WindowCommitArgs c, int B, hipStream_t st) {
+    c.chk_colptr = d->d_colptr; c.chk_rows = d->d_rows; c.obs_mask = d->d_obs.p ? d->d_obs.as<uint32_t>() : nullptr;
+    hipLaunchKernelGGL(window_commit_kernel, dim3(B), dim3(256), (size_t)((c.nrows + 3) / 4) * 4, st, c);
+    SWD_HIP(hipGetLastError());
+    return 0;
+}
+
+static int session_push_dev(Session *s, Plan *d, int32_t nrows, const uint8_t *det_rows, int64_t stride, int32_t *first, int32_t *count,
+                            hipStream_t st) {
     const int W = s->W;
     if (!s->B) { set_error("session push: call swd_pipeline_session_begin first"); return -1; }
     if (s->done == W) { set_error("session push: the last window has been committed (all %d rows received); finish or begin a new batch", s->rows); return -1; }
@@ -126,10 +233,7 @@ static int session_push_dev(Session *s, int32_t nrows, const uint8_t *det_rows, 
     char *dv = (char *)s->dev.p;
     const int B = s->B;
     if (nrows > 0) {
-        const long long nthr = (long long)B * (((s->rows + nrows - 1) >> 2) - (s->rows >> 2) + 1);
-        hipLaunchKernelGGL(session_merge_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, (uint8_t *)dv, s->res_stride, det_rows,
-                           stride ? stride : (int64_t)nrows, B, s->rows, nrows);
-        SWD_HIP(hipGetLastError());
+        if (launch_merge((uint8_t *)dv, s->res_stride, det_rows, stride ? stride : (int64_t)nrows, B, s->rows, nrows, st)) return -1;
         s->rows += nrows;
     }
     const int first_w = s->done;
@@ -137,27 +241,17 @@ static int session_push_dev(Session *s, int32_t nrows, const uint8_t *det_rows, 
     while (s->done < W && s->rows >= session_need(d, s->done)) {
         const int t = s->done;
         const WindowHost &w = d->wins[t];
-        // the window decode: the plan's kernel on window t alone -- a pipeline of length 1 whose `det` is the residual syndrome (the
-        // kernel's window-0 path reads absolute rows row0..), full estimate through win_out, nothing committed by the kernel
-        SwdPipeArgs a{};
-        a.wins = d->d_wins.as<SwdWindowDev>() + t; a.W = 1; a.B = B;
-        a.slot_scratch = 1;
-        fill_params(d, a.P, false, false);
-        a.det = (const uint8_t *)dv; a.det_stride = s->res_stride; a.num_det = d->num_det; a.off_det = d->off_det;
-        a.total = nullptr; a.win_out = (uint8_t *)(dv + s->o_est); a.win_out_stride = s->est_stride;
-        a.stats = (int32_t *)(dv + s->o_stats) + (size_t)t * s->max_shots * SWD_STAT_WORDS;
-        a.min_pm = (double *)(dv + s->o_pm) + (size_t)t * s->max_shots;
-        a.hist = nullptr; a.hist_stride = 4 * (int64_t)d->nmax;
-        if ((rc = launch(d, a, st)) != 0) break;
-        SessionCommitArgs c{};
-        c.resid = (uint8_t *)dv; c.res_stride = s->res_stride;
+        WindowCommitArgs c{}; // (no flag, no shift: the residual syndrome stays where it is, rows that have not arrived yet included)
+        c.rows = (uint8_t *)dv; c.rows_stride = s->res_stride; c.nrows = s->num_det;
         c.est = (const uint8_t *)(dv + s->o_est); c.est_stride = s->est_stride;
-        c.total = (uint8_t *)(dv + s->o_total); c.total_stride = s->num_col;
+        c.out = (uint8_t *)(dv + s->o_total) + w.col0; c.out_stride = s->num_col;
         c.acc = (uint32_t *)(dv + s->o_acc);
-        c.chk_colptr = d->d_colptr; c.chk_rows = d->d_rows; c.obs_mask = d->d_obs.p ? d->d_obs.as<uint32_t>() : nullptr;
-        c.num_det = s->num_det; c.col0 = w.col0; c.commit = w.commit;
-        hipLaunchKernelGGL(session_commit_kernel, dim3(B), dim3(256), (size_t)((s->num_det + 3) / 4) * 4, st, c);
-        SWD_HIP(hipGetLastError());
+        c.col0 = w.col0; c.commit = w.commit;
+        if ((rc = launch_window(d, d->d_wins.as<SwdWindowDev>() + t, B, c.rows, c.rows_stride, c.nrows, (uint8_t *)(dv + s->o_est), s->est_stride,
+                                (int32_t *)(dv + s->o_stats) + (size_t)t * s->max_shots * SWD_STAT_WORDS,
+                                (double *)(dv + s->o_pm) + (size_t)t * s->max_shots, st)) != 0 ||
+            (rc = launch_commit(d, c, B, st)) != 0)
+            break;
         s->done++;
     }
     if (session_leave(s, st)) return -1;
@@ -199,70 +293,35 @@ extern "C" swd_session *swd_pipeline_session_create(swd_pipeline *h, int32_t max
         delete s;
         return nullptr;
     }
-    static std::mutex attr_mu; // (the attribute belongs to the function: a residual syndrome of up to 65 535 rows, one word per four)
-    {
-        std::lock_guard<std::mutex> lk(attr_mu);
-        (void)hipFuncSetAttribute((const void *)session_commit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    }
-    { std::lock_guard<std::recursive_mutex> lk(d->mu); d->sessions.push_back(s); }
+    session_attach(s, d);
     return (swd_session *)s;
 }
 
-extern "C" void swd_pipeline_session_destroy(swd_session *h) {
-    Session *s = (Session *)h;
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (Plan *d = s->plan) { // (a session whose pipeline went first was detached by ~Plan and only frees its own buffers)
-        std::lock_guard<std::recursive_mutex> lk(d->mu);
-        d->sessions.erase(std::remove(d->sessions.begin(), d->sessions.end(), s), d->sessions.end());
-    }
-    delete s;
-}
+extern "C" void swd_pipeline_session_destroy(swd_session *h) { session_destroy((Session *)h); }
 
 extern "C" int swd_pipeline_session_begin(swd_session *h, int32_t B) {
-    Session *s = (Session *)h;
-    if (!s) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(s->mu);
-    Plan *d = session_plan(s);
-    if (!d) return -1;
-    if (B <= 0 || B > s->max_shots) { set_error("session begin: %d shots, the session was created for 1..%d", B, s->max_shots); return -1; }
-    SWD_HIP(hipSetDevice(d->device));
-    if (session_enter(s, s->st)) return -1;
-    // zero residual syndrome, total_e_hat and accumulators of the batch's shots
-    SWD_HIP(hipMemsetAsync(s->dev.p, 0, (size_t)B * s->res_stride, s->st));
-    SWD_HIP(hipMemsetAsync((char *)s->dev.p + s->o_total, 0, (size_t)B * s->num_col, s->st));
-    SWD_HIP(hipMemsetAsync((char *)s->dev.p + s->o_acc, 0, (size_t)B * 4, s->st));
-    s->B = B; s->rows = 0; s->done = 0;
-    return session_leave(s, s->st);
+    SWD_SESSION_PROLOGUE(Session, s, h);
+    // residual syndrome, total_e_hat and accumulators of the batch's shots
+    if (session_begin(s, d, B, "session", {{0, (size_t)s->res_stride}, {s->o_total, (size_t)s->num_col}, {s->o_acc, 4}})) return -1;
+    s->rows = 0; s->done = 0;
+    return 0;
 }
 
 extern "C" int swd_pipeline_session_push_dev(swd_session *h, int32_t nrows, const uint8_t *det_rows, int64_t stride, int32_t *first,
                                              int32_t *count, void *stream) {
-    Session *s = (Session *)h;
-    if (!s) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(s->mu);
-    return session_push_dev(s, nrows, det_rows, stride, first, count, (hipStream_t)stream);
+    SWD_SESSION_PROLOGUE(Session, s, h);
+    return session_push_dev(s, d, nrows, det_rows, stride, first, count, (hipStream_t)stream);
 }
 
 extern "C" int swd_pipeline_session_push(swd_session *h, int32_t nrows, const uint8_t *det_rows, int32_t *first, int32_t *count) {
-    Session *s = (Session *)h;
-    if (!s) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(s->mu);
-    Plan *d = session_plan(s);
-    if (!d) return -1;
+    SWD_SESSION_PROLOGUE(Session, s, h);
     const uint8_t *src = nullptr;
     if (nrows > 0 && det_rows && s->B && s->done < s->W && s->rows + (int64_t)nrows <= s->num_det) { // (anything else: session_push_dev refuses it with its message)
         SWD_HIP(hipSetDevice(d->device));
-        // the call is synchronous, so the page-locked block is free here: rows in, one copy to the device
-        const size_t bytes = (size_t)s->B * nrows;
-        if (s->hin.reserve(bytes)) return -1;
-        memcpy(s->hin.p, det_rows, bytes);
-        if (session_enter(s, s->st)) return -1;
-        SWD_HIP(hipMemcpyAsync((char *)s->dev.p + s->o_in, s->hin.p, bytes, hipMemcpyHostToDevice, s->st));
-        if (session_leave(s, s->st)) return -1;
+        if (session_enter(s, s->st) || session_stage(s, s->o_in, nrows, det_rows, nrows, (size_t)s->B * nrows, s->st) || session_leave(s, s->st)) return -1;
         src = (const uint8_t *)s->dev.p + s->o_in;
     }
-    const int rc = session_push_dev(s, nrows, src ? src : det_rows, 0, first, count, s->st); // (det_rows itself only on the refused paths)
+    const int rc = session_push_dev(s, d, nrows, src ? src : det_rows, 0, first, count, s->st); // (det_rows itself only on the refused paths)
     if (rc) return rc;
     SWD_HIP(hipStreamSynchronize(s->st));
     return 0;
@@ -279,11 +338,7 @@ static int session_fetch(Session *s, size_t dev_off, size_t bytes) {
 }
 
 extern "C" int swd_pipeline_session_window(swd_session *h, int32_t t, uint8_t *faults, int32_t *stats, double *min_pm) {
-    Session *s = (Session *)h;
-    if (!s) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(s->mu);
-    Plan *d = session_plan(s);
-    if (!d) return -1;
+    SWD_SESSION_PROLOGUE(Session, s, h);
     if (t < 0 || t >= s->done) { set_error("session window: window %d has not been committed (%d of %d are)", t, s->done, s->W); return -1; }
     SWD_HIP(hipSetDevice(d->device));
     const size_t B = (size_t)s->B;
@@ -307,11 +362,7 @@ extern "C" int swd_pipeline_session_window(swd_session *h, int32_t t, uint8_t *f
 }
 
 extern "C" int swd_pipeline_session_finish(swd_session *h, uint8_t *total, int32_t *stats, double *min_pm, int32_t *shot_result) {
-    Session *s = (Session *)h;
-    if (!s) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(s->mu);
-    Plan *d = session_plan(s);
-    if (!d) return -1;
+    SWD_SESSION_PROLOGUE(Session, s, h);
     if (!s->B) { set_error("session finish: call swd_pipeline_session_begin first"); return -1; }
     if (s->done < s->W) {
         set_error("session finish: window %d of %d waits for detector rows %d..%d (%d of %d received)", s->done, s->W, s->rows,
@@ -339,10 +390,8 @@ extern "C" int swd_pipeline_session_finish(swd_session *h, uint8_t *total, int32
 
 extern "C" int swd_pipeline_session_buffers(swd_session *h, uint8_t **total, int64_t *total_stride, int32_t *rows_received,
                                             int32_t *windows_done) {
-    Session *s = (Session *)h;
-    if (!s) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (!session_plan(s)) return -1;
+    SWD_SESSION_PROLOGUE(Session, s, h);
+    (void)d;
     if (total) *total = (uint8_t *)s->dev.p + s->o_total;
     if (total_stride) *total_stride = s->num_col;
     if (rows_received) *rows_received = s->rows;
@@ -356,72 +405,14 @@ extern "C" int swd_pipeline_session_buffers(swd_session *h, uint8_t **total, int
 // accumulator and a sticky flagged word -- nothing that grows with the experiment:
 //   arrival of k rows:      frame[:, fill : fill + k] ^= rows                                           (session_merge_kernel)
 //   frame holds a window:   decode it on frame[:, 0 : m] -- the plan's kernel as a pipeline of length 1 on a descriptor whose row0 is 0 --
-//                           commit, fold chk, accumulate observables, flag and drop the F * h rows that leave   (rolling_commit_kernel)
+//                           commit, fold chk, accumulate observables, flag and drop the F * h rows that leave   (window_commit_kernel, shift > 0)
 //   finish:                 the last rows, the tail window, committed whole; every row left in the frame goes into the flag
 // The global check matrix of the template serves every window: body window t of a long experiment commits the columns of the
 // template's window 1, and its rows are those of window 1 moved down -- in frame rows both are `row - row0 of window 1`.
 namespace swd {
 
-struct RollingCommitArgs {
-    uint8_t *frame; int64_t frame_stride;
-    const uint8_t *est; int64_t est_stride;   // the window's full estimate (win_out of the decode launch)
-    uint8_t *out; int64_t out_stride;         // [B][out_stride]: the committed faults of this step
-    uint32_t *acc, *flag;                     // [B] observable accumulators, sticky flagged words
-    const uint32_t *chk_colptr; const uint16_t *chk_rows; const uint32_t *obs_mask;
-    int32_t *shot_result;                     // nullable [B][2]: written by the step that closes the experiment
-    int32_t frame_rows, col0, commit, row_off; // committed columns [col0, col0 + commit) of the template's chk; frame row = row - row_off
-    int32_t shift;                            // rows that leave the frame after this step
-};
-
-// one workgroup per shot: the frame staged in LDS (one byte per bit inside 32-bit words), the committed faults' columns folded in
-// with LDS atomics, the `shift` outgoing rows ORed into the flagged word, the frame written back moved down by `shift` rows (any
-// number: the bytes are gathered one by one) with zeros behind
-__global__ void __launch_bounds__(256) rolling_commit_kernel(const RollingCommitArgs a) {
-    extern __shared__ uint32_t sres[];
-    __shared__ uint32_t sacc;
-    const int tid = threadIdx.x, b = blockIdx.x, nw = (a.frame_rows + 3) >> 2;
-    uint32_t *fr32 = (uint32_t *)(a.frame + (int64_t)b * a.frame_stride);
-    for (int q = tid; q < nw; q += 256) sres[q] = fr32[q];
-    if (tid == 0) sacc = 0;
-    __syncthreads();
-    const uint8_t *est_b = a.est + (int64_t)b * a.est_stride;
-    uint8_t *out_b = a.out + (int64_t)b * a.out_stride;
-    for (int i = tid; i < a.commit; i += 256) {
-        const uint8_t hv = est_b[i];
-        out_b[i] = hv;
-        if (hv) {
-            const int c = a.col0 + i;
-            if (a.obs_mask) { const uint32_t om = a.obs_mask[c]; if (om) atomicXor(&sacc, om); }
-            for (uint32_t e = a.chk_colptr[c]; e < a.chk_colptr[c + 1]; ++e) {
-                const int r = (int)a.chk_rows[e] - a.row_off;
-                if ((unsigned)r < (unsigned)a.frame_rows) atomicXor(&sres[r >> 2], 1u << ((r & 3) * 8)); // (always: checked at creation)
-            }
-        }
-    }
-    __syncthreads();
-    const uint8_t *sb = (const uint8_t *)sres;
-    int nz = 0;
-    for (int r = tid; r < a.shift; r += 256) nz |= sb[r];
-    const int any = __syncthreads_or(nz);
-    for (int q = tid; q < nw; q += 256) {
-        uint32_t x = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int src = 4 * q + j + a.shift;
-            if (src < a.frame_rows && sb[src]) x |= 1u << (8 * j);
-        }
-        fr32[q] = x;
-    }
-    if (tid == 0) {
-        const uint32_t ac = a.acc[b] ^ sacc, fl = a.flag[b] | (any ? 1u : 0u);
-        a.acc[b] = ac; a.flag[b] = fl;
-        if (a.shot_result) { a.shot_result[2 * b] = (int32_t)ac; a.shot_result[2 * b + 1] = fl ? 1 : 0; }
-    }
-}
-
-// A rolling session IS a session for the plan's book-keeping (Plan::sessions: detached when the pipeline goes first) and for the
-// stream ordering; it has its own state layout.
-struct Rolling : Session {
+// the state of a rolling session: nothing in it grows with the experiment
+struct Rolling : SessionBase {
     enum { HEAD = 0, BODY = 1, TAIL = 2 };
     struct Kind { int col0, commit, row_off, rows; } kd[3]{};
     int frame_rows = 0, row_stride = 0, cmax = 0, call = 0; // cmax: head / body commits; call: the tail's too
@@ -459,30 +450,18 @@ static int rolling_step(Rolling *r, Plan *d, int kind, RollingOut &o, hipStream_
     auto dest = [&](auto *caller, size_t slot_elems, size_t own_off) {
         return (!o.host && caller) ? caller + (size_t)k * slot_elems : (decltype(caller))(dv + r->o_out + own_off);
     };
-    uint8_t *faults = dest(o.faults, (size_t)B * fstride, 0);
-    int32_t *stats = dest(o.stats, (size_t)B * SWD_STAT_WORDS, r->s_stats);
-    double *pm = dest(o.min_pm, (size_t)B, r->s_pm);
-    int32_t *shot = kind == Rolling::TAIL ? dest(o.shot_result, 0, r->s_shot) : nullptr;
-    SwdPipeArgs a{};
-    a.wins = r->wins3.as<SwdWindowDev>() + kind; a.W = 1; a.B = B;
-    a.slot_scratch = 1;
-    fill_params(d, a.P, false, false);
-    a.det = (const uint8_t *)dv; a.det_stride = r->frame_stride; a.num_det = r->frame_rows; a.off_det = d->off_det;
-    a.total = nullptr; a.win_out = (uint8_t *)(dv + r->o_est); a.win_out_stride = r->est_stride;
-    a.stats = stats; a.min_pm = pm;
-    a.hist = nullptr; a.hist_stride = 4 * (int64_t)d->nmax;
-    if (launch(d, a, st)) return -1;
-    RollingCommitArgs c{};
-    c.frame = (uint8_t *)dv; c.frame_stride = r->frame_stride; c.frame_rows = r->frame_rows;
+    WindowCommitArgs c{};
+    c.rows = (uint8_t *)dv; c.rows_stride = r->frame_stride; c.nrows = r->frame_rows;
     c.est = (const uint8_t *)(dv + r->o_est); c.est_stride = r->est_stride;
-    c.out = faults; c.out_stride = fstride;
+    c.out = dest(o.faults, (size_t)B * fstride, 0); c.out_stride = fstride;
     c.acc = (uint32_t *)(dv + r->o_acc); c.flag = (uint32_t *)(dv + r->o_flag);
-    c.chk_colptr = d->d_colptr; c.chk_rows = d->d_rows; c.obs_mask = d->d_obs.p ? d->d_obs.as<uint32_t>() : nullptr;
-    c.shot_result = shot;
+    c.shot_result = kind == Rolling::TAIL ? dest(o.shot_result, 0, r->s_shot) : nullptr;
     c.col0 = K.col0; c.commit = K.commit; c.row_off = K.row_off;
     c.shift = kind == Rolling::TAIL ? r->frame_rows : r->row_stride;
-    hipLaunchKernelGGL(rolling_commit_kernel, dim3(B), dim3(256), (size_t)((r->frame_rows + 3) / 4) * 4, st, c);
-    SWD_HIP(hipGetLastError());
+    if (launch_window(d, r->wins3.as<SwdWindowDev>() + kind, B, c.rows, c.rows_stride, c.nrows, (uint8_t *)(dv + r->o_est), r->est_stride,
+                      dest(o.stats, (size_t)B * SWD_STAT_WORDS, r->s_stats), dest(o.min_pm, (size_t)B, r->s_pm), st) ||
+        launch_commit(d, c, B, st))
+        return -1;
     if (o.host) { // the one-step block -> the caller's host arrays, before the next window overwrites it
         if (r->hout.reserve(std::max(r->out_bytes, (size_t)4096))) return -1;
         SWD_HIP(hipMemcpyAsync(r->hout.p, dv + r->o_out, r->out_bytes, hipMemcpyDeviceToHost, st));
@@ -515,16 +494,11 @@ static int rolling_rows(Rolling *r, Plan *d, int nrows, const uint8_t *rows, int
         const int k = std::min(nrows - done, r->frame_rows - r->fill); // (> 0: a frame that holds a window has been decoded)
         const uint8_t *src = rows + done;
         int64_t sstride = stride;
-        if (o.host) { // the piece through the page-locked block (free here: every step of a host call ends synchronised)
-            if (r->hin.reserve(std::max((size_t)B * r->frame_rows, (size_t)4096))) return -1;
-            for (int b = 0; b < B; ++b) memcpy((char *)r->hin.p + (size_t)b * k, rows + (size_t)b * stride + done, (size_t)k);
-            SWD_HIP(hipMemcpyAsync(dv + r->o_in, r->hin.p, (size_t)B * k, hipMemcpyHostToDevice, st));
+        if (o.host) {
+            if (session_stage(r, r->o_in, k, src, stride, std::max((size_t)B * r->frame_rows, (size_t)4096), st)) return -1;
             src = (const uint8_t *)(dv + r->o_in); sstride = k;
         }
-        const long long nthr = (long long)B * (((r->fill + k - 1) >> 2) - (r->fill >> 2) + 1);
-        hipLaunchKernelGGL(session_merge_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, (uint8_t *)dv, r->frame_stride, src,
-                           sstride, B, r->fill, k);
-        SWD_HIP(hipGetLastError());
+        if (launch_merge((uint8_t *)dv, r->frame_stride, src, sstride, B, r->fill, k, st)) return -1;
         r->fill += k; r->rows64 += k; done += k;
         if (o.host) SWD_HIP(hipStreamSynchronize(st)); // (hin is reused by the next piece)
         while (o.decode_windows && r->fill >= r->kd[Rolling::HEAD].rows) {
@@ -535,10 +509,8 @@ static int rolling_rows(Rolling *r, Plan *d, int nrows, const uint8_t *rows, int
     return 0;
 }
 
-static int rolling_push(Rolling *r, int32_t nrows, const uint8_t *rows, int64_t stride, RollingOut &o, int64_t *first, int32_t *count,
+static int rolling_push(Rolling *r, Plan *d, int32_t nrows, const uint8_t *rows, int64_t stride, RollingOut &o, int64_t *first, int32_t *count,
                         hipStream_t st) {
-    Plan *d = session_plan(r);
-    if (!d) return -1;
     if (!r->B) { set_error("rolling push: call swd_pipeline_rolling_begin first"); return -1; }
     if (r->closed) { set_error("rolling push: the experiment has been finished; begin a new batch"); return -1; }
     if (nrows < 0 || (nrows > 0 && !rows)) { set_error(nrows < 0 ? "rolling push: negative row count" : "null input pointer"); return -1; }
@@ -557,9 +529,7 @@ static int rolling_push(Rolling *r, int32_t nrows, const uint8_t *rows, int64_t 
     return rc;
 }
 
-static int rolling_finish(Rolling *r, int32_t nrows, const uint8_t *rows, int64_t stride, RollingOut &o, hipStream_t st) {
-    Plan *d = session_plan(r);
-    if (!d) return -1;
+static int rolling_finish(Rolling *r, Plan *d, int32_t nrows, const uint8_t *rows, int64_t stride, RollingOut &o, hipStream_t st) {
     if (!r->B) { set_error("rolling finish: call swd_pipeline_rolling_begin first"); return -1; }
     if (r->closed) { set_error("rolling finish: the experiment has been finished; begin a new batch"); return -1; }
     if (nrows < 0 || (nrows > 0 && !rows)) { set_error(nrows < 0 ? "rolling finish: negative row count" : "null input pointer"); return -1; }
@@ -612,16 +582,9 @@ extern "C" swd_rolling *swd_pipeline_rolling_create(swd_pipeline *h, int32_t max
         if (w.row0 - d->wins[k - 1].row0 != rs || w.col0 - d->wins[k - 1].col0 != cs) { set_error("rolling template: window %d is not placed one stride after window %d", k, k - 1); return nullptr; }
         if (k < n - 1 && (w.g != w1.g || w.commit != w1.commit || w.new_n != w1.new_n)) { set_error("rolling template: window %d is not periodic (matrix, priors or commit differ from window 1)", k); return nullptr; }
     }
-    // host copy of the CSC of chk and the observable masks: periodicity of the committed columns, and the rows they reach
-    std::vector<uint32_t> cp((size_t)d->num_col + 1);
-    if (hipMemcpy(cp.data(), d->d_colptr, cp.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_error("rolling template: reading chk failed"); return nullptr; }
-    std::vector<uint16_t> rows(cp.back());
-    if (!rows.empty() && hipMemcpy(rows.data(), d->d_rows, rows.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) { set_error("rolling template: reading chk failed"); return nullptr; }
-    std::vector<uint32_t> om;
-    if (d->d_obs.p) {
-        om.resize(d->num_col);
-        if (hipMemcpy(om.data(), d->d_obs.p, om.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_error("rolling template: reading obs failed"); return nullptr; }
-    }
+    // the plan's host copy of the CSC of chk and the observable masks: periodicity of the committed columns, and the rows they reach
+    const std::vector<uint32_t> &cp = d->h_colptr, &om = d->h_obs;
+    const std::vector<uint16_t> &rows = d->h_rows;
     for (int k = 2; k < n - 1; ++k)
         for (int i = 0; i < cs; ++i) {
             const int ca = w1.col0 + i, cb = d->wins[k].col0 + i;
@@ -630,14 +593,17 @@ extern "C" swd_rolling *swd_pipeline_rolling_create(swd_pipeline *h, int32_t max
             if (!same) { set_error("rolling template: chk / obs are not periodic (column %d of window %d against window 1)", i, k); return nullptr; }
         }
     Rolling *r = new Rolling();
-    const WindowHost *kw[3] = {&w0, &w1, &wl};
+    const int idx[3] = {0, 1, n - 1};
+    std::vector<SwdWindowDev> hw(3); // the three descriptors: the plan's own, at frame row 0
     int frame = 0;
     for (int j = 0; j < 3; ++j) {
-        const WindowHost &w = *kw[j];
+        const WindowHost &w = d->wins[idx[j]];
         r->kd[j] = {w.col0, w.commit, w.row0, w.g->m};
+        hw[j] = d->h_wins[idx[j]];
+        hw[j].row0 = 0;
         frame = std::max(frame, w.g->m);
         for (uint32_t e = cp[w.col0]; e < cp[w.col0 + w.commit]; ++e) {
-            if (rows[e] < w.row0) { set_error("rolling template: a committed column of window %d touches row %d, before the window", j == 2 ? n - 1 : j, (int)rows[e]); delete r; return nullptr; }
+            if (rows[e] < w.row0) { set_error("rolling template: a committed column of window %d touches row %d, before the window", idx[j], (int)rows[e]); delete r; return nullptr; }
             frame = std::max(frame, (int)rows[e] - w.row0 + 1);
         }
     }
@@ -659,110 +625,68 @@ extern "C" swd_rolling *swd_pipeline_rolling_create(swd_pipeline *h, int32_t max
     r->out_bytes = r->s_shot + al(B * 8);
     r->o_in = r->o_out + r->out_bytes;
     r->dev_bytes = r->o_in + al(B * (size_t)frame);
-    // the three descriptors: the plan's own, at frame row 0
-    std::vector<SwdWindowDev> hw(3);
-    const int idx[3] = {0, 1, n - 1};
-    bool ok = hipMemcpy(hw.data(), d->d_wins.as<SwdWindowDev>(), sizeof(SwdWindowDev), hipMemcpyDeviceToHost) == hipSuccess;
-    for (int j = 1; ok && j < 3; ++j)
-        ok = hipMemcpy(&hw[j], d->d_wins.as<SwdWindowDev>() + idx[j], sizeof(SwdWindowDev), hipMemcpyDeviceToHost) == hipSuccess;
-    for (auto &w : hw) w.row0 = 0;
-    if (!ok || r->dev.reserve(r->dev_bytes) || r->wins3.reserve(3 * sizeof(SwdWindowDev)) ||
+    if (r->dev.reserve(r->dev_bytes) || r->wins3.reserve(3 * sizeof(SwdWindowDev)) ||
         hipMemcpy(r->wins3.p, hw.data(), 3 * sizeof(SwdWindowDev), hipMemcpyHostToDevice) != hipSuccess ||
         hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&r->ev, hipEventDisableTiming) != hipSuccess) {
-        if (!ok || r->dev.p) set_error("rolling session: descriptor copy / stream / event creation failed");
+        if (r->dev.p) set_error("rolling session: descriptor copy / stream / event creation failed");
         delete r;
         return nullptr;
     }
     r->dev_bytes = r->dev.cap + r->wins3.cap;
-    // (frame_rows <= num_det <= 65 535: the dynamic LDS of rolling_commit_kernel stays below the default limit's 64 KB only up to
-    // 16 384 words -- raise it as session_commit_kernel does)
-    static std::mutex attr_mu;
-    {
-        std::lock_guard<std::mutex> lk(attr_mu);
-        (void)hipFuncSetAttribute((const void *)rolling_commit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    }
-    { std::lock_guard<std::recursive_mutex> lk(d->mu); d->sessions.push_back(r); }
+    session_attach(r, d);
     return (swd_rolling *)r;
 }
 
-extern "C" void swd_pipeline_rolling_destroy(swd_rolling *h) {
-    Rolling *r = (Rolling *)h;
-    if (!r) return;
-    (void)hipSetDevice(r->device);
-    if (Plan *d = r->plan) {
-        std::lock_guard<std::recursive_mutex> lk(d->mu);
-        d->sessions.erase(std::remove(d->sessions.begin(), d->sessions.end(), (Session *)r), d->sessions.end());
-    }
-    delete r;
-}
+extern "C" void swd_pipeline_rolling_destroy(swd_rolling *h) { session_destroy((Rolling *)h); }
 
 extern "C" int swd_pipeline_rolling_begin(swd_rolling *h, int32_t B) {
-    Rolling *r = (Rolling *)h;
-    if (!r) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(r->mu);
-    Plan *d = session_plan(r);
-    if (!d) return -1;
-    if (B <= 0 || B > r->max_shots) { set_error("rolling begin: %d shots, the session was created for 1..%d", B, r->max_shots); return -1; }
-    SWD_HIP(hipSetDevice(d->device));
-    if (session_enter(r, r->st)) return -1;
-    // zero frames, flagged words and accumulators of the batch's shots
-    SWD_HIP(hipMemsetAsync(r->dev.p, 0, (size_t)B * r->frame_stride, r->st));
-    SWD_HIP(hipMemsetAsync((char *)r->dev.p + r->o_flag, 0, (size_t)B * 4, r->st));
-    SWD_HIP(hipMemsetAsync((char *)r->dev.p + r->o_acc, 0, (size_t)B * 4, r->st));
-    r->B = B; r->fill = 0; r->rows64 = 0; r->done64 = 0; r->closed = false;
-    return session_leave(r, r->st);
+    SWD_SESSION_PROLOGUE(Rolling, r, h);
+    // frames, flagged words and accumulators of the batch's shots
+    if (session_begin(r, d, B, "rolling", {{0, (size_t)r->frame_stride}, {r->o_flag, 4}, {r->o_acc, 4}})) return -1;
+    r->fill = 0; r->rows64 = 0; r->done64 = 0; r->closed = false;
+    return 0;
 }
 
 extern "C" int swd_pipeline_rolling_push_dev(swd_rolling *h, int32_t nrows, const uint8_t *det_rows, int64_t stride, int32_t max_windows,
                                              uint8_t *faults, int32_t *stats, double *min_pm, int64_t *first, int32_t *count, void *stream) {
-    Rolling *r = (Rolling *)h;
-    if (!r) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(r->mu);
+    SWD_SESSION_PROLOGUE(Rolling, r, h);
     RollingOut o;
     o.faults = faults; o.stats = stats; o.min_pm = min_pm; o.max_windows = std::max(max_windows, 0);
-    return rolling_push(r, nrows, det_rows, stride, o, first, count, (hipStream_t)stream);
+    return rolling_push(r, d, nrows, det_rows, stride, o, first, count, (hipStream_t)stream);
 }
 
 extern "C" int swd_pipeline_rolling_push(swd_rolling *h, int32_t nrows, const uint8_t *det_rows, int32_t max_windows, uint8_t *faults,
                                          int32_t *stats, double *min_pm, int64_t *first, int32_t *count) {
-    Rolling *r = (Rolling *)h;
-    if (!r) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(r->mu);
+    SWD_SESSION_PROLOGUE(Rolling, r, h);
     RollingOut o;
     o.faults = faults; o.stats = stats; o.min_pm = min_pm; o.max_windows = std::max(max_windows, 0); o.host = true;
-    if (rolling_push(r, nrows, det_rows, 0, o, first, count, r->st)) return -1;
+    if (rolling_push(r, d, nrows, det_rows, 0, o, first, count, r->st)) return -1;
     SWD_HIP(hipStreamSynchronize(r->st));
     return 0;
 }
 
 extern "C" int swd_pipeline_rolling_finish_dev(swd_rolling *h, int32_t nrows, const uint8_t *final_rows, int64_t stride, uint8_t *faults,
                                                int32_t *stats, double *min_pm, int32_t *shot_result, void *stream) {
-    Rolling *r = (Rolling *)h;
-    if (!r) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(r->mu);
+    SWD_SESSION_PROLOGUE(Rolling, r, h);
     RollingOut o;
     o.faults = faults; o.stats = stats; o.min_pm = min_pm; o.shot_result = shot_result;
-    return rolling_finish(r, nrows, final_rows, stride, o, (hipStream_t)stream);
+    return rolling_finish(r, d, nrows, final_rows, stride, o, (hipStream_t)stream);
 }
 
 extern "C" int swd_pipeline_rolling_finish(swd_rolling *h, int32_t nrows, const uint8_t *final_rows, uint8_t *faults, int32_t *stats,
                                            double *min_pm, int32_t *shot_result) {
-    Rolling *r = (Rolling *)h;
-    if (!r) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(r->mu);
+    SWD_SESSION_PROLOGUE(Rolling, r, h);
     RollingOut o;
     o.faults = faults; o.stats = stats; o.min_pm = min_pm; o.shot_result = shot_result; o.host = true;
-    if (rolling_finish(r, nrows, final_rows, 0, o, r->st)) return -1;
+    if (rolling_finish(r, d, nrows, final_rows, 0, o, r->st)) return -1;
     SWD_HIP(hipStreamSynchronize(r->st));
     return 0;
 }
 
 extern "C" int swd_pipeline_rolling_state(swd_rolling *h, int64_t *rows_received, int64_t *windows_done, int32_t *frame_fill, int32_t *info,
                                           int64_t *device_bytes) {
-    Rolling *r = (Rolling *)h;
-    if (!r) { set_error("null session"); return -1; }
-    std::lock_guard<std::mutex> lk(r->mu);
-    if (!session_plan(r)) return -1;
+    SWD_SESSION_PROLOGUE(Rolling, r, h);
+    (void)d;
     if (rows_received) *rows_received = r->rows64;
     if (windows_done) *windows_done = r->done64;
     if (frame_fill) *frame_fill = r->fill;

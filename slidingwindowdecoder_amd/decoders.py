@@ -904,24 +904,15 @@ class SlidingWindowStream:
             raise RuntimeError(f"swd_pipeline_stream_wait failed: {_lib.last_error()}")
 
 
-class SlidingWindowSession:
-    """Online session of a ``SlidingWindowDecoder`` (C ABI: swd_pipeline_session_*): the window loop of
-    /root/reference/osd.py:130-179 driven by the arrival of detector rows.  The session keeps the residual syndrome,
-    total_e_hat and the observable accumulators of one batch on the device; ``push`` takes the next rows of every shot (any
-    number, in row order) and returns the windows they completed, each decoded on the rows received so far and committed --
-    bit-identical to ``decode`` of the whole experiment, whatever the chunking."""
-
-    def __init__(self, dec, max_shots):
-        self.dec, self.max_shots, self.B = dec, int(max_shots), 0
-        self._h = _lib.lib().swd_pipeline_session_create(dec._h, self.max_shots)
-        if not self._h:
-            raise RuntimeError(f"swd_pipeline_session_create failed: {_lib.last_error()}")
+class _SessionBase:
+    """What ``SlidingWindowSession`` and ``RollingSession`` share: the handle's life, ``begin`` and the checks of arriving rows.
+    ``_C``: the prefix of the form's C symbols."""
 
     def close(self):
         h = getattr(self, "_h", None)
         if h:
             try:
-                _lib.lib().swd_pipeline_session_destroy(h)
+                getattr(_lib.lib(), self._C + "_destroy")(h)
             except Exception:
                 pass
             self._h = None
@@ -930,9 +921,41 @@ class SlidingWindowSession:
 
     def begin(self, B):
         """Zero state for a batch of ``B <= max_shots`` shots; also restarts a session that has been used."""
-        if _lib.lib().swd_pipeline_session_begin(self._h, int(B)):
-            raise RuntimeError(f"swd_pipeline_session_begin failed: {_lib.last_error()}")
+        if getattr(_lib.lib(), self._C + "_begin")(self._h, int(B)):
+            raise RuntimeError(f"{self._C}_begin failed: {_lib.last_error()}")
         self.B = int(B)
+
+    def _host_rows(self, rows, name="det_rows"):
+        """[B, k] host rows as a C-contiguous uint8 array"""
+        d = np.asarray(rows)
+        if d.ndim != 2 or d.shape[0] != self.B:
+            raise ValueError(f"{name} must have shape [{self.B}, k]")
+        if d.dtype != np.uint8 or not d.flags.c_contiguous:
+            d = np.ascontiguousarray((d.astype(np.int64) & 0xFF).astype(np.uint8))
+        return d
+
+    def _check_device_rows(self, det_rows):
+        import torch
+        if det_rows.dtype != torch.uint8 or det_rows.dim() != 2 or det_rows.shape[0] != self.B or not det_rows.is_cuda or \
+                (det_rows.shape[1] > 1 and det_rows.stride(1) != 1):
+            raise ValueError(f"det_rows must be a uint8 CUDA tensor [{self.B}, k] with unit column stride")
+        if det_rows.device.index != self.dec.device:
+            raise ValueError(f"det_rows lives on {det_rows.device}, the pipeline on cuda:{self.dec.device}")
+
+
+class SlidingWindowSession(_SessionBase):
+    """Online session of a ``SlidingWindowDecoder`` (C ABI: swd_pipeline_session_*): the window loop of
+    /root/reference/osd.py:130-179 driven by the arrival of detector rows.  The session keeps the residual syndrome,
+    total_e_hat and the observable accumulators of one batch on the device; ``push`` takes the next rows of every shot (any
+    number, in row order) and returns the windows they completed, each decoded on the rows received so far and committed --
+    bit-identical to ``decode`` of the whole experiment, whatever the chunking."""
+    _C = "swd_pipeline_session"
+
+    def __init__(self, dec, max_shots):
+        self.dec, self.max_shots, self.B = dec, int(max_shots), 0
+        self._h = _lib.lib().swd_pipeline_session_create(dec._h, self.max_shots)
+        if not self._h:
+            raise RuntimeError(f"swd_pipeline_session_create failed: {_lib.last_error()}")
 
     def _progress(self):
         rows, done = C.c_int32(), C.c_int32()
@@ -966,11 +989,7 @@ class SlidingWindowSession:
     def push(self, det_rows):
         """det_rows [B, k] (host): the next k detector rows of every shot.  Returns the windows this call committed, in order, as
         ``(t, col0, faults [B, commit], stats [B, 8], min_pm [B])`` -- ``faults`` is ``total_e_hat[:, col0:col0 + commit]``."""
-        d = np.asarray(det_rows)
-        if d.ndim != 2 or d.shape[0] != self.B:
-            raise ValueError(f"det_rows must have shape [{self.B}, k]")
-        if d.dtype != np.uint8 or not d.flags.c_contiguous:
-            d = np.ascontiguousarray((d.astype(np.int64) & 0xFF).astype(np.uint8))
+        d = self._host_rows(det_rows)
         first, count = C.c_int32(), C.c_int32()
         if _lib.lib().swd_pipeline_session_push(self._h, d.shape[1], d.ctypes.data, C.byref(first), C.byref(count)):
             raise RuntimeError(f"swd_pipeline_session_push failed: {_lib.last_error()}")
@@ -980,11 +999,7 @@ class SlidingWindowSession:
         """torch uint8 CUDA tensor [B, k] with unit column stride (a column slice of a [B, num_det] tensor fits); merge, decode and
         commit are queued on ``stream`` (default: the current torch stream).  Returns (first, count) of the windows queued."""
         import torch
-        if det_rows.dtype != torch.uint8 or det_rows.dim() != 2 or det_rows.shape[0] != self.B or not det_rows.is_cuda or \
-                (det_rows.shape[1] > 1 and det_rows.stride(1) != 1):
-            raise ValueError(f"det_rows must be a uint8 CUDA tensor [{self.B}, k] with unit column stride")
-        if det_rows.device.index != self.dec.device:
-            raise ValueError(f"det_rows lives on {det_rows.device}, the pipeline on cuda:{self.dec.device}")
+        self._check_device_rows(det_rows)
         st = torch.cuda.current_stream(det_rows.device) if stream is None else stream
         first, count = C.c_int32(), C.c_int32()
         k = det_rows.shape[1]
@@ -1020,7 +1035,7 @@ class SlidingWindowSession:
         return torch.as_tensor(v, device=f"cuda:{self.dec.device}")
 
 
-class RollingSession:
+class RollingSession(_SessionBase):
     """Rolling session of a ``SlidingWindowDecoder`` (C ABI: swd_pipeline_rolling_*) whose plan of R0 rounds is the template: head =
     window 0, body = window 1, tail = last window.  It decodes experiments of any length ``R = R0 (mod F)`` rounds, known only when
     they end, with device memory that does not depend on R: per shot a frame of residual rows (``template.frame_rows``), an
@@ -1036,6 +1051,7 @@ class RollingSession:
     One thread at a time per session at this layer: ``push`` sizes its output arrays from a state query made before the call, so
     two threads pushing on one session would size them for the wrong state (the library then refuses the call, it does not
     overrun).  The C ABI itself may be called from any thread."""
+    _C = "swd_pipeline_rolling"
 
     def __init__(self, dec, max_shots):
         from .windows import rolling_template
@@ -1053,23 +1069,6 @@ class RollingSession:
                 max(T.head.commit, T.body.commit)]
         if list(info) != [int(x) for x in want]:
             raise RuntimeError(f"rolling template: the library extracted {list(info)}, windows.rolling_template {want}")
-
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.lib().swd_pipeline_rolling_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    __del__ = close
-
-    def begin(self, B):
-        """Zero state for a batch of ``B <= max_shots`` shots; also restarts a session that has been used."""
-        if _lib.lib().swd_pipeline_rolling_begin(self._h, int(B)):
-            raise RuntimeError(f"swd_pipeline_rolling_begin failed: {_lib.last_error()}")
-        self.B = int(B)
 
     def _state(self):
         rows, done, fill, nbytes = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
@@ -1110,11 +1109,7 @@ class RollingSession:
     def push(self, det_rows):
         """det_rows [B, k] (host): the next k rows of the syndrome rounds of every shot.  Returns the windows this call completed, in
         order, as ``(t, faults [B, commit_t], stats [B, 8], min_pm [B])``; ``t`` counts from 0 without bound."""
-        d = np.asarray(det_rows)
-        if d.ndim != 2 or d.shape[0] != self.B:
-            raise ValueError(f"det_rows must have shape [{self.B}, k]")
-        if d.dtype != np.uint8 or not d.flags.c_contiguous:
-            d = np.ascontiguousarray((d.astype(np.int64) & 0xFF).astype(np.uint8))
+        d = self._host_rows(det_rows)
         n, B = self._windows_for(d.shape[1]) if self.B else 0, self.B
         faults = np.zeros((n, B, self._cmax), np.uint8)
         st, pm = np.empty((n, B, _lib.STAT_WORDS), np.int32), np.empty((n, B), np.float64)
@@ -1123,14 +1118,6 @@ class RollingSession:
                                                 C.byref(first), C.byref(count)):
             raise RuntimeError(f"swd_pipeline_rolling_push failed: {_lib.last_error()}")
         return [(first.value + k, faults[k, :, :self._commit(first.value + k)], st[k], pm[k]) for k in range(count.value)]
-
-    def _check_device_rows(self, det_rows):
-        import torch
-        if det_rows.dtype != torch.uint8 or det_rows.dim() != 2 or det_rows.shape[0] != self.B or not det_rows.is_cuda or \
-                (det_rows.shape[1] > 1 and det_rows.stride(1) != 1):
-            raise ValueError(f"det_rows must be a uint8 CUDA tensor [{self.B}, k] with unit column stride")
-        if det_rows.device.index != self.dec.device:
-            raise ValueError(f"det_rows lives on {det_rows.device}, the pipeline on cuda:{self.dec.device}")
 
     def push_device(self, det_rows, faults_out=None, stream=None):
         """torch uint8 CUDA tensor [B, k] with unit column stride; merge, decode and commit are queued on ``stream`` (default: the
@@ -1174,11 +1161,7 @@ class RollingSession:
         is decoded and committed whole.  Returns ``(t, tail_faults [B, tail commit], stats [B, 8], min_pm [B], obs_flips [B],
         flagged [B])`` -- the last two as ``decode`` leaves ``last_obs_flips`` / ``last_flagged``.  ValueError, with the state
         untouched, if the rows do not make an experiment of ``R = R0 (mod F)`` rounds or are fewer than head and tail need."""
-        d = np.asarray(final_rows)
-        if d.ndim != 2 or d.shape[0] != self.B:
-            raise ValueError(f"final_rows must have shape [{self.B}, k]")
-        if d.dtype != np.uint8 or not d.flags.c_contiguous:
-            d = np.ascontiguousarray((d.astype(np.int64) & 0xFF).astype(np.uint8))
+        d = self._host_rows(final_rows, "final_rows")
         self._check_finish(d.shape[1])
         B, t = self.B, self._state()[1]
         faults = np.empty((B, int(self.template.tail.commit)), np.uint8)

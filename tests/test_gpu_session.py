@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from tests.test_gpu_rolling import KW_NO_OSD
+from tests.test_rolling_host import expected_shot_results
 from tests.test_session_host import KW, PLANS, chunkings
 
 pytestmark = pytest.mark.gpu
@@ -122,6 +124,76 @@ def test_ragged_batches_and_unaligned_rows(B):
     got = run_session(ses, plan, chunkings(det[:B])["irregular"], want)
     assert_equals_decode(got, ref)
     assert len(np.unique(got[1][..., 0] & 0xFF)) >= 2
+
+
+# BP alone (KW_NO_OSD): windows that do not converge leave a residual syndrome behind.  With the OSD of KW no shot of ``problem`` ends
+# flagged (0 of 96 for both plans, checked with the oracle), so ``flagged`` of the tests above is only ever compared with zeros.
+FLAGGED = {"w3f1m1": 70, "w3f3m0": 75}  # of the 96 shots, in the oracle's host loop (computed on the CPU)
+
+
+@functools.lru_cache(maxsize=None)
+def bp_only(tag):
+    """(decoder with KW_NO_OSD, what its one-launch ``decode`` leaves, the oracle's total_e_hat, flagged [shots], obs_flips [shots]);
+    the one-launch decode is compared with the oracle here, once"""
+    from oracle import oracle as O
+    from slidingwindowdecoder_amd import SlidingWindowDecoder
+    from slidingwindowdecoder_amd.windows import sliding_window_decode_host
+    plan, det, _ = problem(tag)
+    want, _ = sliding_window_decode_host(plan, det, lambda w: O.osd_window(w.mat, channel_probs=w.prior, **KW_NO_OSD))
+    flagged, flips = expected_shot_results(plan, det, want)
+    flips = (flips.astype(np.uint32) << np.arange(flips.shape[1], dtype=np.uint32)).sum(axis=1).astype(np.uint32)
+    dec = SlidingWindowDecoder(plan, **KW_NO_OSD)
+    total = dec.decode(det).copy()
+    ref = (total, dec.last_stats.copy(), dec.last_min_pm.copy(), dec.last_obs_flips.copy(), dec.last_flagged.copy())
+    for a in ref + (want, flagged, flips):
+        a.setflags(write=False)
+    assert np.array_equal(ref[0], want) and np.array_equal(ref[3], flips) and np.array_equal(ref[4], flagged)
+    return dec, ref, want, flagged, flips
+
+
+@pytest.mark.parametrize("tag", ["w3f1m1", "w3f3m0"])
+def test_flagged_shots_and_begin_again(tag):
+    """No OSD: most shots end flagged, every shot with an observable flip.  The batch, the same rows in reverse shot order (flagged
+    and unflagged shots change places), the batch again in irregular pieces, all through one session: residual syndrome and
+    accumulators are really cleared by ``begin``, and ``flagged`` is compared with both values.  (3, 3, method 0) is the plan whose
+    window-0 commit flips rows that have not arrived yet."""
+    plan, det, _ = problem(tag)
+    dec, ref, want, flagged, flips = bp_only(tag)
+    assert flagged.sum() == FLAGGED[tag] and 0 < flagged.sum() < SHOTS and (flips != 0).sum() == SHOTS
+    assert not np.array_equal(flagged, flagged[::-1])
+    ses = dec.session(SHOTS)
+    assert_equals_decode(run_session(ses, plan, chunkings(det)["rounds"], want), ref)
+    assert_equals_decode(run_session(ses, plan, chunkings(det[::-1])["rounds"], want[::-1]), tuple(r[::-1] for r in ref))
+    assert_equals_decode(run_session(ses, plan, chunkings(det)["irregular"], want), ref)
+    ses.close()
+
+
+def test_fixed_and_rolling_sessions_agree_on_the_template_length():
+    """(3, 1) of 6 rounds, no OSD: one decoder is the fixed plan and the rolling template.  Fed the same rounds -- the rolling session
+    gets the last block through ``finish`` -- both commit the same faults with the same records window by window, and end with the
+    oracle's obs_flips and flagged."""
+    plan, det, _ = problem("w3f1m1")
+    dec, ref, want, flagged, flips = bp_only("w3f1m1")
+    fixed, rolling = dec.session(SHOTS), dec.rolling_session(SHOTS)
+    fixed.begin(SHOTS)
+    rolling.begin(SHOTS)
+    ev_f, ev_r = [], []
+    for ch in chunkings(det)["rounds"][:-1]:
+        ev_f += fixed.push(ch)
+        ev_r += rolling.push(ch)
+    ev_f += fixed.push(det[:, -36:])
+    t, faults, st, pm, flips_r, flagged_r = rolling.finish(det[:, -36:])
+    ev_r.append((t, faults, st, pm))
+    assert [e[0] for e in ev_f] == [e[0] for e in ev_r] == list(range(len(plan.windows)))
+    for (t, col0, ff, sf, pf), (_, fr, sr, pr) in zip(ev_f, ev_r):
+        assert np.array_equal(ff, fr) and np.array_equal(sf, sr) and (pf == pr).all(), f"window {t}"
+        assert np.array_equal(ff, want[:, col0:col0 + ff.shape[1]]), f"window {t}"
+    got = fixed.finish()
+    assert_equals_decode(got, ref)
+    assert np.array_equal(got[3], flips_r) and np.array_equal(got[4], flagged_r)
+    assert np.array_equal(flips_r, flips) and np.array_equal(flagged_r, flagged)
+    fixed.close()
+    rolling.close()
 
 
 def test_guessing_decoder_session():
