@@ -64,15 +64,16 @@ def template_decoder(tag):
     return SlidingWindowDecoder(template_plan(tag), **KW)
 
 
-def run_rolling(ses, plan, det, chunking, ref, stat_words=8, device=False):
-    """pushes the syndrome rounds of ``det`` in pieces, finishes with the final block; every event is compared with ``ref``, the
-    one-launch records of the plan of the experiment's own length"""
-    B, R = det.shape[0], det.shape[1] // 36 - 1
+def run_rolling(ses, plan, det, chunking, ref, stat_words=8, device=False, rows_per_round=36):
+    """pushes the syndrome rounds of ``det`` (``rows_per_round`` rows each) in pieces, finishes with the final block; every event is
+    compared with ``ref``, the one-launch records of the plan of the experiment's own length"""
+    h = int(rows_per_round)
+    B, R = det.shape[0], det.shape[1] // h - 1
     total, st_ref, pm_ref, flips_ref, flagged_ref = [r[:B] for r in ref]
     ses.begin(B)
     events, rows = [], 0
-    for ch in chunkings(det[:, :36 * R])[chunking]:
-        assert ses.rows_received == rows and ses.rounds_received == rows // 36
+    for ch in chunkings(det[:, :h * R], h)[chunking]:
+        assert ses.rows_received == rows and ses.rounds_received == rows // h
         ev = ses.push(ch)
         rows += ch.shape[1]
         # a window is complete when its last row is there, and only syndrome rounds have been pushed: windows 0 .. n - 2 of the plan
@@ -81,7 +82,7 @@ def run_rolling(ses, plan, det, chunking, ref, stat_words=8, device=False):
         if ses.windows_done < len(plan.windows) - 1:
             assert ses.rows_needed == plan.windows[ses.windows_done].row1 - rows
     assert ses.windows_done == len(plan.windows) - 1
-    t, faults, st, pm, flips, flagged = ses.finish(det[:, 36 * R:])
+    t, faults, st, pm, flips, flagged = ses.finish(det[:, h * R:])
     events.append((t, faults, st, pm))
     assert [e[0] for e in events] == list(range(len(plan.windows)))
     for (t, faults, st, pm), w in zip(events, plan.windows):

@@ -11,9 +11,11 @@ KW = dict(pre_max_iter=8, post_max_iter=40, ms_scaling_factor=1.0, osd_method="o
 PLANS = {"w3f3m0": (3, 3, 0), "w3f1m1": (3, 1, 1)}
 
 
-def chunkings(det):
-    """all rows at once; 36 rows per push; an irregular list with a one-row, an unaligned and an empty piece"""
-    n = det.shape[1]
+def chunkings(det, rows_per_round=36):
+    """all rows at once; one round (``rows_per_round`` rows) per push; an irregular list with a one-row piece, one that ends a round,
+    one that spans more than a round and ends off the word grid, an empty one and, where a round is no whole number of 32-bit
+    words, a three-row piece"""
+    n, h = det.shape[1], int(rows_per_round)
 
     def cut(sizes):
         out, r = [], 0
@@ -22,8 +24,9 @@ def chunkings(det):
             r += k
         assert r == n
         return out
-    irregular = [1, 35, 50, 0, 22]
-    return {"whole": cut([n]), "rounds": cut([36] * (n // 36)), "irregular": cut(irregular + [n - sum(irregular)])}
+    irregular = [1, h - 1, h + 14, 0, 22] + ([3] if h % 4 else [])  # (36 rows per round: 1, 35, 50, 0, 22)
+    assert n % h == 0 and sum(irregular) <= n
+    return {"whole": cut([n]), "rounds": cut([h] * (n // h)), "irregular": cut(irregular + [n - sum(irregular)])}
 
 
 @functools.lru_cache(maxsize=None)
