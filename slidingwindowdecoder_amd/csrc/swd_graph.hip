@@ -44,6 +44,38 @@ int gf2_rank(int m, int n, const std::vector<int32_t> &row_ptr, const std::vecto
     return rank;
 }
 
+int csr_check_rows(int m, int n, const std::vector<int32_t> &row_ptr, std::vector<int32_t> &col_idx) {
+    // (all of row_ptr first: with its ends pinned by the caller, monotone means every row lies inside col_idx)
+    for (int r = 0; r < m; ++r)
+        if (row_ptr[r + 1] < row_ptr[r]) { set_error("row_ptr not monotone at row %d", r); return -1; }
+    for (int r = 0; r < m; ++r) {
+        std::sort(col_idx.begin() + row_ptr[r], col_idx.begin() + row_ptr[r + 1]);
+        for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+            if (col_idx[e] < 0 || col_idx[e] >= n) { set_error("column index out of range in row %d", r); return -1; }
+            if (e > row_ptr[r] && col_idx[e] == col_idx[e - 1]) { set_error("duplicate entry in row %d", r); return -1; }
+        }
+    }
+    return 0;
+}
+
+void csr_transpose(int m, int n, const double *channel_probs, bool want_r2c, CsrHost &h) {
+    const int E = (int)h.col_idx.size();
+    h.col_ptr.assign(n + 1, 0);
+    h.row_idx.resize(E);
+    h.c2r.resize(E);
+    std::vector<int32_t> fill(n, 0);
+    for (int e = 0; e < E; ++e) h.col_ptr[h.col_idx[e] + 1]++;
+    for (int v = 0; v < n; ++v) h.col_ptr[v + 1] += h.col_ptr[v];
+    for (int c = 0; c < m; ++c)
+        for (int e = h.row_ptr[c]; e < h.row_ptr[c + 1]; ++e) { const int v = h.col_idx[e], k = h.col_ptr[v] + fill[v]++; h.row_idx[k] = c; h.c2r[k] = e; }
+    if (want_r2c) {
+        h.r2c.resize(E);
+        for (int k = 0; k < E; ++k) h.r2c[h.c2r[k]] = k;
+    }
+    h.llr.resize(n);
+    for (int v = 0; v < n; ++v) h.llr[v] = log((1 - channel_probs[v]) / channel_probs[v]); // osd_window.pyx:113
+}
+
 int Graph::build(const swd_graph_desc *g) {
     if (!g || !g->row_ptr || !g->col_idx || !g->channel_probs) { set_error("null graph description"); return -1; }
     m = g->m; n = g->n; E = g->nnz;
@@ -54,14 +86,7 @@ int Graph::build(const swd_graph_desc *g) {
     if (E > SWD_MAX_E) { set_error("nnz=%d exceeds this build's limit of %d edges", E, SWD_MAX_E); return -1; }
     row_ptr.assign(g->row_ptr, g->row_ptr + m + 1);
     col_idx.assign(g->col_idx, g->col_idx + E);
-    for (int r = 0; r < m; ++r) {
-        if (row_ptr[r + 1] < row_ptr[r]) { set_error("row_ptr not monotone at row %d", r); return -1; }
-        std::sort(col_idx.begin() + row_ptr[r], col_idx.begin() + row_ptr[r + 1]);
-        for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
-            if (col_idx[e] < 0 || col_idx[e] >= n) { set_error("column index out of range in row %d", r); return -1; }
-            if (e > row_ptr[r] && col_idx[e] == col_idx[e - 1]) { set_error("duplicate entry in row %d", r); return -1; }
-        }
-    }
+    if (csr_check_rows(m, n, row_ptr, col_idx)) return -1;
     // degrees
     row_deg.assign(m, 0);
     col_deg.assign(n, 0);

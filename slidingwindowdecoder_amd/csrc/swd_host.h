@@ -95,4 +95,16 @@ struct Graph {
 
 int gf2_rank(int m, int n, const std::vector<int32_t> &row_ptr, const std::vector<int32_t> &col_idx);
 
+// The row check of every graph ingest, on a copied CSR whose row_ptr spans col_idx: row_ptr monotone, every row sorted in place
+// (columns ascending), column indices in range and distinct.  0, or -1 with the message set.
+int csr_check_rows(int m, int n, const std::vector<int32_t> &row_ptr, std::vector<int32_t> &col_idx);
+
+// A checked CSR with its transpose: CSC (rows ascending inside a column), c2r = CSC position -> CSR edge, r2c = its inverse
+// (on request), llr[v] = log((1 - p[v]) / p[v]) (osd_window.pyx:113).
+struct CsrHost {
+    std::vector<int32_t> row_ptr, col_idx, col_ptr, row_idx, c2r, r2c;
+    std::vector<double> llr;
+};
+void csr_transpose(int m, int n, const double *channel_probs, bool want_r2c, CsrHost &h);
+
 } // namespace swd

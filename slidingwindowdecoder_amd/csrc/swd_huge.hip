@@ -10,27 +10,18 @@
 #include <string.h>
 
 #include <memory>
-#include <mutex>
 
-#include "swd_host.h"
 #include "swd_huge_common.h"
-#include "swd_plan.h"
 
 namespace swd {
 
 struct SwdHugeArgs {
-    int32_t m, n, E, new_n, rank, wm, npad;
+    HugeGraphDev g;
+    HugeIo io;
+    int32_t E, new_n, rank, wm, npad;
     int32_t pre_iter, post_iter, osd_method, osd_order, B;
     double alpha;
-    const int32_t *row_ptr, *col_idx;        // CSR, columns ascending inside a row
-    const int32_t *col_ptr, *row_idx, *c2r;  // CSC (rows ascending inside a column), CSC position -> CSR edge
-    const double *llr;
-    const uint8_t *synd; int64_t synd_stride;
-    uint8_t *out; int64_t out_stride;
-    int32_t *stats; double *min_pm;
-    double *hist; int32_t hist_is_state;     // nullable [B][4][n]
     uint8_t *osd0, *bp_dec;                  // nullable [B][n]
-    uint8_t *scratch; int64_t scratch_stride;
     // offsets inside a workgroup's scratch slice
     int64_t o_b2c, o_c2b, o_hist, o_key, o_idx, o_pos, o_cnval, o_cndeg, o_vn, o_hard, o_bak, o_lv, o_lc, o_T, o_pc, o_pr,
         o_rowof, o_plist, o_ht, o_ycand, o_pm, o_best, o_tmp;
@@ -44,20 +35,14 @@ struct HugeView {
     double *pm;
 };
 
-// masked min-sum (osd_window.pyx:381-485) over the live lists, swd_huge_common.h
-__device__ int huge_bp(const SwdHugeArgs &a, const HugeView &v, const uint8_t *synd, int iters, const int32_t *lc, int nlc,
-                       const int32_t *lv, int nlv, HugeLds &s, int *done) {
-    const HugeGraphDev g{a.m, a.n, a.row_ptr, a.col_idx, a.col_ptr, a.row_idx, a.c2r, a.llr};
-    return huge_minsum(g, a.alpha, v.b2c, v.c2b, v.hist, v.hard, nullptr, v.vn, v.cnval, synd, iters, lc, nlc, lv, nlv, s, done);
-}
-
 // vn_set_value (osd_window.pyx:340-368) by ONE thread, on the live state
+// (not hg_set_value of swd_huge_gdg.hip: bpgd.cpp:51-80 also fails on a check that is already met or has degree 0)
 __device__ int huge_set_value(const SwdHugeArgs &a, const HugeView &v, int x, int value) {
     if (v.vn[x] != -1) return (v.vn[x] == value) ? 0 : -1;
     v.vn[x] = value;
     v.hard[x] = (uint8_t)value;
-    for (int k = a.col_ptr[x]; k < a.col_ptr[x + 1]; ++k) {
-        const int c = a.row_idx[k];
+    for (int k = a.g.col_ptr[x]; k < a.g.col_ptr[x + 1]; ++k) {
+        const int c = a.g.row_idx[k];
         if (v.cnval[c] == -1) continue;
         const int deg = v.cndeg[c] - 1;
         if (value) v.cnval[c] = 1 - v.cnval[c];
@@ -70,10 +55,24 @@ __device__ int huge_set_value(const SwdHugeArgs &a, const HugeView &v, int x, in
     return 0;
 }
 
+// the member columns (indices into the candidate columns) of candidate l in the reference's order: osd_cs -- k of weight one, then the
+// pairs i < j < order (osd_window.pyx:134-155); osd_e -- every pattern of the first `order` columns, pattern l = the binary digits
+// of l (:128-132).  Returns how many.
+__device__ int huge_cand_members(int osd_method, int w, int k, long long l, int *mem) {
+    int nm = 0;
+    if (osd_method == 2) {
+        if (l < k) mem[nm++] = (int)l;
+        else { long long q = l - k; int i = 0; while (q >= w - 1 - i) { q -= w - 1 - i; ++i; } mem[nm++] = i; mem[nm++] = i + 1 + (int)q; }
+    } else {
+        for (int bit = 0; bit < w; ++bit) if ((l >> bit) & 1) mem[nm++] = bit;
+    }
+    return nm;
+}
+
 __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
     __shared__ HugeLds s;
-    const int tid = threadIdx.x, m = a.m, n = a.n, wm = a.wm;
-    uint8_t *base = a.scratch + (int64_t)blockIdx.x * a.scratch_stride;
+    const int tid = threadIdx.x, m = a.g.m, n = a.g.n, wm = a.wm;
+    uint8_t *base = a.io.scratch + (int64_t)blockIdx.x * a.io.scratch_stride;
     HugeView v;
     v.b2c = (double *)(base + a.o_b2c); v.c2b = (double *)(base + a.o_c2b); v.hist = (double *)(base + a.o_hist);
     v.key = (uint64_t *)(base + a.o_key); v.idx = (int32_t *)(base + a.o_idx); v.pos = (int32_t *)(base + a.o_pos);
@@ -84,29 +83,21 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
     v.ycand = (uint64_t *)(base + a.o_ycand); v.pm = (double *)(base + a.o_pm); v.best = (int32_t *)(base + a.o_best);
     v.tmp = (int32_t *)(base + a.o_tmp);
     for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const uint8_t *synd = a.synd + (int64_t)b * a.synd_stride;
-        uint8_t *out = a.out + (int64_t)b * a.out_stride;
-        double *hio = a.hist ? a.hist + (int64_t)b * 4 * n : nullptr;
+        const uint8_t *synd = a.io.synd + (int64_t)b * a.io.synd_stride;
+        uint8_t *out = a.io.out + (int64_t)b * a.io.out_stride;
+        double *hio = a.io.hist ? a.io.hist + (int64_t)b * 4 * n : nullptr;
         __syncthreads();
         // reset (osd_window.pyx:288-303) + bp_init
-        for (int c = tid; c < m; c += HNT) { v.cnval[c] = synd[c] ? 1 : 0; v.cndeg[c] = a.row_ptr[c + 1] - a.row_ptr[c]; v.lc[c] = c; }
-        for (int x = tid; x < n; x += HNT) { v.vn[x] = -1; v.hard[x] = 0; v.lv[x] = x; }
-        for (int i = tid; i < 4 * n; i += HNT) v.hist[i] = (hio && a.hist_is_state) ? hio[i] : 0.0; // a new reference object starts from zeros
-        for (int e = tid; e < a.E; e += HNT) v.b2c[e] = a.llr[a.col_idx[e]];
+        huge_shot_reset(a.g, a.E, synd, a.io.hist_is_state ? hio : nullptr, v.cnval, v.cndeg, v.lc, v.vn, v.hard, v.lv, v.hist, v.b2c);
         __syncthreads();
         int it_pre = 0, it_post = 0, exit_class = -1, conv = 0, nlv = 0, nlc = 0, nle = 0, rowadds = 0;
         double min_pm = 0.0;
         const uint8_t *ret = v.hard;
-        conv = huge_bp(a, v, synd, a.pre_iter, v.lc, m, v.lv, n, s, &it_pre);
+        conv = huge_minsum(a.g, a.alpha, v.b2c, v.c2b, v.hist, v.hard, nullptr, v.vn, v.cnval, synd, a.pre_iter, v.lc, m, v.lv, n, s, &it_pre);
         if (conv) exit_class = SWD_EXIT_PRE;
         else {
             // history sum in slot order, stable sort, decimation of cols[new_n:] to 0 (osd_window.pyx:172-181)
-            for (int i = tid; i < a.npad; i += HNT) {
-                if (i < n) { v.key[i] = huge_f2key(((v.hist[i] + v.hist[n + i]) + v.hist[2 * (size_t)n + i]) + v.hist[3 * (size_t)n + i]); v.idx[i] = i; }
-                else { v.key[i] = ~0ull; v.idx[i] = 0x7FFFFFFF; }
-            }
-            __syncthreads();
-            huge_sort(v.key, v.idx, a.npad);
+            huge_history_order(v.hist, n, a.npad, nullptr, v.key, v.idx);
             for (int i = tid; i < n; i += HNT) v.pos[v.idx[i]] = i;
             __syncthreads();
             // a check whose live nodes are ALL decimated reaches degree 0 when the last of them (in sorted order) is set: with a residual
@@ -115,7 +106,7 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
             __syncthreads();
             for (int c = tid; c < m; c += HNT) {
                 int cnt = 0, last = -1;
-                for (int e = a.row_ptr[c]; e < a.row_ptr[c + 1]; ++e) { const int p = v.pos[a.col_idx[e]]; if (p >= a.new_n) { ++cnt; last = max(last, p); } }
+                for (int e = a.g.row_ptr[c]; e < a.g.row_ptr[c + 1]; ++e) { const int p = v.pos[a.g.col_idx[e]]; if (p >= a.new_n) { ++cnt; last = max(last, p); } }
                 v.tmp[c] = cnt;
                 if (cnt > 0 && cnt == v.cndeg[c] && v.cnval[c] == 1) atomicMin(&s.flag[1], last);
             }
@@ -149,7 +140,7 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
                         if (v.cnval[c] == -1 || v.cndeg[c] >= 2) continue;
                         work = true;
                         int x = -1;
-                        for (int e = a.row_ptr[c]; e < a.row_ptr[c + 1]; ++e) if (v.vn[a.col_idx[e]] == -1) { x = a.col_idx[e]; break; }
+                        for (int e = a.g.row_ptr[c]; e < a.g.row_ptr[c + 1]; ++e) if (v.vn[a.g.col_idx[e]] == -1) { x = a.g.col_idx[e]; break; }
                         if (x < 0) { bad = true; continue; }
                         v.tmp[c] = x; // proposal: node x takes the check's residual value
                     }
@@ -160,14 +151,14 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
                         const int x = v.tmp[c];
                         if (x < 0) continue;
                         bool first = true;
-                        for (int k = a.col_ptr[x]; k < a.col_ptr[x + 1]; ++k) { const int c2 = a.row_idx[k]; if (c2 < c && v.tmp[c2] == x) { first = false; break; } }
+                        for (int k = a.g.col_ptr[x]; k < a.g.col_ptr[x + 1]; ++k) { const int c2 = a.g.row_idx[k]; if (c2 < c && v.tmp[c2] == x) { first = false; break; } }
                         if (first) { v.vn[x] = v.cnval[c]; v.hard[x] = (uint8_t)v.cnval[c]; v.pos[x] = -2 - v.cnval[c]; } // (pos marks "decided in this round")
                     }
                     __syncthreads();
                     for (int c = tid; c < m; c += HNT) {
                         if (v.cnval[c] == -1) continue;
                         int dec = 0, flip = 0;
-                        for (int e = a.row_ptr[c]; e < a.row_ptr[c + 1]; ++e) { const int p = v.pos[a.col_idx[e]]; if (p <= -2) { ++dec; flip ^= (p == -3) ? 1 : 0; } }
+                        for (int e = a.g.row_ptr[c]; e < a.g.row_ptr[c + 1]; ++e) { const int p = v.pos[a.g.col_idx[e]]; if (p <= -2) { ++dec; flip ^= (p == -3) ? 1 : 0; } }
                         if (!dec) continue;
                         const int d = v.cndeg[c] - dec, val = v.cnval[c] ^ flip;
                         v.cndeg[c] = d;
@@ -191,7 +182,7 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
                                 if (v.cnval[c] == -1 || v.cndeg[c] >= 2) continue;
                                 degree_check = 0;
                                 int x = -1;
-                                for (int e = a.row_ptr[c]; e < a.row_ptr[c + 1]; ++e) if (v.vn[a.col_idx[e]] == -1) { x = a.col_idx[e]; break; }
+                                for (int e = a.g.row_ptr[c]; e < a.g.row_ptr[c + 1]; ++e) if (v.vn[a.g.col_idx[e]] == -1) { x = a.g.col_idx[e]; break; }
                                 if (x < 0 || huge_set_value(a, v, x, v.cnval[c]) == -1) rc = -1;
                             }
                             if (rc || degree_check) break;
@@ -209,13 +200,11 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
                     int le = 0;
                     for (int q = tid; q < nlv; q += HNT) {
                         const int x = v.lv[q];
-                        for (int k = a.col_ptr[x]; k < a.col_ptr[x + 1]; ++k) { v.b2c[a.c2r[k]] = a.llr[x]; le += (v.cnval[a.row_idx[k]] != -1) ? 1 : 0; }
+                        for (int k = a.g.col_ptr[x]; k < a.g.col_ptr[x + 1]; ++k) { v.b2c[a.g.c2r[k]] = a.g.llr[x]; le += (v.cnval[a.g.row_idx[k]] != -1) ? 1 : 0; }
                     }
-                    int dummy;
                     (void)huge_scan(le, s, &nle);
-                    (void)dummy;
                     __syncthreads();
-                    conv = huge_bp(a, v, synd, a.post_iter, v.lc, nlc, v.lv, nlv, s, &it_post);
+                    conv = huge_minsum(a.g, a.alpha, v.b2c, v.c2b, v.hist, v.hard, nullptr, v.vn, v.cnval, synd, a.post_iter, v.lc, nlc, v.lv, nlv, s, &it_post);
                     if (conv) exit_class = SWD_EXIT_POST;
                     else if (a.osd_order < 0) exit_class = SWD_EXIT_NO_OSD;
                 }
@@ -223,7 +212,7 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
         }
         if (exit_class == SWD_EXIT_PRE || exit_class == SWD_EXIT_POST) {
             const int cnt = huge_compact(n, v.plist, s, [&](int x) { return v.hard[x] != 0; });
-            if (tid == 0) v.pm[0] = huge_ordered_sum(v.plist, cnt, a.llr);
+            if (tid == 0) v.pm[0] = huge_ordered_sum(v.plist, cnt, a.g.llr);
             __syncthreads();
             min_pm = v.pm[0];
         }
@@ -231,16 +220,7 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
             // ---- OSD (osd_window.pyx:201-284) ----
             exit_class = SWD_EXIT_OSD;
             if (a.bp_dec) for (int x = tid; x < n; x += HNT) a.bp_dec[(int64_t)b * n + x] = v.hard[x];
-            const uint64_t kp = huge_f2key(1000.0), km = huge_f2key(-1000.0);
-            for (int i = tid; i < a.npad; i += HNT) {
-                if (i < n) {
-                    const int st = v.vn[i];
-                    v.key[i] = st == 1 ? km : (st == 0 ? kp : huge_f2key(((v.hist[i] + v.hist[n + i]) + v.hist[2 * (size_t)n + i]) + v.hist[3 * (size_t)n + i]));
-                    v.idx[i] = i;
-                } else { v.key[i] = ~0ull; v.idx[i] = 0x7FFFFFFF; }
-            }
-            __syncthreads();
-            huge_sort(v.key, v.idx, a.npad); // idx = orig_cols
+            huge_history_order(v.hist, n, a.npad, v.vn, v.key, v.idx); // idx = orig_cols
             // transform matrix T (word-major: T[w * m + j] = word w of column j), identity
             for (int i = tid; i < wm * m; i += HNT) { const int w = i / m, j = i - w * m; v.T[i] = (j >> 6) == w ? (1ull << (j & 63)) : 0ull; }
             for (int x = tid; x < n; x += HNT) v.rowof[x] = -1;
@@ -258,7 +238,7 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
                     uint64_t y = 0ull;
                     if (kk < n && lane < wm) {
                         const int col = v.idx[kk];
-                        for (int k = a.col_ptr[col]; k < a.col_ptr[col + 1]; ++k) y ^= v.T[(size_t)lane * m + a.row_idx[k]];
+                        for (int k = a.g.col_ptr[col]; k < a.g.col_ptr[col + 1]; ++k) y ^= v.T[(size_t)lane * m + a.g.row_idx[k]];
                     }
                     s.y[wv * 64 + lane] = y;
                     const uint64_t cand = (lane < wm) ? (y & ~pivmask[lane]) : 0ull;
@@ -316,13 +296,12 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
             const int npiv = huge_compact(n, v.plist, s, [&](int x) { return v.rowof[x] >= 0; }); // pivot columns, ascending
             {
                 const int cnt = huge_compact(n, v.lv, s, [&](int x) { return o0[x] != 0; });
-                if (tid == 0) v.best[2] = cnt, ((double *)v.best)[2] = huge_ordered_sum(v.lv, cnt, a.llr);
+                if (tid == 0) v.best[2] = cnt, ((double *)v.best)[2] = huge_ordered_sum(v.lv, cnt, a.g.llr);
                 __syncthreads();
             }
             min_pm = ((double *)v.best)[2];
             if (a.osd0) for (int x = tid; x < n; x += HNT) a.osd0[(int64_t)b * n + x] = o0[x];
             ret = o0;
-            int bestc = -1;
             if (a.osd_order > 0) {
                 // candidate columns: the first k = new_n - rank non-pivot columns among the first new_n of the sorted order (:243-256)
                 const int k = a.new_n - a.rank;
@@ -333,24 +312,17 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
                 const int nyc = (a.osd_method == 2) ? nht : min(nht, a.osd_order); // columns whose reduced form the sweep needs
                 for (int j = wv; j < nyc; j += 16) {
                     uint64_t y = 0ull;
-                    if (lane < wm) { const int col = v.ht[j]; for (int q = a.col_ptr[col]; q < a.col_ptr[col + 1]; ++q) y ^= v.T[(size_t)lane * m + a.row_idx[q]]; }
+                    if (lane < wm) { const int col = v.ht[j]; for (int q = a.g.col_ptr[col]; q < a.g.col_ptr[col + 1]; ++q) y ^= v.T[(size_t)lane * m + a.g.row_idx[q]]; }
                     if (lane < wm) v.ycand[(size_t)j * wm + lane] = y;
                 }
                 __syncthreads();
-                // candidates in the reference's order: osd_cs -- k of weight one, then the pairs i < j < order (:134-155); osd_e -- every
-                // pattern of the first `order` columns, pattern l = the binary digits of l (:128-132)
                 const int w = a.osd_order;
                 const long long ncand = (a.osd_method == 2) ? (long long)k + (long long)w * (w - 1) / 2 : (1ll << w);
                 double bpm = min_pm;
                 long long bidx = -1;
                 for (long long l = tid; l < ncand; l += HNT) {
-                    int mem[16], nm = 0;
-                    if (a.osd_method == 2) {
-                        if (l < k) mem[nm++] = (int)l;
-                        else { long long q = l - k; int i = 0; while (q >= w - 1 - i) { q -= w - 1 - i; ++i; } mem[nm++] = i; mem[nm++] = i + 1 + (int)q; }
-                    } else {
-                        for (int bit = 0; bit < w; ++bit) if ((l >> bit) & 1) mem[nm++] = bit;
-                    }
+                    int mem[16];
+                    const int nm = huge_cand_members(a.osd_method, w, k, l, mem);
                     // members beyond the candidate columns that exist contribute nothing (enc rows are k long: they cannot occur)
                     int nmv = 0;
                     int memc[16];
@@ -361,12 +333,12 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
                     int nx = 0;
                     for (int i = 0; i < npiv; ++i) {
                         const int col = v.plist[i], r = v.rowof[col];
-                        while (nx < nmv && memc[nx] < col) pm += a.llr[memc[nx++]];
+                        while (nx < nmv && memc[nx] < col) pm += a.g.llr[memc[nx++]];
                         uint64_t bit = (basev[r >> 6] >> (r & 63)) & 1ull;
                         for (int q = 0; q < nmv; ++q) bit ^= (v.ycand[(size_t)mem[q] * wm + (r >> 6)] >> (r & 63)) & 1ull;
-                        if (bit) pm += a.llr[col];
+                        if (bit) pm += a.g.llr[col];
                     }
-                    while (nx < nmv) pm += a.llr[memc[nx++]];
+                    while (nx < nmv) pm += a.g.llr[memc[nx++]];
                     if (pm < bpm) { bpm = pm; bidx = l; } // (ascending l per thread: strict < keeps the earliest)
                 }
                 // block minimum of (pm, index): the reference keeps the first candidate that is strictly better than everything before
@@ -386,16 +358,9 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
                 }
                 __syncthreads();
                 if (bidx >= 0 && bpm < min_pm) {
-                    bestc = 1;
                     min_pm = bpm;
-                    int mem[16], nm = 0;
-                    const long long l = bidx;
-                    if (a.osd_method == 2) {
-                        if (l < k) mem[nm++] = (int)l;
-                        else { long long q = l - k; int i = 0; while (q >= w - 1 - i) { q -= w - 1 - i; ++i; } mem[nm++] = i; mem[nm++] = i + 1 + (int)q; }
-                    } else {
-                        for (int bit = 0; bit < w; ++bit) if ((l >> bit) & 1) mem[nm++] = bit;
-                    }
+                    int mem[16];
+                    const int nm = huge_cand_members(a.osd_method, w, k, bidx, mem);
                     uint8_t *ow = v.hard; // (the BP decisions went out above)
                     for (int x = tid; x < n; x += HNT) {
                         const int r = v.rowof[x];
@@ -412,121 +377,61 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
                     ret = ow;
                 }
             }
-            (void)bestc;
         }
         __syncthreads();
         for (int x = tid; x < n; x += HNT) out[x] = ret[x];
         if (hio) for (int i = tid; i < 4 * n; i += HNT) hio[i] = v.hist[i];
         if (tid == 0) {
-            if (a.stats) {
-                int32_t *st = a.stats + (int64_t)b * SWD_STAT_WORDS;
+            if (a.io.stats) {
+                int32_t *st = a.io.stats + (int64_t)b * SWD_STAT_WORDS;
                 st[0] = exit_class | (conv ? SWD_STATUS_CONVERGE : 0);
                 st[1] = it_pre + it_post; st[2] = it_pre; st[3] = it_post; st[4] = nlv; st[5] = nlc; st[6] = nle; st[7] = rowadds;
             }
-            if (a.min_pm) a.min_pm[b] = min_pm;
+            if (a.io.min_pm) a.io.min_pm[b] = min_pm;
         }
     }
 }
 
-struct Huge : HugeIface {
-    int device = 0, wm = 0, npad = 0, E = 0;
-    swd_osdw_params p{};
-    DevBuf graph, scratch;
+struct Huge : HugeHost {
     SwdHugeArgs tmpl{};
-    int64_t stride = 0;
-    int grid_max = 0;
-    std::mutex mu;
-
-    int decode_dev(int32_t B, const uint8_t *synd, int64_t synd_stride, uint8_t *out, int64_t out_stride, int32_t *stats,
-                   double *min_pm, double *hist, int32_t hist_is_state, uint8_t *osd0, uint8_t *bp_dec, void *stream) override {
-        std::lock_guard<std::mutex> lk(mu); // one scratch area: launches of one handle run one after the other
-        SWD_HIP(hipSetDevice(device));
-        const int grid = std::max(1, std::min(B, grid_max));
-        if (scratch.reserve((size_t)grid * (size_t)stride)) return -1;
+    void launch(int32_t B, const HugeIo &io, uint8_t *osd0, uint8_t *bp_dec, int grid, hipStream_t st) override {
         SwdHugeArgs a = tmpl;
-        a.B = B; a.synd = synd; a.synd_stride = synd_stride ? synd_stride : m; a.out = out; a.out_stride = out_stride ? out_stride : n;
-        a.stats = stats; a.min_pm = min_pm; a.hist = hist; a.hist_is_state = hist_is_state; a.osd0 = osd0; a.bp_dec = bp_dec;
-        a.scratch = scratch.as<uint8_t>(); a.scratch_stride = stride;
-        hipStream_t st = (hipStream_t)stream;
-        // (the scratch area is shared by consecutive launches of this handle: order them on the device too)
-        if (last_stream_set && last_stream != st) SWD_HIP(hipStreamSynchronize(last_stream));
+        a.io = io; a.B = B; a.osd0 = osd0; a.bp_dec = bp_dec;
         hipLaunchKernelGGL(huge_kernel, dim3(grid), dim3(HNT), 0, st, a);
-        SWD_HIP(hipGetLastError());
-        last_stream = st; last_stream_set = true;
-        return 0;
     }
-    hipStream_t last_stream = nullptr;
-    bool last_stream_set = false;
 };
 
 // builds the general form for a graph beyond the kernel variants; NULL (with a message) when even that cannot take it
 HugeIface *huge_create(const swd_graph_desc *g, const swd_osdw_params *p, int device) {
+    if (HugeHost::check_desc(g)) return nullptr;
     const int m = g->m, n = g->n, E = g->nnz;
-    if (m <= 0 || n <= 0 || E <= 0 || g->row_ptr[0] != 0 || g->row_ptr[m] != E) { set_error("empty or inconsistent check matrix"); return nullptr; }
     if (m > 4096) { set_error("m=%d exceeds the general form's limit of 4096 checks (64 words per column of the elimination's transform matrix)", m); return nullptr; }
     if ((long long)n > (1 << 22)) { set_error("n=%d exceeds the general form's limit of 4194304 columns", n); return nullptr; }
     std::unique_ptr<Huge> h(new Huge());
-    h->device = device; h->p = *p; h->m = m; h->n = n; h->E = E;
-    std::vector<int32_t> row_ptr(g->row_ptr, g->row_ptr + m + 1), col_idx(g->col_idx, g->col_idx + E);
-    for (int r = 0; r < m; ++r) {
-        if (row_ptr[r + 1] < row_ptr[r]) { set_error("row_ptr not monotone at row %d", r); return nullptr; }
-        std::sort(col_idx.begin() + row_ptr[r], col_idx.begin() + row_ptr[r + 1]);
-        for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
-            if (col_idx[e] < 0 || col_idx[e] >= n) { set_error("column index out of range in row %d", r); return nullptr; }
-            if (e > row_ptr[r] && col_idx[e] == col_idx[e - 1]) { set_error("duplicate entry in row %d", r); return nullptr; }
-        }
-    }
-    std::vector<int32_t> col_ptr(n + 1, 0), row_idx(E), c2r(E), fill(n, 0);
-    for (int e = 0; e < E; ++e) col_ptr[col_idx[e] + 1]++;
-    for (int v = 0; v < n; ++v) col_ptr[v + 1] += col_ptr[v];
-    for (int c = 0; c < m; ++c)
-        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) { const int v = col_idx[e], k = col_ptr[v] + fill[v]++; row_idx[k] = c; c2r[k] = e; }
-    std::vector<double> llr(n);
-    for (int v = 0; v < n; ++v) llr[v] = log((1 - g->channel_probs[v]) / g->channel_probs[v]); // osd_window.pyx:113
-    h->rank = gf2_rank(m, n, row_ptr, col_idx);
+    SwdHugeArgs &a = h->tmpl;
+    CsrHost c;
+    if (h->ingest(g, device, c, &a.g)) return nullptr;
+    h->rank = gf2_rank(m, n, c.row_ptr, c.col_idx);
     h->new_n = (p->new_n <= 0) ? std::min(n, 2 * m) : std::min(p->new_n, n); // osd_window.pyx:60-63
-    if (h->p.osd_method == 0) h->p.osd_order = 0;
-    if (h->p.osd_order > h->new_n - h->rank) {
+    const int order = p->osd_method == 0 ? 0 : p->osd_order;
+    if (order > h->new_n - h->rank) {
         set_error("For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", h->new_n - h->rank);
         return nullptr;
     }
-    if (h->p.osd_method == 1 && h->p.osd_order > 15) { set_error("osd_e supports osd_order <= 15 on the device"); return nullptr; }
-    const int wm = (m + 63) / 64;
-    int npad = 2; while (npad < n) npad <<= 1;
-    h->wm = wm; h->npad = npad;
-    if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return nullptr; }
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t g_rp = 0, g_ci = al((size_t)(m + 1) * 4), g_cp = g_ci + al((size_t)E * 4), g_ri = g_cp + al((size_t)(n + 1) * 4),
-                 g_cr = g_ri + al((size_t)E * 4), g_llr = g_cr + al((size_t)E * 4), g_tot = g_llr + al((size_t)n * 8);
-    if (h->graph.reserve(g_tot)) return nullptr;
-    char *gd = (char *)h->graph.p;
-    auto up = [&](size_t off, const void *src, size_t bytes) { return hipMemcpy(gd + off, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
-    if (!up(g_rp, row_ptr.data(), (size_t)(m + 1) * 4) || !up(g_ci, col_idx.data(), (size_t)E * 4) || !up(g_cp, col_ptr.data(), (size_t)(n + 1) * 4) ||
-        !up(g_ri, row_idx.data(), (size_t)E * 4) || !up(g_cr, c2r.data(), (size_t)E * 4) || !up(g_llr, llr.data(), (size_t)n * 8)) {
-        set_error("hipMemcpy of the graph failed");
-        return nullptr;
-    }
-    SwdHugeArgs &a = h->tmpl;
-    a.m = m; a.n = n; a.E = E; a.new_n = h->new_n; a.rank = h->rank; a.wm = wm; a.npad = npad;
-    a.pre_iter = h->p.pre_max_iter; a.post_iter = h->p.post_max_iter; a.osd_method = h->p.osd_method; a.osd_order = h->p.osd_order;
-    a.alpha = h->p.ms_scaling_factor;
-    a.row_ptr = (const int32_t *)(gd + g_rp); a.col_idx = (const int32_t *)(gd + g_ci); a.col_ptr = (const int32_t *)(gd + g_cp);
-    a.row_idx = (const int32_t *)(gd + g_ri); a.c2r = (const int32_t *)(gd + g_cr); a.llr = (const double *)(gd + g_llr);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return (int64_t)at; };
+    if (p->osd_method == 1 && order > 15) { set_error("osd_e supports osd_order <= 15 on the device"); return nullptr; }
+    const int wm = (m + 63) / 64, npad = h->npad;
+    a.E = E; a.new_n = h->new_n; a.rank = h->rank; a.wm = wm; a.npad = npad;
+    a.pre_iter = p->pre_max_iter; a.post_iter = p->post_max_iter; a.osd_method = p->osd_method; a.osd_order = order;
+    a.alpha = p->ms_scaling_factor;
     const int k = std::max(h->new_n - h->rank, 0);
-    const int nyc = h->p.osd_order <= 0 ? 0 : (h->p.osd_method == 2 ? k : std::min(k, h->p.osd_order));
-    a.o_b2c = take((size_t)E * 8); a.o_c2b = take((size_t)E * 8); a.o_hist = take((size_t)4 * n * 8);
-    a.o_key = take((size_t)npad * 8); a.o_idx = take((size_t)npad * 4); a.o_pos = take((size_t)n * 4);
-    a.o_cnval = take((size_t)m * 4); a.o_cndeg = take((size_t)m * 4); a.o_vn = take((size_t)n * 4); a.o_hard = take((size_t)n);
-    a.o_bak = take((size_t)n * 4 + (size_t)m * 8 + (size_t)n + 64); a.o_lv = take((size_t)n * 4); a.o_lc = take((size_t)std::max(m, h->new_n) * 4);
-    a.o_T = take((size_t)wm * m * 8); a.o_pc = take((size_t)(h->rank + 1) * 4); a.o_pr = take((size_t)(h->rank + 1) * 4);
-    a.o_rowof = take((size_t)n * 4); a.o_plist = take((size_t)std::max(n, m) * 4); a.o_ht = take((size_t)(k + 1) * 4);
-    a.o_ycand = take((size_t)std::max(nyc, 1) * wm * 8); a.o_pm = take((size_t)(2 * wm + 4) * 8); a.o_best = take(64); a.o_tmp = take((size_t)m * 4);
-    h->stride = (int64_t)al(o);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 64;
-    h->grid_max = std::max(1, cus);
+    const int nyc = order <= 0 ? 0 : (p->osd_method == 2 ? k : std::min(k, order));
+    a.o_b2c = h->take((size_t)E * 8); a.o_c2b = h->take((size_t)E * 8); a.o_hist = h->take((size_t)4 * n * 8);
+    a.o_key = h->take((size_t)npad * 8); a.o_idx = h->take((size_t)npad * 4); a.o_pos = h->take((size_t)n * 4);
+    a.o_cnval = h->take((size_t)m * 4); a.o_cndeg = h->take((size_t)m * 4); a.o_vn = h->take((size_t)n * 4); a.o_hard = h->take((size_t)n);
+    a.o_bak = h->take((size_t)n * 4 + (size_t)m * 8 + (size_t)n + 64); a.o_lv = h->take((size_t)n * 4); a.o_lc = h->take((size_t)std::max(m, h->new_n) * 4);
+    a.o_T = h->take((size_t)wm * m * 8); a.o_pc = h->take((size_t)(h->rank + 1) * 4); a.o_pr = h->take((size_t)(h->rank + 1) * 4);
+    a.o_rowof = h->take((size_t)n * 4); a.o_plist = h->take((size_t)std::max(n, m) * 4); a.o_ht = h->take((size_t)(k + 1) * 4);
+    a.o_ycand = h->take((size_t)std::max(nyc, 1) * wm * 8); a.o_pm = h->take((size_t)(2 * wm + 4) * 8); a.o_best = h->take(64); a.o_tmp = h->take((size_t)m * 4);
     return h.release();
 }
 

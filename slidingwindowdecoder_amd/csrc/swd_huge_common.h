@@ -1,9 +1,14 @@
-// Device helpers of the general forms (swd_huge.hip: osd_window, swd_huge_gdg.hip: the guessing decoders): one 1024-thread
-// workgroup per decode, every array in HBM, LDS only for block-wide scans and reductions.
+// What the general forms share (swd_huge.hip: osd_window, swd_huge_gdg.hip: the guessing decoders).  Device helpers: one 1024-thread
+// workgroup per decode, every array in HBM, LDS only for block-wide scans and reductions.  Host side (at the end): the handle both
+// forms derive from -- CSR ingest and upload, the scratch layout, the launch path.
 #pragma once
 #include <stdint.h>
 
+#include <mutex>
+
 #include <hip/hip_runtime.h>
+
+#include "swd_plan.h"
 
 namespace swd {
 
@@ -93,6 +98,42 @@ struct HugeGraphDev {
     const double *llr;
 };
 
+// what a launch adds to an argument template, next to B (which stays where each form had it: spill counts follow the layout)
+struct HugeIo {
+    const uint8_t *synd; int64_t synd_stride;
+    uint8_t *out; int64_t out_stride;
+    int32_t *stats; double *min_pm;
+    double *hist; int32_t hist_is_state;     // nullable [B][4][n]
+    uint8_t *scratch; int64_t scratch_stride; // a workgroup's slice: scratch + blockIdx.x * scratch_stride
+};
+
+// start of a shot in both forms: every check and node live (check value = syndrome bit, degree = row weight where cndeg is given),
+// decisions 0, the 4-slot history from hist_in (a stateful caller's; null: zeros, a new reference object), messages = priors
+// (bp_init).  No barrier.
+__device__ __forceinline__ void huge_shot_reset(const HugeGraphDev &g, int E, const uint8_t *synd, const double *hist_in, int32_t *cnval,
+                                                int32_t *cndeg, int32_t *lc, int32_t *vn, uint8_t *hard, int32_t *lv, double *hist, double *b2c) {
+    const int tid = threadIdx.x;
+    for (int c = tid; c < g.m; c += HNT) { cnval[c] = synd[c] ? 1 : 0; if (cndeg) cndeg[c] = g.row_ptr[c + 1] - g.row_ptr[c]; lc[c] = c; }
+    for (int x = tid; x < g.n; x += HNT) { vn[x] = -1; hard[x] = 0; lv[x] = x; }
+    for (int i = tid; i < 4 * g.n; i += HNT) hist[i] = hist_in ? hist_in[i] : 0.0;
+    for (int e = tid; e < E; e += HNT) b2c[e] = g.llr[g.col_idx[e]];
+}
+
+// idx[] = the stable ascending argsort of the summed history ((h0 + h1) + h2) + h3 (osd_window.pyx:172, bp_guessing_decoder.pyx:
+// 259-271), padded to npad.  With vn (the OSD's order, osd_window.pyx:205-215) a node decided 1 sorts as -1000, one decided 0 as +1000.
+__device__ inline void huge_history_order(const double *hist, int n, int npad, const int32_t *vn, uint64_t *key, int32_t *idx) {
+    const uint64_t kp = huge_f2key(1000.0), km = huge_f2key(-1000.0);
+    for (int i = threadIdx.x; i < npad; i += HNT) {
+        if (i < n) {
+            const int st = vn ? vn[i] : -1;
+            key[i] = st == 1 ? km : (st == 0 ? kp : huge_f2key(((hist[i] + hist[n + i]) + hist[2 * (size_t)n + i]) + hist[3 * (size_t)n + i]));
+            idx[i] = i;
+        } else { key[i] = ~0ull; idx[i] = 0x7FFFFFFF; }
+    }
+    __syncthreads();
+    huge_sort(key, idx, npad);
+}
+
 // masked min-sum (osd_window.pyx:381-485 == bp_guessing_decoder.pyx:64-126 == bpgd.cpp:103-182): `iters` flooding iterations at
 // most over the listed live checks / live nodes (nlc / nlv entries).  A node is live when vn[x] == -1, a check when cnval[c] != -1
 // (its value seeds the sign).  Posterior of iteration `it` into hist[(it % 4) * n + x], decisions into hard[], the parity of every
@@ -164,5 +205,78 @@ __device__ inline int huge_minsum(const HugeGraphDev &g, double alpha, double *b
     }
     return 0;
 }
+
+// ---- host side ----
+
+// What both general forms own and do alike; each derives its handle from this and adds its argument template and kernel launch.
+struct HugeHost : HugeIface {
+    int device = 0, npad = 0; // npad: n rounded up to a power of two, the length of the bitonic sort
+    DevBuf graph, scratch;
+    int64_t stride = 0;       // scratch bytes of one workgroup: the sum of what take() handed out
+    int grid_max = 0;         // one workgroup per CU, each looping over the batch
+    std::mutex mu;
+    hipStream_t last_stream = nullptr;
+    bool last_stream_set = false;
+
+    static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+    // the header check of a description (the size limits follow in the create functions, each in its decoder's wording)
+    static int check_desc(const swd_graph_desc *g) {
+        if (!g || !g->row_ptr || !g->col_idx || !g->channel_probs) { set_error("null graph description"); return -1; }
+        if (g->m <= 0 || g->n <= 0 || g->nnz <= 0 || g->row_ptr[0] != 0 || g->row_ptr[g->m] != g->nnz) { set_error("empty or inconsistent check matrix"); return -1; }
+        return 0;
+    }
+
+    // Copies, checks and sorts the CSR (c keeps the host arrays for the caller), builds the CSC, c2r, llr and on request r2c, and
+    // uploads all of it as one buffer of 256-byte aligned arrays: *gd, *r2c point into it.
+    int ingest(const swd_graph_desc *g, int dev, CsrHost &c, HugeGraphDev *gd, const int32_t **r2c = nullptr) {
+        m = g->m; n = g->n; device = dev;
+        const size_t E = (size_t)g->nnz;
+        c.row_ptr.assign(g->row_ptr, g->row_ptr + m + 1);
+        c.col_idx.assign(g->col_idx, g->col_idx + E);
+        if (csr_check_rows(m, n, c.row_ptr, c.col_idx)) return -1;
+        csr_transpose(m, n, g->channel_probs, r2c != nullptr, c);
+        npad = 2; while (npad < n) npad <<= 1;
+        if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return -1; }
+        const struct { const void *src; size_t bytes; } seg[7] = {
+            {c.row_ptr.data(), (size_t)(m + 1) * 4}, {c.col_idx.data(), E * 4}, {c.col_ptr.data(), (size_t)(n + 1) * 4}, {c.row_idx.data(), E * 4},
+            {c.c2r.data(), E * 4}, {c.llr.data(), (size_t)n * 8}, {c.r2c.data(), r2c ? E * 4 : 0}};
+        size_t off[8] = {0};
+        for (int i = 0; i < 7; ++i) off[i + 1] = off[i] + al(seg[i].bytes);
+        if (graph.reserve(off[7])) return -1;
+        char *d = (char *)graph.p;
+        for (int i = 0; i < 7; ++i)
+            if (seg[i].bytes && hipMemcpy(d + off[i], seg[i].src, seg[i].bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy of the graph failed"); return -1; }
+        *gd = HugeGraphDev{m, n, (const int32_t *)(d + off[0]), (const int32_t *)(d + off[1]), (const int32_t *)(d + off[2]),
+                           (const int32_t *)(d + off[3]), (const int32_t *)(d + off[4]), (const double *)(d + off[5])};
+        if (r2c) *r2c = (const int32_t *)(d + off[6]);
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 64;
+        grid_max = std::max(1, cus);
+        return 0;
+    }
+
+    // the next array of a workgroup's scratch slice: 256-byte aligned offsets in call order
+    int64_t take(size_t bytes) { const int64_t at = stride; stride += (int64_t)al(bytes); return at; }
+
+    int decode_dev(int32_t B, const uint8_t *synd, int64_t synd_stride, uint8_t *out, int64_t out_stride, int32_t *stats,
+                   double *min_pm, double *hist, int32_t hist_is_state, uint8_t *osd0, uint8_t *bp_dec, void *stream) final {
+        std::lock_guard<std::mutex> lk(mu); // one scratch area: launches of one handle run one after the other
+        SWD_HIP(hipSetDevice(device));
+        const int grid = std::max(1, std::min(B, grid_max));
+        if (scratch.reserve((size_t)grid * (size_t)stride)) return -1;
+        const HugeIo io{synd, synd_stride ? synd_stride : m, out, out_stride ? out_stride : n, stats, min_pm, hist, hist_is_state,
+                        scratch.as<uint8_t>(), stride};
+        hipStream_t st = (hipStream_t)stream;
+        // (the scratch area is shared by consecutive launches of this handle: order them on the device too)
+        if (last_stream_set && last_stream != st) SWD_HIP(hipStreamSynchronize(last_stream));
+        launch(B, io, osd0, bp_dec, grid, st);
+        SWD_HIP(hipGetLastError());
+        last_stream = st; last_stream_set = true;
+        return 0;
+    }
+    // the form's kernel on `grid` workgroups of HNT threads: its argument template with io (and what else a launch sets) filled in
+    virtual void launch(int32_t B, const HugeIo &io, uint8_t *osd0, uint8_t *bp_dec, int grid, hipStream_t st) = 0;
+};
 
 } // namespace swd

@@ -16,11 +16,8 @@
 #include <string.h>
 
 #include <memory>
-#include <mutex>
 
-#include "swd_host.h"
 #include "swd_huge_common.h"
-#include "swd_plan.h"
 
 namespace swd {
 
@@ -31,11 +28,7 @@ struct SwdHugeGdgArgs {
     int32_t mode, ens;                     // mode 0 bpgdg, 1 bpgd, 2 bp_history; ens: the threaded ensemble (multi_thread=True)
     int32_t pre_iter, mips, max_step, D, S, tree_step, side_step, low_error, max_guess, NS;
     double alpha, factor;
-    const uint8_t *synd; int64_t synd_stride;
-    uint8_t *out; int64_t out_stride;
-    int32_t *stats; double *min_pm;
-    double *hist; int32_t hist_is_state;   // nullable [B][4][n]
-    uint8_t *scratch; int64_t scratch_stride;
+    HugeIo io;
     int64_t rec;                           // bytes of one snapshot: vn by position (new_n), check values (m), check degrees (4 m)
     // offsets inside a slot's scratch slice
     int64_t o_b2c, o_c2b, o_hist, o_post, o_key, o_idx, o_pos, o_vn, o_hard, o_bph, o_dec, o_cnval, o_cndeg, o_tsyn, o_tmp, o_lc,
@@ -83,6 +76,7 @@ __device__ __forceinline__ double hg_key2f(uint64_t k) {
 }
 
 // BPGD::vn_set_value (bpgd.cpp:51-80) by ONE thread
+// (not huge_set_value of swd_huge.hip: osd_window.pyx:340-368 skips a check that is already met, this one fails on it or on degree 0)
 __device__ int hg_set_value(const SwdHugeGdgArgs &a, const HgView &v, int x, int value) {
     if (v.vn[x] != -1) return (v.vn[x] == value) ? 0 : -1;
     v.vn[x] = value;
@@ -114,7 +108,7 @@ __device__ int hg_set1(const SwdHugeGdgArgs &a, const HgView &v, int x, int valu
 // BPGD::peel (bpgd.cpp:13-49).  Parallel rounds: the closure does not depend on the order unless a contradiction appears.  Only the
 // main branch of a shot uses the decisions a failed peel leaves behind (its vector is the answer when nothing converges); there
 // (`exact`) the state before the peel is restored and thread 0 replays the reference's sweep to the point where it stops.  Returns
-// 0 / -1.
+// 0 / -1.  (Not the peel of swd_huge.hip: this one walks the per-shot sub-matrix, with BPGD's failure rules and the event-driven replay.)
 __device__ int hg_peel(const SwdHugeGdgArgs &a, const HgView &v, HugeLds &s, bool exact) {
     const int tid = threadIdx.x, m = a.g.m;
     bool any = false;
@@ -407,7 +401,7 @@ __device__ void hg_offer(const SwdHugeGdgArgs &a, const HgView &v, HugeLds &s, i
 __global__ void __launch_bounds__(HNT) huge_gdg_kernel(const SwdHugeGdgArgs a) {
     __shared__ HugeLds s;
     const int tid = threadIdx.x, m = a.g.m, n = a.g.n, new_n = a.new_n;
-    uint8_t *base = a.scratch + (int64_t)blockIdx.x * a.scratch_stride;
+    uint8_t *base = a.io.scratch + (int64_t)blockIdx.x * a.io.scratch_stride;
     HgView v;
     v.b2c = (double *)(base + a.o_b2c); v.c2b = (double *)(base + a.o_c2b); v.hist = (double *)(base + a.o_hist);
     v.post = (double *)(base + a.o_post); v.key = (uint64_t *)(base + a.o_key); v.idx = (int32_t *)(base + a.o_idx);
@@ -420,15 +414,15 @@ __global__ void __launch_bounds__(HNT) huge_gdg_kernel(const SwdHugeGdgArgs a) {
     const int nslots = a.ens ? a.NS + 2 : a.max_guess;
     const HgMeta M{v.meta, v.meta + nslots, v.meta + 2 * nslots, v.meta + 3 * nslots};
     for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const uint8_t *synd = a.synd + (int64_t)b * a.synd_stride;
-        uint8_t *out = a.out + (int64_t)b * a.out_stride;
-        double *hio = a.hist ? a.hist + (int64_t)b * 4 * n : nullptr;
+        const uint8_t *synd = a.io.synd + (int64_t)b * a.io.synd_stride;
+        uint8_t *out = a.io.out + (int64_t)b * a.io.out_stride;
+        double *hio = a.io.hist ? a.io.hist + (int64_t)b * 4 * n : nullptr;
         __syncthreads();
         // ---- bp_history_decoder.bp_decode_llr (bp_guessing_decoder.pyx:48-139): every node and check live, sign seed = syndrome
-        for (int c = tid; c < m; c += HNT) { v.cnval[c] = synd[c] ? 1 : 0; v.lc[c] = c; v.tsyn[c] = 0; }
-        for (int x = tid; x < n; x += HNT) { v.vn[x] = -1; v.hard[x] = 0; v.lv[x] = x; v.dec[x] = -1; }
-        for (int i = tid; i < 4 * n; i += HNT) { v.hist[i] = (hio && a.hist_is_state) ? hio[i] : 0.0; v.post[i] = 0.0; }
-        for (int e = tid; e < a.E; e += HNT) v.b2c[e] = a.g.llr[a.g.col_idx[e]];
+        huge_shot_reset(a.g, a.E, synd, a.io.hist_is_state ? hio : nullptr, v.cnval, nullptr, v.lc, v.vn, v.hard, v.lv, v.hist, v.b2c);
+        for (int c = tid; c < m; c += HNT) v.tsyn[c] = 0;
+        for (int x = tid; x < n; x += HNT) v.dec[x] = -1;
+        for (int i = tid; i < 4 * n; i += HNT) v.post[i] = 0.0;
         __syncthreads();
         int it_pre = 0, it_post = 0, exit_class = -1, conv = 0;
         int w4 = n, w5 = m, w6 = a.E, w7 = 0; // statistics words 4-7 of the exits without a decimation tree
@@ -439,13 +433,8 @@ __global__ void __launch_bounds__(HNT) huge_gdg_kernel(const SwdHugeGdgArgs a) {
         const uint8_t *ret = v.hard; // over columns
         if (exit_class < 0) {
             // ---- order by the summed history (pyx:259-271), BPGD::reset on the first new_n sorted columns (bpgd.cpp:199-239)
-            for (int i = tid; i < a.npad; i += HNT) {
-                if (i < n) { v.key[i] = huge_f2key(((v.hist[i] + v.hist[n + i]) + v.hist[2 * (size_t)n + i]) + v.hist[3 * (size_t)n + i]); v.idx[i] = i; }
-                else { v.key[i] = ~0ull; v.idx[i] = 0x7FFFFFFF; }
-            }
             for (int x = tid; x < n; x += HNT) v.bph[x] = v.hard[x];
-            __syncthreads();
-            huge_sort(v.key, v.idx, a.npad);
+            huge_history_order(v.hist, n, a.npad, nullptr, v.key, v.idx);
             for (int i = tid; i < n; i += HNT) {
                 const int x = v.idx[i];
                 v.pos[x] = i;
@@ -667,73 +656,35 @@ __global__ void __launch_bounds__(HNT) huge_gdg_kernel(const SwdHugeGdgArgs a) {
         for (int x = tid; x < n; x += HNT) out[x] = ret[x];
         if (hio) for (int i = tid; i < 4 * n; i += HNT) hio[i] = v.hist[i];
         if (tid == 0) {
-            if (a.stats) {
-                int32_t *st = a.stats + (int64_t)b * SWD_STAT_WORDS;
+            if (a.io.stats) {
+                int32_t *st = a.io.stats + (int64_t)b * SWD_STAT_WORDS;
                 st[0] = exit_class | (conv ? SWD_STATUS_CONVERGE : 0);
                 st[1] = it_pre + it_post; st[2] = it_pre; st[3] = it_post; st[4] = w4; st[5] = w5; st[6] = w6; st[7] = w7;
             }
-            if (a.min_pm) a.min_pm[b] = min_pm;
+            if (a.io.min_pm) a.io.min_pm[b] = min_pm;
         }
     }
 }
 
-struct HugeGdg : HugeIface {
-    int device = 0;
-    DevBuf graph, scratch;
+struct HugeGdg : HugeHost {
     SwdHugeGdgArgs tmpl{};
-    int64_t stride = 0;
-    int grid_max = 0;
-    std::mutex mu;
-    hipStream_t last_stream = nullptr;
-    bool last_stream_set = false;
-
-    int decode_dev(int32_t B, const uint8_t *synd, int64_t synd_stride, uint8_t *out, int64_t out_stride, int32_t *stats,
-                   double *min_pm, double *hist, int32_t hist_is_state, uint8_t *, uint8_t *, void *stream) override {
-        std::lock_guard<std::mutex> lk(mu); // one scratch area: launches of one handle run one after the other
-        SWD_HIP(hipSetDevice(device));
-        const int grid = std::max(1, std::min(B, grid_max));
-        if (scratch.reserve((size_t)grid * (size_t)stride)) return -1;
+    void launch(int32_t B, const HugeIo &io, uint8_t *, uint8_t *, int grid, hipStream_t st) override {
         SwdHugeGdgArgs a = tmpl;
-        a.B = B; a.synd = synd; a.synd_stride = synd_stride ? synd_stride : m; a.out = out; a.out_stride = out_stride ? out_stride : n;
-        a.stats = stats; a.min_pm = min_pm; a.hist = hist; a.hist_is_state = hist_is_state;
-        a.scratch = scratch.as<uint8_t>(); a.scratch_stride = stride;
-        hipStream_t st = (hipStream_t)stream;
-        // (the scratch area is shared by consecutive launches of this handle: order them on the device too)
-        if (last_stream_set && last_stream != st) SWD_HIP(hipStreamSynchronize(last_stream));
+        a.io = io; a.B = B;
         hipLaunchKernelGGL(huge_gdg_kernel, dim3(grid), dim3(HNT), 0, st, a);
-        SWD_HIP(hipGetLastError());
-        last_stream = st; last_stream_set = true;
-        return 0;
     }
 };
 
 // builds the general form of the guessing decoders; NULL (with a message naming the bound) when it cannot take the graph
 HugeIface *huge_gdg_create(const swd_graph_desc *g, const swd_gdg_params *p, int device) {
+    if (HugeHost::check_desc(g)) return nullptr;
     const int m = g->m, n = g->n, E = g->nnz;
-    if (m <= 0 || n <= 0 || E <= 0 || g->row_ptr[0] != 0 || g->row_ptr[m] != E) { set_error("empty or inconsistent check matrix"); return nullptr; }
     if (m > 4096) { set_error("m=%d exceeds the guessing decoders' general form limit of 4096 checks", m); return nullptr; }
     if ((long long)n > (1 << 22)) { set_error("n=%d exceeds the guessing decoders' general form limit of 4194304 columns", n); return nullptr; }
     if (p->multi_thread == 2) {
         set_error("hypotheses= / multi_thread=2 needs a kernel variant, and none takes this graph (m=%d, n=%d) with these parameters: the "
                   "general form runs the reference's modes only", m, n);
         return nullptr;
-    }
-    std::unique_ptr<HugeGdg> h(new HugeGdg());
-    h->device = device; h->m = m; h->n = n;
-    std::vector<int32_t> row_ptr(g->row_ptr, g->row_ptr + m + 1), col_idx(g->col_idx, g->col_idx + E);
-    for (int r = 0; r < m; ++r) {
-        if (row_ptr[r + 1] < row_ptr[r]) { set_error("row_ptr not monotone at row %d", r); return nullptr; }
-        std::sort(col_idx.begin() + row_ptr[r], col_idx.begin() + row_ptr[r + 1]);
-        for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
-            if (col_idx[e] < 0 || col_idx[e] >= n) { set_error("column index out of range in row %d", r); return nullptr; }
-            if (e > row_ptr[r] && col_idx[e] == col_idx[e - 1]) { set_error("duplicate entry in row %d", r); return nullptr; }
-        }
-        // the reference keeps check degrees in char (bpgd.hpp:23, bpgd.cpp:204-223): from 128 on they wrap, no answer is pinned
-        if (p->mode != 2 && row_ptr[r + 1] - row_ptr[r] >= 128) {
-            set_error("check %d has weight %d: the guessing decoders' general form takes check weights below 128 (the reference's "
-                      "char check degrees wrap there)", r, row_ptr[r + 1] - row_ptr[r]);
-            return nullptr;
-        }
     }
     const int D = p->max_tree_depth, S = p->max_side_depth;
     int max_guess = ((1 << D) - 1) * 2 + S - D; // bp_guessing_decoder.pyx:181
@@ -742,57 +693,35 @@ HugeIface *huge_gdg_create(const swd_graph_desc *g, const swd_gdg_params *p, int
     const bool ens = p->mode == 0 && p->multi_thread == 1;
     const int nslots = p->mode == 0 ? (ens ? NS + 2 : max_guess) : 1;
     if (nslots > 4096) { set_error("%d snapshots per shot exceed the guessing decoders' general form limit of 4096", nslots); return nullptr; }
-    std::vector<int32_t> col_ptr(n + 1, 0), row_idx(E), c2r(E), fill(n, 0);
-    for (int e = 0; e < E; ++e) col_ptr[col_idx[e] + 1]++;
-    for (int v = 0; v < n; ++v) col_ptr[v + 1] += col_ptr[v];
-    for (int c = 0; c < m; ++c)
-        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) { const int v = col_idx[e], k = col_ptr[v] + fill[v]++; row_idx[k] = c; c2r[k] = e; }
-    std::vector<int32_t> r2c(E);
-    for (int k = 0; k < E; ++k) r2c[c2r[k]] = k;
-    std::vector<double> llr(n);
-    for (int v = 0; v < n; ++v) llr[v] = log((1 - g->channel_probs[v]) / g->channel_probs[v]); // osd_window.pyx:113
-    h->new_n = (p->new_n <= 0) ? std::min(n, 2 * m) : std::min(p->new_n, n); // bp_guessing_decoder.pyx:186-189
-    int npad = 2; while (npad < n) npad <<= 1;
-    if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return nullptr; }
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t g_rp = 0, g_ci = al((size_t)(m + 1) * 4), g_cp = g_ci + al((size_t)E * 4), g_ri = g_cp + al((size_t)(n + 1) * 4),
-                 g_cr = g_ri + al((size_t)E * 4), g_rc = g_cr + al((size_t)E * 4), g_llr = g_rc + al((size_t)E * 4),
-                 g_tot = g_llr + al((size_t)n * 8);
-    if (h->graph.reserve(g_tot)) return nullptr;
-    char *gd = (char *)h->graph.p;
-    auto up = [&](size_t off, const void *src, size_t bytes) { return hipMemcpy(gd + off, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
-    if (!up(g_rp, row_ptr.data(), (size_t)(m + 1) * 4) || !up(g_ci, col_idx.data(), (size_t)E * 4) || !up(g_cp, col_ptr.data(), (size_t)(n + 1) * 4) ||
-        !up(g_ri, row_idx.data(), (size_t)E * 4) || !up(g_cr, c2r.data(), (size_t)E * 4) || !up(g_rc, r2c.data(), (size_t)E * 4) ||
-        !up(g_llr, llr.data(), (size_t)n * 8)) {
-        set_error("hipMemcpy of the graph failed");
-        return nullptr;
-    }
+    std::unique_ptr<HugeGdg> h(new HugeGdg());
     SwdHugeGdgArgs &a = h->tmpl;
-    a.g = HugeGraphDev{m, n, (const int32_t *)(gd + g_rp), (const int32_t *)(gd + g_ci), (const int32_t *)(gd + g_cp),
-                       (const int32_t *)(gd + g_ri), (const int32_t *)(gd + g_cr), (const double *)(gd + g_llr)};
-    a.r2c = (const int32_t *)(gd + g_rc);
+    CsrHost c;
+    if (h->ingest(g, device, c, &a.g, &a.r2c)) return nullptr;
+    // the reference keeps check degrees in char (bpgd.hpp:23, bpgd.cpp:204-223): from 128 on they wrap, no answer is pinned
+    for (int r = 0; r < m && p->mode != 2; ++r)
+        if (c.row_ptr[r + 1] - c.row_ptr[r] >= 128) {
+            set_error("check %d has weight %d: the guessing decoders' general form takes check weights below 128 (the reference's "
+                      "char check degrees wrap there)", r, c.row_ptr[r + 1] - c.row_ptr[r]);
+            return nullptr;
+        }
+    h->new_n = (p->new_n <= 0) ? std::min(n, 2 * m) : std::min(p->new_n, n); // bp_guessing_decoder.pyx:186-189
+    const int npad = h->npad;
     a.E = E; a.new_n = h->new_n; a.npad = npad;
     a.mode = p->mode; a.ens = ens ? 1 : 0;
     a.pre_iter = p->max_iter; a.mips = p->max_iter_per_step; a.max_step = p->max_step; a.D = D; a.S = S;
     a.tree_step = p->max_tree_branch_step; a.side_step = p->max_side_branch_step; a.low_error = p->low_error_mode ? 1 : 0;
     a.max_guess = max_guess; a.NS = NS;
     a.alpha = p->ms_scaling_factor; a.factor = p->gdg_factor;
-    a.rec = (int64_t)al((size_t)((h->new_n + 15) & ~15) + (size_t)((m + 15) & ~15) + (size_t)m * 4);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return (int64_t)at; };
-    a.o_b2c = take((size_t)E * 8); a.o_c2b = take((size_t)E * 8); a.o_hist = take((size_t)4 * n * 8); a.o_post = take((size_t)4 * n * 8);
-    a.o_key = take((size_t)npad * 8); a.o_idx = take((size_t)npad * 4); a.o_pos = take((size_t)n * 4); a.o_vn = take((size_t)n * 4);
-    a.o_hard = take((size_t)n); a.o_bph = take((size_t)n); a.o_dec = take((size_t)n);
-    a.o_cnval = take((size_t)m * 4); a.o_cndeg = take((size_t)m * 4); a.o_tsyn = take((size_t)m); a.o_tmp = take((size_t)m * 4);
-    a.o_lc = take((size_t)m * 4); a.o_lv = take((size_t)n * 4);
-    a.o_bvn = take((size_t)n * 4); a.o_bh = take((size_t)n); a.o_bcv = take((size_t)m * 4); a.o_bcd = take((size_t)m * 4);
-    a.o_best = take((size_t)h->new_n); a.o_merr = take((size_t)h->new_n); a.o_meta = take((size_t)4 * nslots * 4);
-    a.o_snap = take((size_t)nslots * (size_t)a.rec);
-    a.o_srp = take((size_t)(m + 1) * 4); a.o_sci = take((size_t)E * 4); a.o_sc2r = take((size_t)E * 4);
-    h->stride = (int64_t)al(o);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 64;
-    h->grid_max = std::max(1, cus);
+    a.rec = (int64_t)HugeHost::al((size_t)((h->new_n + 15) & ~15) + (size_t)((m + 15) & ~15) + (size_t)m * 4);
+    a.o_b2c = h->take((size_t)E * 8); a.o_c2b = h->take((size_t)E * 8); a.o_hist = h->take((size_t)4 * n * 8); a.o_post = h->take((size_t)4 * n * 8);
+    a.o_key = h->take((size_t)npad * 8); a.o_idx = h->take((size_t)npad * 4); a.o_pos = h->take((size_t)n * 4); a.o_vn = h->take((size_t)n * 4);
+    a.o_hard = h->take((size_t)n); a.o_bph = h->take((size_t)n); a.o_dec = h->take((size_t)n);
+    a.o_cnval = h->take((size_t)m * 4); a.o_cndeg = h->take((size_t)m * 4); a.o_tsyn = h->take((size_t)m); a.o_tmp = h->take((size_t)m * 4);
+    a.o_lc = h->take((size_t)m * 4); a.o_lv = h->take((size_t)n * 4);
+    a.o_bvn = h->take((size_t)n * 4); a.o_bh = h->take((size_t)n); a.o_bcv = h->take((size_t)m * 4); a.o_bcd = h->take((size_t)m * 4);
+    a.o_best = h->take((size_t)h->new_n); a.o_merr = h->take((size_t)h->new_n); a.o_meta = h->take((size_t)4 * nslots * 4);
+    a.o_snap = h->take((size_t)nslots * (size_t)a.rec);
+    a.o_srp = h->take((size_t)(m + 1) * 4); a.o_sci = h->take((size_t)E * 4); a.o_sc2r = h->take((size_t)E * 4);
     return h.release();
 }
 
