@@ -424,6 +424,15 @@ int swd_pipeline_get_timing(swd_pipeline *pl, double *total_ms, int64_t *launche
  * residency (tests/test_gpu_forward_progress.py: blocks that each take more than half a CU's LDS hold one CU apiece). */
 int swd_diag_occupy(int device, int32_t blocks, int32_t threads, int32_t lds_bytes, int32_t microseconds, void *stream);
 
+/* diagnostics, host only (needs no device): the message-slot layout of graph g as a pipeline built now would lay it out with up to
+ * `pads` pad cells -- the bank-conflict-aware layout, or with SWD_NATURAL_LAYOUT set in the environment the natural one (positions
+ * in column order, no pads).  info[8] = { slots, K, D, model cost of the loads, of the stores, the natural layout's two costs,
+ * pad cells used }; the arrays (any of them may be NULL) are sized jptr [K + 1], row_col [slots], perm / iperm / row_deg [m],
+ * vn_edge / vn_edge_s [D * n], vperm [n]: call once with NULL arrays for the sizes.  The cost is in LDS-array cycles of one
+ * variable-node pass over the full graph (csrc/swd_graph.hip, Graph::layout_cost). */
+int swd_graph_layout(const swd_graph_desc *g, int32_t pads, int32_t *info, uint16_t *jptr, uint16_t *row_col, uint16_t *perm,
+                     uint16_t *iperm, uint8_t *row_deg, uint32_t *vn_edge, uint32_t *vn_edge_s, uint16_t *vperm);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,7 @@ SYMBOLS = [
     ("swd_sampler_sample", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("swd_sampler_sample_dev", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _vp, _i64, _vp, _vp, _i64, _vp]),
     ("swd_diag_occupy", C.c_int, [C.c_int, _i32, _i32, _i32, _i32, _vp]),
+    ("swd_graph_layout", C.c_int, [C.POINTER(GraphDesc), _i32] + [_vp] * 9),
 ]
 
 STAT_WORDS = 8

@@ -1535,7 +1535,7 @@ __device__ __forceinline__ void decode_window_gdg(const SwdGraphDev &g_in, const
     __syncthreads();
     int it = 0;
     R.conv = 0; R.pm = 0.0; R.pre_it = R.post_it = 0;
-    R.live_vn = n; R.live_cn = m; R.live_e = g.E; R.osd_rowadds = 0;
+    R.live_vn = n; R.live_cn = m; R.live_e = g.nnz; R.osd_rowadds = 0;
     R.t[1] = wall_clock64();
     // bp_history_decoder.bp_decode_llr (bp_guessing_decoder.pyx:48-139)
     R.conv = bp_run<NT, VF, DM, KG, true>(g, P, s, P.pre_iter, n, vc, cn, hist_b, it, P.alpha, false);

@@ -7,8 +7,14 @@
 //     perm[l].  Edge slots use the jagged-diagonal numbering slot(j, l) = jptr[j] + l
 //     (j = position inside the row), so for a fixed j consecutive lanes touch consecutive
 //     8-byte LDS words (conflict-free ds_read_b64 / ds_write_b64) and the slot count is
-//     exactly nnz -- no ELL padding, which is what lets the fp64 messages of a 5976-edge
-//     window fit the LDS budget;
+//     nnz plus a few pad cells -- no ELL padding, which is what lets the fp64 messages of a
+//     5976-edge window fit the LDS budget;
+//   * which edge of a check sits at which position j, which of several checks of one degree takes
+//     which lane, and pad cells between consecutive diagonals (jptr[j + 1] - jptr[j] >= checks of
+//     degree > j) are free -- no result depends on them -- and a plan's graphs use them so that the
+//     variable-node pass, which gathers one cell per lane, spreads over the LDS banks
+//     (swd_graph.hip, Graph::optimize_layout); the natural layout is ascending columns, lanes
+//     stable in the check index, no pads;
 //   * row_col[slot]  = column of that edge (coalesced for a fixed j);
 //   * vn_edge[k*n+v] = k-th edge of column v in row-ascending order (the order the
 //     reference's variable-node update sums in, osd_window.pyx:446-471), packed
@@ -24,10 +30,11 @@
 #define SWD_PAD_EDGE 0xFFFFFFFFu
 
 struct SwdGraphDev {
-    int32_t m, n, E, K, D;   // K = max row degree, D = max column degree
+    int32_t m, n, E, K, D;   // E = message slots (edges + pad cells), K = max row degree, D = max column degree
     int32_t new_n, rank, wm; // wm = ceil(m / 64)
+    int32_t nnz, pad_;       // edges
     const uint16_t *jptr;    // [K+1]
-    const uint16_t *row_col; // [E]
+    const uint16_t *row_col; // [E] (pad slots: 0)
     const uint8_t *row_deg;  // [m] by lane
     const uint16_t *perm;    // [m] lane -> original check
     const uint16_t *iperm;   // [m] original check -> lane

@@ -2,6 +2,7 @@
 // Replaces numpy2mod2sparse / spmatrix2mod2sparse (/root/reference/src/mod2sparse.pyx:5-31) and
 // mod2sparse_rank (/root/reference/src/include/mod2sparse_extra.cpp:32-76, value only).
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <mutex>
@@ -76,6 +77,163 @@ void csr_transpose(int m, int n, const double *channel_probs, bool want_r2c, Csr
     for (int v = 0; v < n; ++v) h.llr[v] = log((1 - channel_probs[v]) / channel_probs[v]); // osd_window.pyx:113
 }
 
+// Every table that names a message slot, from the one assignment (epos, iperm, dpad): slot of the edge at position j of the check on
+// lane l = jptr[j] + l, jptr[j + 1] = jptr[j] + (checks of degree > j) + dpad[j].  Pad slots keep column 0 in row_col and are named
+// by no edge word.
+void Graph::fill_tables() {
+    jptr.assign(K + 1, 0);
+    for (int j = 0; j < K; ++j) {
+        int cnt = 0;
+        for (int l = 0; l < m; ++l) cnt += (row_deg[l] > j);
+        jptr[j + 1] = (uint16_t)(jptr[j] + cnt + dpad[j]);
+    }
+    S = jptr[K];
+    row_col.assign(S, 0);
+    vn_edge.assign((size_t)std::max(D, 1) * n, SWD_PAD_EDGE);
+    vn_row.assign((size_t)std::max(D, 1) * n, 0xFFFF);
+    std::vector<int> fill(n, 0);
+    for (int r = 0; r < m; ++r) {
+        const int l = iperm[r];
+        for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+            const int j = epos[e];
+            const int v = col_idx[e];
+            const int slot = jptr[j] + l;
+            row_col[slot] = (uint16_t)v;
+            const int k = fill[v]++; // rows ascending: the order the reference's variable-node update sums in
+            vn_edge[(size_t)k * n + v] = (uint32_t)slot | ((uint32_t)l << 16) | ((uint32_t)j << 26);
+            vn_row[(size_t)k * n + v] = (uint16_t)r;
+        }
+    }
+}
+
+void Graph::fill_listed() {
+    vn_edge_s.assign((size_t)std::max(D, 1) * n, SWD_PAD_EDGE);
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < D; ++k) vn_edge_s[(size_t)k * n + i] = vn_edge[(size_t)k * n + vperm[i]];
+}
+
+// LDS-array cycles of one variable-node pass over the full graph, from the tables: thread t serves column t, edge index k, one
+// 8-byte cell per lane.  ds_read_b64 is served in aligned groups of 32 lanes, bank = cell mod 32; ds_write_b64 in aligned groups
+// of 16 lanes, bank = cell mod 16.  A group costs the largest number of (distinct) cells on one bank.
+long Graph::layout_cost(long *loads, long *stores) const {
+    long cl = 0, cs = 0;
+    for (int k = 0; k < D; ++k)
+        for (int v0 = 0; v0 < n; v0 += 16) {
+            if ((v0 & 31) == 0) {
+                int h[32] = {0}, mx = 0;
+                for (int v = v0; v < std::min(n, v0 + 32); ++v) {
+                    const uint32_t e = vn_edge[(size_t)k * n + v];
+                    if (e != SWD_PAD_EDGE) mx = std::max(mx, ++h[swd_edge_slot(e) & 31]);
+                }
+                cl += mx;
+            }
+            int h[16] = {0}, mx = 0;
+            for (int v = v0; v < std::min(n, v0 + 16); ++v) {
+                const uint32_t e = vn_edge[(size_t)k * n + v];
+                if (e != SWD_PAD_EDGE) mx = std::max(mx, ++h[swd_edge_slot(e) & 15]);
+            }
+            cs += mx;
+        }
+    if (loads) *loads = cl;
+    if (stores) *stores = cs;
+    return cl + cs;
+}
+
+// Layout optimiser: lowers layout_cost() with the three freedoms no result depends on -- the order of a check's edges over its
+// positions (the check pass takes two minima and a parity), which of several checks of one degree takes which lane, and up to
+// `pads` pad cells between consecutive diagonals.  Deterministic (no random choice), bounded work; keeps the natural layout when it
+// finds nothing better.
+void Graph::optimize_layout(int pads) {
+    if (pads < 0) pads = 0;
+    if (E + pads > SWD_MAX_E) pads = SWD_MAX_E - E;
+    // per CSR edge: its check, and the load / store group of its (column, edge index inside the column)
+    std::vector<int> gl(E), gs(E), erow(E);
+    {
+        std::vector<int> fill(n, 0);
+        for (int r = 0; r < m; ++r)
+            for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+                const int v = col_idx[e];
+                const int k = fill[v]++;
+                erow[e] = r;
+                gl[e] = (v >> 5) * D + k;
+                gs[e] = (v >> 4) * D + k;
+            }
+    }
+    const int NGL = ((n + 31) >> 5) * D, NGS = ((n + 15) >> 4) * D;
+    // one pad cell after each of the first diagonals: consecutive diagonals then start on different banks
+    std::vector<uint16_t> pad(K, 0);
+    for (int j = 0, left = pads; j + 1 < K && left > 0; ++j, --left) pad[j] = 1;
+    std::vector<int> jp(K + 1, 0);
+    for (int j = 0; j < K; ++j) {
+        int cnt = 0;
+        for (int l = 0; l < m; ++l) cnt += (row_deg[l] > j);
+        jp[j + 1] = jp[j] + cnt + pad[j];
+    }
+    std::vector<uint8_t> pos(epos);
+    std::vector<uint16_t> lane(iperm);
+    std::vector<int> slot(E);
+    std::vector<uint8_t> hl((size_t)NGL * 32, 0), hs((size_t)NGS * 16, 0);
+    for (int e = 0; e < E; ++e) {
+        slot[e] = jp[pos[e]] + lane[erow[e]];
+        hl[(size_t)gl[e] * 32 + (slot[e] & 31)]++;
+        hs[(size_t)gs[e] * 16 + (slot[e] & 15)]++;
+    }
+    // The search descends on the sum over groups and banks of (cells on the bank)^2, loads counted twice (a load conflict always
+    // costs a cycle, a store's only once the array cycles exceed the instruction's six): it falls with every cell that leaves a
+    // busier bank for an emptier one, where the cost itself -- the busiest bank per group -- is flat almost everywhere.
+    auto mv = [&](int e, int s0, int s1) -> int { // moves edge e from cell s0 to s1, returns the change of the sum
+        uint8_t *L = &hl[(size_t)gl[e] * 32], *T = &hs[(size_t)gs[e] * 16];
+        int d = 0;
+        if ((s0 ^ s1) & 31) { d += 2 * (2 * ((int)L[s1 & 31] - (int)L[s0 & 31]) + 2); L[s0 & 31]--; L[s1 & 31]++; }
+        if ((s0 ^ s1) & 15) { d += 2 * ((int)T[s1 & 15] - (int)T[s0 & 15]) + 2; T[s0 & 15]--; T[s1 & 15]++; }
+        return d;
+    };
+    // lanes that may trade places: runs of equal degree
+    std::vector<int> run1(m), lane_row(m);
+    for (int l = 0; l < m;) { int h = l; while (h < m && row_deg[h] == row_deg[l]) ++h; for (int q = l; q < h; ++q) run1[q] = h; l = h; }
+    for (int r = 0; r < m; ++r) lane_row[lane[r]] = r;
+    // Every other sweep also takes the moves that leave the sum as it is (they lead off plateaus); lanes trade places in every
+    // fourth sweep only, a lane pair costs as much as all the position pairs of its two checks.
+    const int kSweeps = 12; // bounds the time of a create: a sweep visits every pair of positions of a check and every pair of lanes of a run
+    for (int sweep = 0; sweep < kSweeps; ++sweep) {
+        long gained = 0;
+        for (int r = 0; r < m; ++r)
+            for (int a = row_ptr[r]; a < row_ptr[r + 1]; ++a)
+                for (int b = a + 1; b < row_ptr[r + 1]; ++b) { // same check, same lane: the two edges trade cells
+                    const int sa = slot[a], sb = slot[b];
+                    const int d = mv(a, sa, sb) + mv(b, sb, sa);
+                    if (d < 0 || (d == 0 && (sweep & 1))) { std::swap(pos[a], pos[b]); slot[a] = sb; slot[b] = sa; gained -= d; }
+                    else { mv(b, sa, sb); mv(a, sb, sa); }
+                }
+        for (int la = 0; la < m && (sweep & 3) == 0; ++la)
+            for (int lb = la + 1; lb < run1[la]; ++lb) {
+                const int r1 = lane_row[la], r2 = lane_row[lb];
+                int d = 0;
+                for (int e = row_ptr[r1]; e < row_ptr[r1 + 1]; ++e) d += mv(e, slot[e], slot[e] - la + lb);
+                for (int e = row_ptr[r2]; e < row_ptr[r2 + 1]; ++e) d += mv(e, slot[e], slot[e] - lb + la);
+                if (d < 0) {
+                    for (int e = row_ptr[r1]; e < row_ptr[r1 + 1]; ++e) slot[e] += lb - la;
+                    for (int e = row_ptr[r2]; e < row_ptr[r2 + 1]; ++e) slot[e] += la - lb;
+                    lane[r1] = (uint16_t)lb; lane[r2] = (uint16_t)la; lane_row[lb] = r1; lane_row[la] = r2;
+                    gained -= d;
+                } else {
+                    for (int e = row_ptr[r2]; e < row_ptr[r2 + 1]; ++e) mv(e, slot[e] - lb + la, slot[e]);
+                    for (int e = row_ptr[r1]; e < row_ptr[r1 + 1]; ++e) mv(e, slot[e] - la + lb, slot[e]);
+                }
+            }
+        if (!gained && !(sweep & 1)) break;
+    }
+    long cur = 0;
+    for (int g = 0; g < NGL; ++g) { int mx = 0; for (int b = 0; b < 32; ++b) mx = std::max(mx, (int)hl[(size_t)g * 32 + b]); cur += mx; }
+    for (int g = 0; g < NGS; ++g) { int mx = 0; for (int b = 0; b < 16; ++b) mx = std::max(mx, (int)hs[(size_t)g * 16 + b]); cur += mx; }
+    if (cur >= cost_natural) return; // nothing better than positions in column order without pads
+    epos = pos; iperm = lane; dpad = pad;
+    for (int r = 0; r < m; ++r) perm[iperm[r]] = (uint16_t)r; // (equal-degree lanes traded places: row_deg by lane is unchanged)
+    fill_tables();
+    fill_listed();
+    cost = layout_cost();
+}
+
 int Graph::build(const swd_graph_desc *g) {
     if (!g || !g->row_ptr || !g->col_idx || !g->channel_probs) { set_error("null graph description"); return -1; }
     m = g->m; n = g->n; E = g->nnz;
@@ -112,33 +270,22 @@ int Graph::build(const swd_graph_desc *g) {
         return (row_ptr[a + 1] - row_ptr[a]) > (row_ptr[b + 1] - row_ptr[b]);
     });
     for (int l = 0; l < m; ++l) { perm[l] = (uint16_t)order[l]; iperm[order[l]] = (uint16_t)l; row_deg[l] = (uint8_t)(row_ptr[order[l] + 1] - row_ptr[order[l]]); }
-    jptr.assign(K + 1, 0);
-    for (int j = 0; j < K; ++j) {
-        int cnt = 0;
-        for (int l = 0; l < m; ++l) cnt += (row_deg[l] > j);
-        jptr[j + 1] = (uint16_t)(jptr[j] + cnt);
-    }
-    row_col.assign(E, 0);
+    // natural layout: positions in ascending column order, no pad cells
+    epos.resize(E);
+    for (int r = 0; r < m; ++r)
+        for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) epos[e] = (uint8_t)(e - row_ptr[r]);
+    dpad.assign(K, 0);
     // CSC with row-ascending entries
     col_ptr.assign(n + 1, 0);
     for (int v = 0; v < n; ++v) col_ptr[v + 1] = col_ptr[v] + cdeg[v];
     row_idx.assign(E, 0);
-    vn_edge.assign((size_t)std::max(D, 1) * n, SWD_PAD_EDGE);
-    vn_row.assign((size_t)std::max(D, 1) * n, 0xFFFF);
-    std::vector<int> fill(n, 0);
-    for (int r = 0; r < m; ++r) {
-        const int l = iperm[r];
-        for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
-            const int j = e - row_ptr[r];
-            const int v = col_idx[e];
-            const int slot = jptr[j] + l;
-            row_col[slot] = (uint16_t)v;
-            const int k = fill[v]++;
-            row_idx[col_ptr[v] + k] = r;
-            vn_edge[(size_t)k * n + v] = (uint32_t)slot | ((uint32_t)l << 16) | ((uint32_t)j << 26);
-            vn_row[(size_t)k * n + v] = (uint16_t)r;
-        }
+    {
+        std::vector<int> fill(n, 0);
+        for (int r = 0; r < m; ++r)
+            for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) { const int v = col_idx[e]; row_idx[col_ptr[v] + fill[v]++] = r; }
     }
+    fill_tables();
+    cost_natural = cost = layout_cost();
     llr.resize(n);
     for (int v = 0; v < n; ++v) {
         const double p = g->channel_probs[v];
@@ -151,12 +298,8 @@ int Graph::build(const swd_graph_desc *g) {
         for (int v = 0; v < n; ++v) ord[v] = v;
         std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return (cdeg[a] + 1) / 2 > (cdeg[b] + 1) / 2; });
         vperm.resize(n); llr_s.resize(n);
-        vn_edge_s.assign((size_t)std::max(D, 1) * n, SWD_PAD_EDGE);
-        for (int i = 0; i < n; ++i) {
-            vperm[i] = (uint16_t)ord[i];
-            llr_s[i] = llr[ord[i]];
-            for (int k = 0; k < D; ++k) vn_edge_s[(size_t)k * n + i] = vn_edge[(size_t)k * n + ord[i]];
-        }
+        for (int i = 0; i < n; ++i) { vperm[i] = (uint16_t)ord[i]; llr_s[i] = llr[ord[i]]; }
+        fill_listed();
     }
     rank = gf2_rank(m, n, row_ptr, col_idx);
     wm = (m + 63) / 64;
@@ -194,7 +337,7 @@ int Graph::upload() {
     if (dev.reserve(total)) return -1;
     SWD_HIP(hipMemcpy(dev.p, h.data(), total, hipMemcpyHostToDevice));
     char *b = (char *)dev.p;
-    d.m = m; d.n = n; d.E = E; d.K = K; d.D = D; d.rank = rank; d.wm = wm; d.new_n = 0;
+    d.m = m; d.n = n; d.E = S; d.nnz = E; d.pad_ = 0; d.K = K; d.D = D; d.rank = rank; d.wm = wm; d.new_n = 0;
     d.jptr = (const uint16_t *)(b + o_jptr);
     d.row_col = (const uint16_t *)(b + o_rowcol);
     d.row_deg = (const uint8_t *)(b + o_rowdeg);
@@ -210,7 +353,32 @@ int Graph::upload() {
     return 0;
 }
 
+bool natural_layout_requested() { return getenv("SWD_NATURAL_LAYOUT") != nullptr; }
+
 } // namespace swd
+
+extern "C" int swd_graph_layout(const swd_graph_desc *g, int32_t pads, int32_t *info, uint16_t *jptr, uint16_t *row_col, uint16_t *perm,
+                                uint16_t *iperm, uint8_t *row_deg, uint32_t *vn_edge, uint32_t *vn_edge_s, uint16_t *vperm) {
+    swd::Graph G;
+    if (G.build(g)) return -1;
+    long nl = 0, ns = 0, cl = 0, cs = 0;
+    G.layout_cost(&nl, &ns);
+    if (!swd::natural_layout_requested()) G.optimize_layout(pads);
+    G.layout_cost(&cl, &cs);
+    if (info) {
+        const int32_t v[8] = {G.S, G.K, G.D, (int32_t)cl, (int32_t)cs, (int32_t)nl, (int32_t)ns, G.S - G.E};
+        memcpy(info, v, sizeof v);
+    }
+    if (jptr) memcpy(jptr, G.jptr.data(), G.jptr.size() * 2);
+    if (row_col) memcpy(row_col, G.row_col.data(), G.row_col.size() * 2);
+    if (perm) memcpy(perm, G.perm.data(), G.perm.size() * 2);
+    if (iperm) memcpy(iperm, G.iperm.data(), G.iperm.size() * 2);
+    if (row_deg) memcpy(row_deg, G.row_deg.data(), G.row_deg.size());
+    if (vn_edge) memcpy(vn_edge, G.vn_edge.data(), G.vn_edge.size() * 4);
+    if (vn_edge_s) memcpy(vn_edge_s, G.vn_edge_s.data(), G.vn_edge_s.size() * 4);
+    if (vperm) memcpy(vperm, G.vperm.data(), G.vperm.size() * 2);
+    return 0;
+}
 
 extern "C" const char *swd_last_error(void) { return swd::last_error(); }
 extern "C" int swd_abi_version(void) { return SWD_ABI_VERSION; }

@@ -79,6 +79,10 @@ struct PinnedBuf {
 // Host copy of the device graph arrays + the device allocation holding them.
 struct Graph {
     int m = 0, n = 0, E = 0, K = 0, D = 0, rank = 0, wm = 0;
+    int S = 0;                   // message slots: E + pad cells (swd_graph.h)
+    std::vector<uint8_t> epos;   // [E] position of CSR edge e inside its check's row
+    std::vector<uint16_t> dpad;  // [K] pad cells behind diagonal j
+    long cost_natural = 0, cost = 0; // layout_cost() of the natural layout and of this one
     std::vector<uint16_t> jptr, row_col, perm, iperm, vn_row;
     std::vector<uint8_t> row_deg, col_deg;
     std::vector<uint32_t> vn_edge, vn_edge_s;
@@ -89,9 +93,16 @@ struct Graph {
     DevBuf dev;
     SwdGraphDev d{};
 
-    int build(const swd_graph_desc *g);   // validates, fills host arrays, computes rank
+    int build(const swd_graph_desc *g);   // validates, fills host arrays (natural layout), computes rank
+    void optimize_layout(int pads);        // bank-conflict-aware layout with up to `pads` pad cells; build() first, upload() after
+    long layout_cost(long *loads = nullptr, long *stores = nullptr) const;
+    void fill_tables();
+    void fill_listed();
     int upload();                          // hipMalloc + copy, fills d
 };
+
+// SWD_NATURAL_LAYOUT in the environment (diagnostics, A/B runs): plans keep the natural layout of their graphs
+bool natural_layout_requested();
 
 int gf2_rank(int m, int n, const std::vector<int32_t> &row_ptr, const std::vector<int32_t> &col_idx);
 

@@ -12,7 +12,7 @@
 namespace swd {
 
 int make_layout(const Graph &g, int new_n, int nt, int kind, SwdLdsLayout &L, bool big, int lds_budget) {
-    const int m = g.m, n = g.n, E = g.E, wm = g.wm;
+    const int m = g.m, n = g.n, E = g.S, wm = g.wm; // (E: message slots, pad cells included)
     const int npad = std::max(next_pow2(n), 2);
     L.npad = npad;
     L.off_idx = npad * 8;

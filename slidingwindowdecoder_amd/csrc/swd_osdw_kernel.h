@@ -2905,7 +2905,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
 
     int it = 0;
     R.conv = 0; R.pm = 0.0; R.pre_it = R.post_it = 0;
-    R.live_vn = n; R.live_cn = m; R.live_e = g.E; R.osd_rowadds = 0;
+    R.live_vn = n; R.live_cn = m; R.live_e = g.nnz; R.osd_rowadds = 0;
     uint16_t *list0 = (uint16_t *)s.scratch;
     R.t[1] = wall_clock64();
 #ifdef SWD_INITPROF // diagnostic build: where the set-up of a window goes (reset loops | cache loads | barrier | bp_init | check caches)

@@ -228,7 +228,7 @@ struct Plan {
             w.g = std::make_shared<Graph>();
             if (w.g->build(gd)) return -1;
             if (w.g->D > SWD_DMAX) { set_error("column weight %d exceeds this build's bound %d", w.g->D, SWD_DMAX); return -1; }
-            if (w.g->upload()) return -1;
+            // (finalize uploads it: the kernel variant decides how many pad cells its layout may take)
             cache[key] = w.g;
         }
         const int m = w.g->m, n = w.g->n;
@@ -257,6 +257,45 @@ struct Plan {
             snap_stride = std::max(snap_stride, rec * (gdg_parallel ? SWD_GDG_SLOTS : std::max(std::max(max_guess, 1), ens_slots)));
         }
         snap_stride = (snap_stride + 15) & ~(int64_t)15;
+    }
+
+    // Message-slot layout of the plan's graphs (swd_graph.hip, Graph::optimize_layout), then their upload.  A graph takes pad cells
+    // where the kernels keep the full graph's messages in LDS (osd_window, not the large-graph form) and the cells cost nothing:
+    // launch_nt counts a workgroup's LDS in granules of 1280 B, so the plan may grow up to the granule it ends in, as long as
+    // every window layout keeps its form (what lies over what in the scratch region).  SWD_NATURAL_LAYOUT in the environment,
+    // read here, keeps the natural layout (A/B runs, tests).
+    int layout_graphs(int lmax) {
+        std::vector<Graph *> uniq;
+        for (auto &w : wins)
+            if (std::find(uniq.begin(), uniq.end(), w.g.get()) == uniq.end()) uniq.push_back(w.g.get());
+        if (!big && !natural_layout_requested()) {
+            const int tail = lds_total - align_up(lmax, 16); // accumulators and syndrome bytes behind the largest window layout
+            const int limit = std::min(align_up(lds_total, 1280), 160 * 1024);
+            for (Graph *g : uniq) {
+                int pads = (kind == 0) ? std::min(g->K - 1, SWD_MAX_E - g->E) : 0;
+                for (; pads > 0; --pads) {
+                    bool ok = true;
+                    g->S = g->E + pads;
+                    for (auto &w : wins) {
+                        if (w.g.get() != g) continue;
+                        SwdLdsLayout L{};
+                        make_layout(*g, w.new_n, nt, kind, L);
+                        ok = ok && align_up(L.total, 16) + tail <= limit && (nt > SWD_TUNED_NT || L.total <= 65536) &&
+                             L.off_lslot == w.L.off_lslot && L.post_lds == w.L.post_lds && L.off_cord == w.L.off_cord && L.off_rc == w.L.off_rc &&
+                             L.off_cs == w.L.off_cs && L.cs_par == w.L.cs_par && L.off_oring == w.L.off_oring && L.off_oslot == w.L.off_oslot;
+                    }
+                    if (ok) break;
+                }
+                g->S = g->E;
+                g->optimize_layout(pads);
+            }
+            for (auto &w : wins) { make_layout(*w.g, w.new_n, nt, kind, w.L); lmax = std::max(lmax, w.L.total); }
+            off_det = align_up(lmax, 16) + 16;
+            lds_total = align_up(lmax, 16) + tail;
+        }
+        for (Graph *g : uniq)
+            if (g->upload()) return -1;
+        return 0;
     }
 
     int finalize(const swd_graph_desc *chk) {
@@ -332,6 +371,7 @@ struct Plan {
             break;
         }
         if (!variant) return -1;
+        if (layout_graphs(lmax)) return -1;
         post_depth2 = kind != 0 && !getenv("SWD_GDG_NO_DEPTH2");
         for (auto &w : wins) post_depth2 = post_depth2 && w.new_n <= 2 * nt;
         if (kind == 1 && gp.multi_thread == 1) {
@@ -342,7 +382,7 @@ struct Plan {
             const int vfp = (post_depth2 && vf > 2) ? 2 : vf;
             for (auto &w : wins) {
                 const int64_t rec = ((w.new_n + 2 * w.g->m + 7) & ~7) + 8 * (int64_t)w.g->m;
-                const int64_t cells = std::max<int64_t>(w.g->E + 1 + 2 * (nt / 64), (int64_t)vfp * variant->dm * nt);
+                const int64_t cells = std::max<int64_t>(w.g->S + 1 + 2 * (nt / 64), (int64_t)vfp * variant->dm * nt);
                 const int64_t forkb = ((rec + 15) & ~(int64_t)15) + ((cells * 8 + 15) & ~(int64_t)15);
                 snap_stride = std::max(snap_stride, ((rec * ens_slots + 15) & ~(int64_t)15) + gp.max_tree_depth * forkb + 2 * (((int64_t)w.new_n + 15) & ~(int64_t)15) + 16);
             }
@@ -452,7 +492,7 @@ int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
             const int vfp = (d->post_depth2 && d->vf > 2) ? 2 : d->vf;
             for (auto &w : d->wins) {
                 const int64_t rec = ((w.new_n + 2 * w.g->m + 7) & ~7) + 8 * (int64_t)w.g->m;
-                const int64_t cells = std::max<int64_t>(w.g->E + 1 + 2 * (NT / 64), (int64_t)vfp * DM * NT);
+                const int64_t cells = std::max<int64_t>(w.g->S + 1 + 2 * (NT / 64), (int64_t)vfp * DM * NT);
                 forkb = std::max(forkb, ((rec + 15) & ~(int64_t)15) + ((cells * 8 + 15) & ~(int64_t)15));
                 rec16 = std::max(rec16, (rec + 15) & ~(int64_t)15);
             }
