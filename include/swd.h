@@ -226,6 +226,58 @@ int swd_sampler_sample_dev(swd_sampler *s, int32_t B, uint64_t seed, uint64_t fi
                            int64_t det_stride, uint32_t *obs_flips, uint8_t *faults, int64_t faults_stride,
                            void *stream);
 
+/* ---- code-capacity experiments: Pauli sampler and CSS accounting -------------------------------
+ * The data-noise Monte Carlo of the reference on the device: sample, decode (swd_bp4_* or a binary decoder), account, count.
+ *
+ * Pauli sampler.  Replaces /root/reference/Misc.ipynb cell 2 lines 10-14 (the same lines in cell 8 and in `Data noise.ipynb`):
+ *     noise = np.random.uniform(0, 1, (num_shots, code.N))
+ *     err_z = np.logical_and(noise > px, noise < (px+py+pz));  syndrome_x = (err_z @ code.hx.T) % 2
+ *     err_x = noise < (px+py);                                 syndrome_z = (err_x @ code.hz.T) % 2
+ * Per shot and qubit q one 32-bit word u: u < tx -> X, tx <= u < txy -> Y, txy <= u < txyz -> Z, else I, with
+ * tx, txy, txyz = round(px 2^32), round((px + py) 2^32), round(((px + py) + pz) 2^32) (floor(v 2^32 + 0.5) clamped to 2^32 - 1, the
+ * DEM sampler's rule).  A probability outside [0, 1] or a sum above 1 is refused.  Stream: Philox4x32-10 keyed by `seed`, counter
+ * (shot lo, shot hi, q / 4, 1) -- the last word keeps it disjoint from the DEM sampler's stream, which has 0 there -- and output word
+ * q % 4 decides qubit q; shot b of a call is shot number first_shot + b, so a result does not depend on batching, lanes or the rank.
+ * hx [mx x n], hz [mz x n] CSR (channel_probs ignored); at most 16384 qubits and 65535 checks in total.
+ *   err [B][2][n]  row 0 the X string, row 1 the Z string: the layout swd_bp4_decode_batch returns
+ *   sx  [B][mx]    Hx err_z          sz [B][mz]  Hz err_x                                  (all uint8) */
+typedef struct swd_pauli_sampler swd_pauli_sampler;
+swd_pauli_sampler *swd_pauli_sampler_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *px, const double *py,
+                                            const double *pz, int device);
+void swd_pauli_sampler_destroy(swd_pauli_sampler *s);
+int swd_pauli_sampler_info(const swd_pauli_sampler *s, int32_t *mx, int32_t *mz, int32_t *n);
+/* host pointers */
+int swd_pauli_sampler_sample(swd_pauli_sampler *s, int32_t B, uint64_t seed, uint64_t first_shot, uint8_t *err, uint8_t *sx,
+                             uint8_t *sz);
+/* device pointers (strides in bytes per shot, 0 = dense), asynchronous on `stream` */
+int swd_pauli_sampler_sample_dev(swd_pauli_sampler *s, int32_t B, uint64_t seed, uint64_t first_shot, uint8_t *err,
+                                 int64_t err_stride, uint8_t *sx, int64_t sx_stride, uint8_t *sz, int64_t sz_stride, void *stream);
+
+/* CSS accounting: did the correction leave a logical error?  Replaces Misc.ipynb cell 2 lines 32-36, 39-43 and 45 (cell 8: 26-32)
+ *     e_diff_z = (e_hat_z + err_z[i]) % 2;  logical_z_err = ((e_diff_z @ code.hz_perp.T) % 2).any()
+ *     e_diff_x = (e_hat_x + err_x[i]) % 2;  logical_x_err = ((e_diff_x @ code.hx_perp.T) % 2).any()
+ *     num_log_err += (logical_z_err or logical_x_err);  num_flag_err += 1 - bpd.converge
+ * and /root/reference/src/simulation.py:25-28, 51-56, 90-93 (one basis).  hz_perp = ker(hz) has the row space of [Hx; Lx], so "some row of
+ * hz_perp has odd overlap" is "some row of [Hx; Lx] has"; the rows are passed split, which also tells a residual syndrome from
+ * a logical flip.
+ *   cx  CSR applied to the Z string: its first stab_x rows are stabilisers (Hx), the rest logical operators (Lx)
+ *   cz  CSR applied to the X string: Hz, then Lz
+ * Either may be NULL: estimate and error are then single strings of n bytes per shot (the binary decoders, simulation.py); with
+ * both, [2][n] bytes per shot as the Pauli sampler and swd_bp4_decode_batch lay them out.  Any number of logical rows; at most
+ * 65535 rows in total, 16384 qubits.
+ * account: with d = est ^ err, result[b] (nullable) =
+ *   bit 0  some row has odd overlap with its string of d                       (the reference's criterion)
+ *   bit 1  some stabiliser row has: the residual syndrome is not zero          (implies bit 0)
+ *   bit 2  stats is given and stats[b * SWD_STAT_WORDS] & stat_mask is zero: with SWD_STATUS_CONVERGE, the mask of every
+ *          decode call above, the decoder did not converge                      (1 - converge)
+ * counters: nullable device uint64[4] = shots, bit-0, bit-1, bit-2 counts, ADDED to (one integer atomic per counter and
+ * workgroup); the caller zeroes them.  Device pointers, strides in bytes per shot (0 = dense), asynchronous on `stream`. */
+typedef struct swd_css_account swd_css_account;
+swd_css_account *swd_css_account_create(const swd_graph_desc *cx, int32_t stab_x, const swd_graph_desc *cz, int32_t stab_z, int device);
+void swd_css_account_destroy(swd_css_account *a);
+int swd_css_account_dev(swd_css_account *a, int32_t B, const uint8_t *est, int64_t est_stride, const uint8_t *err, int64_t err_stride,
+                        const int32_t *stats, int32_t stat_mask, int32_t *result, uint64_t *counters, void *stream);
+
 /* ---- sliding-window pipeline ---------------------------------------------------------------
  * Replaces the window loop of the reference harness (/root/reference/osd.py:130-179, identical in
  * guessing.py:135-214 and the notebooks): for every shot, decode window t on the residual

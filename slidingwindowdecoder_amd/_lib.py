@@ -109,6 +109,14 @@ SYMBOLS = [
     ("swd_sampler_info", C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     ("swd_sampler_sample", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("swd_sampler_sample_dev", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _vp, _i64, _vp, _vp, _i64, _vp]),
+    ("swd_pauli_sampler_create", _vp, [C.POINTER(GraphDesc), C.POINTER(GraphDesc), _vp, _vp, _vp, C.c_int]),
+    ("swd_pauli_sampler_destroy", None, [_vp]),
+    ("swd_pauli_sampler_info", C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    ("swd_pauli_sampler_sample", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
+    ("swd_pauli_sampler_sample_dev", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    ("swd_css_account_create", _vp, [C.POINTER(GraphDesc), _i32, C.POINTER(GraphDesc), _i32, C.c_int]),
+    ("swd_css_account_destroy", None, [_vp]),
+    ("swd_css_account_dev", C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
     ("swd_diag_occupy", C.c_int, [C.c_int, _i32, _i32, _i32, _i32, _vp]),
     ("swd_graph_layout", C.c_int, [C.POINTER(GraphDesc), _i32] + [_vp] * 9),
 ]

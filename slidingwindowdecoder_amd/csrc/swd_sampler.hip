@@ -5,6 +5,7 @@
 // (shot, column / 4): the four outputs decide columns 4c..4c+3, fault iff x < round(p * 2^32).  The
 // result is a pure function of (seed, shot index, column), independent of batch size and of the GPU a
 // shot lands on; tests/philox_ref.py restates it in numpy.
+// Further down: the Pauli sampler and the CSS accounting of the code-capacity experiments (same generator, counter word 3 = 1).
 #include <string.h>
 
 #include "swd_host.h"
@@ -161,6 +162,293 @@ extern "C" int swd_sampler_info(const swd_sampler *h, int32_t *num_det, int32_t 
     if (num_det) *num_det = s->num_det;
     if (num_col) *num_col = s->num_col;
     if (num_obs) *num_obs = s->num_obs;
+    return 0;
+}
+
+// ---- code-capacity experiments (include/swd.h: swd_pauli_sampler_*, swd_css_account_*) ---------------------------------------
+// The data-noise Monte Carlo of the reference (/root/reference/Misc.ipynb cells 2 and 8, src/simulation.py:15-16) draws its errors and
+// judges its corrections on the host; these two kernels do both on the device, so that only counters come back.  Both give a shot one
+// wave (four shots share a 256-thread workgroup) while a wave covers the shot's bytes in two strides (n <= 512), else the workgroup;
+// the shot's strings live in LDS and every lane computes whole checks by gathering its CSR row from them: no atomics in the
+// parities, a fixed order, ordinary vector stores.
+namespace {
+
+constexpr int kWaveShotMaxN = 512;   // one wave per shot up to this many qubits (2 strides of 64 lanes x 4 qubits)
+constexpr int kCapacityMaxN = 16384; // two padded strings of a shot within 32 KB of LDS
+
+// CSR rows over a shot's LDS bytes: row r is the parity of bytes idx[ptr[r] .. ptr[r + 1])
+struct LdsRows {
+    std::vector<uint32_t> ptr{0};
+    std::vector<uint16_t> idx;
+    // rows [r0, r1) of g, column c -> byte `base + c`; -1 with the message set on a bad matrix
+    int append(const swd_graph_desc *g, int r0, int r1, int n, int base, const char *what) {
+        for (int r = r0; r < r1; ++r) {
+            if (g->row_ptr[r] > g->row_ptr[r + 1] || g->row_ptr[r] < 0) { set_error("%s: row_ptr is not monotone", what); return -1; }
+            for (int e = g->row_ptr[r]; e < g->row_ptr[r + 1]; ++e) {
+                if (g->col_idx[e] < 0 || g->col_idx[e] >= n) { set_error("%s: column out of range", what); return -1; }
+                idx.push_back((uint16_t)(base + g->col_idx[e]));
+            }
+            ptr.push_back((uint32_t)idx.size());
+        }
+        return 0;
+    }
+};
+
+int capacity_device_ok(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: the MI355X decoder has no CPU fallback"); return -1; }
+    if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return -1; }
+    return 0;
+}
+
+bool csr_desc_ok(const swd_graph_desc *g) { return g && g->row_ptr && g->col_idx && g->m >= 0 && g->n > 0; }
+
+struct PauliSampler {
+    int device = 0, n = 0, n4 = 0, mx = 0, mz = 0;
+    DevBuf buf;                 // thr[3][n4] u32 (tx | txy | txyz, pad qubits 0) | ptr[mx + mz + 1] u32 | idx[E] u16
+    const uint32_t *d_thr = nullptr, *d_ptr = nullptr;
+    const uint16_t *d_idx = nullptr;
+    DevBuf err, sx, sz;         // staging for the host-pointer entry point
+};
+
+// T threads per shot (64: a wave, 256: the workgroup), 256 / T shots per workgroup; LDS [256 / T][2][n4] bytes: X string, Z string
+template <int T>
+__global__ void __launch_bounds__(256) pauli_sample_kernel(int B, int n, int mx, int mz, const uint32_t *thr, const uint32_t *ptr,
+                                                           const uint16_t *idx, uint64_t seed, uint64_t first_shot, uint8_t *err,
+                                                           int64_t err_stride, uint8_t *sx, int64_t sx_stride, uint8_t *sz,
+                                                           int64_t sz_stride) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t pauli_lds[];
+    const int n4 = (n + 3) & ~3, slot = threadIdx.x / T, lane = threadIdx.x % T;
+    const int64_t b = (int64_t)blockIdx.x * (256 / T) + slot;
+    const bool live = b < B;
+    uint8_t *str = pauli_lds + (size_t)slot * 2 * n4;
+    if (live) {
+        const uint64_t shot = first_shot + (uint64_t)b;
+        for (int g = lane; g < n4 / 4; g += T) {
+            uint32_t u[4], xw = 0, zw = 0;
+            philox4x32_10((uint32_t)shot, (uint32_t)(shot >> 32), (uint32_t)g, 1u, (uint32_t)seed, (uint32_t)(seed >> 32), u);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int q = 4 * g + k; // u < tx: X, < txy: Y, < txyz: Z, else I
+                xw |= (u[k] < thr[n4 + q] ? 1u : 0u) << (8 * k);
+                zw |= (u[k] >= thr[q] && u[k] < thr[2 * n4 + q] ? 1u : 0u) << (8 * k);
+            }
+            ((uint32_t *)str)[g] = xw;
+            ((uint32_t *)(str + n4))[g] = zw;
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    uint8_t *e = err + b * err_stride;
+    for (int i = lane; i < n; i += T) { e[i] = str[i]; e[n + i] = str[n4 + i]; }
+    for (int r = lane; r < mx + mz; r += T) {
+        uint32_t p = 0;
+        for (uint32_t k = ptr[r]; k < ptr[r + 1]; ++k) p ^= str[idx[k]];
+        if (r < mx) sx[b * sx_stride + r] = (uint8_t)p;
+        else sz[b * sz_stride + (r - mx)] = (uint8_t)p;
+    }
+}
+
+struct CssAccount {
+    int device = 0, n = 0, len = 0, rows = 0, stab = 0; // len = bytes of a shot's estimate: 2 n, or n in the single-string form
+    DevBuf buf;                                         // ptr[rows + 1] u32 | idx[E] u16; stabiliser rows first
+    const uint32_t *d_ptr = nullptr;
+    const uint16_t *d_idx = nullptr;
+};
+
+constexpr int kAccountGrid = 2048; // workgroups of the accounting launch at most: each walks its shots, then adds its sums once
+
+// LDS: cnt[4] u32 | flags[256 / T] u32 | d[256 / T][len] bytes, d = est ^ err
+template <int T>
+__global__ void __launch_bounds__(256) css_account_kernel(int B, int len, int rows, int stab, const uint32_t *ptr, const uint16_t *idx,
+                                                          const uint8_t *est, int64_t est_stride, const uint8_t *err,
+                                                          int64_t err_stride, const int32_t *stats, int32_t stat_mask,
+                                                          int32_t *result, unsigned long long *counters) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t acct_lds[];
+    constexpr int SPW = 256 / T;
+    uint32_t *cnt = (uint32_t *)acct_lds, *flags = cnt + 4;
+    const int slot = threadIdx.x / T, lane = threadIdx.x % T;
+    uint8_t *d = acct_lds + 16 + 4 * SPW + (size_t)slot * len;
+    if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
+    for (int64_t base = (int64_t)blockIdx.x * SPW; base < B; base += (int64_t)gridDim.x * SPW) {
+        const int64_t b = base + slot;
+        const bool live = b < B;
+        if (lane == 0) flags[slot] = 0;
+        if (live) {
+            const uint8_t *pe = est + b * est_stride, *pr = err + b * err_stride;
+            for (int i = lane; i < len; i += T) d[i] = pe[i] ^ pr[i];
+        }
+        __syncthreads();
+        uint32_t f = 0;
+        if (live)
+            for (int r = lane; r < rows; r += T) {
+                uint32_t p = 0;
+                for (uint32_t k = ptr[r]; k < ptr[r + 1]; ++k) p ^= d[idx[k]];
+                if (p & 1u) f |= r < stab ? 3u : 1u;
+            }
+        if (f) atomicOr(&flags[slot], f);
+        __syncthreads();
+        if (live && lane == 0) {
+            uint32_t w = flags[slot];
+            if (stats && !(stats[b * SWD_STAT_WORDS] & stat_mask)) w |= 4u;
+            if (result) result[b] = (int32_t)w;
+            atomicAdd(&cnt[0], 1u);
+            if (w & 1u) atomicAdd(&cnt[1], 1u);
+            if (w & 2u) atomicAdd(&cnt[2], 1u);
+            if (w & 4u) atomicAdd(&cnt[3], 1u);
+        }
+    }
+    __syncthreads();
+    if (counters && threadIdx.x < 4 && cnt[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+}
+
+} // namespace
+
+extern "C" swd_pauli_sampler *swd_pauli_sampler_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *px,
+                                                       const double *py, const double *pz, int device) {
+    if (!csr_desc_ok(hx) || !csr_desc_ok(hz) || !px || !py || !pz) { set_error("null argument"); return nullptr; }
+    if (hx->n != hz->n) { set_error("Hx, Hz blocklength does not match!"); return nullptr; }
+    const int n = hx->n, n4 = (n + 3) & ~3;
+    if (n > kCapacityMaxN || (int64_t)hx->m + hz->m > 65535) {
+        set_error("Pauli sampler: %d qubits, %d + %d checks out of range (%d qubits, 65535 checks)", n, hx->m, hz->m, kCapacityMaxN);
+        return nullptr;
+    }
+    if (capacity_device_ok(device)) return nullptr;
+    std::vector<uint32_t> thr(3 * (size_t)n4, 0);
+    auto threshold = [](double v) { const double t = v * 4294967296.0 + 0.5; return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t; };
+    for (int q = 0; q < n; ++q) {
+        const double x = px[q], y = py[q], z = pz[q], xy = x + y, xyz = xy + z;
+        if (!(x >= 0.0 && x <= 1.0) || !(y >= 0.0 && y <= 1.0) || !(z >= 0.0 && z <= 1.0)) {
+            set_error("qubit %d: (%g, %g, %g) are not probabilities", q, x, y, z);
+            return nullptr;
+        }
+        if (!(xyz <= 1.0)) { set_error("qubit %d: px + py + pz = %.17g exceeds 1", q, xyz); return nullptr; }
+        thr[q] = threshold(x); thr[n4 + q] = threshold(xy); thr[2 * (size_t)n4 + q] = threshold(xyz);
+    }
+    LdsRows rows; // sx = Hx err_z reads the Z string at byte n4, sz = Hz err_x the X string at byte 0
+    if (rows.append(hx, 0, hx->m, n, n4, "Hx") || rows.append(hz, 0, hz->m, n, 0, "Hz")) return nullptr;
+    PauliSampler *s = new PauliSampler();
+    s->device = device; s->n = n; s->n4 = n4; s->mx = hx->m; s->mz = hz->m;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_thr = 0, o_ptr = al(thr.size() * 4), o_idx = al(o_ptr + rows.ptr.size() * 4), total = al(o_idx + rows.idx.size() * 2 + 2);
+    std::vector<char> h(total, 0);
+    memcpy(&h[o_thr], thr.data(), thr.size() * 4); memcpy(&h[o_ptr], rows.ptr.data(), rows.ptr.size() * 4);
+    if (!rows.idx.empty()) memcpy(&h[o_idx], rows.idx.data(), rows.idx.size() * 2);
+    if (hipSetDevice(device) != hipSuccess || s->buf.reserve(total) || hipMemcpy(s->buf.p, h.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("Pauli sampler: device allocation failed on device %d", device);
+        delete s;
+        return nullptr;
+    }
+    char *b = (char *)s->buf.p;
+    s->d_thr = (const uint32_t *)(b + o_thr); s->d_ptr = (const uint32_t *)(b + o_ptr); s->d_idx = (const uint16_t *)(b + o_idx);
+    return (swd_pauli_sampler *)s;
+}
+
+extern "C" void swd_pauli_sampler_destroy(swd_pauli_sampler *h) { delete (PauliSampler *)h; }
+
+extern "C" int swd_pauli_sampler_info(const swd_pauli_sampler *h, int32_t *mx, int32_t *mz, int32_t *n) {
+    const PauliSampler *s = (const PauliSampler *)h;
+    if (!s) { set_error("null sampler"); return -1; }
+    if (mx) *mx = s->mx;
+    if (mz) *mz = s->mz;
+    if (n) *n = s->n;
+    return 0;
+}
+
+extern "C" int swd_pauli_sampler_sample_dev(swd_pauli_sampler *h, int32_t B, uint64_t seed, uint64_t first_shot, uint8_t *err,
+                                            int64_t err_stride, uint8_t *sx, int64_t sx_stride, uint8_t *sz, int64_t sz_stride,
+                                            void *stream) {
+    PauliSampler *s = (PauliSampler *)h;
+    if (!s || !err || !sx || !sz) { set_error("null argument"); return -1; }
+    if (B <= 0) return 0;
+    err_stride = err_stride ? err_stride : 2 * (int64_t)s->n; sx_stride = sx_stride ? sx_stride : s->mx; sz_stride = sz_stride ? sz_stride : s->mz;
+    if (err_stride < 2 * (int64_t)s->n || sx_stride < s->mx || sz_stride < s->mz) { set_error("Pauli sampler: a stride is shorter than a shot's row"); return -1; }
+    SWD_HIP(hipSetDevice(s->device));
+    const bool wave = s->n <= kWaveShotMaxN;
+    const int spw = wave ? 4 : 1;
+    const size_t lds = (size_t)spw * 2 * s->n4;
+    auto kern = wave ? pauli_sample_kernel<64> : pauli_sample_kernel<256>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((B + spw - 1) / spw)), dim3(256), lds, (hipStream_t)stream, B, s->n, s->mx, s->mz, s->d_thr,
+                       s->d_ptr, s->d_idx, seed, first_shot, err, err_stride, sx, sx_stride, sz, sz_stride);
+    SWD_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int swd_pauli_sampler_sample(swd_pauli_sampler *h, int32_t B, uint64_t seed, uint64_t first_shot, uint8_t *err, uint8_t *sx,
+                                        uint8_t *sz) {
+    PauliSampler *s = (PauliSampler *)h;
+    if (!s || !err || !sx || !sz) { set_error("null argument"); return -1; }
+    if (B <= 0) return 0;
+    SWD_HIP(hipSetDevice(s->device));
+    // (+ 1: a code without checks of one type still gets a device pointer)
+    if (s->err.reserve((size_t)B * 2 * s->n) || s->sx.reserve((size_t)B * s->mx + 1) || s->sz.reserve((size_t)B * s->mz + 1)) return -1;
+    if (swd_pauli_sampler_sample_dev(h, B, seed, first_shot, s->err.as<uint8_t>(), 0, s->sx.as<uint8_t>(), 0, s->sz.as<uint8_t>(), 0, nullptr))
+        return -1;
+    SWD_HIP(hipDeviceSynchronize());
+    SWD_HIP(hipMemcpy(err, s->err.p, (size_t)B * 2 * s->n, hipMemcpyDeviceToHost));
+    if (s->mx) SWD_HIP(hipMemcpy(sx, s->sx.p, (size_t)B * s->mx, hipMemcpyDeviceToHost));
+    if (s->mz) SWD_HIP(hipMemcpy(sz, s->sz.p, (size_t)B * s->mz, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" swd_css_account *swd_css_account_create(const swd_graph_desc *cx, int32_t stab_x, const swd_graph_desc *cz, int32_t stab_z,
+                                                   int device) {
+    if (!cx && !cz) { set_error("CSS accounting: cx and cz are both NULL"); return nullptr; }
+    if ((cx && !csr_desc_ok(cx)) || (cz && !csr_desc_ok(cz))) { set_error("null argument"); return nullptr; }
+    if (cx && cz && cx->n != cz->n) { set_error("cx, cz blocklength does not match!"); return nullptr; }
+    const int n = cx ? cx->n : cz->n;
+    const int64_t rows = (int64_t)(cx ? cx->m : 0) + (cz ? cz->m : 0);
+    if (n > kCapacityMaxN || rows > 65535) {
+        set_error("CSS accounting: %d qubits, %lld rows out of range (%d qubits, 65535 rows)", n, (long long)rows, kCapacityMaxN);
+        return nullptr;
+    }
+    if ((cx && (stab_x < 0 || stab_x > cx->m)) || (cz && (stab_z < 0 || stab_z > cz->m))) {
+        set_error("CSS accounting: the stabiliser row count exceeds the matrix");
+        return nullptr;
+    }
+    if (capacity_device_ok(device)) return nullptr;
+    // a shot's LDS bytes mirror its estimate: [X string | Z string] (cx reads the Z string), or the one string of the single-string form
+    const int zbase = cx && cz ? n : 0;
+    LdsRows lr;
+    if ((cx && lr.append(cx, 0, stab_x, n, zbase, "cx")) || (cz && lr.append(cz, 0, stab_z, n, 0, "cz")) ||
+        (cx && lr.append(cx, stab_x, cx->m, n, zbase, "cx")) || (cz && lr.append(cz, stab_z, cz->m, n, 0, "cz")))
+        return nullptr;
+    CssAccount *a = new CssAccount();
+    a->device = device; a->n = n; a->len = cx && cz ? 2 * n : n; a->rows = (int)rows; a->stab = (cx ? stab_x : 0) + (cz ? stab_z : 0);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_idx = al(lr.ptr.size() * 4), total = al(o_idx + lr.idx.size() * 2 + 2);
+    std::vector<char> h(total, 0);
+    memcpy(&h[0], lr.ptr.data(), lr.ptr.size() * 4);
+    if (!lr.idx.empty()) memcpy(&h[o_idx], lr.idx.data(), lr.idx.size() * 2);
+    if (hipSetDevice(device) != hipSuccess || a->buf.reserve(total) || hipMemcpy(a->buf.p, h.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("CSS accounting: device allocation failed on device %d", device);
+        delete a;
+        return nullptr;
+    }
+    a->d_ptr = (const uint32_t *)a->buf.p; a->d_idx = (const uint16_t *)((char *)a->buf.p + o_idx);
+    return (swd_css_account *)a;
+}
+
+extern "C" void swd_css_account_destroy(swd_css_account *h) { delete (CssAccount *)h; }
+
+extern "C" int swd_css_account_dev(swd_css_account *h, int32_t B, const uint8_t *est, int64_t est_stride, const uint8_t *err,
+                                   int64_t err_stride, const int32_t *stats, int32_t stat_mask, int32_t *result, uint64_t *counters,
+                                   void *stream) {
+    CssAccount *a = (CssAccount *)h;
+    if (!a || !est || !err) { set_error("null argument"); return -1; }
+    if (B <= 0) return 0;
+    est_stride = est_stride ? est_stride : a->len; err_stride = err_stride ? err_stride : a->len;
+    if (est_stride < a->len || err_stride < a->len) { set_error("CSS accounting: a stride is shorter than a shot's %d bytes", a->len); return -1; }
+    SWD_HIP(hipSetDevice(a->device));
+    const bool wave = a->n <= kWaveShotMaxN && a->rows <= 4 * kWaveShotMaxN;
+    const int spw = wave ? 4 : 1;
+    const size_t lds = 16 + 4 * (size_t)spw + (size_t)spw * a->len;
+    const int64_t groups = ((int64_t)B + spw - 1) / spw;
+    auto kern = wave ? css_account_kernel<64> : css_account_kernel<256>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(groups, kAccountGrid)), dim3(256), lds, (hipStream_t)stream, B, a->len, a->rows,
+                       a->stab, a->d_ptr, a->d_idx, est, est_stride, err, err_stride, stats, stat_mask, result,
+                       (unsigned long long *)counters);
+    SWD_HIP(hipGetLastError());
     return 0;
 }
 

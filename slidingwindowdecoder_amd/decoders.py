@@ -1247,3 +1247,284 @@ class DemSampler:
                                              None, 0, st):
             raise RuntimeError(f"swd_sampler_sample_dev failed: {_lib.last_error()}")
         return det, flips
+
+
+class PauliSampler:
+    """Samples Pauli errors of a CSS code and their syndromes on the device: what the first lines of the reference's data-noise
+    cells compute with ``np.random.uniform`` and two dense products (/root/reference/Misc.ipynb cell 2:
+    ``err_x = noise < px+py``, ``err_z = px < noise < px+py+pz``, ``syndrome_x = err_z @ hx.T``, ``syndrome_z = err_x @ hz.T``).
+    The stream is Philox4x32-10, a pure function of (seed, shot number, qubit) (include/swd.h; tests/pauli_ref.py restates it):
+    batches, lanes and ranks can be cut anywhere with ``first_shot``."""
+
+    def __init__(self, Hx, Hz, channel_probs_x, channel_probs_y, channel_probs_z, device=0):
+        L = _lib.lib()
+        if Hx.shape[1] != Hz.shape[1]:
+            raise ValueError("Hx, Hz blocklength does not match!")
+        n = Hx.shape[1]
+        probs = [np.ascontiguousarray(v, dtype=np.float64) for v in (channel_probs_x, channel_probs_y, channel_probs_z)]
+        for v in probs:
+            if v.ndim != 1 or len(v) != n:
+                raise ValueError(f"The length of the channel probability vector must be eqaul to the block length n={n}.")
+        px, py, pz = probs
+        if not all(((v >= 0.0) & (v <= 1.0)).all() for v in probs) or not ((px + py) + pz <= 1.0).all():
+            raise ValueError("channel probabilities must lie in [0, 1] and px + py + pz must not exceed 1")
+        self._px, self._py, self._pz = probs
+        self._cx, self._cz = _Csr(Hx, px), _Csr(Hz, pz)
+        self.mx, self.mz, self.n = self._cx.m, self._cz.m, n
+        self.device = int(device)
+        self._h = L.swd_pauli_sampler_create(C.byref(self._cx.desc), C.byref(self._cz.desc), px.ctypes.data, py.ctypes.data,
+                                             pz.ctypes.data, self.device)
+        if not self._h:
+            msg = _lib.last_error()
+            if "probabilit" in msg or "exceeds 1" in msg or "out of range" in msg:
+                raise ValueError(msg)
+            raise RuntimeError(f"swd_pauli_sampler_create failed: {msg}")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                _lib.lib().swd_pauli_sampler_destroy(self._h)
+            except Exception:  # interpreter shutdown: the module globals may be gone already
+                pass
+            self._h = None
+
+    def sample(self, shots, seed=20240318, first_shot=0):
+        """-> err uint8 [shots, 2, n] (row 0 the X string, row 1 the Z string), sx uint8 [shots, mx] = Hx err_z,
+        sz uint8 [shots, mz] = Hz err_x."""
+        err = np.zeros((shots, 2, self.n), np.uint8)
+        sx, sz = np.zeros((shots, self.mx), np.uint8), np.zeros((shots, self.mz), np.uint8)
+        if _lib.lib().swd_pauli_sampler_sample(self._h, shots, int(seed), int(first_shot), err.ctypes.data, sx.ctypes.data,
+                                               sz.ctypes.data):
+            raise RuntimeError(f"swd_pauli_sampler_sample failed: {_lib.last_error()}")
+        return err, sx, sz
+
+    def sample_device(self, shots, seed=20240318, first_shot=0, out=None, stream=None):
+        """The same as torch uint8 tensors on the device, asynchronous on the current (or given) torch stream; ``out`` = (err, sx,
+        sz) tensors to fill (contiguous, at least ``shots`` rows)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = (torch.empty((shots, 2, self.n), dtype=torch.uint8, device=dev),
+                   torch.empty((shots, self.mx), dtype=torch.uint8, device=dev),
+                   torch.empty((shots, self.mz), dtype=torch.uint8, device=dev))
+        err, sx, sz = out
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        if _lib.lib().swd_pauli_sampler_sample_dev(self._h, shots, int(seed), int(first_shot), err.data_ptr(), 0, sx.data_ptr(), 0,
+                                                   sz.data_ptr(), 0, st.cuda_stream):
+            raise RuntimeError(f"swd_pauli_sampler_sample_dev failed: {_lib.last_error()}")
+        return err[:shots], sx[:shots], sz[:shots]
+
+
+class _CssAccount:
+    """swd_css_account handle: ``cx`` = [Hx; Lx] on the Z string, ``cz`` = [Hz; Lz] on the X string, either None."""
+
+    def __init__(self, cx, stab_x, cz, stab_z, device):
+        self._keep, descs = [], []
+        for mat in (cx, cz):
+            if mat is None:
+                descs.append(None)
+                continue
+            a = sp.csr_matrix(mat)
+            a.data = (np.asarray(a.data) % 2 != 0).astype(np.uint8)
+            a.eliminate_zeros()
+            a.sort_indices()
+            rp, ci = np.ascontiguousarray(a.indptr, np.int32), np.ascontiguousarray(a.indices, np.int32)
+            self._keep += [rp, ci]
+            descs.append(_lib.GraphDesc(a.shape[0], a.shape[1], int(rp[-1]), rp.ctypes.data, ci.ctypes.data, None))
+        self._h = _lib.lib().swd_css_account_create(C.byref(descs[0]) if descs[0] is not None else None, int(stab_x),
+                                                    C.byref(descs[1]) if descs[1] is not None else None, int(stab_z), int(device))
+        if not self._h:
+            raise RuntimeError(f"swd_css_account_create failed: {_lib.last_error()}")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                _lib.lib().swd_css_account_destroy(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+    def account(self, B, est, err, stats, result, counters, stream):
+        """torch tensors (rows may be strided); ``stats`` / ``result`` / ``counters`` may be None."""
+        if _lib.lib().swd_css_account_dev(self._h, B, est.data_ptr(), est.stride(0), err.data_ptr(), err.stride(0),
+                                          stats.data_ptr() if stats is not None else None, STATUS_CONVERGE,
+                                          result.data_ptr() if result is not None else None,
+                                          counters.data_ptr() if counters is not None else None, stream.cuda_stream):
+            raise RuntimeError(f"swd_css_account_dev failed: {_lib.last_error()}")
+
+
+class CodeCapacityResult:
+    """Counters of a code-capacity run.  ``logical_errors``: shots whose correction leaves a logical error by the reference's
+    criterion (a residual syndrome counts: it is not in ker(h) either); ``residual_syndromes``: those among them whose correction
+    does not even reproduce the syndrome; ``not_converged``: shots with ``converge`` = 0 (the notebooks' "flagged");
+    ``osd0_logical_errors``: logical errors of the OSD-0 solutions, None unless asked for."""
+
+    def __init__(self, shots, logical_errors, residual_syndromes, not_converged, osd0_logical_errors=None):
+        self.shots, self.logical_errors, self.residual_syndromes = int(shots), int(logical_errors), int(residual_syndromes)
+        self.not_converged = int(not_converged)
+        self.osd0_logical_errors = None if osd0_logical_errors is None else int(osd0_logical_errors)
+
+    @property
+    def ler(self):
+        return self.logical_errors / self.shots if self.shots else float("nan")
+
+    @property
+    def ler_stderr(self):
+        """binomial standard error of ``ler``"""
+        p = self.ler
+        return float(np.sqrt(p * (1.0 - p) / self.shots)) if self.shots else float("nan")
+
+    def _fields(self):
+        return (self.shots, self.logical_errors, self.residual_syndromes, self.not_converged, self.osd0_logical_errors)
+
+    def __eq__(self, other):
+        return isinstance(other, CodeCapacityResult) and self._fields() == other._fields()
+
+    def __repr__(self):
+        return ("CodeCapacityResult(shots={}, logical_errors={}, residual_syndromes={}, not_converged={}, "
+                "osd0_logical_errors={})".format(*self._fields()))
+
+
+class CodeCapacityExperiment:
+    """The reference's data-noise (code-capacity) Monte Carlo on the device: sample, decode, account, count -- only counters come
+    back to the host.
+
+    ``decoder="bp4_osd"`` with ``method="decode"`` is /root/reference/Misc.ipynb cell 2, with ``method="camel_decode"`` cell 8:
+    Pauli errors from ``channel_probs_x / _y / _z`` (``PauliSampler``), ``bp4_osd(Hx, Hz, **decoder_kwargs)``, and the criterion
+    ``(dz @ hz_perp.T).any() or (dx @ hx_perp.T).any()`` on the difference of estimate and error.
+    ``decoder`` in ``osd_window``, ``bpgdg_decoder``, ``bpgd_decoder``, ``bp_history_decoder`` is the single-basis harness of
+    /root/reference/src/simulation.py: errors Bernoulli(``channel_probs``) (``DemSampler`` with ``chk = Hx``), syndrome
+    ``err @ hx.T``, ``decoder(Hx, **decoder_kwargs)``, criterion ``(d @ hz_perp.T).any()``.
+
+    ``code_or_matrices``: a ``codes.CSSCode`` or ``(Hx, Hz)``; ``lx`` / ``lz`` (keyword arguments, optional) are logical operators
+    spanning ker(Hz) / rowspace(Hx) and ker(Hx) / rowspace(Hz), computed as ``codes.CSSCode`` does when absent."""
+
+    _BINARY = {"osd_window": osd_window, "bpgdg_decoder": bpgdg_decoder, "bpgd_decoder": bpgd_decoder,
+               "bp_history_decoder": bp_history_decoder}
+
+    def __init__(self, code_or_matrices, decoder="bp4_osd", method="decode", device=0, **decoder_kwargs):
+        from . import codes
+        if decoder != "bp4_osd" and decoder not in self._BINARY:
+            raise ValueError(f"unknown decoder '{decoder}': choose bp4_osd, " + ", ".join(self._BINARY))
+        if method not in ("decode", "camel_decode") or (method == "camel_decode" and decoder != "bp4_osd"):
+            raise ValueError(f"unknown method '{method}' for {decoder}: 'decode', or 'camel_decode' with bp4_osd")
+        lx, lz = decoder_kwargs.pop("lx", None), decoder_kwargs.pop("lz", None)
+        if isinstance(code_or_matrices, codes.CSSCode):
+            code = code_or_matrices
+        else:
+            hx, hz = (m.toarray() if sp.issparse(m) else np.asarray(m) for m in code_or_matrices)
+            code = codes.CSSCode(hx, hz, lx=lx, lz=lz)
+        self.code, self.decoder_name, self.method, self.device = code, decoder, method, int(device)
+        self.n, self.mx, self.mz = code.N, code.hx.shape[0], code.hz.shape[0]
+        kw = dict(decoder_kwargs, device=self.device)
+        if decoder == "bp4_osd":
+            self.decoder = bp4_osd(code.hx, code.hz, **kw)
+            self.sampler = PauliSampler(code.hx, code.hz, kw["channel_probs_x"], kw["channel_probs_y"], kw["channel_probs_z"],
+                                        device=self.device)
+            self._acct = _CssAccount(np.vstack([code.hx, code.lx]), self.mx, np.vstack([code.hz, code.lz]), self.mz, self.device)
+        else:
+            self.decoder = self._BINARY[decoder](code.hx, **kw)
+            self.sampler = DemSampler(code.hx, None, kw["channel_probs"], device=self.device)
+            self._acct = _CssAccount(np.vstack([code.hx, code.lx]), self.mx, None, 0, self.device)
+        self._lanes = []
+
+    # ---- one batch on one lane: sample, decode, account, all enqueued on the lane's stream -----------------------------------
+    def _lane_buffers(self, k, B, osd0):
+        import torch
+        while len(self._lanes) <= k:  # (streams of both priorities: streams of one priority may share a hardware queue and then run back to back)
+            self._lanes.append(dict(cap=0, stream=torch.cuda.Stream(torch.device("cuda", self.device), priority=-(len(self._lanes) & 1))))
+        ln = self._lanes[k]
+        if ln["cap"] < B or (osd0 and ln.get("osd0") is None):
+            dev, u8 = torch.device("cuda", self.device), torch.uint8
+            ln["stream"].synchronize()  # (the buffers it replaces may still be in use)
+            cap = max(B, ln["cap"])
+            width = (2, self.n) if self.decoder_name == "bp4_osd" else (self.n,)
+            ln.update(cap=cap, err=torch.empty((cap,) + width, dtype=u8, device=dev), est=torch.empty((cap,) + width, dtype=u8, device=dev),
+                      sx=torch.empty((cap, self.mx), dtype=u8, device=dev), sz=torch.empty((cap, self.mz), dtype=u8, device=dev),
+                      stats=torch.empty((cap, _lib.STAT_WORDS), dtype=torch.int32, device=dev),
+                      result=torch.empty((cap,), dtype=torch.int32, device=dev), result0=torch.empty((cap,), dtype=torch.int32, device=dev),
+                      min_pm=torch.empty((cap,), dtype=torch.float64, device=dev),
+                      osd0=torch.empty((cap,) + width, dtype=u8, device=dev) if osd0 else None)
+        return ln
+
+    def _enqueue(self, ln, B, seed, first_shot, osd0, counters, counters0):
+        import torch
+        L, st, d = _lib.lib(), ln["stream"], self.decoder
+        s = st.cuda_stream
+        with torch.cuda.stream(st):
+            if self.decoder_name == "bp4_osd":
+                self.sampler.sample_device(B, seed, first_shot, out=(ln["err"], ln["sx"], ln["sz"]), stream=st)
+                if self.method == "camel_decode":
+                    rc = L.swd_bp4_camel_decode_batch_dev(d._h, B, ln["sx"].data_ptr(), ln["sz"].data_ptr(), ln["est"].data_ptr(),
+                                                          ln["stats"].data_ptr(), None, s)
+                else:
+                    if osd0:  # (the decoder writes a shot's OSD-0 vector when BP converged or the OSD ran)
+                        ln["osd0"][:B].zero_()
+                    rc = L.swd_bp4_decode_batch_dev(d._h, B, ln["sx"].data_ptr(), ln["sz"].data_ptr(), ln["est"].data_ptr(),
+                                                    ln["stats"].data_ptr(), None, ln["osd0"].data_ptr() if osd0 else None, None, s)
+            else:
+                if L.swd_sampler_sample_dev(self.sampler._h, B, int(seed), int(first_shot), ln["sx"].data_ptr(), 0, None,
+                                            ln["err"].data_ptr(), 0, s):
+                    raise RuntimeError(f"swd_sampler_sample_dev failed: {_lib.last_error()}")
+                if self.decoder_name == "osd_window":
+                    rc = L.swd_osdw_decode_batch_dev(d._h, B, ln["sx"].data_ptr(), 0, ln["est"].data_ptr(), 0, ln["stats"].data_ptr(),
+                                                     ln["min_pm"].data_ptr(), None, 0, None, None, s)
+                else:
+                    rc = L.swd_gdg_decode_batch_dev(d._h, B, ln["sx"].data_ptr(), 0, ln["est"].data_ptr(), 0, ln["stats"].data_ptr(),
+                                                    ln["min_pm"].data_ptr(), s)
+            if rc:
+                raise RuntimeError(f"{self.decoder_name} device decode failed: {_lib.last_error()}")
+            self._acct.account(B, ln["est"], ln["err"], ln["stats"], ln["result"], counters, st)
+            if osd0:
+                self._acct.account(B, ln["osd0"], ln["err"], None, ln["result0"], counters0, st)
+
+    def _check_osd0(self, osd0):
+        if osd0 and not (self.decoder_name == "bp4_osd" and self.method == "decode"):
+            raise ValueError("osd0=True needs decoder='bp4_osd' with method='decode'")
+
+    def run(self, shots, batch=65536, seed=20240318, first_shot=0, lanes=4, osd0=False, max_errors=None):
+        """``shots`` shots numbered ``first_shot ..`` in batches of ``batch`` that go round ``lanes`` streams (``bp4_osd`` has four
+        launch slots), each lane with buffers of its own.  The host reads the counters once at the end; the result is then a pure
+        function of (seed, first_shot, shots), whatever ``batch`` and ``lanes``.  With ``max_errors`` the counters are read after
+        every round of lanes and the run stops once ``logical_errors >= max_errors``: it stops at batch granularity -- whole rounds of
+        ``lanes`` batches -- so ``result.shots`` tells how many shots were run and the count may overshoot ``max_errors``.
+        ``osd0=True`` (``bp4_osd`` / ``decode``) accounts the OSD-0 solutions in a second pass.  -> ``CodeCapacityResult``."""
+        import torch
+        shots, batch, lanes = int(shots), int(batch), int(lanes)
+        if shots < 0 or batch <= 0 or lanes <= 0:
+            raise ValueError("shots >= 0, batch > 0, lanes > 0")
+        self._check_osd0(osd0)
+        dev = torch.device("cuda", self.device)
+        counters = torch.zeros((2, 4), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the lanes add into zeroed counters
+        start, k = 0, 0
+        while start < shots:
+            B = min(batch, shots - start)
+            ln = self._lane_buffers(k % lanes, min(batch, shots), osd0)
+            self._enqueue(ln, B, seed, first_shot + start, osd0, counters[0], counters[1] if osd0 else None)
+            start, k = start + B, k + 1
+            if max_errors is not None and k % lanes == 0:
+                for l2 in self._lanes[:lanes]:
+                    l2["stream"].synchronize()
+                if int(counters[0, 1].item()) >= max_errors:
+                    break
+        for l2 in self._lanes:
+            l2["stream"].synchronize()
+        c = counters.cpu().numpy()
+        return CodeCapacityResult(c[0, 0], c[0, 1], c[0, 2], c[0, 3], c[1, 1] if osd0 else None)
+
+    def run_batch(self, B, seed=20240318, first_shot=0, osd0=False):
+        """One batch with the per-shot arrays on the host (tests and debugging): dict with ``err``, ``sx``, ``sz`` (``bp4_osd``:
+        [B, 2, n] and both syndromes; binary decoders: [B, n], ``sx`` only), ``est``, ``stats`` [B, 8], ``result`` (the result words
+        of include/swd.h: bit 0 logical error, bit 1 residual syndrome, bit 2 not converged) and, with ``osd0``, ``osd0`` /
+        ``result_osd0``."""
+        self._check_osd0(osd0)
+        B = int(B)
+        ln = self._lane_buffers(0, B, osd0)
+        self._enqueue(ln, B, seed, int(first_shot), osd0, None, None)
+        ln["stream"].synchronize()
+        keys = ["err", "sx", "est", "stats", "result"] + (["sz"] if self.decoder_name == "bp4_osd" else [])
+        out = {key: ln[key][:B].cpu().numpy() for key in keys}
+        if osd0:
+            out["osd0"], out["result_osd0"] = ln["osd0"][:B].cpu().numpy(), ln["result0"][:B].cpu().numpy()
+        return out
