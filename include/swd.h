@@ -368,6 +368,32 @@ int swd_pipeline_stream_pending(swd_stream *s); /* host batches pushed and not y
 int swd_pipeline_stream_push_dev(swd_stream *s, int32_t B, const uint8_t *det, int64_t det_stride, uint8_t *total,
                                  int64_t total_stride, int32_t *stats, double *min_pm, int32_t *shot_result, void *after);
 int swd_pipeline_stream_wait(swd_stream *s, void *stream);
+/* `stream` waits (device-side) for the lane of the most recent push or push_dev alone -- what the consumer of batch k needs, so that
+ * batch k + 1 on the other lane stays in flight.  Fails if nothing has been pushed on this stream object. */
+int swd_pipeline_stream_wait_last(swd_stream *s, void *stream);
+
+/* ---- memory experiments: per-shot accounting of a window-loop batch ------------------------------
+ * The last lines of the reference's sliding_window_decoder (/root/reference/osd.py:181-191) on the device, so that sample -> window
+ * loop -> count needs no per-shot array on the host.
+ *   shot_result [B][2]  as swd_pipeline_decode_dev writes it     true_flips [B]  as swd_sampler_sample_dev writes obs_flips
+ *   stats [B][W][SWD_STAT_WORDS], nullable: only words 0 and 1 are read
+ * result[b] (nullable) =
+ *   bit 1  flagged: shot_result[2b+1] != 0
+ *   bit 2  observable mismatch: shot_result[2b] != true_flips[b]
+ *   bit 0  bit 1 or bit 2                                         (np.logical_or(flagged_err, logical_err), osd.py:184-188)
+ * counters (nullable) uint64[4] = shots, bit-0, bit-1, bit-2 counts: the layout of swd_css_account_dev.
+ * window_counters (nullable, used with stats) uint64[W][SWD_WINDOW_COUNTER_WORDS]: words 0-7 the histogram of the exit class
+ * stats[b][t][0] & 7, word 8 the shots with stats[b][t][0] & SWD_STATUS_CONVERGE zero, word 9 the sum of stats[b][t][1].
+ * failed (nullable) uint64[1 + failed_cap]: word 0 is ADDED to with the number of shots that have bit 0; the global number
+ * first_shot + b of such a shot is stored at 1 + slot while slot < failed_cap, slot = what word 0 held before the add of its
+ * workgroup plus its rank among the workgroup's failing shots; later ones are counted only.  Which shots are stored when they do
+ * not all fit, and the order of those stored, depend on arrival; the counts and the sorted complete list do not.
+ * All three are ADDED to with integer atomics (one per non-zero sum and workgroup); the caller zeroes them.  Device pointers,
+ * asynchronous on `stream`; B = 0 does nothing. */
+#define SWD_WINDOW_COUNTER_WORDS 10
+int swd_shot_account_dev(int device, int32_t B, int32_t W, const int32_t *shot_result, const uint32_t *true_flips,
+                         const int32_t *stats, uint64_t first_shot, int32_t *result, uint64_t *counters,
+                         uint64_t *window_counters, uint64_t *failed, int32_t failed_cap, void *stream);
 
 /* ---- online sessions: the window loop driven by the arrival of detector rows --------------------
  * The (W, F) scheme exists so that corrections are committed while the experiment still runs; the loop of the reference harness

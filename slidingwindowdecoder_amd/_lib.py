@@ -83,6 +83,7 @@ SYMBOLS = [
     ("swd_pipeline_stream_pending", C.c_int, [_vp]),
     ("swd_pipeline_stream_push_dev", C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     ("swd_pipeline_stream_wait", C.c_int, [_vp, _vp]),
+    ("swd_pipeline_stream_wait_last", C.c_int, [_vp, _vp]),
     ("swd_pipeline_session_create", _vp, [_vp, _i32]),
     ("swd_pipeline_session_destroy", None, [_vp]),
     ("swd_pipeline_session_begin", C.c_int, [_vp, _i32]),
@@ -117,11 +118,13 @@ SYMBOLS = [
     ("swd_css_account_create", _vp, [C.POINTER(GraphDesc), _i32, C.POINTER(GraphDesc), _i32, C.c_int]),
     ("swd_css_account_destroy", None, [_vp]),
     ("swd_css_account_dev", C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    ("swd_shot_account_dev", C.c_int, [C.c_int, _i32, _i32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _i32, _vp]),
     ("swd_diag_occupy", C.c_int, [C.c_int, _i32, _i32, _i32, _i32, _vp]),
     ("swd_graph_layout", C.c_int, [C.POINTER(GraphDesc), _i32] + [_vp] * 9),
 ]
 
 STAT_WORDS = 8
+WINDOW_COUNTER_WORDS = 10  # include/swd.h: SWD_WINDOW_COUNTER_WORDS
 STREAM_PACKED, STREAM_NO_STATS = 1, 2
 STREAM_NO_DEPENDENCY = C.c_void_p(-1).value  # include/swd.h: SWD_STREAM_NO_DEPENDENCY
 

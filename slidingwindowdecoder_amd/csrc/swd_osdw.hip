@@ -900,6 +900,17 @@ extern "C" int swd_pipeline_stream_wait(swd_stream *s, void *stream) {
     return 0;
 }
 
+extern "C" int swd_pipeline_stream_wait_last(swd_stream *s, void *stream) {
+    HostStream *hs = (HostStream *)s;
+    if (!hs) { set_error("null stream"); return -1; }
+    std::lock_guard<std::mutex> lk(hs->mu);
+    if (!stream_plan(hs)) return -1;
+    if (hs->npush == 0) { set_error("stream wait_last: nothing has been pushed on this stream object"); return -1; }
+    SWD_HIP(hipSetDevice(hs->plan->device));
+    SWD_HIP(hipStreamWaitEvent((hipStream_t)stream, hs->lane[(hs->npush - 1) & 1].done, 0)); // (recorded by the push behind its launch)
+    return 0;
+}
+
 // diagnostics: per-phase device timers of the last pipeline launch (100 MHz ticks), [B][W][8]
 extern "C" int swd_pipeline_set_profiling(swd_pipeline *h, int32_t on) {
     Plan *d = (Plan *)h;

@@ -452,6 +452,102 @@ extern "C" int swd_css_account_dev(swd_css_account *h, int32_t B, const uint8_t 
     return 0;
 }
 
+// ---- memory experiments (include/swd.h: swd_shot_account_dev) ------------------------------------------------------------------------
+// The last lines of the reference's sliding_window_decoder (/root/reference/osd.py:181-191) for a batch of the window loop: the
+// decisions the pipeline left in shot_result against the sampler's true observable flips, and the per-window records reduced to
+// counts.  One thread per shot, the grid walks the shots like css_account_kernel; a wave counts with ballots, the workgroup sums
+// in LDS and adds each non-zero sum to the global counters once.  Everything is integer: no result depends on arrival order.
+namespace {
+
+constexpr int kWindowTile = 64; // windows whose counters a workgroup keeps in LDS at a time (64 x 10 x 8 B = 5 KB)
+
+__global__ void __launch_bounds__(256) shot_account_kernel(int B, int W, const int32_t *shot_result, const uint32_t *true_flips,
+                                                           const int32_t *stats, uint64_t first_shot, int32_t *result,
+                                                           unsigned long long *counters, unsigned long long *window_counters,
+                                                           unsigned long long *failed, int failed_cap) {
+    __shared__ unsigned long long hist[kWindowTile * SWD_WINDOW_COUNTER_WORDS];
+    __shared__ unsigned long long fail_base;
+    __shared__ uint32_t cnt[4], wave_fail[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool windows = stats && window_counters && W > 0;
+    if (tid < 4) cnt[tid] = 0;
+    // the shots are walked once per tile of windows; the per-shot part belongs to the first walk
+    for (int t0 = 0; t0 == 0 || (windows && t0 < W); t0 += kWindowTile) {
+        const int nt = windows ? min(kWindowTile, W - t0) : 0;
+        for (int i = tid; i < nt * SWD_WINDOW_COUNTER_WORDS; i += 256) hist[i] = 0;
+        __syncthreads();
+        for (int64_t base = (int64_t)blockIdx.x * 256; base < B; base += (int64_t)gridDim.x * 256) {
+            const int64_t b = base + tid;
+            const bool live = b < B;
+            if (t0 == 0) {
+                uint32_t w = 0;
+                if (live) {
+                    if (shot_result[2 * b + 1] != 0) w |= 2u;
+                    if ((uint32_t)shot_result[2 * b] != true_flips[b]) w |= 4u;
+                    if (w) w |= 1u; // np.logical_or(flagged_err, logical_err), osd.py:184-188
+                    if (result) result[b] = (int32_t)w;
+                }
+                const unsigned long long m_live = __ballot(live), m_fail = __ballot(w & 1u), m_flag = __ballot(w & 2u), m_obs = __ballot(w & 4u);
+                const unsigned long long m = lane == 0 ? m_live : lane == 1 ? m_fail : lane == 2 ? m_flag : m_obs;
+                if (lane < 4 && m) atomicAdd(&cnt[lane], (uint32_t)__popcll(m));
+                if (failed) { // slots for the pass's failing shots: counted in LDS, reserved with one atomic
+                    if (lane == 0) wave_fail[wave] = (uint32_t)__popcll(m_fail);
+                    __syncthreads();
+                    const uint32_t n = wave_fail[0] + wave_fail[1] + wave_fail[2] + wave_fail[3];
+                    if (tid == 0 && n) fail_base = atomicAdd(&failed[0], (unsigned long long)n);
+                    __syncthreads();
+                    if (w & 1u) {
+                        uint32_t before = (uint32_t)__popcll(m_fail & ((1ull << lane) - 1ull));
+                        for (int k = 0; k < wave; ++k) before += wave_fail[k];
+                        const unsigned long long slot = fail_base + before;
+                        if (slot < (unsigned long long)failed_cap) failed[1 + slot] = first_shot + (uint64_t)b;
+                    }
+                    __syncthreads(); // (the next pass writes wave_fail and fail_base again)
+                }
+            }
+            for (int t = 0; t < nt; ++t) {
+                const int32_t *st = stats + (live ? (b * W + (t0 + t)) * SWD_STAT_WORDS : 0); // words 0 and 1 only
+                const int32_t s0 = live ? st[0] : 0, s1 = live ? st[1] : 0;
+                unsigned long long mine = 0, its = (unsigned long long)(long long)s1;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    const unsigned long long mc = __ballot(live && (s0 & 7) == c);
+                    if (lane == c) mine = (unsigned long long)__popcll(mc);
+                }
+                const unsigned long long mn = __ballot(live && !(s0 & SWD_STATUS_CONVERGE));
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) its += __shfl_xor(its, off);
+                if (lane == 8) mine = (unsigned long long)__popcll(mn);
+                if (lane == 9) mine = its;
+                if (lane < SWD_WINDOW_COUNTER_WORDS && mine) atomicAdd(&hist[t * SWD_WINDOW_COUNTER_WORDS + lane], mine);
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < nt * SWD_WINDOW_COUNTER_WORDS; i += 256)
+            if (hist[i]) atomicAdd(&window_counters[(size_t)t0 * SWD_WINDOW_COUNTER_WORDS + i], hist[i]);
+        __syncthreads();
+    }
+    if (counters && tid < 4 && cnt[tid]) atomicAdd(&counters[tid], (unsigned long long)cnt[tid]);
+}
+
+} // namespace
+
+extern "C" int swd_shot_account_dev(int device, int32_t B, int32_t W, const int32_t *shot_result, const uint32_t *true_flips,
+                                    const int32_t *stats, uint64_t first_shot, int32_t *result, uint64_t *counters,
+                                    uint64_t *window_counters, uint64_t *failed, int32_t failed_cap, void *stream) {
+    if (B <= 0) return 0;
+    if (!shot_result || !true_flips) { set_error("null argument"); return -1; }
+    if (W < 0 || (failed && failed_cap < 0)) { set_error("shot accounting: W = %d, failed_cap = %d must not be negative", W, failed_cap); return -1; }
+    if (capacity_device_ok(device)) return -1;
+    SWD_HIP(hipSetDevice(device));
+    const int64_t groups = ((int64_t)B + 255) / 256;
+    hipLaunchKernelGGL(shot_account_kernel, dim3((unsigned)std::min<int64_t>(groups, kAccountGrid)), dim3(256), 0, (hipStream_t)stream, B, W,
+                       shot_result, true_flips, stats, first_shot, result, (unsigned long long *)counters,
+                       (unsigned long long *)window_counters, (unsigned long long *)failed, failed ? failed_cap : 0);
+    SWD_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- diagnostics: a foreign kernel that holds workgroup slots for a bounded time (include/swd.h: swd_diag_occupy) ----
 namespace swd {
 __global__ void __launch_bounds__(1024) occupy_kernel(long long ticks, uint32_t *sink) {

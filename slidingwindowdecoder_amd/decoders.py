@@ -903,6 +903,12 @@ class SlidingWindowStream:
         if _lib.lib().swd_pipeline_stream_wait(self._h, stream.cuda_stream if stream is not None else None):
             raise RuntimeError(f"swd_pipeline_stream_wait failed: {_lib.last_error()}")
 
+    def wait_last(self, stream):
+        """the torch stream ``stream`` waits (device-side) for the lane of the most recent push alone: the batch on the other lane
+        stays in flight.  RuntimeError if nothing has been pushed."""
+        if _lib.lib().swd_pipeline_stream_wait_last(self._h, stream.cuda_stream or None):
+            raise RuntimeError(f"swd_pipeline_stream_wait_last failed: {_lib.last_error()}")
+
 
 class _SessionBase:
     """What ``SlidingWindowSession`` and ``RollingSession`` share: the handle's life, ``begin`` and the checks of arriving rows.
@@ -1527,4 +1533,235 @@ class CodeCapacityExperiment:
         out = {key: ln[key][:B].cpu().numpy() for key in keys}
         if osd0:
             out["osd0"], out["result_osd0"] = ln["osd0"][:B].cpu().numpy(), ln["result0"][:B].cpu().numpy()
+        return out
+
+
+def shot_account_device(shot_result, true_flips, stats=None, first_shot=0, result=None, counters=None, window_counters=None,
+                        failed=None, stream=None):
+    """swd_shot_account_dev on torch CUDA tensors (include/swd.h): ``shot_result`` int32 [B, 2] and ``true_flips`` int32 [B] as the
+    window loop and the DEM sampler write them, ``stats`` int32 [B, W, 8] or None; ``result`` int32 [B], ``counters`` int64 [4],
+    ``window_counters`` int64 [W, 10] and ``failed`` int64 [1 + cap] are optional outputs, the last three ADDED to (the caller zeroes
+    them).  Asynchronous on the current (or given) torch stream."""
+    import torch
+    B, dev = int(shot_result.shape[0]), shot_result.device
+    for name, t in (("shot_result", shot_result), ("true_flips", true_flips), ("stats", stats), ("result", result), ("counters", counters),
+                    ("window_counters", window_counters), ("failed", failed)):
+        if t is not None and (not t.is_cuda or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous CUDA tensor on {dev}")
+    if tuple(shot_result.shape) != (B, 2) or shot_result.dtype != torch.int32 or tuple(true_flips.shape) != (B,) or true_flips.dtype != torch.int32:
+        raise ValueError("shot_result must be int32 [B, 2] and true_flips int32 [B]")
+    W = 0
+    if stats is not None:
+        if stats.dim() != 3 or stats.shape[0] != B or stats.shape[2] != _lib.STAT_WORDS or stats.dtype != torch.int32:
+            raise ValueError(f"stats must be int32 [B, W, {_lib.STAT_WORDS}]")
+        W = int(stats.shape[1])
+    if result is not None and (result.dtype != torch.int32 or result.numel() < B):
+        raise ValueError("result must be int32 [B]")
+    if counters is not None and (counters.dtype != torch.int64 or counters.numel() != 4):
+        raise ValueError("counters must be int64 [4]")
+    if window_counters is not None and (stats is None or window_counters.dtype != torch.int64
+                                        or tuple(window_counters.shape) != (W, _lib.WINDOW_COUNTER_WORDS)):
+        raise ValueError(f"window_counters needs stats and must be int64 [W, {_lib.WINDOW_COUNTER_WORDS}]")
+    if failed is not None and (failed.dtype != torch.int64 or failed.dim() != 1 or failed.numel() < 1):
+        raise ValueError("failed must be int64 [1 + cap]")
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    if _lib.lib().swd_shot_account_dev(dev.index, B, W, ptr(shot_result), ptr(true_flips), ptr(stats), int(first_shot), ptr(result),
+                                       ptr(counters), ptr(window_counters), ptr(failed), failed.numel() - 1 if failed is not None else 0,
+                                       st.cuda_stream or None):
+        raise RuntimeError(f"swd_shot_account_dev failed: {_lib.last_error()}")
+
+
+class MemoryResult:
+    """Counters of a memory experiment under sliding windows -- what the reference's ``sliding_window_decoder`` prints
+    (/root/reference/osd.py:181-194).  ``logical_errors``: shots that are flagged or whose predicted observable flips differ from
+    the true ones ("Logical Errors"); ``flagged``: shots whose residual syndrome is not zero ("Overall Flagged Errors");
+    ``observable_mismatches``: shots with a wrong observable, flagged or not.  Per window, or None when the run kept no window
+    statistics: ``window_exit_classes`` [W, 8] (how many shots left window t through exit class c), ``window_not_converged`` [W]
+    ("Window i, flagged Errors") and ``window_bp_iterations`` [W] (summed over the shots).  ``failed_shots``: sorted global numbers
+    of shots with a logical error, at most ``keep_failures`` of the run; ``failed_shots_complete``: every such shot is in it (which
+    shots an incomplete list holds is not reproducible, and ``==`` then leaves the list out)."""
+
+    def __init__(self, shots, logical_errors, flagged, observable_mismatches, window_exit_classes=None, window_not_converged=None,
+                 window_bp_iterations=None, failed_shots=None, failed_shots_complete=None):
+        self.shots, self.logical_errors, self.flagged = int(shots), int(logical_errors), int(flagged)
+        self.observable_mismatches = int(observable_mismatches)
+        as64 = lambda a: None if a is None else np.array(a, dtype=np.int64)  # noqa: E731
+        self.window_exit_classes, self.window_not_converged = as64(window_exit_classes), as64(window_not_converged)
+        self.window_bp_iterations = as64(window_bp_iterations)
+        self.failed_shots = np.sort(np.array([] if failed_shots is None else failed_shots, dtype=np.uint64))
+        self.failed_shots_complete = (len(self.failed_shots) == self.logical_errors) if failed_shots_complete is None \
+            else bool(failed_shots_complete)
+
+    @property
+    def ler(self):
+        return self.logical_errors / self.shots if self.shots else float("nan")
+
+    @property
+    def ler_stderr(self):
+        """binomial standard error of ``ler``"""
+        p = self.ler
+        return float(np.sqrt(p * (1.0 - p) / self.shots)) if self.shots else float("nan")
+
+    def ler_per_round(self, num_repeat):
+        """osd.py:190-191: ``1 - (1 - ler) ** (1 / num_repeat)``"""
+        return 1.0 - (1.0 - self.ler) ** (1.0 / num_repeat)
+
+    def _fields(self):
+        return (self.shots, self.logical_errors, self.flagged, self.observable_mismatches, self.failed_shots_complete)
+
+    def __eq__(self, other):
+        if not isinstance(other, MemoryResult) or self._fields() != other._fields():
+            return False
+        for a, b in ((self.window_exit_classes, other.window_exit_classes), (self.window_not_converged, other.window_not_converged),
+                     (self.window_bp_iterations, other.window_bp_iterations)):
+            if (a is None) != (b is None) or (a is not None and not np.array_equal(a, b)):
+                return False
+        return not self.failed_shots_complete or np.array_equal(self.failed_shots, other.failed_shots)
+
+    __hash__ = None
+
+    def __add__(self, other):
+        """counters of two runs over disjoint shots (batches of a run, ranks that shard with ``first_shot``)"""
+        if not isinstance(other, MemoryResult):
+            return NotImplemented
+        win = [None if a is None or b is None else a + b for a, b in
+               ((self.window_exit_classes, other.window_exit_classes), (self.window_not_converged, other.window_not_converged),
+                (self.window_bp_iterations, other.window_bp_iterations))]
+        return MemoryResult(self.shots + other.shots, self.logical_errors + other.logical_errors, self.flagged + other.flagged,
+                            self.observable_mismatches + other.observable_mismatches, *win,
+                            failed_shots=np.concatenate([self.failed_shots, other.failed_shots]),
+                            failed_shots_complete=self.failed_shots_complete and other.failed_shots_complete)
+
+    def __repr__(self):
+        s = "MemoryResult(shots={}, logical_errors={}, flagged={}, observable_mismatches={}".format(*self._fields()[:4])
+        if self.window_not_converged is not None:
+            s += f", window_not_converged={self.window_not_converged.tolist()}"
+        return s + f", failed_shots={len(self.failed_shots)}{'' if self.failed_shots_complete else ' (incomplete)'})"
+
+
+class MemoryExperiment:
+    """The reference's ``sliding_window_decoder(N, p, num_repeat, num_shots, W, F, ...)`` (/root/reference/osd.py:123-194, guessing.py)
+    on the device: sample the detector error model (``DemSampler``), run the (W, F) window loop (``SlidingWindowDecoder``), compare
+    the predicted observable flips with the true ones and reduce the per-window records -- only counters come back to the host.
+
+    ``plan``: a ``windows.WindowPlan`` with 1..32 observables that the one-launch pipeline takes; ``decoder`` and the keyword
+    arguments are those of ``SlidingWindowDecoder``."""
+
+    def __init__(self, plan, decoder="osd_window", device=0, **decoder_kwargs):
+        num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
+        if num_obs == 0:
+            raise ValueError("a memory experiment needs observables: plan.obs is empty")
+        if num_obs > 32:
+            raise ValueError(f"a memory experiment carries at most 32 observables per shot, plan.obs has {num_obs}")
+        self.plan, self.device = plan, int(device)
+        self.decoder = SlidingWindowDecoder(plan, device=self.device, decoder=decoder, **decoder_kwargs)
+        self.decoder._no_loop("MemoryExperiment")
+        self.sampler = DemSampler(plan.chk, plan.obs, plan.priors, device=self.device)
+        self.W = self.decoder.W
+        self._stream, self._lanes = None, []
+
+    @classmethod
+    def bb(cls, N, p, num_repeat, W, F, method=1, z_basis=True, decoder="osd_window", **kw):
+        """the plan as the notebooks build it: ``bb_code(N)``, ``bb_dem(code, A, B, p, num_repeat, z_basis)``, ``plan_windows``"""
+        from .circuit import bb_dem
+        from .codes import bb_code
+        from .windows import plan_windows
+        code, A, B = bb_code(N)
+        dem = bb_dem(code, A, B, p, num_repeat, z_basis=z_basis)
+        return cls(plan_windows(dem.chk, dem.obs, dem.priors, N // 2, W, F, method, z_basis), decoder=decoder, **kw)
+
+    def close(self):
+        if getattr(self, "_stream", None) is not None:
+            self._stream.close()
+            self._stream = None
+
+    __del__ = close
+
+    # ---- one batch on one lane: sample, window loop, account, all ordered on the lane's torch stream ---------------------------
+    def _lane(self, k, cap, window_stats):
+        import torch
+        dev = torch.device("cuda", self.device)
+        while len(self._lanes) <= k:  # (streams of both priorities: streams of one priority may share a hardware queue)
+            self._lanes.append(dict(cap=0, stats=None, stream=torch.cuda.Stream(dev, priority=-(len(self._lanes) & 1))))
+        ln, d = self._lanes[k], self.decoder
+        if ln["cap"] < cap or (window_stats and ln["stats"] is None):
+            ln["stream"].synchronize()  # (the buffers it replaces may still be in use)
+            cap, i32 = max(cap, ln["cap"]), torch.int32
+            ln.update(cap=cap, det=torch.empty((cap, d.num_det), dtype=torch.uint8, device=dev), flips=torch.empty((cap,), dtype=i32, device=dev),
+                      total=torch.empty((cap, d.num_col), dtype=torch.uint8, device=dev), shot_result=torch.empty((cap, 2), dtype=i32, device=dev),
+                      result=torch.empty((cap,), dtype=i32, device=dev),
+                      stats=torch.empty((cap, self.W, _lib.STAT_WORDS), dtype=i32, device=dev) if window_stats or ln["stats"] is not None else None)
+        return ln
+
+    def _enqueue(self, ln, B, seed, first_shot, streamed, window_stats, counters, window_counters, failed):
+        st, d = ln["stream"], self.decoder
+        det, total, shot, stats = ln["det"][:B], ln["total"][:B], ln["shot_result"][:B], ln["stats"][:B] if window_stats else None
+        if _lib.lib().swd_sampler_sample_dev(self.sampler._h, B, int(seed), int(first_shot), det.data_ptr(), 0, ln["flips"].data_ptr(),
+                                             None, 0, st.cuda_stream):
+            raise RuntimeError(f"swd_sampler_sample_dev failed: {_lib.last_error()}")
+        if streamed:  # the stream object's lane starts behind the sampler; the accounting waits for that lane alone
+            self._stream.push_device(det, total, stats=stats, min_pm=None, shot_result=shot, after=st)
+            self._stream.wait_last(st)
+        else:
+            d.decode_device(det, total=total, stats=stats, shot_result=shot, stream=st, want_stats=window_stats, want_min_pm=False)
+        shot_account_device(shot, ln["flips"][:B], stats, first_shot, ln["result"], counters, window_counters, failed, stream=st)
+
+    def run(self, shots, batch=4096, seed=20240318, first_shot=0, lanes=2, max_errors=None, keep_failures=0, window_stats=True):
+        """``shots`` shots numbered ``first_shot ..`` in batches of ``batch``.  ``lanes=2``: batch j goes to lane ``j & 1`` of one
+        ``SlidingWindowStream``, each lane with a torch stream and buffers of its own, so that two batches are in flight;
+        ``lanes=1``: ``decode_device`` launches on one stream.  The host reads the counters once at the end; the result is a pure
+        function of (seed, first_shot, shots), whatever ``batch`` and ``lanes``.  With ``max_errors`` the counters are read after every
+        round of lanes and the run stops once ``logical_errors >= max_errors``: it stops at batch granularity -- whole rounds of
+        ``lanes`` batches -- so ``result.shots`` tells how many shots were run and the count may overshoot ``max_errors``.
+        ``keep_failures``: how many numbers of failing shots to bring back; ``window_stats=False`` leaves the per-window records
+        out (the window loop then writes none).  -> ``MemoryResult``."""
+        import torch
+        shots, batch, lanes, keep = int(shots), int(batch), int(lanes), int(keep_failures)
+        if shots < 0 or batch <= 0 or lanes not in (1, 2) or keep < 0:
+            raise ValueError("shots >= 0, batch > 0, lanes 1 or 2 (a stream object has two), keep_failures >= 0")
+        dev = torch.device("cuda", self.device)
+        cap = max(1, min(batch, shots))
+        if lanes == 2 and (self._stream is None or self._stream.max_shots < cap):
+            for ln in self._lanes:
+                ln["stream"].synchronize()
+            self.close()
+            self._stream = self.decoder.stream(cap, want_stats=window_stats)
+        counters = torch.zeros((4,), dtype=torch.int64, device=dev)
+        wc = torch.zeros((self.W, _lib.WINDOW_COUNTER_WORDS), dtype=torch.int64, device=dev) if window_stats else None
+        failed = torch.zeros((1 + keep,), dtype=torch.int64, device=dev) if keep else None
+        torch.cuda.current_stream(dev).synchronize()  # the lanes add into zeroed counters
+        start, k = 0, 0
+        while start < shots:
+            B = min(batch, shots - start)
+            ln = self._lane(k % lanes, cap, window_stats)
+            self._enqueue(ln, B, seed, first_shot + start, lanes == 2, window_stats, counters, wc, failed)
+            start, k = start + B, k + 1
+            if max_errors is not None and k % lanes == 0:
+                for l2 in self._lanes[:lanes]:
+                    l2["stream"].synchronize()
+                if int(counters[1].item()) >= max_errors:
+                    break
+        for l2 in self._lanes:
+            l2["stream"].synchronize()
+        self.decoder.check_status()
+        c = counters.cpu().numpy()
+        w = wc.cpu().numpy() if wc is not None else None
+        kept = failed.cpu().numpy().view(np.uint64) if failed is not None else np.zeros(1, np.uint64)
+        return MemoryResult(c[0], c[1], c[2], c[3], *((w[:, :8], w[:, 8], w[:, 9]) if w is not None else (None, None, None)),
+                            failed_shots=kept[1:1 + min(int(kept[0]), keep)], failed_shots_complete=int(c[1]) <= keep)
+
+    def run_batch(self, B, seed=20240318, first_shot=0):
+        """One batch with the per-shot arrays on the host (tests and debugging): dict with ``det`` [B, num_det], ``true_flips`` uint32
+        [B], ``total`` [B, num_col], ``stats`` [B, W, 8], ``shot_result`` [B, 2] and ``result`` (the words of include/swd.h: bit 0
+        logical error, bit 1 flagged, bit 2 observable mismatch)."""
+        B = int(B)
+        if B <= 0:
+            raise ValueError("B > 0")
+        ln = self._lane(0, B, True)
+        self._enqueue(ln, B, seed, int(first_shot), False, True, None, None, None)
+        ln["stream"].synchronize()
+        self.decoder.check_status()
+        out = {key: ln[key][:B].cpu().numpy() for key in ("det", "total", "stats", "shot_result", "result")}
+        out["true_flips"] = ln["flips"][:B].cpu().numpy().view(np.uint32)
         return out

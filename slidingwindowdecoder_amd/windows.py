@@ -237,6 +237,38 @@ def logical_error_stats(plan: WindowPlan, det_data, obs_data, total_e_hat):
     return flagged, np.logical_or(flagged, logical)
 
 
+def memory_experiment_host(plan: WindowPlan, det_data, obs_data, decoder_factory):
+    """The whole of the reference's ``sliding_window_decoder`` after sampling (osd.py:130-191) on the host -- the executable
+    specification of ``MemoryExperiment``: ``sliding_window_decode_host``, then ``logical_error_stats``.  ``obs_data`` [shots,
+    num_obs]: the true observable flips.  Returns a dict: the counters ``shots``, ``logical_errors`` (flagged or a wrong
+    observable), ``flagged``, ``observable_mismatches``; ``result`` [shots], the per-shot words of include/swd.h (bit 0 logical
+    error, bit 1 flagged, bit 2 observable mismatch); ``total_e_hat``; and, when the factory's decoders expose ``exit_class``,
+    ``converge`` and ``bp_iteration``, the per-window counts ``window_exit_classes`` [W, 8], ``window_not_converged`` [W] and
+    ``window_bp_iterations`` [W] (None otherwise)."""
+    det_data, obs_data = np.asarray(det_data, dtype=np.uint8), np.asarray(obs_data, dtype=np.uint8)
+    W = len(plan.windows)
+    cls, ncv, its = np.zeros((W, 8), np.int64), np.zeros(W, np.int64), np.zeros(W, np.int64)
+    seen = []
+
+    def tap(wi, j, dec, s, e_hat):
+        if all(hasattr(dec, a) for a in ("exit_class", "converge", "bp_iteration")):
+            cls[wi, int(dec.exit_class) & 7] += 1
+            ncv[wi] += 0 if dec.converge else 1
+            its[wi] += int(dec.bp_iteration)
+            seen.append(wi)
+
+    total, _ = sliding_window_decode_host(plan, det_data, decoder_factory, on_decode=tap)
+    flagged, logical = logical_error_stats(plan, det_data, obs_data, total)
+    wrong = ((obs_data + (sp.csr_matrix(total) @ plan.obs.T.astype(np.int32)).toarray()) % 2).any(axis=1)
+    assert np.array_equal(logical, flagged | wrong)
+    have = len(seen) == W * det_data.shape[0] and W > 0
+    return dict(shots=int(det_data.shape[0]), logical_errors=int(logical.sum()), flagged=int(flagged.sum()),
+                observable_mismatches=int(wrong.sum()),
+                result=(logical.astype(np.int32) | (flagged.astype(np.int32) << 1) | (wrong.astype(np.int32) << 2)),
+                total_e_hat=total, window_exit_classes=cls if have else None, window_not_converged=ncv if have else None,
+                window_bp_iterations=its if have else None)
+
+
 @dataclass
 class RollingTemplate:
     """What a rolling session keeps of a template ``WindowPlan`` of R0 rounds (``rolling_template``): the head, body and tail
