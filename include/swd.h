@@ -395,6 +395,49 @@ int swd_shot_account_dev(int device, int32_t B, int32_t W, const int32_t *shot_r
                          const int32_t *stats, uint64_t first_shot, int32_t *result, uint64_t *counters,
                          uint64_t *window_counters, uint64_t *failed, int32_t failed_cap, void *stream);
 
+/* ---- rolling DEM sampler: the detector rows of an experiment of any length, round block by round block ----------
+ * A detector error model of R0 rounds whose columns are region-permuted (windows.plan_windows) falls into R0 + 1 column blocks,
+ * one per row block of h = n_half detector rows: block b = columns [anchor_cols[b], anchor_cols[b + 1]) holds the faults that first
+ * show in row block b, and they reach into row block b + 1 at most.  When the blocks j0 .. j1 - 1 (the BODY) are translates of one
+ * another, the model of R rounds of the same circuit is, for every R >= R0 - (j1 - j0):
+ *     the head blocks 0 .. j0 - 1 as they are | block j0 repeated (j1 - j0) + (R - R0) times, copy k with its rows moved down by k h
+ *     (observable masks and priors as they are) | the tail blocks j1 .. R0 with their rows moved down by (R - R0) h
+ * (windows.extend_template is the executable statement; tests/test_rolling_experiment_host.py holds it against plan_windows(R)).
+ * The rolling sampler draws that model's detector rows a few row blocks at a time, bit-identical to swd_sampler_* on the R-round
+ * model, in device memory that does not depend on R: what a memory experiment on a rolling session needs.
+ *   create   chk: (R0 + 1) h x num_col CSR with channel_probs = priors; obs: (<= 32) x num_col CSR or NULL; anchor_cols [num_blocks + 1]
+ *            = first column of every block, then num_col (strictly increasing from 0; num_blocks = R0 + 1); 0 <= j0 < j1 <=
+ *            num_blocks - 1.  Refused with a message: a column of block b with a row outside [b h, (b + 2) h); body blocks that
+ *            differ in length, rows (moved), observable masks or thresholds; more than 32 observables; h > 32767.  Per template
+ *            column the device keeps the threshold (round(p 2^32), the rule of swd_sampler_create), the observable mask and the
+ *            rows as u16 relative to the block's first row (0 .. 2 h - 1).
+ *   rows_dev ONE STATELESS call: det_rows[b][0 .. nblocks h) = rows [block0 h, (block0 + nblocks) h) of shot first_shot + b of
+ *            the `rounds`-round experiment (stride = bytes between shots, 0 = nblocks h); obs_flips [B] (nullable) is XORed INTO
+ *            with the observable masks of the faults in column blocks block0 .. block0 + nblocks - 1, so a sweep of calls over all
+ *            R + 1 blocks counts every column once (the caller zeroes it first); faults (nullable) [b][0 .. columns of those blocks)
+ *            = the faults of these same column blocks (faults_stride = bytes between shots, 0 = their number of columns).  The
+ *            call draws column blocks block0 - 1 .. block0 + nblocks - 1: a block between two calls is drawn by both, each keeping
+ *            its own half of the rows.  Stream: that of swd_sampler_* on the GLOBAL column number c of the R-round model --
+ *            Philox4x32-10 keyed by `seed`, counter (shot lo, shot hi, c >> 2, 0), output word c & 3, fault iff x < threshold of
+ *            the template column c maps to.  The result is a pure function of (seed, shot number, rounds, block range): nothing
+ *            depends on the order of calls.  Refused: rounds < R0 - (j1 - j0); a block range outside 0 .. rounds; rounds whose
+ *            model has 2^34 columns or more (c >> 2 is counter word 2).  Asynchronous on `stream`; long calls are split into
+ *            several launches.  B = 0 does nothing.
+ *   rows     the same with host pointers, dense ([B][nblocks h], [B], [B][columns]); obs_flips is read, XORed into and written back
+ *   info     info[8] = { h, num_col, num_obs, R0, j0, j1, least rounds served, 0 }; with rounds >= 0 also (all nullable) the
+ *            R-round model's first column of block `block0` and the number of columns of blocks block0 .. block0 + nblocks - 1 */
+typedef struct swd_rolling_sampler swd_rolling_sampler;
+swd_rolling_sampler *swd_rolling_sampler_create(const swd_graph_desc *chk, const swd_graph_desc *obs, int32_t n_half, int32_t j0,
+                                                int32_t j1, const int64_t *anchor_cols, int32_t num_blocks, int device);
+void swd_rolling_sampler_destroy(swd_rolling_sampler *s);
+int swd_rolling_sampler_info(const swd_rolling_sampler *s, int32_t *info, int32_t rounds, int32_t block0, int32_t nblocks,
+                             int64_t *first_col, int64_t *num_cols);
+int swd_rolling_sampler_rows_dev(swd_rolling_sampler *s, int32_t B, uint64_t seed, uint64_t first_shot, int32_t rounds,
+                                 int32_t block0, int32_t nblocks, uint8_t *det_rows, int64_t stride, uint32_t *obs_flips,
+                                 uint8_t *faults, int64_t faults_stride, void *stream);
+int swd_rolling_sampler_rows(swd_rolling_sampler *s, int32_t B, uint64_t seed, uint64_t first_shot, int32_t rounds, int32_t block0,
+                             int32_t nblocks, uint8_t *det_rows, uint32_t *obs_flips, uint8_t *faults);
+
 /* ---- online sessions: the window loop driven by the arrival of detector rows --------------------
  * The (W, F) scheme exists so that corrections are committed while the experiment still runs; the loop of the reference harness
  * (/root/reference/osd.py:130-179) is causal -- window t reads only rows < row1 of det ^ chk @ total_e_hat.  A session owns the state

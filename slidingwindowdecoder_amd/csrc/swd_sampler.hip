@@ -548,6 +548,301 @@ extern "C" int swd_shot_account_dev(int device, int32_t B, int32_t W, const int3
     return 0;
 }
 
+// ---- rolling DEM sampler (include/swd.h: swd_rolling_sampler_*) ------------------------------------------------------------------------
+// The detector rows of an experiment of ANY number of rounds from a periodic template of R0 rounds, a few row blocks per call: what a
+// memory experiment on a rolling session feeds its windows with.  A call emits the rows of row blocks block0 .. block0 + nblocks - 1
+// and for that draws the column blocks block0 - 1 .. block0 + nblocks - 1 of the R-round model -- a contiguous range of its GLOBAL
+// columns, each mapped to a template column by a table of at most eight entries (one per column block) that the host fills in.  The
+// stream is sample_kernel's on the global column, so the rows are those of swd_sampler_* on the R-round model.  A call covers few rows
+// and one or two thousand columns, so the shape is the Pauli sampler's: a wave per shot, four shots per workgroup (the workgroup per
+// shot when the columns are many); the shot's row bits and observable word live in LDS, faults scatter into them with atomicXor, rows
+// outside the emitted range are dropped.  Lanes of shots past B stay predicated to the last barrier.
+namespace {
+
+constexpr int kRollEntries = 8;     // column blocks one launch draws: the one before the first emitted row block and up to 7 more
+constexpr int kRollMaxRows = 65504; // rows one launch emits at most: 2047 words of row bits + the observable word, 32 KB for four shots
+constexpr int kRollWaveCols = 2048; // up to this many columns a wave draws a shot, beyond it the workgroup
+
+struct RollCall {
+    uint64_t g0, g1;                // global columns drawn: [g0, g1) = the entries' columns, in order and without gaps
+    uint64_t fcol0;                 // the global column that faults[..][0] stands for
+    uint64_t gstart[kRollEntries];  // per entry: first global column,
+    uint32_t tstart[kRollEntries];  //   first template column,
+    uint32_t len[kRollEntries];     //   number of columns,
+    int32_t rshift[kRollEntries];   //   the block's first row relative to the first emitted row (-h for the block before it),
+    uint32_t counted;               //   bit e: its observable masks and faults belong to this call
+    int32_t n, nrows;
+};
+
+struct RollingSampler {
+    int device = 0, h = 0, ncol = 0, nobs = 0, R0 = 0, j0 = 0, j1 = 0, nblk = 0;
+    std::vector<int64_t> anchor;    // template: first column of every block, then ncol
+    DevBuf buf;                     // thr[ncol] u32 | colptr[ncol + 1] u32 | rows[E] u16, relative to the block's first row | obs_mask[ncol] u32
+    const uint32_t *d_thr = nullptr, *d_colptr = nullptr, *d_obs = nullptr;
+    const uint16_t *d_rows = nullptr;
+    DevBuf det, obs, faults;        // staging for the host-pointer entry point
+
+    int64_t cs() const { return anchor[j0 + 1] - anchor[j0]; }
+    int least_rounds() const { return R0 - (j1 - j0); }
+    // column block b of the model of `rounds` rounds: its first global column, its template block
+    void block(int rounds, int b, int64_t *g, int *tb) const {
+        const int64_t up = rounds - R0, nbody = (j1 - j0) + up;
+        if (b < j0) { *tb = b; *g = anchor[b]; }
+        else if (b < j0 + nbody) { *tb = j0; *g = anchor[j0] + (int64_t)(b - j0) * cs(); }
+        else { *tb = (int)(b - up); *g = anchor[*tb] + up * cs(); }
+    }
+    int64_t first_col(int rounds, int b) const { // b = rounds + 1: the model's number of columns
+        if (b == rounds + 1) return anchor[nblk] + (int64_t)(rounds - R0) * cs();
+        int64_t g; int tb;
+        block(rounds, b, &g, &tb);
+        return g;
+    }
+};
+
+// T threads per shot (64: a wave, 256: the workgroup), 256 / T shots per workgroup; LDS [256 / T][words of row bits + 1]
+template <int T>
+__global__ void __launch_bounds__(256) rolling_rows_kernel(int B, RollCall call, const uint32_t *thr, const uint32_t *colptr,
+                                                           const uint16_t *rows, const uint32_t *obs_mask, uint64_t seed,
+                                                           uint64_t first_shot, uint8_t *det, int64_t det_stride, uint32_t *obs_flips,
+                                                           uint8_t *faults, int64_t faults_stride) {
+    extern __shared__ uint32_t roll_bits[];
+    __shared__ RollCall tb; // (the entries are looked up with a per-lane index)
+    const int nrows = call.nrows, nw = (nrows + 31) >> 5, slot = threadIdx.x / T, lane = threadIdx.x % T;
+    uint32_t *bits = roll_bits + (size_t)slot * (nw + 1);
+    const int64_t b = (int64_t)blockIdx.x * (256 / T) + slot;
+    const bool live = b < B;
+    if (threadIdx.x == 0) tb = call;
+    for (int i = lane; i <= nw; i += T) bits[i] = 0;
+    __syncthreads();
+    if (live) {
+        const uint64_t shot = first_shot + (uint64_t)b, g0 = call.g0, g1 = call.g1;
+        const uint32_t gfirst = (uint32_t)(g0 >> 2), ngroups = (uint32_t)((g1 - 1) >> 2) - gfirst + 1;
+        for (uint32_t gi = lane; gi < ngroups; gi += T) {
+            const uint32_t g = gfirst + gi;
+            uint32_t x[4];
+            philox4x32_10((uint32_t)shot, (uint32_t)(shot >> 32), g, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+            int e = 0;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint64_t c = ((uint64_t)g << 2) + u;
+                if (c < g0 || c >= g1) continue;
+                while (c >= tb.gstart[e] + tb.len[e]) ++e; // (c < g1 = the end of the last entry)
+                const uint32_t tc = tb.tstart[e] + (uint32_t)(c - tb.gstart[e]);
+                const bool f = x[u] < thr[tc], mine = (tb.counted >> e) & 1u;
+                if (faults && mine) faults[b * faults_stride + (int64_t)(c - call.fcol0)] = f ? 1 : 0;
+                if (f) {
+                    const int shift = tb.rshift[e];
+                    for (uint32_t k = colptr[tc]; k < colptr[tc + 1]; ++k) {
+                        const int r = shift + (int)rows[k];
+                        if (r >= 0 && r < nrows) atomicXor(&bits[r >> 5], 1u << (r & 31));
+                    }
+                    if (mine && obs_mask && obs_mask[tc]) atomicXor(&bits[nw], obs_mask[tc]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (live) {
+        for (int r = lane; r < nrows; r += T) det[b * det_stride + r] = (uint8_t)((bits[r >> 5] >> (r & 31)) & 1u);
+        if (lane == 0 && obs_flips) obs_flips[b] ^= bits[nw];
+    }
+}
+
+// one launch: the rows of row blocks b0 .. b0 + n - 1 (n <= kRollEntries - 1, n h <= kRollMaxRows)
+int rolling_launch(RollingSampler *s, int B, uint64_t seed, uint64_t first_shot, int rounds, int b0, int n, uint8_t *det, int64_t stride,
+                   uint32_t *obs_flips, uint8_t *faults, int64_t faults_stride, uint64_t fcol0, hipStream_t st) {
+    RollCall c{};
+    for (int b = std::max(b0 - 1, 0); b < b0 + n; ++b) {
+        int64_t g; int tb;
+        s->block(rounds, b, &g, &tb);
+        const int e = c.n++;
+        c.gstart[e] = (uint64_t)g; c.tstart[e] = (uint32_t)s->anchor[tb]; c.len[e] = (uint32_t)(s->anchor[tb + 1] - s->anchor[tb]);
+        c.rshift[e] = (b - b0) * s->h;
+        if (b >= b0) c.counted |= 1u << e;
+    }
+    c.g0 = c.gstart[0]; c.g1 = c.gstart[c.n - 1] + c.len[c.n - 1]; c.fcol0 = fcol0; c.nrows = n * s->h;
+    const bool wave = c.g1 - c.g0 <= (uint64_t)kRollWaveCols;
+    const int spw = wave ? 4 : 1;
+    const size_t lds = (size_t)spw * ((size_t)(c.nrows + 31) / 32 + 1) * 4;
+    auto kern = wave ? rolling_rows_kernel<64> : rolling_rows_kernel<256>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((B + spw - 1) / spw)), dim3(256), lds, st, B, c, s->d_thr, s->d_colptr, s->d_rows, s->d_obs, seed,
+                       first_shot, det, stride, obs_flips, faults, faults_stride);
+    SWD_HIP(hipGetLastError());
+    return 0;
+}
+
+// the checks of a call; -> the first column and the number of columns of column blocks block0 .. block0 + nblocks - 1
+int rolling_range(const RollingSampler *s, int rounds, int block0, int nblocks, int64_t *col0, int64_t *ncols) {
+    if (rounds < s->least_rounds()) {
+        set_error("rolling sampler: %d rounds; a template of %d rounds with %d body rounds serves %d rounds and more", rounds, s->R0, s->j1 - s->j0,
+                  s->least_rounds());
+        return -1;
+    }
+    if (rounds >= 1 << 30 || s->first_col(rounds, rounds + 1) >= (int64_t)1 << 34) {
+        set_error("rolling sampler: the model of %d rounds has 2^34 columns or more (%lld per round): they do not fit the generator's counter", rounds,
+                  (long long)s->cs());
+        return -1;
+    }
+    if (block0 < 0 || nblocks <= 0 || (int64_t)block0 + nblocks > (int64_t)rounds + 1) {
+        set_error("rolling sampler: row blocks %d .. %lld are not within the %d + 1 blocks of the experiment", block0, (long long)block0 + nblocks - 1, rounds);
+        return -1;
+    }
+    *col0 = s->first_col(rounds, block0);
+    *ncols = s->first_col(rounds, block0 + nblocks) - *col0;
+    return 0;
+}
+
+} // namespace
+
+extern "C" swd_rolling_sampler *swd_rolling_sampler_create(const swd_graph_desc *chk, const swd_graph_desc *obs, int32_t n_half, int32_t j0,
+                                                           int32_t j1, const int64_t *anchor_cols, int32_t num_blocks, int device) {
+    if (!chk || !chk->row_ptr || !chk->col_idx || !chk->channel_probs || !anchor_cols) { set_error("null argument"); return nullptr; }
+    const int h = n_half, n = chk->n, nb = num_blocks;
+    if (h <= 0 || h > 65535 / 2) { set_error("rolling sampler: n_half = %d out of range (1 .. 32767: a column's rows are 16-bit offsets within two blocks)", h); return nullptr; }
+    if (nb <= 0 || n <= 0 || (int64_t)chk->m != (int64_t)nb * h) { set_error("rolling sampler: %d detector rows are not %d blocks of %d", chk->m, nb, h); return nullptr; }
+    if (obs && (!obs->row_ptr || !obs->col_idx || obs->m > 32 || obs->n != n)) { set_error("observable matrix must be (<= 32) x %d: at most 32 observables", n); return nullptr; }
+    if (j0 < 0 || j1 <= j0 || j1 > nb - 1) { set_error("rolling sampler: body blocks %d .. %d are not within the %d blocks (a tail block must follow)", j0, j1 - 1, nb); return nullptr; }
+    if (anchor_cols[0] != 0 || anchor_cols[nb] != n) { set_error("rolling sampler: anchor columns must run from 0 to %d", n); return nullptr; }
+    for (int b = 0; b < nb; ++b)
+        if (anchor_cols[b + 1] <= anchor_cols[b]) { set_error("rolling sampler: anchor columns must increase (block %d)", b); return nullptr; }
+    if (capacity_device_ok(device)) return nullptr;
+    const int E = chk->row_ptr[chk->m];
+    std::vector<uint32_t> thr(n), colptr(n + 1, 0), omask(n, 0);
+    std::vector<int> block_of(n);
+    std::vector<uint16_t> rows(std::max(E, 1));
+    for (int b = 0; b < nb; ++b)
+        for (int64_t c = anchor_cols[b]; c < anchor_cols[b + 1]; ++c) block_of[c] = b;
+    for (int c = 0; c < n; ++c) {
+        const double p = chk->channel_probs[c];
+        if (!(p >= 0.0 && p <= 1.0)) { set_error("prior %d = %g is not a probability", c, p); return nullptr; }
+        const double t = p * 4294967296.0 + 0.5;
+        thr[c] = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+    }
+    for (int e = 0; e < E; ++e) {
+        if (chk->col_idx[e] < 0 || chk->col_idx[e] >= n) { set_error("detector matrix: column out of range"); return nullptr; }
+        colptr[chk->col_idx[e] + 1]++;
+    }
+    for (int c = 0; c < n; ++c) colptr[c + 1] += colptr[c];
+    {
+        std::vector<uint32_t> fill(colptr.begin(), colptr.end() - 1);
+        for (int r = 0; r < chk->m; ++r)
+            for (int e = chk->row_ptr[r]; e < chk->row_ptr[r + 1]; ++e) {
+                const int c = chk->col_idx[e], b = block_of[c];
+                if (r < b * h || r >= (b + 2) * h) { // (r < chk->m = nb h holds: the last block keeps to its own rows)
+                    set_error("rolling sampler: column %d of round block %d touches row %d, outside the rows [%d, %d) of blocks %d and %d", c, b, r,
+                              b * h, (b + 2) * h, b, b + 1);
+                    return nullptr;
+                }
+                rows[fill[c]++] = (uint16_t)(r - b * h);
+            }
+    }
+    if (obs)
+        for (int k = 0; k < obs->m; ++k)
+            for (int e = obs->row_ptr[k]; e < obs->row_ptr[k + 1]; ++e) {
+                if (obs->col_idx[e] < 0 || obs->col_idx[e] >= n) { set_error("observable matrix: column out of range"); return nullptr; }
+                omask[obs->col_idx[e]] ^= 1u << k;
+            }
+    // the body blocks: translates of block j0 -- the rows are relative already
+    const int64_t a0 = anchor_cols[j0], cs = anchor_cols[j0 + 1] - a0;
+    for (int j = j0 + 1; j < j1; ++j) {
+        const int64_t aj = anchor_cols[j];
+        if (anchor_cols[j + 1] - aj != cs) {
+            set_error("rolling sampler: the body blocks are not translates: block %d has %lld columns, block %d has %lld", j, (long long)(anchor_cols[j + 1] - aj), j0, (long long)cs);
+            return nullptr;
+        }
+        for (int64_t i = 0; i < cs; ++i) {
+            const uint32_t da = colptr[a0 + i + 1] - colptr[a0 + i], db = colptr[aj + i + 1] - colptr[aj + i];
+            const char *what = thr[a0 + i] != thr[aj + i] ? "prior" : omask[a0 + i] != omask[aj + i] ? "observable mask" : da != db ? "rows" : nullptr;
+            for (uint32_t e = 0; !what && e < da; ++e)
+                if (rows[colptr[a0 + i] + e] != rows[colptr[aj + i] + e]) what = "rows";
+            if (what) {
+                set_error("rolling sampler: the body blocks are not translates: column %lld of block %d differs from that of block %d in its %s", (long long)i, j, j0, what);
+                return nullptr;
+            }
+        }
+    }
+    RollingSampler *s = new RollingSampler();
+    s->device = device; s->h = h; s->ncol = n; s->nobs = obs ? obs->m : 0; s->R0 = nb - 1; s->j0 = j0; s->j1 = j1; s->nblk = nb;
+    s->anchor.assign(anchor_cols, anchor_cols + nb + 1);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_thr = 0, o_cp = al(o_thr + (size_t)n * 4), o_rows = al(o_cp + ((size_t)n + 1) * 4), o_obs = al(o_rows + rows.size() * 2),
+                 total = al(o_obs + (size_t)n * 4);
+    std::vector<char> hb(total, 0);
+    memcpy(&hb[o_thr], thr.data(), (size_t)n * 4); memcpy(&hb[o_cp], colptr.data(), ((size_t)n + 1) * 4);
+    memcpy(&hb[o_rows], rows.data(), rows.size() * 2); memcpy(&hb[o_obs], omask.data(), (size_t)n * 4);
+    if (hipSetDevice(device) != hipSuccess || s->buf.reserve(total) || hipMemcpy(s->buf.p, hb.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("rolling sampler: device allocation failed on device %d", device);
+        delete s;
+        return nullptr;
+    }
+    char *bp = (char *)s->buf.p;
+    s->d_thr = (const uint32_t *)(bp + o_thr); s->d_colptr = (const uint32_t *)(bp + o_cp);
+    s->d_rows = (const uint16_t *)(bp + o_rows); s->d_obs = obs ? (const uint32_t *)(bp + o_obs) : nullptr;
+    return (swd_rolling_sampler *)s;
+}
+
+extern "C" void swd_rolling_sampler_destroy(swd_rolling_sampler *h) { delete (RollingSampler *)h; }
+
+extern "C" int swd_rolling_sampler_info(const swd_rolling_sampler *h, int32_t *info, int32_t rounds, int32_t block0, int32_t nblocks,
+                                        int64_t *first_col, int64_t *num_cols) {
+    const RollingSampler *s = (const RollingSampler *)h;
+    if (!s) { set_error("null sampler"); return -1; }
+    if (info) {
+        const int v[8] = {s->h, s->ncol, s->nobs, s->R0, s->j0, s->j1, s->least_rounds(), 0};
+        for (int i = 0; i < 8; ++i) info[i] = v[i];
+    }
+    if (rounds >= 0 && (first_col || num_cols)) {
+        int64_t c0, nc;
+        if (rolling_range(s, rounds, block0, nblocks, &c0, &nc)) return -1;
+        if (first_col) *first_col = c0;
+        if (num_cols) *num_cols = nc;
+    }
+    return 0;
+}
+
+extern "C" int swd_rolling_sampler_rows_dev(swd_rolling_sampler *h, int32_t B, uint64_t seed, uint64_t first_shot, int32_t rounds,
+                                            int32_t block0, int32_t nblocks, uint8_t *det_rows, int64_t stride, uint32_t *obs_flips,
+                                            uint8_t *faults, int64_t faults_stride, void *stream) {
+    RollingSampler *s = (RollingSampler *)h;
+    if (!s || !det_rows) { set_error("null argument"); return -1; }
+    int64_t col0, ncols;
+    if (rolling_range(s, rounds, block0, nblocks, &col0, &ncols)) return -1;
+    if (B <= 0) return 0;
+    const int64_t nrows = (int64_t)nblocks * s->h;
+    stride = stride ? stride : nrows; faults_stride = faults_stride ? faults_stride : ncols;
+    if (stride < nrows || (faults && faults_stride < ncols)) { set_error("rolling sampler: a stride is shorter than a shot's %lld rows / %lld columns", (long long)nrows, (long long)ncols); return -1; }
+    SWD_HIP(hipSetDevice(s->device));
+    const int per = std::max(1, std::min(kRollEntries - 1, kRollMaxRows / s->h));
+    for (int b = block0; b < block0 + nblocks; b += per) {
+        const int n = std::min(per, block0 + nblocks - b);
+        if (rolling_launch(s, B, seed, first_shot, rounds, b, n, det_rows + (int64_t)(b - block0) * s->h, stride, obs_flips, faults, faults_stride,
+                           (uint64_t)col0, (hipStream_t)stream))
+            return -1;
+    }
+    return 0;
+}
+
+extern "C" int swd_rolling_sampler_rows(swd_rolling_sampler *h, int32_t B, uint64_t seed, uint64_t first_shot, int32_t rounds, int32_t block0,
+                                        int32_t nblocks, uint8_t *det_rows, uint32_t *obs_flips, uint8_t *faults) {
+    RollingSampler *s = (RollingSampler *)h;
+    if (!s || !det_rows) { set_error("null argument"); return -1; }
+    int64_t col0, ncols;
+    if (rolling_range(s, rounds, block0, nblocks, &col0, &ncols)) return -1;
+    if (B <= 0) return 0;
+    const size_t nrows = (size_t)nblocks * s->h;
+    SWD_HIP(hipSetDevice(s->device));
+    if (s->det.reserve((size_t)B * nrows) || s->obs.reserve((size_t)B * 4) || (faults && s->faults.reserve((size_t)B * (size_t)ncols))) return -1;
+    if (obs_flips) SWD_HIP(hipMemcpy(s->obs.p, obs_flips, (size_t)B * 4, hipMemcpyHostToDevice));
+    if (swd_rolling_sampler_rows_dev(h, B, seed, first_shot, rounds, block0, nblocks, s->det.as<uint8_t>(), 0, obs_flips ? s->obs.as<uint32_t>() : nullptr,
+                                     faults ? s->faults.as<uint8_t>() : nullptr, 0, nullptr))
+        return -1;
+    SWD_HIP(hipDeviceSynchronize());
+    SWD_HIP(hipMemcpy(det_rows, s->det.p, (size_t)B * nrows, hipMemcpyDeviceToHost));
+    if (obs_flips) SWD_HIP(hipMemcpy(obs_flips, s->obs.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (faults) SWD_HIP(hipMemcpy(faults, s->faults.p, (size_t)B * (size_t)ncols, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ---- diagnostics: a foreign kernel that holds workgroup slots for a bounded time (include/swd.h: swd_diag_occupy) ----
 namespace swd {
 __global__ void __launch_bounds__(1024) occupy_kernel(long long ticks, uint32_t *sink) {

@@ -1765,3 +1765,335 @@ class MemoryExperiment:
         out = {key: ln[key][:B].cpu().numpy() for key in ("det", "total", "stats", "shot_result", "result")}
         out["true_flips"] = ln["flips"][:B].cpu().numpy().view(np.uint32)
         return out
+
+
+class RollingDemSampler:
+    """Samples the detector rows of a memory experiment of ANY number of rounds from a template of R0 rounds, a few row blocks (of
+    ``n_half`` rows) per call and bit-identical to ``DemSampler`` on the model of that many rounds (C ABI: swd_rolling_sampler_*;
+    ``windows.extend_template`` with the Philox stream on the global column number is the executable specification).  Its device
+    memory is the template's.  ``template_plan``: a ``windows.WindowPlan`` that ``windows.rolling_template`` accepts, or the
+    ``RollingTemplate`` itself; ``from_blocks`` takes any periodic model."""
+
+    def __init__(self, template_plan, device=0):
+        from .windows import _as_template, template_blocks
+        T = _as_template(template_plan)  # ValueError names what is not periodic
+        j0, j1, cols = template_blocks(T)
+        self._create(T.plan.chk, T.plan.obs, T.plan.priors, T.n_half, j0, j1, cols, device)
+        self.template, self.min_rounds = T, max(self.min_rounds, int(T.min_rounds))
+
+    @classmethod
+    def from_blocks(cls, chk, obs, priors, n_half, j0, j1, anchor_cols, device=0):
+        """a periodic model given as ``windows.extend_periodic`` takes it: column blocks ``j0 .. j1 - 1`` are the body rounds"""
+        self = cls.__new__(cls)
+        self.template = None
+        self._create(chk, obs, priors, n_half, j0, j1, anchor_cols, device)
+        return self
+
+    def _create(self, chk, obs, priors, n_half, j0, j1, anchor_cols, device):
+        L = _lib.lib()
+        self._h = None
+        self._chk = _Csr(chk, priors)
+        self.num_col = self._chk.n
+        od = None
+        if obs is not None and obs.shape[0]:
+            a = sp.csr_matrix(obs)
+            a.sort_indices()
+            if a.shape[0] > 32:
+                raise ValueError(f"at most 32 observables, obs has {a.shape[0]}")
+            self._orp, self._oci = np.ascontiguousarray(a.indptr, np.int32), np.ascontiguousarray(a.indices, np.int32)
+            od = _lib.GraphDesc(a.shape[0], a.shape[1], int(self._orp[-1]), self._orp.ctypes.data, self._oci.ctypes.data, None)
+        cols = np.ascontiguousarray(anchor_cols, dtype=np.int64)
+        self.device = int(device)
+        self._h = L.swd_rolling_sampler_create(C.byref(self._chk.desc), C.byref(od) if od is not None else None, int(n_half), int(j0), int(j1),
+                                               cols.ctypes.data, len(cols) - 1, self.device)
+        if not self._h:
+            msg = _lib.last_error()
+            raise (ValueError if msg.startswith("rolling sampler:") or "observable" in msg else RuntimeError)(
+                f"swd_rolling_sampler_create failed: {msg}")
+        info = (C.c_int32 * 8)()
+        L.swd_rolling_sampler_info(self._h, info, -1, 0, 0, None, None)
+        self.n_half, self.num_obs, self.R0, self.min_rounds = int(info[0]), int(info[2]), int(info[3]), int(info[6])
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                _lib.lib().swd_rolling_sampler_destroy(self._h)
+            except Exception:  # interpreter shutdown: the module globals may be gone already
+                pass
+            self._h = None
+
+    def _check_rounds(self, rounds):
+        if int(rounds) < self.min_rounds:
+            serves = f"this template serves {self.template.lengths()}" if self.template is not None else f"at least {self.min_rounds}"
+            raise ValueError(f"{rounds} rounds are fewer than the template's shortest experiment: {serves}")
+
+    def columns(self, rounds, block0=0, nblocks=None):
+        """(first column, number of columns) of column blocks ``block0 .. block0 + nblocks - 1`` (default: to the end) of the model of
+        ``rounds`` rounds"""
+        self._check_rounds(rounds)
+        nblocks = int(rounds) + 1 - int(block0) if nblocks is None else int(nblocks)
+        c0, nc = C.c_int64(), C.c_int64()
+        if _lib.lib().swd_rolling_sampler_info(self._h, None, int(rounds), int(block0), nblocks, C.byref(c0), C.byref(nc)):
+            raise ValueError(f"swd_rolling_sampler_info failed: {_lib.last_error()}")
+        return c0.value, nc.value
+
+    def rows_device(self, shots, rounds, block0, nblocks, seed=20240318, first_shot=0, out=None, flips=None, stream=None, faults=None):
+        """One stateless call on the device: rows ``[block0 * n_half, (block0 + nblocks) * n_half)`` of shots ``first_shot ..`` of the
+        ``rounds``-round experiment into ``out`` (uint8 CUDA tensor [shots, nblocks * n_half] with unit column stride -- a column
+        slice of a wider tensor fits; allocated when None).  ``flips`` int32 [shots] is XORed INTO with the observable masks of the
+        faults in column blocks ``block0 .. block0 + nblocks - 1`` (None: not computed); ``faults`` uint8 [shots, columns of those
+        blocks] likewise optional.  Asynchronous on ``stream`` (default: the current torch stream).  -> ``out``."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        shots, nrows = int(shots), int(nblocks) * self.n_half
+        ncols = self.columns(rounds, block0, nblocks)[1]  # ValueError: rounds or blocks out of range
+        if out is None:
+            out = torch.empty((shots, nrows), dtype=torch.uint8, device=dev)
+        for name, t, shape, dt in (("out", out, (shots, nrows), torch.uint8), ("flips", flips, (shots,), torch.int32),
+                                   ("faults", faults, (shots, ncols), torch.uint8)):
+            if t is not None and (not t.is_cuda or t.device != dev or t.dtype != dt or tuple(t.shape) != shape
+                                  or (t.dim() == 2 and t.shape[1] > 1 and t.stride(1) != 1) or (t.dim() == 1 and not t.is_contiguous())):
+                raise ValueError(f"{name} must be a {dt} CUDA tensor {list(shape)} on {dev} with unit column stride")
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        if _lib.lib().swd_rolling_sampler_rows_dev(self._h, shots, int(seed), int(first_shot), int(rounds), int(block0), int(nblocks), out.data_ptr(),
+                                                   out.stride(0) if shots > 1 else 0, flips.data_ptr() if flips is not None else None,
+                                                   faults.data_ptr() if faults is not None else None,
+                                                   faults.stride(0) if faults is not None and shots > 1 else 0, st.cuda_stream or None):
+            raise RuntimeError(f"swd_rolling_sampler_rows_dev failed: {_lib.last_error()}")
+        return out
+
+    def sample(self, shots, rounds, seed=20240318, first_shot=0, return_faults=False):
+        """The whole experiment of ``rounds`` rounds on the host (tests and debugging): det uint8 [shots, (rounds + 1) * n_half], obs
+        uint8 [shots, num_obs] (, faults uint8 [shots, columns of the model]) -- what ``DemSampler`` on the model of ``rounds`` rounds
+        returns for the same seed and shot numbers."""
+        ncols = self.columns(rounds)[1]
+        det = np.zeros((shots, (int(rounds) + 1) * self.n_half), np.uint8)
+        flips = np.zeros(shots, np.uint32)
+        faults = np.zeros((shots, ncols), np.uint8) if return_faults else None
+        if _lib.lib().swd_rolling_sampler_rows(self._h, shots, int(seed), int(first_shot), int(rounds), 0, int(rounds) + 1, det.ctypes.data,
+                                               flips.ctypes.data, faults.ctypes.data if return_faults else None):
+            raise RuntimeError(f"swd_rolling_sampler_rows failed: {_lib.last_error()}")
+        obs = ((flips[:, None] >> np.arange(self.num_obs, dtype=np.uint32)) & 1).astype(np.uint8)
+        return (det, obs, faults) if return_faults else (det, obs)
+
+
+class RollingMemoryResult(MemoryResult):
+    """``MemoryResult`` of a rolling experiment of ``rounds`` syndrome rounds (``windows_per_shot`` windows a shot).  The per-window
+    arrays have THREE rows whatever the length: the head window, all body windows summed, the tail window.  Results of different
+    ``rounds`` do not add."""
+
+    def __init__(self, rounds, windows_per_shot, *args, **kw):
+        super().__init__(*args, **kw)
+        self.rounds, self.windows_per_shot = int(rounds), int(windows_per_shot)
+
+    def ler_per_round(self, num_repeat=None):
+        return super().ler_per_round(self.rounds if num_repeat is None else num_repeat)
+
+    def _fields(self):
+        return super()._fields() + (self.rounds, self.windows_per_shot)
+
+    def __eq__(self, other):
+        return isinstance(other, RollingMemoryResult) and super().__eq__(other)
+
+    __hash__ = None
+
+    def __add__(self, other):
+        if not isinstance(other, RollingMemoryResult):
+            return NotImplemented
+        if other.rounds != self.rounds:
+            raise ValueError(f"results of experiments of {self.rounds} and of {other.rounds} rounds do not add")
+        s = MemoryResult.__add__(self, other)
+        return RollingMemoryResult(self.rounds, self.windows_per_shot, s.shots, s.logical_errors, s.flagged, s.observable_mismatches,
+                                   s.window_exit_classes, s.window_not_converged, s.window_bp_iterations, failed_shots=s.failed_shots,
+                                   failed_shots_complete=s.failed_shots_complete)
+
+    def __repr__(self):
+        return "Rolling" + super().__repr__()[:-1] + f", rounds={self.rounds})"
+
+
+class RollingMemoryExperiment:
+    """``MemoryExperiment`` for experiments of any length: the reference's ``sliding_window_decoder(N, p, num_repeat, ...)`` swept over
+    ``num_repeat`` from ONE template plan of R0 rounds, in device memory that does not depend on the length.  Per batch and lane:
+    ``RollingSession.begin``; per window the rows it still needs from ``RollingDemSampler`` and one window step of the session;
+    the tail rows and ``finish``; the accounting of ``MemoryExperiment``.  Only counters come back.  The result equals
+    ``MemoryExperiment(plan_windows(rounds)).run`` for the same seed and shot numbers, the per-window counts reduced to head / body
+    / tail.  ``template_plan``: a ``windows.WindowPlan`` with 1..32 observables that the one-launch pipeline takes and
+    ``windows.rolling_template`` accepts; it serves ``rounds = R0 (mod F)``, ``rounds >= min_rounds``."""
+
+    def __init__(self, template_plan, decoder="osd_window", device=0, **decoder_kwargs):
+        from .windows import rolling_template
+        plan = template_plan
+        num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
+        if num_obs == 0:
+            raise ValueError("a memory experiment needs observables: plan.obs is empty")
+        if num_obs > 32:
+            raise ValueError(f"a memory experiment carries at most 32 observables per shot, plan.obs has {num_obs}")
+        self.plan, self.device = plan, int(device)
+        self.decoder = SlidingWindowDecoder(plan, device=self.device, decoder=decoder, **decoder_kwargs)
+        self.decoder._no_loop("RollingMemoryExperiment")
+        self.template = rolling_template(plan)  # ValueError names what is not periodic
+        self.sampler = RollingDemSampler(self.template, device=self.device)
+        T = self.template
+        self.rounds = int(T.R0)  # the default length of run()
+        # row blocks a step hands over at most: the head's W, a body window's F, what finish takes
+        self._step_blocks = max(T.W, T.F, (T.tail.row1 - T.tail.row0) // T.n_half - (T.W - T.F))
+        self._lanes = []
+
+    @classmethod
+    def bb(cls, N, p, num_repeat, W, F, method=1, z_basis=True, decoder="osd_window", **kw):
+        """the experiment of ``num_repeat`` rounds as the notebooks build it, on the SMALLEST template that serves it: the plan of
+        ``bb_dem(bb_code(N), p, R0)`` with the least ``R0 = num_repeat (mod F)``, ``R0 <= num_repeat``, that ``rolling_template``
+        accepts.  ``run()`` then defaults to ``num_repeat`` rounds."""
+        from .circuit import bb_dem
+        from .codes import bb_code
+        from .windows import plan_windows, rolling_template
+        code, A, B = bb_code(N)
+        num_repeat, why = int(num_repeat), "none was tried"
+        R0 = W + (num_repeat - W) % F
+        while R0 <= num_repeat:
+            dem = bb_dem(code, A, B, p, R0, z_basis=z_basis)
+            plan = plan_windows(dem.chk, dem.obs, dem.priors, N // 2, W, F, method, z_basis)
+            try:
+                rolling_template(plan)
+            except ValueError as e:
+                why, R0 = f"R0 = {R0}: {e}", R0 + F
+                continue
+            exp = cls(plan, decoder=decoder, **kw)
+            exp.rounds = num_repeat
+            return exp
+        raise ValueError(f"no rolling template serves {num_repeat} rounds with (W, F) = ({W}, {F}): it needs R0 = {num_repeat} (mod {F}), "
+                         f"R0 <= {num_repeat}, periodic between its first and its last window, and {why}.  Use MemoryExperiment.bb for "
+                         f"an experiment this short")
+
+    def close(self):
+        for ln in getattr(self, "_lanes", []):
+            ln["stream"].synchronize()
+            ln["session"].close()
+        self._lanes = []
+
+    __del__ = close
+
+    @property
+    def device_bytes(self):
+        """bytes of device memory the lanes own (sessions and buffers): a function of the template, the batch and the lanes used --
+        not of the number of rounds"""
+        return sum(ln["session"].device_bytes + sum(t.numel() * t.element_size() for t in ln.values() if hasattr(t, "element_size"))
+                   for ln in self._lanes)
+
+    # ---- one batch on one lane: per window sample + step (+ its counts), then the tail and the accounting, all on the lane's stream ---
+    def _lane(self, k, cap):
+        import torch
+        dev = torch.device("cuda", self.device)
+        while len(self._lanes) <= k:
+            self._lanes.append(dict(cap=0, session=None, stream=torch.cuda.Stream(dev, priority=-(len(self._lanes) & 1))))
+        ln = self._lanes[k]
+        if ln["cap"] < cap:
+            ln["stream"].synchronize()  # (the buffers it replaces may still be in use)
+            if ln["session"] is not None:
+                ln["session"].close()
+            i32 = torch.int32
+            ln.update(cap=cap, session=self.decoder.rolling_session(cap),
+                      rows=torch.empty((cap, self._step_blocks * self.template.n_half), dtype=torch.uint8, device=dev),
+                      flips=torch.empty((cap,), dtype=i32, device=dev), shot_result=torch.empty((cap, 2), dtype=i32, device=dev),
+                      result=torch.empty((cap,), dtype=i32, device=dev), stats=torch.empty((cap, _lib.STAT_WORDS), dtype=i32, device=dev))
+        return ln
+
+    def _enqueue(self, ln, B, rounds, sched, seed, first_shot, window_stats, counters, window_counters, failed, det=None, stats_all=None):
+        """``det`` [B, (rounds + 1) * n_half] / ``stats_all`` [windows, B, 8]: run_batch's own arrays, written instead of the lane's"""
+        import torch
+        L, h, ses = _lib.lib(), self.template.n_half, ln["session"]
+        sp_ = ln["stream"].cuda_stream
+        flips, shot = ln["flips"], ln["shot_result"]
+        first, count = C.c_int64(), C.c_int32()
+        ses.begin(B)
+        with torch.cuda.stream(ln["stream"]):
+            flips[:B].zero_()
+        for k, (b0, n) in enumerate(sched):
+            last = k == len(sched) - 1
+            rows = ln["rows"] if det is None else det[:, b0 * h:]
+            stats = ln["stats"] if stats_all is None else stats_all[k]
+            if L.swd_rolling_sampler_rows_dev(self.sampler._h, B, int(seed), int(first_shot), rounds, b0, n, rows.data_ptr(), rows.stride(0),
+                                              flips.data_ptr(), None, 0, sp_):
+                raise RuntimeError(f"swd_rolling_sampler_rows_dev failed: {_lib.last_error()}")
+            sptr = stats.data_ptr() if window_stats else None
+            if not last:
+                if L.swd_pipeline_rolling_push_dev(ses._h, n * h, rows.data_ptr(), rows.stride(0), 1, None, sptr, None, C.byref(first),
+                                                   C.byref(count), sp_) or count.value != 1 or first.value != k:
+                    raise RuntimeError(f"swd_pipeline_rolling_push_dev failed at window {k}: {_lib.last_error()}")
+                if window_stats and window_counters is not None:  # the counts of this window alone, into the row of its kind
+                    if L.swd_shot_account_dev(self.device, B, 1, shot.data_ptr(), flips.data_ptr(), sptr, 0, None, None,
+                                              window_counters[min(k, 1)].data_ptr(), None, 0, sp_):
+                        raise RuntimeError(f"swd_shot_account_dev failed: {_lib.last_error()}")
+                continue
+            if L.swd_pipeline_rolling_finish_dev(ses._h, n * h, rows.data_ptr(), rows.stride(0), None, sptr, None, shot.data_ptr(), sp_):
+                raise RuntimeError(f"swd_pipeline_rolling_finish_dev failed: {_lib.last_error()}")
+            wins = window_stats and window_counters is not None
+            if L.swd_shot_account_dev(self.device, B, 1 if wins else 0, shot.data_ptr(), flips.data_ptr(), sptr if wins else None, int(first_shot),
+                                      ln["result"].data_ptr(), counters.data_ptr() if counters is not None else None,
+                                      window_counters[2].data_ptr() if wins else None, failed.data_ptr() if failed is not None else None,
+                                      failed.numel() - 1 if failed is not None else 0, sp_):
+                raise RuntimeError(f"swd_shot_account_dev failed: {_lib.last_error()}")
+
+    def _schedule(self, rounds):
+        from .windows import rolling_schedule
+        rounds = self.rounds if rounds is None else int(rounds)
+        return rounds, rolling_schedule(self.template, rounds)  # ValueError names the lengths served
+
+    def run(self, shots, rounds=None, batch=4096, seed=20240318, first_shot=0, lanes=2, max_errors=None, keep_failures=0, window_stats=True):
+        """``shots`` shots numbered ``first_shot ..`` of the experiment of ``rounds`` syndrome rounds (default: the template's, or what
+        ``bb`` was asked for) in batches of ``batch``; batch j goes to lane ``j % lanes``, each lane a torch stream, a
+        ``RollingSession`` and buffers of its own -- ``[batch, rows of one step]``, whatever ``rounds``.  The host reads the counters
+        once at the end; the result is a pure function of (seed, first_shot, shots, rounds), whatever ``batch`` and ``lanes``.
+        ``max_errors``, ``keep_failures`` and ``window_stats`` as in ``MemoryExperiment.run``.  ValueError, before anything is
+        launched, when the template does not serve ``rounds``.  -> ``RollingMemoryResult``."""
+        import torch
+        shots, batch, lanes, keep = int(shots), int(batch), int(lanes), int(keep_failures)
+        if shots < 0 or batch <= 0 or lanes not in (1, 2) or keep < 0:
+            raise ValueError("shots >= 0, batch > 0, lanes 1 or 2, keep_failures >= 0")
+        rounds, sched = self._schedule(rounds)
+        dev = torch.device("cuda", self.device)
+        cap = max(1, min(batch, shots))
+        counters = torch.zeros((4,), dtype=torch.int64, device=dev)
+        wc = torch.zeros((3, _lib.WINDOW_COUNTER_WORDS), dtype=torch.int64, device=dev) if window_stats else None
+        failed = torch.zeros((1 + keep,), dtype=torch.int64, device=dev) if keep else None
+        torch.cuda.current_stream(dev).synchronize()  # the lanes add into zeroed counters
+        start, k = 0, 0
+        while start < shots:
+            B = min(batch, shots - start)
+            self._enqueue(self._lane(k % lanes, cap), B, rounds, sched, seed, first_shot + start, window_stats, counters, wc, failed)
+            start, k = start + B, k + 1
+            if max_errors is not None and k % lanes == 0:
+                for l2 in self._lanes[:lanes]:
+                    l2["stream"].synchronize()
+                if int(counters[1].item()) >= max_errors:
+                    break
+        for l2 in self._lanes:
+            l2["stream"].synchronize()
+        self.decoder.check_status()
+        c = counters.cpu().numpy()
+        w = wc.cpu().numpy() if wc is not None else None
+        kept = failed.cpu().numpy().view(np.uint64) if failed is not None else np.zeros(1, np.uint64)
+        return RollingMemoryResult(rounds, len(sched), c[0], c[1], c[2], c[3], *((w[:, :8], w[:, 8], w[:, 9]) if w is not None else (None, None, None)),
+                                   failed_shots=kept[1:1 + min(int(kept[0]), keep)], failed_shots_complete=int(c[1]) <= keep)
+
+    def run_batch(self, B, rounds=None, seed=20240318, first_shot=0):
+        """One batch with the per-shot arrays on the host (tests and debugging; unlike ``run`` it holds the whole experiment's rows):
+        dict with ``det`` [B, (rounds + 1) * n_half], ``true_flips`` uint32 [B], ``stats`` [B, windows, 8], ``shot_result`` [B, 2] and
+        ``result`` (the words of include/swd.h: bit 0 logical error, bit 1 flagged, bit 2 observable mismatch)."""
+        import torch
+        B = int(B)
+        if B <= 0:
+            raise ValueError("B > 0")
+        rounds, sched = self._schedule(rounds)
+        dev = torch.device("cuda", self.device)
+        ln = self._lane(0, B)
+        with torch.cuda.stream(ln["stream"]):
+            det = torch.empty((B, (rounds + 1) * self.template.n_half), dtype=torch.uint8, device=dev)
+            stats = torch.empty((len(sched), B, _lib.STAT_WORDS), dtype=torch.int32, device=dev)
+        self._enqueue(ln, B, rounds, sched, seed, int(first_shot), True, None, None, None, det=det, stats_all=stats)
+        ln["stream"].synchronize()
+        self.decoder.check_status()
+        out = {key: ln[key][:B].cpu().numpy() for key in ("shot_result", "result")}
+        out.update(det=det.cpu().numpy(), stats=np.ascontiguousarray(stats.cpu().numpy().transpose(1, 0, 2)),
+                   true_flips=ln["flips"][:B].cpu().numpy().view(np.uint32))
+        return out

@@ -461,3 +461,85 @@ def sliding_window_decode_rolling_host(template_plan, chunks, final_rows, decode
     frame[:, fill:fill + k] ^= final_rows & 1
     step("tail", T.tail, T.tail_chk, T.tail_obs, T.frame_rows)
     return events, obs_flips, flagged
+
+
+def _as_template(template_or_plan) -> RollingTemplate:
+    return template_or_plan if isinstance(template_or_plan, RollingTemplate) else rolling_template(template_or_plan)
+
+
+def template_blocks(template_or_plan):
+    """``(j0, j1, anchor_cols)`` of a rolling template: the column blocks (one per round, ``plan.anchors``) ``j0 .. j1 - 1`` are the body
+    rounds, the translates of one another that an experiment of another length repeats; ``anchor_cols`` [R0 + 2]: the first column of
+    every block and the number of columns.  What ``extend_periodic`` and the rolling DEM sampler take."""
+    T = _as_template(template_or_plan)
+    cols = [int(a[1]) for a in T.plan.anchors]
+    return cols.index(int(T.body.col0)), cols.index(int(T.tail.col0)), np.asarray(cols, dtype=np.int64)
+
+
+def extend_periodic(chk, obs, priors, n_half: int, j0: int, j1: int, anchor_cols, rounds: int):
+    """The model of ``rounds`` rounds that a periodic model of R0 rounds stands for: the head columns ``[0, c0)`` as they are, the
+    body block ``[c0, c1)`` -- column block ``j0`` -- ``(j1 - j0) + (rounds - R0)`` times, copy k with its rows moved down by
+    ``k * n_half`` (observables and priors as they are), then the tail columns ``[c2, end)`` with their rows moved down by
+    ``(rounds - R0) * n_half``.  -> (chk, obs, priors) as scipy CSC matrices and a numpy vector."""
+    chk, priors = sp.csc_matrix(chk), np.asarray(priors, dtype=np.float64)
+    obs = sp.csc_matrix(obs) if obs is not None else sp.csc_matrix((0, chk.shape[1]), dtype=np.uint8)
+    a = [int(x) for x in anchor_cols]
+    h, R0 = int(n_half), len(a) - 2
+    nbody = (j1 - j0) + (int(rounds) - R0)
+    if not 0 <= j0 < j1 <= R0 or chk.shape[0] != (R0 + 1) * h or a[-1] != chk.shape[1]:
+        raise ValueError("anchor columns, body blocks and matrix shape do not describe a model of whole rounds")
+    if nbody < 0:
+        raise ValueError(f"{rounds} rounds: the model of {R0} rounds cannot lose more than its {j1 - j0} body rounds")
+    c0, c1, c2 = a[j0], a[j0 + 1], a[j1]
+    num_det = (int(rounds) + 1) * h
+
+    def moved(m, lo, hi, shift):
+        c = sp.csc_matrix(m[:, lo:hi])
+        c.sort_indices()
+        return sp.csc_matrix((np.ones(c.nnz, np.uint8), c.indices + shift, c.indptr), shape=(num_det, hi - lo))
+
+    parts = [moved(chk, 0, c0, 0)] + [moved(chk, c0, c1, k * h) for k in range(nbody)] + [moved(chk, c2, a[-1], (int(rounds) - R0) * h)]
+    oparts = [obs[:, :c0]] + [obs[:, c0:c1]] * nbody + [obs[:, c2:]]
+    pparts = [priors[:c0]] + [priors[c0:c1]] * nbody + [priors[c2:]]
+    return sp.hstack(parts, format="csc"), sp.hstack(oparts, format="csc"), np.concatenate(pparts)
+
+
+def extended_block_cols(anchor_cols, j0: int, j1: int, rounds: int) -> np.ndarray:
+    """[rounds + 2]: the first column of every column block of ``extend_periodic``'s model of ``rounds`` rounds, and its number of
+    columns.  Block b holds the faults that first show in row block b; they reach into row block b + 1 at most."""
+    a = np.asarray(anchor_cols, dtype=np.int64)
+    R0 = len(a) - 2
+    nbody, cs = (j1 - j0) + (int(rounds) - R0), int(a[j0 + 1] - a[j0])
+    if nbody < 0:
+        raise ValueError(f"{rounds} rounds: the model of {R0} rounds cannot lose more than its {j1 - j0} body rounds")
+    return np.concatenate([a[:j0], a[j0] + cs * np.arange(nbody, dtype=np.int64), a[j1:] + cs * (int(rounds) - R0)])
+
+
+def extend_template(template_or_plan, rounds: int):
+    """The region-permuted ``chk``, ``obs`` and ``priors`` of ``plan_windows`` of the SAME circuit with ``rounds`` syndrome rounds,
+    built from the template of R0 rounds alone (``extend_periodic`` on its blocks): equal to them for every ``rounds >=
+    min_rounds``, whatever its residue mod F.  Together with the Philox restatement of the sampler's stream this is the executable
+    specification of ``RollingDemSampler``.  ValueError below ``min_rounds``."""
+    T = _as_template(template_or_plan)
+    if int(rounds) < T.min_rounds:
+        raise ValueError(f"{rounds} rounds are fewer than the template's shortest experiment; this template serves {T.lengths()}")
+    j0, j1, cols = template_blocks(T)
+    return extend_periodic(T.plan.chk, T.plan.obs, T.plan.priors, T.n_half, j0, j1, cols, rounds)
+
+
+def rolling_schedule(template_or_plan, rounds: int):
+    """``[(block0, nblocks), ...]``: the row blocks (of ``n_half`` detector rows) in the order a rolling experiment of ``rounds``
+    rounds hands them to its session -- the head window's W blocks, then F blocks per body window (each entry but the last
+    completes one window), and last what ``finish`` takes: the rest, the final block included.  ValueError naming the lengths
+    served when the template does not serve ``rounds``."""
+    T = _as_template(template_or_plan)
+    if not T.serves(int(rounds)):
+        raise ValueError(f"{rounds} syndrome rounds: this template serves {T.lengths()}")
+    blocks, tail = int(rounds) + 1, (T.tail.row1 - T.tail.row0) // T.n_half
+    # the tail window starts where the last head / body window's frame ends up: F blocks of it are new
+    out, b = [(0, T.W)], T.W
+    while blocks - b > tail - (T.W - T.F):
+        out.append((b, T.F))
+        b += T.F
+    out.append((b, blocks - b))
+    return out
