@@ -167,7 +167,11 @@ int swd_gdg_decode_batch_dev(swd_gdg *d, int32_t B, const uint8_t *synd, int64_t
  * variable-node update uses exp/log1p; the device evaluates them with the algorithms of the C library the
  * reference links (glibc >= 2.28: table-driven exp in its FMA build, fdlibm log1p -- csrc/swd_libm.h), so
  * posterior LLRs, decisions and OSD orderings are bit-identical to a reference run on an FMA-capable x86-64.
- * Restrictions (swd_bp4_create fails with a message): column weight of Hx / Hz <= 10; osd_order > 0 needs
+ * Restrictions (swd_bp4_create fails with a message): column weight of Hx / Hz <= 10, except for up to 8 HEAVY columns
+ * (weight above 10 in Hx or Hz, any position, any weight up to m <= 1024: the last qubit of the cycle-assembled and EG codes of
+ * Misc.ipynb cells 6-8, H = (H1 | 1), touches every check), which are accepted with osd_order = -1 only (decode returns the BP
+ * decisions of a shot that did not converge; camel_decode never runs OSD) -- with osd_method 0 the caller's -1 stands on such a
+ * graph, where the reference resets it to 0 (bp4_osd.pyx:74-76); osd_order > 0 needs
  * rank(Hx) >= rank(Hz) -- the reference sizes BOTH sweeps with kx = n - rank_x (bp4_osd.pyx:103-104, :284): with
  * rank(Hx) > rank(Hz) its z-basis sweep walks fewer candidate columns than exist, which is reproduced (pinned by
  * tests/golden/bp4_unequal_ranks.npz); with rank(Hx) < rank(Hz) it reads past its column array, which is not. */
@@ -182,6 +186,9 @@ swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, cons
                         const double *pz, const swd_bp4_params *p, int device); /* channel_probs of hx/hz ignored */
 void swd_bp4_destroy(swd_bp4 *d);
 int swd_bp4_info(const swd_bp4 *d, int32_t *mx, int32_t *mz, int32_t *n, int32_t *rank_x, int32_t *rank_z);
+/* Heavy columns of the handle's graphs (both pointers nullable): how many columns the decoder treats as heavy (0: none -- the
+ * kernel forms of graphs within the column-weight bound) and the largest of their weights in Hx or Hz (0 when there is none). */
+int swd_bp4_heavy_info(const swd_bp4 *d, int32_t *count, int32_t *max_degree);
 /* The form of the BP kernel the handle's most recent launch took (diagnostics and tests; every pointer nullable):
  * split 1 = two threads per qubit, lazy 1 = the two-half node update, fast 1 = the specialised instantiation (0: generic),
  * wmax / dm = the instantiation's most waves per workgroup and column-weight bound, threads = the workgroup size, skew = the

@@ -63,6 +63,7 @@ SYMBOLS = [
     ("swd_bp4_create", _vp, [C.POINTER(GraphDesc), C.POINTER(GraphDesc), _vp, _vp, _vp, C.POINTER(Bp4Params), C.c_int]),
     ("swd_bp4_destroy", None, [_vp]),
     ("swd_bp4_info", C.c_int, [_vp] + [C.POINTER(_i32)] * 5),
+    ("swd_bp4_heavy_info", C.c_int, [_vp] + [C.POINTER(_i32)] * 2),
     ("swd_bp4_last_form", C.c_int, [_vp] + [C.POINTER(_i32)] * 8),
     ("swd_bp4_decode_batch", C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("swd_bp4_decode_batch_dev", C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

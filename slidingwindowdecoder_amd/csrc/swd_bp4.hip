@@ -15,6 +15,7 @@ struct Bp4 {
     Graph gx, gz;
     swd_bp4_params p{};
     int device = 0, nt = 256, nt_osd = 256, dm = 4, n = 0;
+    int heavy = 0, heavy_deg = 0; // heavy columns (weight above SWD_DMAX in Hx or Hz: the HEAVY instantiation) and the largest of their weights
     int nt_split = 0; // > 0: threads of the launch with two threads per qubit (the specialised instantiation; swd_bp4_kernel.h) // nt: threads of the BP kernel (a launch parameter), nt_osd: of the OSD kernel (its layouts)
     SwdLdsLayout Lx{}, Lz{};
     SwdBp4Layout L{};
@@ -50,7 +51,7 @@ struct Bp4 {
     }
 };
 
-template <int WMAX, int NTO, int DM, bool FAST, bool LAZY>
+template <int WMAX, int NTO, int DM, bool FAST, bool LAZY, bool HEAVY = false>
 static int bp4_launch(Bp4 *d, const SwdBp4Args &a0, hipStream_t st, int nt) {
     SwdBp4Args a = a0;
     a.split = (FAST && nt == d->nt_split) ? 1 : 0;
@@ -59,25 +60,25 @@ static int bp4_launch(Bp4 *d, const SwdBp4Args &a0, hipStream_t st, int nt) {
     std::lock_guard<std::mutex> fn_lock(fn_mu);
     static int lds_limit[64] = {0};
     if (d->L.total > lds_limit[d->device & 63]) {
-        SWD_HIP(hipFuncSetAttribute((const void *)bp4_kernel<WMAX, DM, FAST, LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, d->L.total));
+        SWD_HIP(hipFuncSetAttribute((const void *)bp4_kernel<WMAX, DM, FAST, LAZY, HEAVY>, hipFuncAttributeMaxDynamicSharedMemorySize, d->L.total));
         lds_limit[d->device & 63] = d->L.total;
     }
     // persistent grid: as many workgroups as the device holds at once, each walks its share of the units
     static int slots[64] = {0}, slots_lds[64] = {0}, slots_nt[64] = {0};
     if (!slots[d->device & 63] || slots_lds[d->device & 63] != d->L.total || slots_nt[d->device & 63] != nt) {
         int per_cu = 0, cus = 0;
-        SWD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bp4_kernel<WMAX, DM, FAST, LAZY>, nt, (size_t)d->L.total));
+        SWD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bp4_kernel<WMAX, DM, FAST, LAZY, HEAVY>, nt, (size_t)d->L.total));
         SWD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d->device));
         while (per_cu > 1 && (long long)per_cu * ((d->L.total + 2048 + 1279) / 1280 * 1280) > 160 * 1024) --per_cu; // LDS is granted in granules of 1280 B (swd_plan.h); + the kernel's 2 KB exp table
         slots[d->device & 63] = std::max(1, per_cu) * std::max(1, cus);
         slots_lds[d->device & 63] = d->L.total; slots_nt[d->device & 63] = nt;
     }
     const int units = a.camel ? 4 * a.B : a.B;
-    const bool with_osd = !a.camel && a.osd_order >= 0;
+    const bool with_osd = !HEAVY && !a.camel && a.osd_order >= 0; // (graphs with heavy columns are created with osd_order = -1 only)
     if (with_osd || a.ticket) SWD_HIP(hipMemsetAsync(a.osd_count, 0, 4 * sizeof(uint32_t), st)); // (queue counter, ticket counter)
-    hipLaunchKernelGGL((bp4_kernel<WMAX, DM, FAST, LAZY>), dim3(std::min(units, slots[d->device & 63])), dim3(nt), d->L.total, st, a);
+    hipLaunchKernelGGL((bp4_kernel<WMAX, DM, FAST, LAZY, HEAVY>), dim3(std::min(units, slots[d->device & 63])), dim3(nt), d->L.total, st, a);
     SWD_HIP(hipGetLastError());
-    if (with_osd) { // the queue of unconverged decodes (often empty: its workgroups then read the count and leave)
+    if constexpr (!HEAVY) if (with_osd) { // the queue of unconverged decodes (often empty: its workgroups then read the count and leave)
         static int lds_limit2[64] = {0}, slots2[64] = {0}, slots2_lds[64] = {0};
         if (d->L.total > lds_limit2[d->device & 63]) {
             SWD_HIP(hipFuncSetAttribute((const void *)bp4_osd_kernel<NTO, DM>, hipFuncAttributeMaxDynamicSharedMemorySize, d->L.total));
@@ -131,6 +132,11 @@ static int bp4_skew_switch() {
 static int bp4_dispatch(Bp4 *d, const SwdBp4Args &a, hipStream_t st) {
     // the specialised instantiation: a thread per qubit and per check, no camel run (swd_bp4_kernel.h); two threads per qubit for
     // small codes (swd_bp4_create; SWD_BP4_NOSPLIT: the one-thread form)
+    // graphs with heavy columns: the generic form with the side list (swd_bp4_kernel.h, HEAVY), one instantiation per workgroup size
+    if (d->heavy)
+        return d->nt <= 256 ? bp4_launch<4, 256, SWD_DMAX, false, false, true>(d, a, st, d->nt)
+                            : (d->nt <= 512 ? bp4_launch<8, 256, SWD_DMAX, false, false, true>(d, a, st, d->nt)
+                                            : bp4_launch<16, 256, SWD_DMAX, false, false, true>(d, a, st, d->nt));
     const bool fast = !a.camel && d->n <= d->nt && d->gx.m + d->gz.m <= d->nt && !getenv("SWD_BP4_GENERIC");
     if (fast) return bp4_dispatch_nt<true>(d, a, st, d->nt_split ? d->nt_split : d->nt);
     return bp4_dispatch_nt<false>(d, a, st, d->nt);
@@ -149,6 +155,7 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
     Bp4 *d = new Bp4();
     d->device = device; d->p = *p; d->n = hx->n;
     const int n = hx->n;
+    const int asked_order = d->p.osd_order;
     if (d->p.osd_method == 0) d->p.osd_order = 0;
     if (d->p.osd_method < 0 || d->p.osd_method > 2) { set_error("ERROR: OSD method '%d' invalid.", d->p.osd_method); delete d; return nullptr; }
     // OSD path metrics use prior_llr_x = log((1-(px+py))/(px+py)), prior_llr_z = log((1-(pz+py))/(pz+py)) (bp4_osd.pyx:134-137)
@@ -156,7 +163,40 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
     for (int v = 0; v < n; ++v) { qx[v] = px[v] + py[v]; qz[v] = pz[v] + py[v]; }
     swd_graph_desc dx = *hx, dz = *hz;
     dx.channel_probs = qx.data(); dz.channel_probs = qz.data();
-    if (d->gx.build(&dx) || d->gz.build(&dz)) { delete d; return nullptr; }
+    // Heavy columns: weight above SWD_DMAX in Hx or in Hz (the last qubit of the cycle-assembled and EG codes touches every check).
+    // Up to SWD_MAX_HEAVY of them, of any weight (a weight is at most m <= 1024, the lane field of an edge word), leave the ELL tables
+    // for a side list; every other column stays within SWD_DMAX.
+    std::vector<int32_t> heavy;
+    if (hx->row_ptr && hx->col_idx && hz->row_ptr && hz->col_idx && hx->m > 0 && hz->m > 0 && n > 0 && hx->nnz > 0 && hz->nnz > 0 &&
+        hx->row_ptr[0] == 0 && hz->row_ptr[0] == 0 && hx->row_ptr[hx->m] == hx->nnz && hz->row_ptr[hz->m] == hz->nnz) {
+        std::vector<int> w(n, 0); // the larger of a column's two weights (entries out of range are build()'s to report)
+        for (const swd_graph_desc *g : {hx, hz}) {
+            std::vector<int> c(n, 0);
+            for (int e = 0; e < g->nnz; ++e) if (g->col_idx[e] >= 0 && g->col_idx[e] < n) c[g->col_idx[e]]++;
+            for (int v = 0; v < n; ++v) w[v] = std::max(w[v], c[v]);
+        }
+        for (int v = 0; v < n; ++v) if (w[v] > SWD_DMAX) { heavy.push_back(v); d->heavy_deg = std::max(d->heavy_deg, w[v]); }
+        if ((int)heavy.size() > SWD_MAX_HEAVY) {
+            std::vector<int> ws;
+            for (int v : heavy) ws.push_back(w[v]);
+            std::sort(ws.begin(), ws.end(), [](int a, int b) { return a > b; });
+            set_error("column weight %d exceeds this build's bound %d (accepted beside it: up to %d heavy columns of any weight up to m <= %d, "
+                      "with osd_order=-1 or camel_decode; this graph has %d columns above the bound)",
+                      ws[SWD_MAX_HEAVY], SWD_DMAX, SWD_MAX_HEAVY, SWD_MAX_M, (int)heavy.size());
+            delete d; return nullptr;
+        }
+    }
+    d->heavy = (int)heavy.size();
+    if (d->heavy && asked_order >= 0) {
+        // (the elimination kernel's ELL column tables hold light columns only; with osd_method "osd_0" the reference resets the order to
+        // 0, bp4_osd.pyx:74-76, which its camel_decode never looks at -- here the caller's -1 stands, and decode returns the BP
+        // decisions of a shot that did not converge, as the reference does for the other methods with osd_order = -1)
+        set_error("OSD on a graph with heavy columns (%d of weight above %d, up to %d) is not supported: create the decoder with "
+                  "osd_order=-1 (decode then returns the BP decisions) or use camel_decode", d->heavy, SWD_DMAX, d->heavy_deg);
+        delete d; return nullptr;
+    }
+    if (d->heavy) d->p.osd_order = -1;
+    if (d->gx.build(&dx, d->heavy ? &heavy : nullptr) || d->gz.build(&dz, d->heavy ? &heavy : nullptr)) { delete d; return nullptr; }
     const int kmin = std::min(n - d->gx.rank, n - d->gz.rank);
     if (d->p.osd_order > kmin) { // bp4_osd.pyx:92-98
         set_error("For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", kmin);
@@ -170,8 +210,8 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
     }
     if (d->p.osd_method == 1 && d->p.osd_order > 15) { set_error("osd_e supports osd_order <= 15 on the device"); delete d; return nullptr; }
     const int D = std::max(d->gx.D, d->gz.D);
-    if (D > SWD_DMAX) { set_error("column weight %d exceeds this build's bound %d", D, SWD_DMAX); delete d; return nullptr; }
-    d->dm = D <= 4 ? 4 : (D <= 8 ? 8 : SWD_DMAX); // SHYPS stabiliser matrices reach column weight 9
+    if (D > SWD_DMAX) { set_error("column weight %d exceeds this build's bound %d", D, SWD_DMAX); delete d; return nullptr; } // (not reached: such a column is heavy)
+    d->dm = d->heavy ? SWD_DMAX : (D <= 4 ? 4 : (D <= 8 ? 8 : SWD_DMAX)); // SHYPS stabiliser matrices reach column weight 9
     d->nt_osd = n <= 3072 ? 256 : 1024;
     d->nt = n <= 1024 ? std::max(64, (n + 63) / 64 * 64) : 1024;
     if (const char *e = getenv("SWD_BP4_NT")) { const int v = atoi(e); if (v >= 64 && v <= 1024 && v % 64 == 0) d->nt = v; } // (diagnostics)
@@ -179,7 +219,7 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
     // decodes/s, SHYPS r = 3 23.9 -> 24.9 M; [[144]] on five waves 35.9 -> 28.0 M, so larger codes keep one thread per qubit;
     // SWD_BP4_SPLIT_MAX overrides the bound on 2 n for experiments)
     const int split_max = getenv("SWD_BP4_SPLIT_MAX") ? atoi(getenv("SWD_BP4_SPLIT_MAX")) : 256;
-    d->nt_split = (2 * n <= std::min(split_max, 512) && !getenv("SWD_BP4_NOSPLIT")) ? std::max(64, (2 * n + 63) / 64 * 64) : 0;
+    d->nt_split = (!d->heavy && 2 * n <= std::min(split_max, 512) && !getenv("SWD_BP4_NOSPLIT")) ? std::max(64, (2 * n + 63) / 64 * 64) : 0;
     if (d->gx.upload() || d->gz.upload()) { delete d; return nullptr; }
     d->gx.d.new_n = n; d->gz.d.new_n = n;
     // rank(Hx) > rank(Hz): the z-basis sweep walks the first kx = n - rank_x non-pivot columns like the reference's (not the n - rank_z
@@ -189,8 +229,10 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
     // are pivots, so at least kx are not: the first kx non-pivot columns of the whole order always lie among them, whatever their rank
     // (pinned by tests/golden/bp4_unequal_prefix.npz, where that prefix is rank-deficient on every OSD shot).
     if (d->p.osd_order > 0 && d->gx.rank > d->gz.rank) d->gz.d.new_n = n - d->gx.rank + d->gz.rank;
-    make_layout_for_osd(d->gx, d->nt_osd, d->Lx);
-    make_layout_for_osd(d->gz, d->nt_osd, d->Lz);
+    if (!d->heavy) { // (no OSD on a graph with heavy columns: no elimination scratch)
+        make_layout_for_osd(d->gx, d->nt_osd, d->Lx);
+        make_layout_for_osd(d->gz, d->nt_osd, d->Lz);
+    }
     auto al = [](int x, int a) { return (x + a - 1) / a * a; };
     const int msgx_b = al((d->gx.E + 1) * 8, 16), msgz_b = al((d->gz.E + 1) * 8, 16);
     int scratch = std::max(msgx_b + msgz_b, std::max(d->Lx.off_livemask, d->Lz.off_livemask));
@@ -210,6 +252,11 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
     L.off_decz = o; o += n;
     L.off_hard = o; o = al(o + n, 16);
     L.off_misc = o; o += 640;
+    if (d->heavy) { // the side list of the heavy nodes (swd_bp4_kernel.h, SwdBp4Layout)
+        L.off_hvd = o; o += d->heavy * 64;
+        L.off_hvt = o; o += d->heavy * 32;
+        L.off_hve = o; o += ((int)d->gx.hv_edge.size() + (int)d->gz.hv_edge.size()) * 4;
+    }
     L.total = al(o, 16);
     if (L.total > 160 * 1024) { set_error("code needs %d bytes of LDS per shot (> 163840)", L.total); delete d; return nullptr; }
     // channel LLRs (bp4_osd.pyx:127-133)
@@ -240,6 +287,14 @@ extern "C" int swd_bp4_info(const swd_bp4 *h, int32_t *mx, int32_t *mz, int32_t 
     if (n) *n = d->n;
     if (rank_x) *rank_x = d->gx.rank;
     if (rank_z) *rank_z = d->gz.rank;
+    return 0;
+}
+
+extern "C" int swd_bp4_heavy_info(const swd_bp4 *h, int32_t *count, int32_t *max_degree) {
+    const Bp4 *d = (const Bp4 *)h;
+    if (!d) { set_error("null decoder"); return -1; }
+    if (count) *count = d->heavy;
+    if (max_degree) *max_degree = d->heavy ? d->heavy_deg : 0;
     return 0;
 }
 
@@ -280,7 +335,7 @@ extern "C" int swd_bp4_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8_t *sx
         lpr = sl->lpr.as<double>();
     }
     SwdBp4Args a{};
-    a.gx = d->gx.d; a.gz = d->gz.d; a.Lx = d->Lx; a.Lz = d->Lz; a.L = d->L;
+    a.gx = d->gx.d; a.gz = d->gz.d; a.Lx = d->Lx; a.Lz = d->Lz; a.L = d->L; a.hvx = d->gx.hv; a.hvz = d->gz.hv;
     a.llr_x = d->d_llr_x; a.llr_y = d->d_llr_y; a.llr_z = d->d_llr_z;
     a.max_iter = d->p.max_iter; a.osd_method = d->p.osd_method; a.osd_order = d->p.osd_order; a.alpha = d->p.ms_scaling_factor;
     a.B = B; a.sx = sx; a.sz = sz; a.out = out; a.osd0 = osd0; a.bp_dec = bp_dec; a.stats = stats; a.lpr = lpr;
@@ -341,7 +396,7 @@ extern "C" int swd_bp4_camel_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8
         sl->cst.reserve((size_t)4 * B * 2 * 4))
         return -1;
     SwdBp4Args a{};
-    a.gx = d->gx.d; a.gz = d->gz.d; a.Lx = d->Lx; a.Lz = d->Lz; a.L = d->L;
+    a.gx = d->gx.d; a.gz = d->gz.d; a.Lx = d->Lx; a.Lz = d->Lz; a.L = d->L; a.hvx = d->gx.hv; a.hvz = d->gz.hv;
     a.llr_x = d->d_llr_x; a.llr_y = d->d_llr_y; a.llr_z = d->d_llr_z;
     a.max_iter = d->p.max_iter; a.osd_method = d->p.osd_method; a.osd_order = d->p.osd_order; a.alpha = d->p.ms_scaling_factor;
     a.B = B; a.sx = sx; a.sz = sz; a.out = nullptr; a.osd0 = nullptr; a.stats = nullptr; a.lpr = sl->lpr.as<double>();

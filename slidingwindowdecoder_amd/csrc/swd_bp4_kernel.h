@@ -14,6 +14,10 @@ struct SwdBp4Layout {
     int32_t off_msgz;   // msgX at 0 (Ex+1 doubles), msgZ here (Ez+1 doubles); both inside the scratch region
     int32_t off_jptrx, off_jptrz, off_cnx, off_cnz, off_parx, off_parz, off_sxo, off_szo, off_decx, off_decz,
         off_hard, off_misc, total;
+    // graphs with heavy columns (the HEAVY instantiation; 0 otherwise): per heavy node 8 doubles -- the three posteriors, the two
+    // numerators of its new messages, its two bp_init messages -- then 8 ints -- column, degrees and edge-word offsets in Hx / Hz,
+    // its decision -- then the edge words of all of them, Hx lists first
+    int32_t off_hvd, off_hvt, off_hve;
 };
 
 struct SwdBp4Args {
@@ -49,6 +53,7 @@ struct SwdBp4Args {
     uint8_t *camel_dec;      // [4B][2][n] decisions of every run
     double *camel_pm;        // [4B] cal_pm of the converged runs
     int32_t *camel_st;       // [4B][2] converged, iterations
+    SwdHeavyDev hvx, hvz;    // HEAVY instantiation: the heavy columns (the same ones, in the same order, in both) with their Hx / Hz edges
 };
 
 namespace swd {
@@ -108,6 +113,22 @@ __device__ __forceinline__ void bp4_split_edges(bool hx, const uint32_t (&ex)[DM
         msg[swd_edge_slot(e)] = num - bp4_logaddexp(-1. * aa, -1. * bb, xt);
         if (flip) atomicXor(&par[swd_edge_lane(e)], 1u);
     }
+}
+
+// HEAVY instantiation: the sum of a heavy node's check messages along one of its edge lists, in list order -- rows ascending, the order
+// the reference's vn_update adds them in (bp4_osd.pyx:539-549).  fp64 addition order is part of the result, so ONE lane walks the chain
+// (a tree or a wave reduction would round differently); the LDS reads of eight edges are issued ahead of their eight dependent adds.
+__device__ __forceinline__ double bp4_heavy_sum(const uint32_t *ew, int deg, const double *msg) {
+    double s = 0.0;
+#pragma unroll 1
+    for (int k0 = 0; k0 < deg; k0 += 8) {
+        double c[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) c[j] = msg[swd_edge_slot(ew[min(k0 + j, deg - 1)])];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s = (k0 + j < deg) ? s + c[j] : s;
+    }
+    return s;
 }
 
 // SWD_BP4_SKEW (diagnostics): the waves of one parity fall ~65 k cycles behind the others before a node pass that stores messages, so
@@ -222,10 +243,18 @@ __device__ __forceinline__ bool bp4_cn_pass(int nthreads, const SwdGraphDev &g, 
 // The LAZY instantiation of up to four waves is compiled for three waves per SIMD (139 registers, 48 B of scratch) instead of five (96 and
 // 224 B): its short decodes are chains of dependent steps that want their values in registers more than they want neighbours --
 // [[144]], 1 / 2 / 3 / 4 launches in flight: 36.7 / 67.4 / 73.5 / 78.9 -> 37.4 / 73.5 / 78.2 / 84.3 M decodes/s (four waves: 38.0 / 69.7 / 76.8 / 81.8).
+// HEAVY: graphs with a few variable nodes of any degree (the last qubit of the cycle-assembled and EG codes of Misc.ipynb cells 6-8
+// touches every check) beside nodes of degree <= DM, in the generic form only (not FAST, not LAZY).  The ELL tables list the light
+// columns; the heavy ones come in a side list (a.hvx / a.hvz, swd_graph.h) and live in LDS.  bp_init: the node's channel messages,
+// computed once per workgroup, go to all of its edges, spread over the threads.  Node pass: the node's thread walks the two sums in the
+// reference's order (bp4_heavy_sum), forms posteriors and decision like any node and leaves them in LDS; behind a barrier that only this
+// instantiation has, the per-edge outputs num - logaddexp(..) -- independent of each other, each reads and overwrites its own slot --
+// and their parity flips are spread over all threads.  The decided qubit of a camel run, when heavy, has no update: the spread pass
+// puts its bp_init messages back into the slots the check pass overwrote.
 #ifndef SWD_BP4_WAVES_LAZY
 #define SWD_BP4_WAVES_LAZY 3
 #endif
-template <int WMAX, int DM, bool FAST, bool LAZY = false>
+template <int WMAX, int DM, bool FAST, bool LAZY = false, bool HEAVY = false>
 #ifndef SWD_BP4_WAVES_LAZY8
 #define SWD_BP4_WAVES_LAZY8 4 // ... and the five- to eight-wave ones for four (128 registers, 96 B; six: 80 registers, the fused form's choice): [[288]] 19.6 -> 22.8 M decodes/s one launch at a time, 26.8 -> 32.0 M with two in flight; [[360]] 15.7 -> 20.7, 20.5 -> 27.7 (three waves: 15.4 / 19.9, 14.1 / 18.3)
 #endif
@@ -258,6 +287,32 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
     for (int j = tid; j <= gx.K; j += NT) jpx[j] = gx.jptr[j];
     for (int j = tid; j <= gz.K; j += NT) jpz[j] = gz.jptr[j];
     const bool one = FAST || n <= NT;
+    double *hvd = nullptr;
+    int *hvt = nullptr;
+    uint32_t *hve = nullptr;
+    int nh = 0, fixed_h = -1; // heavy nodes; the place of the decided qubit among them
+    if constexpr (HEAVY) {
+        hvd = (double *)(smem + a.L.off_hvd); hvt = (int *)(smem + a.L.off_hvt); hve = (uint32_t *)(smem + a.L.off_hve);
+        nh = a.hvx.count;
+        const int nex = a.hvx.edges, nez = a.hvz.edges;
+        for (int h = tid; h < nh; h += NT) {
+            const int v = a.hvx.id[h];
+            hvt[8 * h + 0] = v; hvt[8 * h + 1] = a.hvx.deg[h]; hvt[8 * h + 2] = a.hvz.deg[h];
+            hvt[8 * h + 3] = a.hvx.ptr[h]; hvt[8 * h + 4] = nex + a.hvz.ptr[h];
+            const double llrx = a.llr_x[v], llry = a.llr_y[v], llrz = a.llr_z[v];
+            hvd[8 * h + 5] = bp4_log1pexp(-1. * llrx, xt) - bp4_logaddexp(-1. * llry, -1. * llrz, xt);
+            hvd[8 * h + 6] = bp4_log1pexp(-1. * llrz, xt) - bp4_logaddexp(-1. * llry, -1. * llrz, xt); // sic (bp4_osd.pyx:438)
+        }
+        for (int i = tid; i < nex; i += NT) hve[i] = a.hvx.edge[i];
+        for (int i = tid; i < nez; i += NT) hve[nex + i] = a.hvz.edge[i];
+        for (int h = 0; h < nh; ++h) if (a.hvx.id[h] == fixed) fixed_h = h;
+    }
+    // (HEAVY) the place of node v in the side list, -1: a light node
+    auto hv_of = [&](int v) -> int {
+        int r = -1;
+        for (int h = 0; h < nh; ++h) r = (hvt[8 * h] == v) ? h : r;
+        return r;
+    };
     // Round 6: two threads per qubit (a.split; FAST launches with 2 n <= 1024).  Both compute the node's three posteriors from all of its
     // messages (same operations in the same order), one then updates the Hx edges, the other the Hz edges: the chain of eight
     // dependent exp / log1p evaluations per node and iteration -- what a launch waits for once its units are ticket-scheduled: the
@@ -271,6 +326,8 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
     const int vt = split ? tid >> 1 : tid;                       // the thread's qubit
     const int hsel = !split ? 3 : ((tid & 1) ? 2 : 1);           // bit 0: the Hx edges are this thread's, bit 1: the Hz edges
     const bool mine = one && vt < n;
+    int c_hv = -1; // (HEAVY, one node per thread) the thread's place in the side list
+    if constexpr (HEAVY) if (mine) for (int h = 0; h < nh; ++h) c_hv = (a.hvx.id[h] == vt) ? h : c_hv;
     int c_dx = 0, c_dz = 0;
     uint32_t c_ex[DM], c_ez[DM];
     double c_lx = 0.0, c_ly = 0.0, c_lz = 0.0;
@@ -361,12 +418,27 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
             for (int k = 0; k < dz; ++k) msgz[swd_edge_slot(gz.vn_edge[k * n + v])] = m_z;
         }
     }
+    if constexpr (HEAVY) // a heavy node's channel messages to all of its edges
+        for (int h = 0; h < nh; ++h) {
+            const int *t = hvt + 8 * h;
+            const int dxh = t[1], dzh = t[2];
+            for (int i = tid; i < dxh + dzh; i += NT) {
+                if (i < dxh) msgx[swd_edge_slot(hve[t[3] + i])] = hvd[8 * h + 5];
+                else msgz[swd_edge_slot(hve[t[4] + i - dxh])] = hvd[8 * h + 6];
+            }
+        }
     __syncthreads();
     if (camel_run) { // vn_set_value(n - 1, value) after bp_init (bp4_osd.pyx:234-236, 388-423): the qubit keeps its prior messages
         const int value = unit & 3, x = value & 1, z = value >> 1;
         if (tid == 0) { decx[fixed] = (uint8_t)x; decz[fixed] = (uint8_t)z; }
-        if (z) for (int k = tid; k < gx.col_deg[fixed]; k += NT) cnx[swd_edge_lane(gx.vn_edge[k * n + fixed])] ^= 1;
-        if (x) for (int k = tid; k < gz.col_deg[fixed]; k += NT) cnz[swd_edge_lane(gz.vn_edge[k * n + fixed])] ^= 1;
+        if (HEAVY && fixed_h >= 0) { // (its edge lists are those of the side list)
+            const int *t = hvt + 8 * fixed_h;
+            if (z) for (int k = tid; k < t[1]; k += NT) cnx[swd_edge_lane(hve[t[3] + k])] ^= 1;
+            if (x) for (int k = tid; k < t[2]; k += NT) cnz[swd_edge_lane(hve[t[4] + k])] ^= 1;
+        } else {
+            if (z) for (int k = tid; k < gx.col_deg[fixed]; k += NT) cnx[swd_edge_lane(gx.vn_edge[k * n + fixed])] ^= 1;
+            if (x) for (int k = tid; k < gz.col_deg[fixed]; k += NT) cnz[swd_edge_lane(gz.vn_edge[k * n + fixed])] ^= 1;
+        }
         __syncthreads();
     }
 
@@ -498,6 +570,32 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
         if (it > 0 && !any) { conv = 1; iters = it; break; }
         if (split) bp4_skew(a.skew);
         for (int v = vt; v < n; v += NT) { // vn_update (bp4_osd.pyx:533-589)
+            if constexpr (HEAVY) {
+                if (v == fixed && fixed_h >= 0) continue; // (decided and heavy: the spread pass below puts its messages back)
+                const int h = one ? c_hv : hv_of(v);
+                if (h >= 0) { // a heavy node: sums in the reference's order on this lane, the per-edge outputs in the spread pass below
+                    const int *t = hvt + 8 * h;
+                    const double v_lx = one ? c_lx : a.llr_x[v], v_ly = one ? c_ly : a.llr_y[v], v_lz = one ? c_lz : a.llr_z[v];
+                    double llrx_hx = bp4_heavy_sum(hve + t[4], t[2], msgz);
+                    double llrz_hz = bp4_heavy_sum(hve + t[3], t[1], msgx);
+                    const double llry_all = llrx_hx + llrz_hz + v_ly;
+                    llrx_hx = llrx_hx + v_lx;
+                    llrz_hz = llrz_hz + v_lz;
+                    if (one) { p_x = llrx_hx; p_y = llry_all; p_z = llrz_hz; p_set = true; }
+                    else { lpr_b[v] = llrx_hx; lpr_b[n + v] = llry_all; lpr_b[2 * n + v] = llrz_hz; }
+                    int idx;
+                    if (0 < llrx_hx && 0 < llry_all && 0 < llrz_hz) idx = 0;
+                    else if (llrx_hx < llry_all && llrx_hx < llrz_hz) idx = 1;
+                    else if (llry_all > llrz_hz) idx = 2;
+                    else idx = 3;
+                    decx[v] = (uint8_t)(idx & 1); decz[v] = (uint8_t)(idx >> 1);
+                    hvd[8 * h + 0] = llrx_hx; hvd[8 * h + 1] = llry_all; hvd[8 * h + 2] = llrz_hz;
+                    hvd[8 * h + 3] = bp4_log1pexp(-1. * llrx_hx, xt);
+                    hvd[8 * h + 4] = bp4_log1pexp(-1. * llrz_hz, xt);
+                    hvt[8 * h + 5] = idx;
+                    continue;
+                }
+            }
             if (v == fixed) { // decided (bp4_osd.pyx:456-458): its bit-to-check messages stay the priors of bp_init; the
                               // CN pass has just overwritten the shared slots with check-to-bit values, so put them back
                 const double llrx = a.llr_x[v], llry = a.llr_y[v], llrz = a.llr_z[v];
@@ -558,6 +656,26 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
                     if (bx) atomicXor(&parz[swd_edge_lane(ez[k])], 1u); // Hz * x-string
                 }
 #endif
+        }
+        if constexpr (HEAVY) { // the spread pass: every edge of a heavy node on a thread of its own (bp4_osd.pyx:571-589, as bp4_split_edges)
+            __syncthreads(); // the heavy nodes' sums and decisions are in LDS; nothing has overwritten their check messages yet
+            for (int h = 0; h < nh; ++h) {
+                const int *t = hvt + 8 * h;
+                const int dxh = t[1], dzh = t[2];
+                const bool decided = t[0] == fixed;
+                const double llrx_hx = hvd[8 * h + 0], llry_all = hvd[8 * h + 1], llrz_hz = hvd[8 * h + 2];
+                const int idx = t[5], bx = idx & 1, bz = idx >> 1;
+                for (int i = tid; i < dxh + dzh; i += NT) {
+                    const bool hxe = i < dxh;
+                    const uint32_t e = hve[hxe ? t[3] + i : t[4] + i - dxh];
+                    double *const msg = hxe ? msgx : msgz;
+                    if (decided) { msg[swd_edge_slot(e)] = hvd[8 * h + (hxe ? 5 : 6)]; continue; }
+                    const double c = msg[swd_edge_slot(e)];
+                    const double aa = (hxe ? llrz_hz : llrx_hx) - c, bb = llry_all - c;
+                    msg[swd_edge_slot(e)] = hvd[8 * h + (hxe ? 3 : 4)] - bp4_logaddexp(-1. * aa, -1. * bb, xt);
+                    if (hxe ? bz : bx) atomicXor(&(hxe ? parx : parz)[swd_edge_lane(e)], 1u); // Hx * z-string, Hz * x-string
+                }
+            }
         }
         __syncthreads();
         BP4T(7) // barrier behind the node pass

@@ -50,6 +50,17 @@ struct SwdGraphDev {
     const double *llr_s;       // [n]
 };
 
+// Heavy columns (weight above what the ELL tables hold; asked for by swd_bp4_create only): a side list beside the tables above,
+// where such a column has col_deg 0.  Its edges are ordinary message slots of their checks.
+#define SWD_MAX_HEAVY 8
+struct SwdHeavyDev {
+    int32_t count, edges;    // columns listed, sum of their degrees
+    const int32_t *id;       // [count] column
+    const int32_t *deg;      // [count] its weight in this matrix (may be 0: heavy in the other matrix of a pair only)
+    const int32_t *ptr;      // [count + 1] start of its edge words
+    const uint32_t *edge;    // [edges] edge words (slot | lane << 16 | j << 26) in row-ascending order, the order the reference walks a column
+};
+
 __host__ __device__ inline uint32_t swd_edge_slot(uint32_t e) { return e & 0xFFFFu; }
 __host__ __device__ inline uint32_t swd_edge_lane(uint32_t e) { return (e >> 16) & 0x3FFu; }
 __host__ __device__ inline uint32_t swd_edge_j(uint32_t e) { return e >> 26; }

@@ -91,7 +91,12 @@ void Graph::fill_tables() {
     row_col.assign(S, 0);
     vn_edge.assign((size_t)std::max(D, 1) * n, SWD_PAD_EDGE);
     vn_row.assign((size_t)std::max(D, 1) * n, 0xFFFF);
-    std::vector<int> fill(n, 0);
+    std::vector<int> fill(n, 0), hidx; // hidx: column -> place in the side list of heavy columns (only when there is one)
+    if (!hv_id.empty()) {
+        hidx.assign(n, -1);
+        for (size_t h = 0; h < hv_id.size(); ++h) hidx[hv_id[h]] = (int)h;
+        hv_edge.assign(hv_ptr.back(), 0u);
+    }
     for (int r = 0; r < m; ++r) {
         const int l = iperm[r];
         for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
@@ -100,7 +105,9 @@ void Graph::fill_tables() {
             const int slot = jptr[j] + l;
             row_col[slot] = (uint16_t)v;
             const int k = fill[v]++; // rows ascending: the order the reference's variable-node update sums in
-            vn_edge[(size_t)k * n + v] = (uint32_t)slot | ((uint32_t)l << 16) | ((uint32_t)j << 26);
+            const uint32_t word = (uint32_t)slot | ((uint32_t)l << 16) | ((uint32_t)j << 26);
+            if (!hidx.empty() && hidx[v] >= 0) { hv_edge[hv_ptr[hidx[v]] + k] = word; continue; }
+            vn_edge[(size_t)k * n + v] = word;
             vn_row[(size_t)k * n + v] = (uint16_t)r;
         }
     }
@@ -234,7 +241,7 @@ void Graph::optimize_layout(int pads) {
     cost = layout_cost();
 }
 
-int Graph::build(const swd_graph_desc *g) {
+int Graph::build(const swd_graph_desc *g, const std::vector<int32_t> *heavy) {
     if (!g || !g->row_ptr || !g->col_idx || !g->channel_probs) { set_error("null graph description"); return -1; }
     m = g->m; n = g->n; E = g->nnz;
     if (m <= 0 || n <= 0 || E <= 0) { set_error("empty check matrix (m=%d n=%d nnz=%d)", m, n, E); return -1; }
@@ -257,10 +264,22 @@ int Graph::build(const swd_graph_desc *g) {
         K = std::max(K, d);
         for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) cdeg[col_idx[e]]++;
     }
+    hv_id.clear(); hv_deg.clear(); hv_ptr.clear(); hv_edge.clear();
+    std::vector<int> ldeg(cdeg); // weights the ELL tables see: 0 for a column of the side list
+    if (heavy && !heavy->empty()) {
+        if (heavy->size() > SWD_MAX_HEAVY) { set_error("%d heavy columns exceed this build's bound %d", (int)heavy->size(), SWD_MAX_HEAVY); return -1; }
+        hv_ptr.push_back(0);
+        for (size_t h = 0; h < heavy->size(); ++h) {
+            const int v = (*heavy)[h];
+            if (v < 0 || v >= n || (h > 0 && v <= (*heavy)[h - 1])) { set_error("heavy column list not ascending inside [0, %d)", n); return -1; }
+            hv_id.push_back(v); hv_deg.push_back(cdeg[v]); hv_ptr.push_back(hv_ptr.back() + cdeg[v]);
+            ldeg[v] = 0;
+        }
+    }
     for (int v = 0; v < n; ++v) {
-        if (cdeg[v] > SWD_MAX_COL_DEG) { set_error("column %d has weight %d > %d", v, cdeg[v], SWD_MAX_COL_DEG); return -1; }
-        D = std::max(D, cdeg[v]);
-        col_deg[v] = (uint8_t)cdeg[v];
+        if (ldeg[v] > SWD_MAX_COL_DEG) { set_error("column %d has weight %d > %d", v, ldeg[v], SWD_MAX_COL_DEG); return -1; }
+        D = std::max(D, ldeg[v]);
+        col_deg[v] = (uint8_t)ldeg[v];
     }
     // lanes: checks by degree descending (stable in original index)
     perm.resize(m); iperm.resize(m);
@@ -296,7 +315,7 @@ int Graph::build(const swd_graph_desc *g) {
     {
         std::vector<int> ord(n);
         for (int v = 0; v < n; ++v) ord[v] = v;
-        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return (cdeg[a] + 1) / 2 > (cdeg[b] + 1) / 2; });
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return (ldeg[a] + 1) / 2 > (ldeg[b] + 1) / 2; });
         vperm.resize(n); llr_s.resize(n);
         for (int i = 0; i < n; ++i) { vperm[i] = (uint16_t)ord[i]; llr_s[i] = llr[ord[i]]; }
         fill_listed();
@@ -321,7 +340,17 @@ int Graph::upload() {
     size_t o_vnedge_s = al(o_vperm + vperm.size() * 2);
     size_t o_llr_s = al(o_vnedge_s + vn_edge_s.size() * 4);
     size_t total = al(o_llr_s + llr_s.size() * 8);
+    // (the side list of heavy columns behind everything else, only when there is one: the other graphs' images are unchanged)
+    const size_t nh = hv_id.size();
+    const size_t o_hvid = total, o_hvdeg = al(o_hvid + nh * 4), o_hvptr = al(o_hvdeg + nh * 4), o_hvedge = al(o_hvptr + (nh + 1) * 4);
+    if (nh) total = al(o_hvedge + hv_edge.size() * 4 + 4);
     std::vector<char> h(total, 0);
+    if (nh) {
+        memcpy(&h[o_hvid], hv_id.data(), nh * 4);
+        memcpy(&h[o_hvdeg], hv_deg.data(), nh * 4);
+        memcpy(&h[o_hvptr], hv_ptr.data(), (nh + 1) * 4);
+        if (!hv_edge.empty()) memcpy(&h[o_hvedge], hv_edge.data(), hv_edge.size() * 4);
+    }
     memcpy(&h[o_jptr], jptr.data(), jptr.size() * 2);
     memcpy(&h[o_rowcol], row_col.data(), row_col.size() * 2);
     memcpy(&h[o_rowdeg], row_deg.data(), row_deg.size());
@@ -350,6 +379,12 @@ int Graph::upload() {
     d.vperm = (const uint16_t *)(b + o_vperm);
     d.vn_edge_s = (const uint32_t *)(b + o_vnedge_s);
     d.llr_s = (const double *)(b + o_llr_s);
+    hv = SwdHeavyDev{};
+    if (nh) {
+        hv.count = (int32_t)nh; hv.edges = (int32_t)hv_edge.size();
+        hv.id = (const int32_t *)(b + o_hvid); hv.deg = (const int32_t *)(b + o_hvdeg);
+        hv.ptr = (const int32_t *)(b + o_hvptr); hv.edge = (const uint32_t *)(b + o_hvedge);
+    }
     return 0;
 }
 

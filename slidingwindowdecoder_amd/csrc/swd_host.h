@@ -92,8 +92,14 @@ struct Graph {
     std::vector<int32_t> row_ptr, col_idx, col_ptr, row_idx;
     DevBuf dev;
     SwdGraphDev d{};
+    // side list of the heavy columns build() was given (swd_graph.h, SwdHeavyDev); empty otherwise
+    std::vector<int32_t> hv_id, hv_deg, hv_ptr;
+    std::vector<uint32_t> hv_edge;
+    SwdHeavyDev hv{};
 
-    int build(const swd_graph_desc *g);   // validates, fills host arrays (natural layout), computes rank
+    // validates, fills host arrays (natural layout), computes rank.  `heavy` (ascending column ids, at most SWD_MAX_HEAVY): these
+    // columns may have any weight; they leave the ELL tables (col_deg 0) for the side list
+    int build(const swd_graph_desc *g, const std::vector<int32_t> *heavy = nullptr);
     void optimize_layout(int pads);        // bank-conflict-aware layout with up to `pads` pad cells; build() first, upload() after
     long layout_cost(long *loads = nullptr, long *stores = nullptr) const;
     void fill_tables();

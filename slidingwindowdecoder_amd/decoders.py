@@ -378,7 +378,13 @@ class bpgd_decoder(bp_history_decoder):
 
 class bp4_osd:
     """Quaternary BP + OSD (reference: src/bp4_osd.pyx).  ``decode(sx, sz)`` returns the int64 array of
-    shape (2, n) the reference returns (row 0: X string, row 1: Z string)."""
+    shape (2, n) the reference returns (row 0: X string, row 1: Z string).
+
+    Columns of Hx / Hz have weight <= 10, except for up to 8 HEAVY columns (weight above 10 in Hx or in Hz, at any position, of
+    any weight): the last qubit of the cycle-assembled and EG codes of Misc.ipynb cells 6-8, H = (H1 | 1), touches every check.
+    Such a graph takes ``osd_order=-1`` only (``ValueError`` otherwise): ``camel_decode`` never runs OSD, and ``decode`` returns the
+    BP decisions of a shot that did not converge.  With ``osd_method="osd0"`` -- cell 8's spelling -- the reference resets the
+    order to 0; on a graph with heavy columns the caller's -1 stands.  ``heavy_columns`` reports what the decoder found."""
 
     def __init__(self, Hx, Hz, **kwargs):
         L = _lib.lib()
@@ -403,12 +409,15 @@ class bp4_osd:
         self.mx, self.mz, self.n = self._cx.m, self._cz.m, n
         method, order = _parse_osd_method(kwargs.get("osd_method", "osd_0"), kwargs.get("osd_order", 0))
         self.device = int(kwargs.get("device", 0))
+        asked = int(kwargs.get("osd_order", 0))
+        if method == 0 and asked < 0:
+            order = asked  # (swd_bp4_create resets it to 0 like the reference, except on a graph with heavy columns: include/swd.h)
         p = _lib.Bp4Params(int(kwargs.get("max_iter", 32)), float(kwargs.get("ms_scaling_factor", 1.0)), method, order)
         self._h = L.swd_bp4_create(C.byref(self._cx.desc), C.byref(self._cz.desc), self._px.ctypes.data,
                                    self._py.ctypes.data, self._pz.ctypes.data, C.byref(p), self.device)
         if not self._h:
             msg = _lib.last_error()
-            if "OSD order" in msg or "invalid" in msg or "blocklength" in msg:
+            if "OSD order" in msg or "invalid" in msg or "blocklength" in msg or "heavy columns" in msg or "column weight" in msg:
                 raise ValueError(msg)
             raise RuntimeError(f"swd_bp4_create failed: {msg}")
         i = [C.c_int32() for _ in range(5)]
@@ -469,6 +478,15 @@ class bp4_osd:
         if rc:
             raise RuntimeError(f"swd_bp4_decode_batch_dev failed: {_lib.last_error()}")
         return out, stats
+
+    @property
+    def heavy_columns(self):
+        """(count, largest weight) of the columns the decoder treats as heavy (include/swd.h swd_bp4_heavy_info); (0, 0) for a
+        graph within the column-weight bound, which takes the kernel forms ``last_form`` reports."""
+        c, d = C.c_int32(), C.c_int32()
+        if _lib.lib().swd_bp4_heavy_info(self._h, C.byref(c), C.byref(d)):
+            raise RuntimeError(f"swd_bp4_heavy_info failed: {_lib.last_error()}")
+        return c.value, d.value
 
     @property
     def last_form(self):
@@ -1397,7 +1415,9 @@ class CodeCapacityExperiment:
 
     ``decoder="bp4_osd"`` with ``method="decode"`` is /root/reference/Misc.ipynb cell 2, with ``method="camel_decode"`` cell 8:
     Pauli errors from ``channel_probs_x / _y / _z`` (``PauliSampler``), ``bp4_osd(Hx, Hz, **decoder_kwargs)``, and the criterion
-    ``(dz @ hz_perp.T).any() or (dx @ hx_perp.T).any()`` on the difference of estimate and error.
+    ``(dz @ hz_perp.T).any() or (dx @ hx_perp.T).any()`` on the difference of estimate and error.  Cell 8's own codes -- the
+    cycle-assembled and EG codes whose last qubit touches every check -- pass as ``(Hx, Hz)`` with ``osd_order=-1``
+    (``bp4_osd``: up to 8 heavy columns); the sampler and the accounting have no degree bound.
     ``decoder`` in ``osd_window``, ``bpgdg_decoder``, ``bpgd_decoder``, ``bp_history_decoder`` is the single-basis harness of
     /root/reference/src/simulation.py: errors Bernoulli(``channel_probs``) (``DemSampler`` with ``chk = Hx``), syndrome
     ``err @ hx.T``, ``decoder(Hx, **decoder_kwargs)``, criterion ``(d @ hz_perp.T).any()``.
