@@ -402,6 +402,15 @@ int swd_shot_account_dev(int device, int32_t B, int32_t W, const int32_t *shot_r
                          const int32_t *stats, uint64_t first_shot, int32_t *result, uint64_t *counters,
                          uint64_t *window_counters, uint64_t *failed, int32_t failed_cap, void *stream);
 
+/* Logical errors per GROUP of observables (the X and the Z logicals of a two-basis experiment, say): counters[g] is ADDED to with
+ * the number of shots b that have (shot_result[2b] ^ true_flips[b]) & masks[g] != 0, for g < num_groups <= SWD_MAX_OBSERVABLE_GROUPS.
+ * Flagged shots count only through their observables; a zero mask counts nothing; masks may overlap.  `masks` is a HOST array
+ * [num_groups], read before the call returns; shot_result, true_flips and counters (uint64[num_groups], zeroed by the caller) are
+ * device pointers.  One integer atomic per non-zero sum and workgroup, asynchronous on `stream`; B = 0 or no group does nothing. */
+#define SWD_MAX_OBSERVABLE_GROUPS 4
+int swd_group_account_dev(int device, int32_t B, const int32_t *shot_result, const uint32_t *true_flips, int32_t num_groups,
+                          const uint32_t *masks, uint64_t *counters, void *stream);
+
 /* ---- rolling DEM sampler: the detector rows of an experiment of any length, round block by round block ----------
  * A detector error model of R0 rounds whose columns are region-permuted (windows.plan_windows) falls into R0 + 1 column blocks,
  * one per row block of h = n_half detector rows: block b = columns [anchor_cols[b], anchor_cols[b + 1]) holds the faults that first

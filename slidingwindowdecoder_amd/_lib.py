@@ -125,13 +125,15 @@ SYMBOLS = [
     ("swd_css_account_destroy", None, [_vp]),
     ("swd_css_account_dev", C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
     ("swd_shot_account_dev", C.c_int, [C.c_int, _i32, _i32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _i32, _vp]),
-    ("swd_diag_occupy", C.c_int, [C.c_int, _i32, _i32, _i32, _i32, _vp]),
+    ("swd_group_account_dev", C.c_int, [C.c_int, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    ("swd_diag_occupy",C.c_int, [C.c_int, _i32, _i32, _i32, _i32, _vp]),
     ("swd_graph_layout", C.c_int, [C.POINTER(GraphDesc), _i32] + [_vp] * 9),
 ]
 
 STAT_WORDS = 8
 WINDOW_COUNTER_WORDS = 10  # include/swd.h: SWD_WINDOW_COUNTER_WORDS
-STREAM_PACKED, STREAM_NO_STATS = 1, 2
+MAX_OBSERVABLE_GROUPS = 4  # include/swd.h: SWD_MAX_OBSERVABLE_GROUPS
+STREAM_PACKED,STREAM_NO_STATS = 1, 2
 STREAM_NO_DEPENDENCY = C.c_void_p(-1).value  # include/swd.h: SWD_STREAM_NO_DEPENDENCY
 
 

@@ -111,3 +111,40 @@ def create_bivariate_bicycle_codes(l, m, A_x_pows, A_y_pows, B_x_pows, B_y_pows,
 
 def bb_code(N: int):
     return create_bivariate_bicycle_codes(*BB_PARAMS[N])
+
+
+def rep_code(d: int) -> np.ndarray:
+    """(d - 1) x d check matrix of the repetition code: check i compares bits i and i + 1
+    (/root/reference/src/codes_q.py:134-139)."""
+    d = int(d)
+    if d < 2:
+        raise ValueError("a repetition code needs d >= 2")
+    h = np.zeros((d - 1, d), dtype=np.uint8)
+    i = np.arange(d - 1)
+    h[i, i] = h[i, i + 1] = 1
+    return h
+
+
+def hypergraph_product(h1, h2, name=None) -> CSSCode:
+    """Hypergraph product of two classical check matrices h1 [m1, n1] and h2 [m2, n2] in the reference's convention
+    (/root/reference/src/codes_q.py:99-124): n1 n2 + m1 m2 qubits,
+
+        hx = [h1 (x) I_n2 | I_m1 (x) h2^T]        hz = [I_n1 (x) h2 | h1^T (x) I_m2]
+
+    with K = k1 k2 + k1t k2t for k = n - rank and kt = m - rank.  hx hz^T = h1 (x) h2^T + h1 (x) h2^T = 0.  Logicals come from
+    ``_logicals``, as for every ``CSSCode``."""
+    h1, h2 = np.asarray(h1, dtype=np.uint8) % 2, np.asarray(h2, dtype=np.uint8) % 2
+    (m1, n1), (m2, n2) = h1.shape, h2.shape
+    eye = lambda k: np.eye(k, dtype=np.uint8)  # noqa: E731
+    hx = np.hstack((np.kron(h1, eye(n2)), np.kron(eye(m1), h2.T)))
+    hz = np.hstack((np.kron(eye(n1), h2), np.kron(h1.T, eye(m2))))
+    code = CSSCode(hx, hz)
+    code.name = name or f"HP_n{code.N}_k{code.K}"
+    return code
+
+
+def create_surface_codes(d: int) -> CSSCode:
+    """The [[d^2 + (d - 1)^2, 1, d]] surface code: the hypergraph product of the repetition code with itself
+    (/root/reference/src/codes_q.py:141-144)."""
+    h = rep_code(d)
+    return hypergraph_product(h, h, name=f"Surface_n{d * d + (d - 1) * (d - 1)}_k1_d{d}")

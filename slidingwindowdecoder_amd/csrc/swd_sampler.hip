@@ -548,7 +548,57 @@ extern "C" int swd_shot_account_dev(int device, int32_t B, int32_t W, const int3
     return 0;
 }
 
-// ---- rolling DEM sampler (include/swd.h: swd_rolling_sampler_*) ------------------------------------------------------------------------
+// ---- memory experiments: logical errors per group of observables (include/swd.h: swd_group_account_dev) ------------------------------
+// "Any observable of a subset wrong" -- the X and the Z logical error rate of a two-basis experiment -- cannot be had from
+// shot_account_kernel's counts, so it is a launch of its own, made only when groups are asked for.  The same shape: one thread per
+// shot, the grid walks the shots, a ballot per mask, the workgroup sums in LDS and adds each non-zero sum to its counter once.
+namespace {
+
+struct GroupMasks { uint32_t m[SWD_MAX_OBSERVABLE_GROUPS]; };
+
+__global__ void __launch_bounds__(256) group_account_kernel(int B, int G, const int32_t *shot_result, const uint32_t *true_flips,
+                                                            GroupMasks masks, unsigned long long *counters) {
+    __shared__ uint32_t cnt[SWD_MAX_OBSERVABLE_GROUPS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < SWD_MAX_OBSERVABLE_GROUPS) cnt[tid] = 0;
+    __syncthreads();
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < B; base += (int64_t)gridDim.x * 256) {
+        const int64_t b = base + tid;
+        const uint32_t diff = b < B ? (uint32_t)shot_result[2 * b] ^ true_flips[b] : 0u; // (a shot past B has no wrong observable)
+        unsigned long long m = 0;
+#pragma unroll
+        for (int g = 0; g < SWD_MAX_OBSERVABLE_GROUPS; ++g) {
+            const unsigned long long mg = __ballot(diff & masks.m[g]);
+            if (lane == g) m = mg;
+        }
+        if (lane < G && m) atomicAdd(&cnt[lane], (uint32_t)__popcll(m));
+    }
+    __syncthreads();
+    if (tid < G && cnt[tid]) atomicAdd(&counters[tid], (unsigned long long)cnt[tid]);
+}
+
+} // namespace
+
+extern "C" int swd_group_account_dev(int device, int32_t B, const int32_t *shot_result, const uint32_t *true_flips, int32_t num_groups,
+                                     const uint32_t *masks, uint64_t *counters, void *stream) {
+    if (num_groups < 0 || num_groups > SWD_MAX_OBSERVABLE_GROUPS) {
+        set_error("group accounting: %d groups, at most %d", num_groups, SWD_MAX_OBSERVABLE_GROUPS);
+        return -1;
+    }
+    if (B <= 0 || num_groups == 0) return 0;
+    if (!shot_result || !true_flips || !masks || !counters) { set_error("null argument"); return -1; }
+    if (capacity_device_ok(device)) return -1;
+    SWD_HIP(hipSetDevice(device));
+    GroupMasks gm = {};
+    for (int g = 0; g < num_groups; ++g) gm.m[g] = masks[g];
+    const int64_t groups = ((int64_t)B + 255) / 256;
+    hipLaunchKernelGGL(group_account_kernel, dim3((unsigned)std::min<int64_t>(groups, kAccountGrid)), dim3(256), 0, (hipStream_t)stream, B,
+                       (int)num_groups, shot_result, true_flips, gm, (unsigned long long *)counters);
+    SWD_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- rolling DEM sampler (include/swd.h: swd_rolling_sampler_*)------------------------------------------------------------------------
 // The detector rows of an experiment of ANY number of rounds from a periodic template of R0 rounds, a few row blocks per call: what a
 // memory experiment on a rolling session feeds its windows with.  A call emits the rows of row blocks block0 .. block0 + nblocks - 1
 // and for that draws the column blocks block0 - 1 .. block0 + nblocks - 1 of the R-round model -- a contiguous range of its GLOBAL

@@ -1592,6 +1592,55 @@ def shot_account_device(shot_result, true_flips, stats=None, first_shot=0, resul
         raise RuntimeError(f"swd_shot_account_dev failed: {_lib.last_error()}")
 
 
+def _observable_groups(groups, num_obs):
+    """``observable_groups`` of the experiments' ``run`` -> (names, masks uint32 [G]) or None when there are none.  A group is a mask
+    (an int) or a list of observable indices.  ValueError: more groups than one launch counts, an observable the plan does not have."""
+    if not groups:
+        return None
+    if len(groups) > _lib.MAX_OBSERVABLE_GROUPS:
+        raise ValueError(f"at most {_lib.MAX_OBSERVABLE_GROUPS} observable groups, got {len(groups)}")
+    names, masks = [], []
+    for name, g in dict(groups).items():
+        if isinstance(g, (int, np.integer)):
+            mask = int(g)
+        else:
+            idx = [int(i) for i in g]
+            if any(i < 0 for i in idx):
+                raise ValueError(f"observable group {name!r}: negative observable index")
+            mask = 0
+            for i in idx:
+                mask |= 1 << i
+        if mask < 0 or mask >> int(num_obs):
+            raise ValueError(f"observable group {name!r} names an observable at or above the plan's {num_obs}")
+        names.append(name)
+        masks.append(mask)
+    return names, np.array(masks, dtype=np.uint32)
+
+
+def group_account_device(shot_result, true_flips, masks, counters, stream=None):
+    """swd_group_account_dev on torch CUDA tensors (include/swd.h): ``shot_result`` int32 [B, 2] and ``true_flips`` int32 [B] as for
+    ``shot_account_device``; ``masks``: up to 4 observable masks of 32 bits (host integers); ``counters`` int64 [len(masks)] is ADDED to
+    with the shots whose predicted and true flips differ inside each mask (the caller zeroes it).  Asynchronous on the current (or
+    given) torch stream."""
+    import torch
+    B, dev = int(shot_result.shape[0]), shot_result.device
+    for name, t in (("shot_result", shot_result), ("true_flips", true_flips), ("counters", counters)):
+        if not t.is_cuda or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous CUDA tensor on {dev}")
+    if tuple(shot_result.shape) != (B, 2) or shot_result.dtype != torch.int32 or tuple(true_flips.shape) != (B,) or true_flips.dtype != torch.int32:
+        raise ValueError("shot_result must be int32 [B, 2] and true_flips int32 [B]")
+    m = [int(x) for x in masks]
+    if len(m) > _lib.MAX_OBSERVABLE_GROUPS or any(x < 0 or x >> 32 for x in m):
+        raise ValueError(f"at most {_lib.MAX_OBSERVABLE_GROUPS} masks of 32 bits")
+    if counters.dtype != torch.int64 or counters.numel() != len(m):
+        raise ValueError("counters must be int64 [len(masks)]")
+    m = np.array(m, dtype=np.uint32)
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    if _lib.lib().swd_group_account_dev(dev.index, B, shot_result.data_ptr(), true_flips.data_ptr(), len(m), m.ctypes.data, counters.data_ptr(),
+                                        st.cuda_stream or None):
+        raise RuntimeError(f"swd_group_account_dev failed: {_lib.last_error()}")
+
+
 class MemoryResult:
     """Counters of a memory experiment under sliding windows -- what the reference's ``sliding_window_decoder`` prints
     (/root/reference/osd.py:181-194).  ``logical_errors``: shots that are flagged or whose predicted observable flips differ from
@@ -1600,10 +1649,11 @@ class MemoryResult:
     statistics: ``window_exit_classes`` [W, 8] (how many shots left window t through exit class c), ``window_not_converged`` [W]
     ("Window i, flagged Errors") and ``window_bp_iterations`` [W] (summed over the shots).  ``failed_shots``: sorted global numbers
     of shots with a logical error, at most ``keep_failures`` of the run; ``failed_shots_complete``: every such shot is in it (which
-    shots an incomplete list holds is not reproducible, and ``==`` then leaves the list out)."""
+    shots an incomplete list holds is not reproducible, and ``==`` then leaves the list out).  ``group_errors``: name -> shots with a
+    wrong observable inside that group of observables, for the ``observable_groups`` the run was asked for ({} when none)."""
 
     def __init__(self, shots, logical_errors, flagged, observable_mismatches, window_exit_classes=None, window_not_converged=None,
-                 window_bp_iterations=None, failed_shots=None, failed_shots_complete=None):
+                 window_bp_iterations=None, failed_shots=None, failed_shots_complete=None, group_errors=None):
         self.shots, self.logical_errors, self.flagged = int(shots), int(logical_errors), int(flagged)
         self.observable_mismatches = int(observable_mismatches)
         as64 = lambda a: None if a is None else np.array(a, dtype=np.int64)  # noqa: E731
@@ -1612,6 +1662,7 @@ class MemoryResult:
         self.failed_shots = np.sort(np.array([] if failed_shots is None else failed_shots, dtype=np.uint64))
         self.failed_shots_complete = (len(self.failed_shots) == self.logical_errors) if failed_shots_complete is None \
             else bool(failed_shots_complete)
+        self.group_errors = {k: int(v) for k, v in (group_errors or {}).items()}
 
     @property
     def ler(self):
@@ -1631,7 +1682,7 @@ class MemoryResult:
         return (self.shots, self.logical_errors, self.flagged, self.observable_mismatches, self.failed_shots_complete)
 
     def __eq__(self, other):
-        if not isinstance(other, MemoryResult) or self._fields() != other._fields():
+        if not isinstance(other, MemoryResult) or self._fields() != other._fields() or self.group_errors != other.group_errors:
             return False
         for a, b in ((self.window_exit_classes, other.window_exit_classes), (self.window_not_converged, other.window_not_converged),
                      (self.window_bp_iterations, other.window_bp_iterations)):
@@ -1645,16 +1696,21 @@ class MemoryResult:
         """counters of two runs over disjoint shots (batches of a run, ranks that shard with ``first_shot``)"""
         if not isinstance(other, MemoryResult):
             return NotImplemented
+        if set(self.group_errors) != set(other.group_errors):
+            raise ValueError(f"results with observable groups {sorted(self.group_errors)} and {sorted(other.group_errors)} do not add")
         win = [None if a is None or b is None else a + b for a, b in
                ((self.window_exit_classes, other.window_exit_classes), (self.window_not_converged, other.window_not_converged),
                 (self.window_bp_iterations, other.window_bp_iterations))]
         return MemoryResult(self.shots + other.shots, self.logical_errors + other.logical_errors, self.flagged + other.flagged,
                             self.observable_mismatches + other.observable_mismatches, *win,
                             failed_shots=np.concatenate([self.failed_shots, other.failed_shots]),
-                            failed_shots_complete=self.failed_shots_complete and other.failed_shots_complete)
+                            failed_shots_complete=self.failed_shots_complete and other.failed_shots_complete,
+                            group_errors={k: v + other.group_errors[k] for k, v in self.group_errors.items()})
 
     def __repr__(self):
         s = "MemoryResult(shots={}, logical_errors={}, flagged={}, observable_mismatches={}".format(*self._fields()[:4])
+        if self.group_errors:
+            s += f", group_errors={self.group_errors}"
         if self.window_not_converged is not None:
             s += f", window_not_converged={self.window_not_converged.tolist()}"
         return s + f", failed_shots={len(self.failed_shots)}{'' if self.failed_shots_complete else ' (incomplete)'})"
@@ -1667,6 +1723,8 @@ class MemoryExperiment:
 
     ``plan``: a ``windows.WindowPlan`` with 1..32 observables that the one-launch pipeline takes; ``decoder`` and the keyword
     arguments are those of ``SlidingWindowDecoder``."""
+
+    observable_groups = None  # what ``run`` counts per group when it is not told (``phenomenological(basis="both")`` sets it)
 
     def __init__(self, plan, decoder="osd_window", device=0, **decoder_kwargs):
         num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
@@ -1691,6 +1749,22 @@ class MemoryExperiment:
         dem = bb_dem(code, A, B, p, num_repeat, z_basis=z_basis)
         return cls(plan_windows(dem.chk, dem.obs, dem.priors, N // 2, W, F, method, z_basis), decoder=decoder, **kw)
 
+    @classmethod
+    def phenomenological(cls, code_or_matrices, p, num_repeat, W, F, q=None, basis="z", noise="bitflip", decoder="osd_window", **kw):
+        """the memory experiment of ANY CSS code under phenomenological noise (``phenomenological.css_phenomenological_dem``): data
+        faults with probability ``p`` before each of ``num_repeat`` rounds and before the final exact one, measurement faults with
+        probability ``q`` (``None``: ``p``).  ``code_or_matrices``: a ``codes.CSSCode``, or a pair ``(H, logicals)`` where there is none.
+        The plan is ``plan_windows(..., n_half=<detectors per round>, method=0)``: the generic windows (``method=1`` hard-codes the BB
+        circuit's column offsets), which end in the identity block of the last round's measurement faults by themselves.
+        ``basis="both"`` counts the Z and the X logical errors apart by default: ``observable_groups = {"z": the first k
+        observables, "x": the last k}``."""
+        from .phenomenological import experiment_model
+        from .windows import plan_windows
+        dem, n_half, groups = experiment_model(code_or_matrices, p, num_repeat, q, basis, noise)
+        exp = cls(plan_windows(dem.chk, dem.obs, dem.priors, n_half, W, F, method=0), decoder=decoder, **kw)
+        exp.observable_groups = groups
+        return exp
+
     def close(self):
         if getattr(self, "_stream", None) is not None:
             self._stream.close()
@@ -1714,7 +1788,8 @@ class MemoryExperiment:
                       stats=torch.empty((cap, self.W, _lib.STAT_WORDS), dtype=i32, device=dev) if window_stats or ln["stats"] is not None else None)
         return ln
 
-    def _enqueue(self, ln, B, seed, first_shot, streamed, window_stats, counters, window_counters, failed):
+    def _enqueue(self, ln, B, seed, first_shot, streamed, window_stats, counters, window_counters, failed, groups=None):
+        """``groups``: (masks, counters int64 [len(masks)]) or None"""
         st, d = ln["stream"], self.decoder
         det, total, shot, stats = ln["det"][:B], ln["total"][:B], ln["shot_result"][:B], ln["stats"][:B] if window_stats else None
         if _lib.lib().swd_sampler_sample_dev(self.sampler._h, B, int(seed), int(first_shot), det.data_ptr(), 0, ln["flips"].data_ptr(),
@@ -1726,8 +1801,19 @@ class MemoryExperiment:
         else:
             d.decode_device(det, total=total, stats=stats, shot_result=shot, stream=st, want_stats=window_stats, want_min_pm=False)
         shot_account_device(shot, ln["flips"][:B], stats, first_shot, ln["result"], counters, window_counters, failed, stream=st)
+        if groups is not None:
+            group_account_device(shot, ln["flips"][:B], groups[0], groups[1], stream=st)
 
-    def run(self, shots, batch=4096, seed=20240318, first_shot=0, lanes=2, max_errors=None, keep_failures=0, window_stats=True):
+    def _groups(self, observable_groups, dev):
+        """-> (names, (masks, zeroed device counters)) of ``observable_groups`` (None: the experiment's own), or (None, None)"""
+        import torch
+        g = _observable_groups(self.observable_groups if observable_groups is None else observable_groups, self.plan.obs.shape[0])
+        if g is None:
+            return None, None
+        return g[0], (g[1], torch.zeros((len(g[1]),), dtype=torch.int64, device=dev))
+
+    def run(self, shots, batch=4096, seed=20240318, first_shot=0, lanes=2, max_errors=None, keep_failures=0, window_stats=True,
+            observable_groups=None):
         """``shots`` shots numbered ``first_shot ..`` in batches of ``batch``.  ``lanes=2``: batch j goes to lane ``j & 1`` of one
         ``SlidingWindowStream``, each lane with a torch stream and buffers of its own, so that two batches are in flight;
         ``lanes=1``: ``decode_device`` launches on one stream.  The host reads the counters once at the end; the result is a pure
@@ -1735,12 +1821,15 @@ class MemoryExperiment:
         round of lanes and the run stops once ``logical_errors >= max_errors``: it stops at batch granularity -- whole rounds of
         ``lanes`` batches -- so ``result.shots`` tells how many shots were run and the count may overshoot ``max_errors``.
         ``keep_failures``: how many numbers of failing shots to bring back; ``window_stats=False`` leaves the per-window records
-        out (the window loop then writes none).  -> ``MemoryResult``."""
+        out (the window loop then writes none).  ``observable_groups``: name -> observable mask or list of observable indices, at
+        most 4; ``result.group_errors[name]`` then counts the shots with a wrong observable inside the group, in one more small launch
+        per batch (none without groups; ``{}`` switches the experiment's own groups off).  -> ``MemoryResult``."""
         import torch
         shots, batch, lanes, keep = int(shots), int(batch), int(lanes), int(keep_failures)
         if shots < 0 or batch <= 0 or lanes not in (1, 2) or keep < 0:
             raise ValueError("shots >= 0, batch > 0, lanes 1 or 2 (a stream object has two), keep_failures >= 0")
         dev = torch.device("cuda", self.device)
+        gnames, groups = self._groups(observable_groups, dev)
         cap = max(1, min(batch, shots))
         if lanes == 2 and (self._stream is None or self._stream.max_shots < cap):
             for ln in self._lanes:
@@ -1755,7 +1844,7 @@ class MemoryExperiment:
         while start < shots:
             B = min(batch, shots - start)
             ln = self._lane(k % lanes, cap, window_stats)
-            self._enqueue(ln, B, seed, first_shot + start, lanes == 2, window_stats, counters, wc, failed)
+            self._enqueue(ln, B, seed, first_shot + start, lanes == 2, window_stats, counters, wc, failed, groups)
             start, k = start + B, k + 1
             if max_errors is not None and k % lanes == 0:
                 for l2 in self._lanes[:lanes]:
@@ -1769,21 +1858,29 @@ class MemoryExperiment:
         w = wc.cpu().numpy() if wc is not None else None
         kept = failed.cpu().numpy().view(np.uint64) if failed is not None else np.zeros(1, np.uint64)
         return MemoryResult(c[0], c[1], c[2], c[3], *((w[:, :8], w[:, 8], w[:, 9]) if w is not None else (None, None, None)),
-                            failed_shots=kept[1:1 + min(int(kept[0]), keep)], failed_shots_complete=int(c[1]) <= keep)
+                            failed_shots=kept[1:1 + min(int(kept[0]), keep)], failed_shots_complete=int(c[1]) <= keep,
+                            group_errors=dict(zip(gnames, groups[1].cpu().tolist())) if groups is not None else None)
 
-    def run_batch(self, B, seed=20240318, first_shot=0):
+    def run_batch(self, B, seed=20240318, first_shot=0, observable_groups=None):
         """One batch with the per-shot arrays on the host (tests and debugging): dict with ``det`` [B, num_det], ``true_flips`` uint32
         [B], ``total`` [B, num_col], ``stats`` [B, W, 8], ``shot_result`` [B, 2] and ``result`` (the words of include/swd.h: bit 0
-        logical error, bit 1 flagged, bit 2 observable mismatch)."""
+        logical error, bit 1 flagged, bit 2 observable mismatch); with ``observable_groups`` (as in ``run``) also ``group_errors``."""
+        import torch
         B = int(B)
         if B <= 0:
             raise ValueError("B > 0")
+        dev = torch.device("cuda", self.device)
+        gnames, groups = self._groups(observable_groups, dev)
+        if groups is not None:
+            torch.cuda.current_stream(dev).synchronize()  # the lane adds into zeroed counters
         ln = self._lane(0, B, True)
-        self._enqueue(ln, B, seed, int(first_shot), False, True, None, None, None)
+        self._enqueue(ln, B, seed, int(first_shot), False, True, None, None, None, groups)
         ln["stream"].synchronize()
         self.decoder.check_status()
         out = {key: ln[key][:B].cpu().numpy() for key in ("det", "total", "stats", "shot_result", "result")}
         out["true_flips"] = ln["flips"][:B].cpu().numpy().view(np.uint32)
+        if groups is not None:
+            out["group_errors"] = dict(zip(gnames, groups[1].cpu().tolist()))
         return out
 
 
@@ -1925,7 +2022,7 @@ class RollingMemoryResult(MemoryResult):
         s = MemoryResult.__add__(self, other)
         return RollingMemoryResult(self.rounds, self.windows_per_shot, s.shots, s.logical_errors, s.flagged, s.observable_mismatches,
                                    s.window_exit_classes, s.window_not_converged, s.window_bp_iterations, failed_shots=s.failed_shots,
-                                   failed_shots_complete=s.failed_shots_complete)
+                                   failed_shots_complete=s.failed_shots_complete, group_errors=s.group_errors)
 
     def __repr__(self):
         return "Rolling" + super().__repr__()[:-1] + f", rounds={self.rounds})"
@@ -1939,6 +2036,9 @@ class RollingMemoryExperiment:
     ``MemoryExperiment(plan_windows(rounds)).run`` for the same seed and shot numbers, the per-window counts reduced to head / body
     / tail.  ``template_plan``: a ``windows.WindowPlan`` with 1..32 observables that the one-launch pipeline takes and
     ``windows.rolling_template`` accepts; it serves ``rounds = R0 (mod F)``, ``rounds >= min_rounds``."""
+
+    observable_groups = None  # as in ``MemoryExperiment``
+    _groups = MemoryExperiment._groups
 
     def __init__(self, template_plan, decoder="osd_window", device=0, **decoder_kwargs):
         from .windows import rolling_template
@@ -1985,6 +2085,30 @@ class RollingMemoryExperiment:
                          f"R0 <= {num_repeat}, periodic between its first and its last window, and {why}.  Use MemoryExperiment.bb for "
                          f"an experiment this short")
 
+    @classmethod
+    def phenomenological(cls, code_or_matrices, p, num_repeat, W, F, q=None, basis="z", noise="bitflip", decoder="osd_window", **kw):
+        """``MemoryExperiment.phenomenological`` for experiments of any length, built as ``bb`` builds its own: on the SMALLEST
+        template that serves ``num_repeat`` -- the model of the least ``R0 = num_repeat (mod F)``, ``R0 <= num_repeat``, that
+        ``rolling_template`` accepts.  ``run()`` then defaults to ``num_repeat`` rounds."""
+        from .phenomenological import experiment_model
+        from .windows import plan_windows, rolling_template
+        num_repeat, why = int(num_repeat), "none was tried"
+        R0 = W + (num_repeat - W) % F
+        while R0 <= num_repeat:
+            dem, n_half, groups = experiment_model(code_or_matrices, p, R0, q, basis, noise)
+            plan = plan_windows(dem.chk, dem.obs, dem.priors, n_half, W, F, method=0)
+            try:
+                rolling_template(plan)
+            except ValueError as e:
+                why, R0 = f"R0 = {R0}: {e}", R0 + F
+                continue
+            exp = cls(plan, decoder=decoder, **kw)
+            exp.rounds, exp.observable_groups = num_repeat, groups
+            return exp
+        raise ValueError(f"no rolling template serves {num_repeat} rounds with (W, F) = ({W}, {F}): it needs R0 = {num_repeat} (mod {F}), "
+                         f"R0 <= {num_repeat}, periodic between its first and its last window, and {why}.  Use "
+                         f"MemoryExperiment.phenomenological for an experiment this short")
+
     def close(self):
         for ln in getattr(self, "_lanes", []):
             ln["stream"].synchronize()
@@ -2018,8 +2142,10 @@ class RollingMemoryExperiment:
                       result=torch.empty((cap,), dtype=i32, device=dev), stats=torch.empty((cap, _lib.STAT_WORDS), dtype=i32, device=dev))
         return ln
 
-    def _enqueue(self, ln, B, rounds, sched, seed, first_shot, window_stats, counters, window_counters, failed, det=None, stats_all=None):
-        """``det`` [B, (rounds + 1) * n_half] / ``stats_all`` [windows, B, 8]: run_batch's own arrays, written instead of the lane's"""
+    def _enqueue(self, ln, B, rounds, sched, seed, first_shot, window_stats, counters, window_counters, failed, det=None, stats_all=None,
+                 groups=None):
+        """``det`` [B, (rounds + 1) * n_half] / ``stats_all`` [windows, B, 8]: run_batch's own arrays, written instead of the lane's;
+        ``groups``: (masks, counters int64 [len(masks)]) or None"""
         import torch
         L, h, ses = _lib.lib(), self.template.n_half, ln["session"]
         sp_ = ln["stream"].cuda_stream
@@ -2053,18 +2179,21 @@ class RollingMemoryExperiment:
                                       window_counters[2].data_ptr() if wins else None, failed.data_ptr() if failed is not None else None,
                                       failed.numel() - 1 if failed is not None else 0, sp_):
                 raise RuntimeError(f"swd_shot_account_dev failed: {_lib.last_error()}")
+            if groups is not None:
+                group_account_device(shot[:B], flips[:B], groups[0], groups[1], stream=ln["stream"])
 
     def _schedule(self, rounds):
         from .windows import rolling_schedule
         rounds = self.rounds if rounds is None else int(rounds)
         return rounds, rolling_schedule(self.template, rounds)  # ValueError names the lengths served
 
-    def run(self, shots, rounds=None, batch=4096, seed=20240318, first_shot=0, lanes=2, max_errors=None, keep_failures=0, window_stats=True):
+    def run(self, shots, rounds=None, batch=4096, seed=20240318, first_shot=0, lanes=2, max_errors=None, keep_failures=0, window_stats=True,
+            observable_groups=None):
         """``shots`` shots numbered ``first_shot ..`` of the experiment of ``rounds`` syndrome rounds (default: the template's, or what
         ``bb`` was asked for) in batches of ``batch``; batch j goes to lane ``j % lanes``, each lane a torch stream, a
         ``RollingSession`` and buffers of its own -- ``[batch, rows of one step]``, whatever ``rounds``.  The host reads the counters
         once at the end; the result is a pure function of (seed, first_shot, shots, rounds), whatever ``batch`` and ``lanes``.
-        ``max_errors``, ``keep_failures`` and ``window_stats`` as in ``MemoryExperiment.run``.  ValueError, before anything is
+        ``max_errors``, ``keep_failures``, ``window_stats`` and ``observable_groups`` as in ``MemoryExperiment.run``.  ValueError, before anything is
         launched, when the template does not serve ``rounds``.  -> ``RollingMemoryResult``."""
         import torch
         shots, batch, lanes, keep = int(shots), int(batch), int(lanes), int(keep_failures)
@@ -2073,6 +2202,7 @@ class RollingMemoryExperiment:
         rounds, sched = self._schedule(rounds)
         dev = torch.device("cuda", self.device)
         cap = max(1, min(batch, shots))
+        gnames, groups = self._groups(observable_groups, dev)
         counters = torch.zeros((4,), dtype=torch.int64, device=dev)
         wc = torch.zeros((3, _lib.WINDOW_COUNTER_WORDS), dtype=torch.int64, device=dev) if window_stats else None
         failed = torch.zeros((1 + keep,), dtype=torch.int64, device=dev) if keep else None
@@ -2080,7 +2210,8 @@ class RollingMemoryExperiment:
         start, k = 0, 0
         while start < shots:
             B = min(batch, shots - start)
-            self._enqueue(self._lane(k % lanes, cap), B, rounds, sched, seed, first_shot + start, window_stats, counters, wc, failed)
+            self._enqueue(self._lane(k % lanes, cap), B, rounds, sched, seed, first_shot + start, window_stats, counters, wc, failed,
+                          groups=groups)
             start, k = start + B, k + 1
             if max_errors is not None and k % lanes == 0:
                 for l2 in self._lanes[:lanes]:
@@ -2094,26 +2225,33 @@ class RollingMemoryExperiment:
         w = wc.cpu().numpy() if wc is not None else None
         kept = failed.cpu().numpy().view(np.uint64) if failed is not None else np.zeros(1, np.uint64)
         return RollingMemoryResult(rounds, len(sched), c[0], c[1], c[2], c[3], *((w[:, :8], w[:, 8], w[:, 9]) if w is not None else (None, None, None)),
-                                   failed_shots=kept[1:1 + min(int(kept[0]), keep)], failed_shots_complete=int(c[1]) <= keep)
+                                   failed_shots=kept[1:1 + min(int(kept[0]), keep)], failed_shots_complete=int(c[1]) <= keep,
+                                   group_errors=dict(zip(gnames, groups[1].cpu().tolist())) if groups is not None else None)
 
-    def run_batch(self, B, rounds=None, seed=20240318, first_shot=0):
+    def run_batch(self, B, rounds=None, seed=20240318, first_shot=0, observable_groups=None):
         """One batch with the per-shot arrays on the host (tests and debugging; unlike ``run`` it holds the whole experiment's rows):
         dict with ``det`` [B, (rounds + 1) * n_half], ``true_flips`` uint32 [B], ``stats`` [B, windows, 8], ``shot_result`` [B, 2] and
-        ``result`` (the words of include/swd.h: bit 0 logical error, bit 1 flagged, bit 2 observable mismatch)."""
+        ``result`` (the words of include/swd.h: bit 0 logical error, bit 1 flagged, bit 2 observable mismatch); with
+        ``observable_groups`` (as in ``run``) also ``group_errors``."""
         import torch
         B = int(B)
         if B <= 0:
             raise ValueError("B > 0")
         rounds, sched = self._schedule(rounds)
         dev = torch.device("cuda", self.device)
+        gnames, groups = self._groups(observable_groups, dev)
+        if groups is not None:
+            torch.cuda.current_stream(dev).synchronize()  # the lane adds into zeroed counters
         ln = self._lane(0, B)
         with torch.cuda.stream(ln["stream"]):
             det = torch.empty((B, (rounds + 1) * self.template.n_half), dtype=torch.uint8, device=dev)
             stats = torch.empty((len(sched), B, _lib.STAT_WORDS), dtype=torch.int32, device=dev)
-        self._enqueue(ln, B, rounds, sched, seed, int(first_shot), True, None, None, None, det=det, stats_all=stats)
+        self._enqueue(ln, B, rounds, sched, seed, int(first_shot), True, None, None, None, det=det, stats_all=stats, groups=groups)
         ln["stream"].synchronize()
         self.decoder.check_status()
         out = {key: ln[key][:B].cpu().numpy() for key in ("shot_result", "result")}
+        if groups is not None:
+            out["group_errors"] = dict(zip(gnames, groups[1].cpu().tolist()))
         out.update(det=det.cpu().numpy(), stats=np.ascontiguousarray(stats.cpu().numpy().transpose(1, 0, 2)),
                    true_flips=ln["flips"][:B].cpu().numpy().view(np.uint32))
         return out
