@@ -570,6 +570,24 @@ int swd_diag_occupy(int device, int32_t blocks, int32_t threads, int32_t lds_byt
 int swd_graph_layout(const swd_graph_desc *g, int32_t pads, int32_t *info, uint16_t *jptr, uint16_t *row_col, uint16_t *perm,
                      uint16_t *iperm, uint8_t *row_deg, uint32_t *vn_edge, uint32_t *vn_edge_s, uint16_t *vperm);
 
+/* Depth-profiled node pass (csrc/swd_variants.h, SWD_DEPTH_PROFILES): an osd_window handle or pipeline whose kernel variant declares
+ * a depth profile and whose window graphs all fit it serves the full graph's nodes in descending-degree order, a fixed number of
+ * edge positions per row of the register cache; every other handle keeps the uniform pass over the variant's column-weight bound.
+ * Both compute the same results.  1: profiled, 0: uniform (the launches of such a handle that write a posterior history keep the
+ * uniform kernel).  Test hook: with SWD_UNIFORM_DEPTH set in the environment (to anything but 0) when a handle is created, the
+ * handle keeps the uniform form (A/B runs, tests), as SWD_NATURAL_LAYOUT keeps the natural message-slot layout. */
+int swd_osdw_node_depth(const swd_osdw *h);
+int swd_pipeline_node_depth(const swd_pipeline *pl);
+
+/* diagnostics, host only: the depth order of graph g and the layout a pipeline that launches a depth-profiled kernel of `nt` threads
+ * and `vf` cache rows of depths depth[vf] would build with up to `pads` pad cells (thread t serves the nodes at listed positions
+ * t, t + nt, ...; SWD_NATURAL_LAYOUT as above).  info[8] = { graph fits the profile, slots, D, listed-order model cost of the loads,
+ * of the stores, the natural layout's two costs in that model, pad cells used }; vdord [n] = the listed nodes (exact degree
+ * descending, stable in the column), vn_edge_d [D * n] / llr_d [n] = the tables in that order, vn_edge [D * n] / llr [n] = the final
+ * tables in column order; any array may be NULL. */
+int swd_graph_node_depth(const swd_graph_desc *g, int32_t pads, int32_t nt, int32_t vf, const int32_t *depth, int32_t *info,
+                         uint16_t *vdord, uint32_t *vn_edge_d, double *llr_d, uint32_t *vn_edge, double *llr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,9 @@ SYMBOLS = [
     ("swd_group_account_dev", C.c_int, [C.c_int, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     ("swd_diag_occupy",C.c_int, [C.c_int, _i32, _i32, _i32, _i32, _vp]),
     ("swd_graph_layout", C.c_int, [C.POINTER(GraphDesc), _i32] + [_vp] * 9),
+    ("swd_graph_node_depth", C.c_int, [C.POINTER(GraphDesc), _i32, _i32, _i32, _vp] + [_vp] * 6),
+    ("swd_osdw_node_depth", C.c_int, [_vp]),
+    ("swd_pipeline_node_depth", C.c_int, [_vp]),
 ]
 
 STAT_WORDS = 8

@@ -42,12 +42,13 @@ struct SwdGraphDev {
     const uint16_t *vn_row;  // [D*n]
     const uint8_t *col_deg;  // [n]
     const double *llr;       // [n]
-    // The full-graph variable-node pass in TIERS (round 5): the nodes listed by decreasing degree in steps of two (stable in the
-    // column index), so that the 64 nodes a wave serves in one cache row need the same number of message positions and the pass
-    // skips the rest -- vperm[i] = the i-th listed node, vn_edge_s / llr_s = vn_edge / llr in listed order (no dependent load).
-    const uint16_t *vperm;     // [n]
-    const uint32_t *vn_edge_s; // [D*n]
-    const double *llr_s;       // [n]
+    // The full-graph variable-node pass by DEPTH (swd_variants.h, SWD_DEPTH_PROFILES): the nodes listed by exact degree descending
+    // (stable in the column index), NT per cache row, so that row i of a profiled kernel walks depth[i] positions and no more --
+    // vdord[i] = the i-th listed node, vn_edge_d / llr_d = vn_edge / llr in that order (coalesced, no dependent load).
+    // (The host keeps the round-5 order in tiers of two, Graph::vperm / vn_edge_s, for swd_graph_layout only.)
+    const uint16_t *vdord;     // [n]
+    const uint32_t *vn_edge_d; // [D*n]
+    const double *llr_d;       // [n]
 };
 
 // Heavy columns (weight above what the ELL tables hold; asked for by swd_bp4_create only): a side list beside the tables above,

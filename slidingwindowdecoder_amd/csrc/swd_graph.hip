@@ -119,11 +119,29 @@ void Graph::fill_listed() {
         for (int k = 0; k < D; ++k) vn_edge_s[(size_t)k * n + i] = vn_edge[(size_t)k * n + vperm[i]];
 }
 
-// LDS-array cycles of one variable-node pass over the full graph, from the tables: thread t serves column t, edge index k, one
-// 8-byte cell per lane.  ds_read_b64 is served in aligned groups of 32 lanes, bank = cell mod 32; ds_write_b64 in aligned groups
+// The device's tables in depth order (swd_graph.h): vn_edge / llr permuted by vdord, after every fill_tables()
+void Graph::fill_depth() {
+    vn_edge_d.assign((size_t)std::max(D, 1) * n, SWD_PAD_EDGE);
+    llr_d.resize(n);
+    for (int i = 0; i < n; ++i) {
+        llr_d[i] = llr[vdord[i]];
+        for (int k = 0; k < D; ++k) vn_edge_d[(size_t)k * n + i] = vn_edge[(size_t)k * n + vdord[i]];
+    }
+}
+
+bool Graph::fits_depth(const int *depth, int vf, int nt) const {
+    if ((long)vf * nt < n) return false;
+    for (int i = 0; i < n; ++i)
+        if ((int)col_deg[vdord[i]] > depth[i / nt]) return false;
+    return true;
+}
+
+// LDS-array cycles of one variable-node pass over the full graph, from the tables: thread t serves column t (listed: the node at
+// position t of the depth order -- 32 resp. 16 consecutive listed positions make a group), edge index k, one 8-byte cell per lane.  ds_read_b64 is served in aligned groups of 32 lanes, bank = cell mod 32; ds_write_b64 in aligned groups
 // of 16 lanes, bank = cell mod 16.  A group costs the largest number of (distinct) cells on one bank.
-long Graph::layout_cost(long *loads, long *stores) const {
+long Graph::layout_cost(long *loads, long *stores, bool listed) const {
     long cl = 0, cs = 0;
+    const std::vector<uint32_t> &vn_edge = listed ? this->vn_edge_d : this->vn_edge; // (v below: the listed position)
     for (int k = 0; k < D; ++k)
         for (int v0 = 0; v0 < n; v0 += 16) {
             if ((v0 & 31) == 0) {
@@ -150,10 +168,12 @@ long Graph::layout_cost(long *loads, long *stores) const {
 // positions (the check pass takes two minima and a parity), which of several checks of one degree takes which lane, and up to
 // `pads` pad cells between consecutive diagonals.  Deterministic (no random choice), bounded work; keeps the natural layout when it
 // finds nothing better.
-void Graph::optimize_layout(int pads) {
+void Graph::optimize_layout(int pads, bool listed) {
+    const long nat = listed ? layout_cost(nullptr, nullptr, true) : cost_natural; // (the layout is the natural one here)
     if (pads < 0) pads = 0;
     if (E + pads > SWD_MAX_E) pads = SWD_MAX_E - E;
-    // per CSR edge: its check, and the load / store group of its (column, edge index inside the column)
+    // per CSR edge: its check, and the load / store group of its (column, edge index inside the column) -- listed: of the column's
+    // position in the depth order, the fourth freedom: which thread serves which node changes no result either
     std::vector<int> gl(E), gs(E), erow(E);
     {
         std::vector<int> fill(n, 0);
@@ -161,9 +181,10 @@ void Graph::optimize_layout(int pads) {
             for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
                 const int v = col_idx[e];
                 const int k = fill[v]++;
+                const int t = listed ? (int)vdpos[v] : v;
                 erow[e] = r;
-                gl[e] = (v >> 5) * D + k;
-                gs[e] = (v >> 4) * D + k;
+                gl[e] = (t >> 5) * D + k;
+                gs[e] = (t >> 4) * D + k;
             }
     }
     const int NGL = ((n + 31) >> 5) * D, NGS = ((n + 15) >> 4) * D;
@@ -233,12 +254,13 @@ void Graph::optimize_layout(int pads) {
     long cur = 0;
     for (int g = 0; g < NGL; ++g) { int mx = 0; for (int b = 0; b < 32; ++b) mx = std::max(mx, (int)hl[(size_t)g * 32 + b]); cur += mx; }
     for (int g = 0; g < NGS; ++g) { int mx = 0; for (int b = 0; b < 16; ++b) mx = std::max(mx, (int)hs[(size_t)g * 16 + b]); cur += mx; }
-    if (cur >= cost_natural) return; // nothing better than positions in column order without pads
+    if (cur >= nat) return; // nothing better than positions in column order without pads
     epos = pos; iperm = lane; dpad = pad;
     for (int r = 0; r < m; ++r) perm[iperm[r]] = (uint16_t)r; // (equal-degree lanes traded places: row_deg by lane is unchanged)
     fill_tables();
     fill_listed();
-    cost = layout_cost();
+    fill_depth();
+    cost = layout_cost(nullptr, nullptr, listed);
 }
 
 int Graph::build(const swd_graph_desc *g, const std::vector<int32_t> *heavy) {
@@ -316,9 +338,18 @@ int Graph::build(const swd_graph_desc *g, const std::vector<int32_t> *heavy) {
         std::vector<int> ord(n);
         for (int v = 0; v < n; ++v) ord[v] = v;
         std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return (ldeg[a] + 1) / 2 > (ldeg[b] + 1) / 2; });
-        vperm.resize(n); llr_s.resize(n);
-        for (int i = 0; i < n; ++i) { vperm[i] = (uint16_t)ord[i]; llr_s[i] = llr[ord[i]]; }
+        vperm.resize(n);
+        for (int i = 0; i < n; ++i) vperm[i] = (uint16_t)ord[i];
         fill_listed();
+    }
+    // depth order: exact degree descending, stable in the index (swd_graph.h)
+    {
+        std::vector<int> ord(n);
+        for (int v = 0; v < n; ++v) ord[v] = v;
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return ldeg[a] > ldeg[b]; });
+        vdord.resize(n); vdpos.resize(n);
+        for (int i = 0; i < n; ++i) { vdord[i] = (uint16_t)ord[i]; vdpos[ord[i]] = (uint16_t)i; }
+        fill_depth();
     }
     rank = gf2_rank(m, n, row_ptr, col_idx);
     wm = (m + 63) / 64;
@@ -336,10 +367,10 @@ int Graph::upload() {
     size_t o_vnrow = al(o_vnedge + vn_edge.size() * 4);
     size_t o_coldeg = al(o_vnrow + vn_row.size() * 2);
     size_t o_llr = al(o_coldeg + col_deg.size());
-    size_t o_vperm = al(o_llr + llr.size() * 8);
-    size_t o_vnedge_s = al(o_vperm + vperm.size() * 2);
-    size_t o_llr_s = al(o_vnedge_s + vn_edge_s.size() * 4);
-    size_t total = al(o_llr_s + llr_s.size() * 8);
+    size_t o_vdord = al(o_llr + llr.size() * 8);
+    size_t o_vnedge_d = al(o_vdord + vdord.size() * 2);
+    size_t o_llr_d = al(o_vnedge_d + vn_edge_d.size() * 4);
+    size_t total = al(o_llr_d + llr_d.size() * 8);
     // (the side list of heavy columns behind everything else, only when there is one: the other graphs' images are unchanged)
     const size_t nh = hv_id.size();
     const size_t o_hvid = total, o_hvdeg = al(o_hvid + nh * 4), o_hvptr = al(o_hvdeg + nh * 4), o_hvedge = al(o_hvptr + (nh + 1) * 4);
@@ -360,9 +391,9 @@ int Graph::upload() {
     memcpy(&h[o_vnrow], vn_row.data(), vn_row.size() * 2);
     memcpy(&h[o_coldeg], col_deg.data(), col_deg.size());
     memcpy(&h[o_llr], llr.data(), llr.size() * 8);
-    memcpy(&h[o_vperm], vperm.data(), vperm.size() * 2);
-    memcpy(&h[o_vnedge_s], vn_edge_s.data(), vn_edge_s.size() * 4);
-    memcpy(&h[o_llr_s], llr_s.data(), llr_s.size() * 8);
+    memcpy(&h[o_vdord], vdord.data(), vdord.size() * 2);
+    memcpy(&h[o_vnedge_d], vn_edge_d.data(), vn_edge_d.size() * 4);
+    memcpy(&h[o_llr_d], llr_d.data(), llr_d.size() * 8);
     if (dev.reserve(total)) return -1;
     SWD_HIP(hipMemcpy(dev.p, h.data(), total, hipMemcpyHostToDevice));
     char *b = (char *)dev.p;
@@ -376,9 +407,9 @@ int Graph::upload() {
     d.vn_row = (const uint16_t *)(b + o_vnrow);
     d.col_deg = (const uint8_t *)(b + o_coldeg);
     d.llr = (const double *)(b + o_llr);
-    d.vperm = (const uint16_t *)(b + o_vperm);
-    d.vn_edge_s = (const uint32_t *)(b + o_vnedge_s);
-    d.llr_s = (const double *)(b + o_llr_s);
+    d.vdord = (const uint16_t *)(b + o_vdord);
+    d.vn_edge_d = (const uint32_t *)(b + o_vnedge_d);
+    d.llr_d = (const double *)(b + o_llr_d);
     hv = SwdHeavyDev{};
     if (nh) {
         hv.count = (int32_t)nh; hv.edges = (int32_t)hv_edge.size();
@@ -412,6 +443,30 @@ extern "C" int swd_graph_layout(const swd_graph_desc *g, int32_t pads, int32_t *
     if (vn_edge) memcpy(vn_edge, G.vn_edge.data(), G.vn_edge.size() * 4);
     if (vn_edge_s) memcpy(vn_edge_s, G.vn_edge_s.data(), G.vn_edge_s.size() * 4);
     if (vperm) memcpy(vperm, G.vperm.data(), G.vperm.size() * 2);
+    return 0;
+}
+
+extern "C" int swd_graph_node_depth(const swd_graph_desc *g, int32_t pads, int32_t nt, int32_t vf, const int32_t *depth, int32_t *info,
+                                    uint16_t *vdord, uint32_t *vn_edge_d, double *llr_d, uint32_t *vn_edge, double *llr) {
+    swd::Graph G;
+    if (G.build(g)) return -1;
+    if (nt <= 0 || vf <= 0 || vf > 64 || !depth) { swd::set_error("swd_graph_node_depth: nt, vf > 0, vf <= 64 and a depth per cache row"); return -1; }
+    int dep[64];
+    for (int i = 0; i < vf; ++i) dep[i] = depth[i];
+    const bool fits = G.fits_depth(dep, vf, nt);
+    long nl = 0, ns = 0, cl = 0, cs = 0;
+    G.layout_cost(&nl, &ns, true);
+    if (!swd::natural_layout_requested()) G.optimize_layout(pads, true);
+    G.layout_cost(&cl, &cs, true);
+    if (info) {
+        const int32_t v[8] = {fits ? 1 : 0, G.S, G.D, (int32_t)cl, (int32_t)cs, (int32_t)nl, (int32_t)ns, G.S - G.E};
+        memcpy(info, v, sizeof v);
+    }
+    if (vdord) memcpy(vdord, G.vdord.data(), G.vdord.size() * 2);
+    if (vn_edge_d) memcpy(vn_edge_d, G.vn_edge_d.data(), G.vn_edge_d.size() * 4);
+    if (llr_d) memcpy(llr_d, G.llr_d.data(), G.llr_d.size() * 8);
+    if (vn_edge) memcpy(vn_edge, G.vn_edge.data(), G.vn_edge.size() * 4);
+    if (llr) memcpy(llr, G.llr.data(), G.llr.size() * 8);
     return 0;
 }
 

@@ -87,7 +87,11 @@ struct Graph {
     std::vector<uint8_t> row_deg, col_deg;
     std::vector<uint32_t> vn_edge, vn_edge_s;
     std::vector<uint16_t> vperm;
-    std::vector<double> llr, llr_s;
+    std::vector<double> llr;
+    // depth order of the nodes (swd_graph.h): exact degree descending, stable in the column index; the tables the device gets
+    std::vector<uint16_t> vdord, vdpos; // [n] i-th listed node; listed position of column v
+    std::vector<uint32_t> vn_edge_d;    // [D*n]
+    std::vector<double> llr_d;          // [n]
     // original CSR/CSC kept for host-side use (rank, OSD-CS setup)
     std::vector<int32_t> row_ptr, col_idx, col_ptr, row_idx;
     DevBuf dev;
@@ -100,10 +104,15 @@ struct Graph {
     // validates, fills host arrays (natural layout), computes rank.  `heavy` (ascending column ids, at most SWD_MAX_HEAVY): these
     // columns may have any weight; they leave the ELL tables (col_deg 0) for the side list
     int build(const swd_graph_desc *g, const std::vector<int32_t> *heavy = nullptr);
-    void optimize_layout(int pads);        // bank-conflict-aware layout with up to `pads` pad cells; build() first, upload() after
-    long layout_cost(long *loads = nullptr, long *stores = nullptr) const;
+    // bank-conflict-aware layout with up to `pads` pad cells; build() first, upload() after.  listed: thread t serves the nodes at
+    // listed positions t, t + NT, ... of the depth order (profiled kernels) instead of columns t, t + NT, ...
+    void optimize_layout(int pads, bool listed = false);
+    long layout_cost(long *loads = nullptr, long *stores = nullptr, bool listed = false) const;
     void fill_tables();
     void fill_listed();
+    void fill_depth();
+    // every listed node i * nt .. (i + 1) * nt - 1 that exists has degree <= depth[i], for each of the vf cache rows
+    bool fits_depth(const int *depth, int vf, int nt) const;
     int upload();                          // hipMalloc + copy, fills d
 };
 

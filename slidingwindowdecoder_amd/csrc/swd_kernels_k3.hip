@@ -14,4 +14,8 @@ namespace swd {
 #define X(nt, vf, dm, kg, sf, k1, k2, k3) SWD_IF(k3, SWD_DEFINE_LAUNCHER(3, nt, vf, dm, kg, sf))
 SWD_VARIANTS(X)
 #undef X
+// ... and the depth-profiled instantiations (swd_variants.h, SWD_DEPTH_PROFILES)
+#define X(nt, vf, dm, kg, ...) SWD_DEFINE_DEPTH_LAUNCHER(nt, vf, dm, kg, __VA_ARGS__)
+SWD_DEPTH_PROFILES(X)
+#undef X
 } // namespace swd

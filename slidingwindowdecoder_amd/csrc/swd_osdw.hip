@@ -166,6 +166,23 @@ static const Variant kVariants[] = {
 #undef X
 };
 
+#define X(nt, vf, dm, kg, ...) SWD_DECLARE_DEPTH_LAUNCHER(nt, vf, dm, kg)
+SWD_DEPTH_PROFILES(X)
+#undef X
+static const DepthProfile kDepthProfiles[] = {
+#define X(nt, vf, dm, kg, ...) {nt, vf, dm, kg, {__VA_ARGS__}, SWD_DEPTH_LAUNCHER_NAME(nt, vf, dm, kg)},
+    SWD_DEPTH_PROFILES(X)
+#undef X
+    {0, 0, 0, 0, {0}, nullptr}};
+
+const DepthProfile *find_depth_profile(const Variant *v) {
+    for (const DepthProfile &p : kDepthProfiles)
+        if (p.launch_acc && v && !v->sf && v->launch_acc && p.nt == v->nt && p.vf == v->vf && p.dm == v->dm && p.kg == v->kg) return &p;
+    return nullptr;
+}
+
+bool uniform_depth_requested() { const char *e = getenv("SWD_UNIFORM_DEPTH"); return e && strcmp(e, "0") != 0; }
+
 #define X(nt, vf, dm, kg) SWD_DECLARE_LAUNCHER(5, nt, vf, dm, kg, 0) SWD_DECLARE_LAUNCHER(6, nt, vf, dm, kg, 0) SWD_DECLARE_LAUNCHER(8, nt, vf, dm, kg, 0) SWD_DECLARE_LAUNCHER(9, nt, vf, dm, kg, 0)
 SWD_BIG_VARIANTS(X)
 #undef X
@@ -252,7 +269,8 @@ int launch(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
     const bool acc = d->kind == 0 && d->variant->launch_acc && !a.hist && !a.P.record_all && !a.P.hist_is_state && !a.P.zero_hist &&
                      a.P.pre_iter >= 4 && a.P.pre_iter % 4 == 0 && a.P.post_iter >= 4 && a.P.post_iter % 4 == 0 && !getenv("SWD_NO_HACC");
     const bool ens = d->kind == 1 && d->gp.multi_thread == 1; // the reference's threaded ensemble: its own kernel (kind 7)
-    rc = (d->kind == 0) ? (acc ? d->variant->launch_acc(d, a, st) : d->variant->launch(d, a, st))
+    // (a plan whose graphs fit the variant's depth profile: the profiled kind-3 kernel; its kind-0 launches keep the uniform pass)
+    rc = (d->kind == 0) ? (acc ? (d->depth ? d->depth->launch_acc(d, a, st) : d->variant->launch_acc(d, a, st)) : d->variant->launch(d, a, st))
                         : (ens ? d->variant->launch_ens(d, a, st) : (par ? d->variant->launch_par(d, a, st) : d->variant->launch_gdg(d, a, st)));
     if (rc) return rc;
     SWD_HIP(hipEventRecord(sl.done, st));
@@ -354,6 +372,12 @@ extern "C" int swd_osdw_info(const swd_osdw *h, int32_t *m, int32_t *n, int32_t 
     if (rank) *rank = w.g->rank;
     return 0;
 }
+
+extern "C" int swd_osdw_node_depth(const swd_osdw *h) {
+    const Plan *d = (const Plan *)h;
+    return (d && !d->huge && d->depth) ? 1 : 0;
+}
+extern "C" int swd_pipeline_node_depth(const swd_pipeline *h) { return swd_osdw_node_depth((const swd_osdw *)h); }
 
 extern "C" int swd_osdw_set_timing(swd_osdw *h, int32_t on) {
     Plan *d = (Plan *)h;

@@ -336,6 +336,25 @@ __device__ __forceinline__ void wave_fence() {
 // Two offsets per register, unpacked where they are used.  SH = 0: byte offsets (kernels of up to 256 threads, whose LDS offsets fit
 // 16 bits, PB: one parity byte per check); SH = 3: slot numbers, shifted where they are used (the 1024-thread osd_window
 // kernels: fewer registers in their 128-VGPR budget, classic parity words).
+// Depth profile of the full-graph node pass (swd_variants.h, SWD_DEPTH_PROFILES): cache row i holds the listed entry vtid + i * NT of
+// the graph's depth order (SwdGraphDev::vdord) and walks depth(i) edge positions, a compile-time constant -- one loop body per row,
+// each no longer than the uniform one.  An odd depth keeps the pair packing; the unused half is never read.  The node's number is
+// not kept in registers: the few places that need it read vdord.  SwdUniformDepth: every row walks DM positions of node vtid + i * NT.
+struct SwdUniformDepth {
+    static constexpr bool on = false;
+    static constexpr int rows = 0;
+    template <int DM> static constexpr int depth(int) { return DM; }
+};
+template <int... DS>
+struct SwdDepthProfile {
+    static constexpr bool on = true;
+    static constexpr int rows = sizeof...(DS);
+    template <int DM> static constexpr int depth(int i) {
+        constexpr int d[] = {DS...};
+        return d[i] < DM ? d[i] : DM;
+    }
+};
+
 template <int VF, int DM, int SH = 0, bool PB = true>
 struct VnCacheP {
     static_assert(DM % 2 == 0, "edge offsets are packed in pairs");
@@ -346,9 +365,10 @@ struct VnCacheP {
     double llr[VF];
     uint32_t edp[VF][DM / 2];
     __device__ __forceinline__ void set_ed(int i, int k, uint32_t v) { v >>= SH; edp[i][k >> 1] = (k & 1) ? ((edp[i][k >> 1] & 0xFFFFu) | (v << 16)) : ((edp[i][k >> 1] & 0xFFFF0000u) | v); }
+    template <int KD = DM> // (the first KD positions, in whole pairs)
     __device__ __forceinline__ void get_ed(int i, uint32_t (&ad)[DM]) const {
 #pragma unroll
-        for (int k = 0; k < DM; k += 2) {
+        for (int k = 0; k < KD; k += 2) {
             uint32_t w = edp[i][k >> 1];
             asm volatile("" : "+v"(w));
             ad[k] = (w & 0xFFFFu) << SH; ad[k + 1] = (w >> 16) << SH;
@@ -408,6 +428,55 @@ __device__ __forceinline__ void vn_cache_pack(const SwdGraphDev &g, const Lds &s
             }
         }
     }
+}
+
+// f(integral_constant<int, I>) for I = 0 .. N - 1: the rows of a register cache with the row number as a compile-time constant
+template <int I, int N, class F>
+__device__ __forceinline__ void swd_rows(F &&f) {
+    if constexpr (I < N) { f(std::integral_constant<int, I>{}); swd_rows<I + 1, N>(f); }
+}
+
+// The two halves for a depth profile PROF: entry idx is the idx-th node of the graph's depth order, read from the tables in that order;
+// row i asks for and packs its first PROF::depth(i) positions only (a plan launches a profiled kernel only on graphs that fit: no
+// node listed in row i has an edge beyond them).  The other positions of the cache do not exist for the profiled routines.
+template <class PROF, int NT, int VF, int DM>
+__device__ __forceinline__ void vn_cache_issue_depth(const SwdGraphDev &g, const Lds &s, VnRaw<NT, VF, DM> &r) {
+    const int n = g.n, D = g.D;
+    const uint32_t *et = g.vn_edge_d;
+    const double *lt = g.llr_d;
+    swd_rows<0, VF>([&](auto i_tag) {
+        constexpr int i = decltype(i_tag)::value, KD = PROF::template depth<DM>(i);
+        const int idx = s.vtid + i * NT;
+        const int v = (idx < n) ? idx : 0;
+        r.llr[i] = (n > 0) ? lt[v] : 0.0;
+#pragma unroll
+        for (int k = 0; k < KD; ++k) r.ev[i][k] = (n > 0) ? et[max(min(k, D - 1), 0) * n + v] : SWD_PAD_EDGE;
+    });
+}
+template <class PROF, int NT, int VF, int DM, int SH, bool PB>
+__device__ __forceinline__ void vn_cache_pack_depth(const SwdGraphDev &g, const Lds &s, const VnRaw<NT, VF, DM> &r, VnCacheP<VF, DM, SH, PB> &c) {
+    const int n = g.n, D = g.D;
+    const uint32_t dead = (uint32_t)swd_slot_zero<NT>(g) << 3;
+    swd_rows<0, VF>([&](auto i_tag) {
+        constexpr int i = decltype(i_tag)::value, KD = PROF::template depth<DM>(i), KD2 = (KD + 1) & ~1; // (whole pairs)
+        const int idx = s.vtid + i * NT;
+        const bool valid = idx < n;
+        c.llr[i] = valid ? r.llr[i] : 0.0;
+#pragma unroll
+        for (int k = 0; k < KD2; ++k) c.set_ed(i, k, dead);
+        constexpr int PS = VnCacheP<VF, DM, SH, PB>::par_shift;
+#pragma unroll
+        for (int k = 0; k < KD2 / 2; ++k) c.par[i][k] = ((uint32_t)g.m << PS) * 0x10001u;
+#pragma unroll
+        for (int k = 0; k < KD; ++k) {
+            const uint32_t e = r.ev[i][k];
+            if (valid && k < D && e != SWD_PAD_EDGE) {
+                c.set_ed(i, k, swd_edge_slot(e) << 3);
+                c.par[i][k >> 1] = (k & 1) ? ((c.par[i][k >> 1] & 0xFFFFu) | ((swd_edge_lane(e) << PS) << 16))
+                                           : ((c.par[i][k >> 1] & 0xFFFF0000u) | (swd_edge_lane(e) << PS));
+            }
+        }
+    });
 }
 
 // ALLEDGES (with !FULL): the listed nodes with every edge of theirs, whatever the state of the checks.
@@ -563,6 +632,17 @@ __device__ __forceinline__ void bp_init(Lds &s, const VnCacheP<VF, DM, SH, PB> &
 #pragma unroll
         for (int k = 0; k < DM; ++k) swd_msg_st<HYB>(s, ad[k], c.llr[i]); // dead positions land in Z_w (re-armed by bp_run)
     }
+}
+// ... for a depth profile: row i over its PROF::depth(i) positions
+template <class PROF, int VF, int DM, int SH, bool PB>
+__device__ __forceinline__ void bp_init_depth(Lds &s, const VnCacheP<VF, DM, SH, PB> &c) {
+    swd_rows<0, VF>([&](auto i_tag) {
+        constexpr int i = decltype(i_tag)::value, KD = PROF::template depth<DM>(i);
+        uint32_t ad[DM];
+        c.template get_ed<KD>(i, ad);
+#pragma unroll
+        for (int k = 0; k < KD; ++k) swd_msg_st<false>(s, ad[k], c.llr[i]);
+    });
 }
 
 
@@ -730,7 +810,9 @@ __device__ __forceinline__ void cn_assign(const SwdGraphDev &g, Lds &s, int *dhi
 // TBL (large-graph kernels, full graph): no register cache of the variable nodes -- a row's edge words and prior come from the graph's
 // tables (coalesced, L2-resident, shared by every workgroup), asked for one row ahead; nine rows of cache do not fit that kernel's 128
 // registers beside the check cache and came back from scratch, row by row, inside the iterations.
-template <int NT, int VF, int DM, int KG, bool FULL, bool SF = false, bool ACC = false, bool SPARSE = false, bool TIER = false, bool HYB = false, bool REC = false, bool TBL = false, int SH, bool PB>
+// PROF (a depth profile, full graph with the history sum in registers): cache row i is the listed entry vtid + i * NT of the graph's
+// depth order and its pass runs over PROF::depth(i) positions; the node's number comes from g.vdord where it is needed (hard_flush).
+template <int NT, int VF, int DM, int KG, bool FULL, bool SF = false, bool ACC = false, bool SPARSE = false, bool TIER = false, bool HYB = false, bool REC = false, bool TBL = false, class PROF = SwdUniformDepth, int SH, bool PB>
 __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParams &P, Lds &s, int max_iter, int nlive,
                       const VnCacheP<VF, DM, SH, PB> &c, const CnCacheP<KG, SH> &cn, double *hist_b, int &iters_done,
                       double alpha, bool force_unsat = false, double *hs = nullptr, double (*h4)[4] = nullptr, bool rec_early = false,
@@ -780,6 +862,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
 #define BPT(x)
 #endif
     static_assert(!TBL || (FULL && !TIER && !REC && !SPARSE && !PB), "table form: the full graph of the large-graph kernels");
+    static_assert(!PROF::on || (FULL && ACC && !SPARSE && !TIER && !HYB && !REC && !TBL && VF <= 32), "depth profiles: the full graph of the kind-3 kernels (no history stores, deferred hard decisions)");
     [[maybe_unused]] uint32_t tbe[3][DM]; // edge words of rows i, i + 1, i + 2 (asked for two rows ahead)
     [[maybe_unused]] double tbl[3];
     [[maybe_unused]] auto tb_addr = [&](int row, const uint32_t (&e)[DM], uint32_t (&ad_)[DM]) {
@@ -808,7 +891,8 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
                 if (i < nch) { // wave-uniform
                     const int idx = s.vtid + i * NT;
                     int v;
-                    if constexpr (!kNodeList) v = (idx < vcnt) ? idx : n; else v = vnode[i];
+                    if constexpr (PROF::on) v = (idx < vcnt) ? (int)g.vdord[idx] : n; // (read here, not held across the loop)
+                    else if constexpr (!kNodeList) v = (idx < vcnt) ? idx : n; else v = vnode[i];
                     ((bool *)s.hard)[v] = ((hdbits >> i) & 1u) != 0u;
                 }
         }
@@ -994,7 +1078,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
 #pragma unroll
                     for (int k = 0; k < KD; ++k) cc[k] = swd_msg_ld<HYB>(s, ad[k]);
                 } else {
-                    c.get_ed(i, ad);
+                    if constexpr (PROF::on) c.template get_ed<KD>(i, ad); else c.get_ed(i, ad);
                     if constexpr (REC) { // the check-to-bit message of edge k from the record of its check (lane in bits 0..9, position in bits 10..15)
 #pragma unroll
                         for (int k = 0; k < KD; ++k) {
@@ -1076,7 +1160,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
             if constexpr (i < VF) {
                 if (i < nch) { // wave-uniform
                     if constexpr (TIER) vn_tier(vn_tier, std::integral_constant<int, kTierStep>{}, i_tag, kcap[i]);
-                    else vn_one(std::integral_constant<int, DM>{}, i_tag);
+                    else vn_one(std::integral_constant<int, PROF::template depth<DM>(i)>{}, i_tag);
                 }
                 self(self, std::integral_constant<int, i + 1>{});
             }
@@ -2803,7 +2887,8 @@ __device__ __forceinline__ void lds_bind(Lds &s, char *smem, const SwdLdsLayout 
 // vraw (kernels that split the cache load): where the raw edge words and priors of the variable nodes go
 // want_pm (uniform over the launch): the caller gave min_pm a destination.  Without one the PRE and POST exits leave R.pm at 0 and skip
 // ordered_pm -- a scan, three barriers and a serial sum on one wave that nothing reads; the OSD exit needs the metric itself.
-template <int NT, int VF, int DM, int KG, bool SF, bool HACC, bool BIG = false>
+// PROF: depth profile of the full-graph phase (kind 3 only); the post phase keeps its own list and tiers
+template <int NT, int VF, int DM, int KG, bool SF, bool HACC, bool BIG = false, class PROF = SwdUniformDepth>
 __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLdsLayout &L, const SwdDecodeParams &P, Lds &s,
                               const uint8_t *synd, double *hist_b, uint8_t *osd0_b, uint8_t *bpdec_b, WinResult &R, const uint32_t *cn_map,
                               VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> &vraw, const bool want_pm) {
@@ -2830,7 +2915,8 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
         if (tid < m) { d_first = g.row_deg[tid]; p_first = g.perm[tid]; }
         if (tid <= g.K) j_first = g.jptr[tid];
         __builtin_amdgcn_sched_barrier(0); // (issued here)
-        vn_cache_issue<NT, VF, DM>(g, s, vraw);
+        if constexpr (PROF::on) vn_cache_issue_depth<PROF, NT, VF, DM>(g, s, vraw);
+        else vn_cache_issue<NT, VF, DM>(g, s, vraw);
     }
     // reset (osd_window.pyx:288-303)
     for (int l = tid; l < m; l += NT) {
@@ -2855,8 +2941,10 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     constexpr bool kRec = BIG && SWD_BIG_REC && !kTbl && !kSplitLoad;
     bool rec_on = false;
     if constexpr (kRec) rec_on = L.off_pmsg >= 0 && m <= 1023 && L.pmsg_bytes >= (m + 1) * 32 + 4096;
+    static_assert(!PROF::on || (kSplitLoad && HACC && !BIG && !SF && PROF::rows == VF), "depth profiles: the tuned kind-3 kernels, a depth per cache row");
     if constexpr (kSplitLoad) {
-        vn_cache_pack<NT, VF, DM>(g, s, vraw, vc);
+        if constexpr (PROF::on) vn_cache_pack_depth<PROF, NT, VF, DM>(g, s, vraw, vc);
+        else vn_cache_pack<NT, VF, DM>(g, s, vraw, vc);
     } else if constexpr (kTbl) { // (no cache)
     } else {
         if (kRec && rec_on) { if constexpr (kRec) vn_cache_load<NT, VF, DM, true, false, true>(g, s, n, vc); }
@@ -2890,6 +2978,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
         s.msg_alt = (char *)s.hard - L.off_hard + (L.off_pmsg >= 0 ? L.off_pmsg + rec_b : 0);
     }
     if constexpr (kTbl) bp_init_tbl<NT, VF, DM, kHyb>(g, s);
+    else if constexpr (PROF::on) bp_init_depth<PROF, VF, DM>(s, vc);
     else bp_init<VF, DM, kHyb>(s, vc);
 #ifdef SWD_INITPROF
     const long long ip3 = wall_clock64();
@@ -2920,7 +3009,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     if (kRec && rec_on) {
         if constexpr (kRec) R.conv = bp_run<NT, VF, DM, KG, true, SF, HACC, false, false, kHyb, true>(g, P, s, P.pre_iter, n, vc, cn, hist_b, it, P.alpha, false, hs);
     } else
-    R.conv = bp_run<NT, VF, DM, KG, true, SF, HACC, false, false, kHyb>(g, P, s, P.pre_iter, n, vc, cn, hist_b, it, P.alpha, false, hs);
+    R.conv = bp_run<NT, VF, DM, KG, true, SF, HACC, false, false, kHyb, false, false, PROF>(g, P, s, P.pre_iter, n, vc, cn, hist_b, it, P.alpha, false, hs);
     R.pre_it = it;
     R.t[2] = wall_clock64();
     if (R.conv) {
@@ -2944,7 +3033,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
 #pragma unroll
         for (int i = 0; i < VF; ++i) { // the keys come straight from the accumulators of the owning thread
             const int li = s.vtid + i * NT;
-            if (li < n) { const int v = li; key[v] = f2key(hs[i]); idx[v] = (uint16_t)v; }
+            if (li < n) { const int v = PROF::on ? (int)g.vdord[li] : li; key[v] = f2key(hs[i]); idx[v] = (uint16_t)v; } // (profiled: the li-th listed node)
         }
         for (int v = n + tid; v < L.npad; v += NT) { key[v] = ~0ull; idx[v] = 0xFFFF; }
     } else {
@@ -3459,7 +3548,7 @@ __global__ void __launch_bounds__(NT) shot_order_kernel(const uint32_t *wt, int 
     }
 }
 
-template <int NT, int VF, int DM, int KG, int KIND, bool SF = false, bool BIG = false, int VFP = VF>
+template <int NT, int VF, int DM, int KG, int KIND, bool SF = false, bool BIG = false, int VFP = VF, class PROF = SwdUniformDepth>
 __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT == 256 && KG <= 12 && (KIND == 0 || KIND == 3)) ? 3 : 2))) pipeline_kernel(const SwdPipeArgs a) {
     static_assert(NT == 64 || NT == 256 || NT == 1024, "workgroup sizes of swd_variants.h (the launch bounds and the sorted form know no other)");
     static_assert(!BIG || KIND == 0 || KIND == 3 || KIND == 1 || KIND == 7, "the HBM-resident scratch region exists for the osd_window kernels and for the guessing decoders' serial walk / ticket-scheduled ensemble");
@@ -3637,7 +3726,7 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
         } else if constexpr (KIND == 0 || KIND == 3) // 3: osd_window with the posterior history accumulated in registers (bp_run, ACC)
         {
             VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> vraw;
-            decode_window<NT, VF, DM, KG, SF, KIND == 3, BIG>(g, L, a.P, s, sdet + (w.row0 - dbase), hist_b, a.osd0 ? a.osd0 + (int64_t)b * g.n : nullptr,
+            decode_window<NT, VF, DM, KG, SF, KIND == 3, BIG, PROF>(g, L, a.P, s, sdet + (w.row0 - dbase), hist_b, a.osd0 ? a.osd0 + (int64_t)b * g.n : nullptr,
                                                          a.bp_dec ? a.bp_dec + (int64_t)b * g.n : nullptr, R, w.cn_map, vraw, a.min_pm != nullptr);
         }
         else {

@@ -105,6 +105,16 @@ struct Variant {
 const Variant *select_variant(const std::vector<WindowHost> &wins, int mmax, int nmax, int dm, int kmax, int kind);
 const Variant *select_big_variant(int mmax, int nmax, int dm, int kmax, int kind = 0); // graphs beyond one CU's LDS: scratch region in HBM
 bool split_map(const Graph &g, int nt, int cap, std::vector<uint32_t> *map);
+// Depth profile of a variant (swd_variants.h, SWD_DEPTH_PROFILES): the depth of each cache row of the full-graph node pass and the
+// launcher of the kind-3 kernel compiled for it.  A plan whose graphs all fit takes it (Plan::depth), any other the variant's own.
+struct DepthProfile {
+    int nt, vf, dm, kg;
+    int depth[16];
+    int (*launch_acc)(Plan *, const SwdPipeArgs &, hipStream_t);
+};
+const DepthProfile *find_depth_profile(const Variant *v);
+// SWD_UNIFORM_DEPTH in the environment (A/B runs, tests; read when a plan is created): plans keep the uniform node pass
+bool uniform_depth_requested();
 
 
 
@@ -139,6 +149,7 @@ struct Plan {
     DevBuf snap;
     int device = 0, nt = 256, vf = 7, dm = 8;
     const Variant *variant = nullptr;
+    const DepthProfile *depth = nullptr; // the kind-3 launches run the variant's depth-profiled kernel: every window graph fits it
     int num_det = 0, num_col = 0, nmax = 0, off_det = 0, lds_total = 0;
     bool post_depth2 = false;  // guessing decoders: every window keeps new_n <= 2 nt columns -> depth-2 cache for the shortened graph
     bool big = false;          // large graphs: the layouts' scratch region lives in HBM (big_stride bytes per workgroup)
@@ -287,7 +298,7 @@ struct Plan {
                     if (ok) break;
                 }
                 g->S = g->E;
-                g->optimize_layout(pads);
+                g->optimize_layout(pads, depth != nullptr); // (a profiled kernel serves the nodes by listed position: the model follows it)
             }
             for (auto &w : wins) { make_layout(*w.g, w.new_n, nt, kind, w.L); lmax = std::max(lmax, w.L.total); }
             off_det = align_up(lmax, 16) + 16;
@@ -371,6 +382,14 @@ struct Plan {
             break;
         }
         if (!variant) return -1;
+        // the depth-profiled form of the full-graph node pass: one kernel serves a launch, so every window graph must fit the profile
+        depth = nullptr;
+        if (kind == 0 && !big && !uniform_depth_requested()) {
+            const DepthProfile *dp = find_depth_profile(variant);
+            bool fit = dp != nullptr;
+            for (auto &w : wins) fit = fit && w.g->fits_depth(dp->depth, dp->vf, dp->nt);
+            if (fit) depth = dp;
+        }
         if (layout_graphs(lmax)) return -1;
         post_depth2 = kind != 0 && !getenv("SWD_GDG_NO_DEPTH2");
         for (auto &w : wins) post_depth2 = post_depth2 && w.new_n <= 2 * nt;
@@ -438,14 +457,14 @@ struct Plan {
 
 
 
-template <int NT, int VF, int DM, int KG, int KIND, bool SF = false, bool BIG = false, int VFP = VF>
+template <int NT, int VF, int DM, int KG, int KIND, bool SF = false, bool BIG = false, int VFP = VF, class PROF = SwdUniformDepth>
 int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
     SwdPipeArgs a = a0;
     static std::mutex fn_mu; // the attribute and the occupancy answer belong to the function, not to a decoder
     std::lock_guard<std::mutex> fn_lock(fn_mu);
     static int lds_limit[64] = {0}; // per device, monotone
     if (d->lds_total > lds_limit[d->device & 63]) {
-        SWD_HIP(hipFuncSetAttribute((const void *)pipeline_kernel<NT, VF, DM, KG, KIND, SF, BIG, VFP>, hipFuncAttributeMaxDynamicSharedMemorySize, d->lds_total));
+        SWD_HIP(hipFuncSetAttribute((const void *)pipeline_kernel<NT, VF, DM, KG, KIND, SF, BIG, VFP, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, d->lds_total));
         lds_limit[d->device & 63] = d->lds_total;
     }
     // persistent grid: as many workgroups as fit the device at once (they draw work units until none is left)
@@ -453,14 +472,14 @@ int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
     static int slots_lds[64] = {0};
     if (!slots[d->device & 63] || slots_lds[d->device & 63] != d->lds_total) {
         int per_cu = 0, cus = 0;
-        SWD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pipeline_kernel<NT, VF, DM, KG, KIND, SF, BIG, VFP>, NT, (size_t)d->lds_total));
+        SWD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pipeline_kernel<NT, VF, DM, KG, KIND, SF, BIG, VFP, PROF>, NT, (size_t)d->lds_total));
         SWD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d->device));
         // the occupancy API accepts 54 592 B of LDS for three workgroups per CU; the hardware placed a third one up to 53 552 B
         // and not at 54 032 B (scripts/residency_check.py): count LDS in granules of 1280 B
         while (per_cu > 1 && (long long)per_cu * align_up(d->lds_total, 1280) > 160 * 1024) --per_cu;
         slots[d->device & 63] = std::max(1, per_cu) * std::max(1, cus);
         slots_lds[d->device & 63] = d->lds_total;
-        if (getenv("SWD_DEBUG")) fprintf(stderr, "[swd] pipeline_kernel<%d,%d,%d,%d,%d>: %d workgroups per CU x %d CUs, %d B LDS\n", NT, VF, DM, KG, KIND, per_cu, cus, d->lds_total);
+        if (getenv("SWD_DEBUG")) fprintf(stderr, "[swd] pipeline_kernel<%d,%d,%d,%d,%d>%s: %d workgroups per CU x %d CUs, %d B LDS\n", NT, VF, DM, KG, KIND, PROF::on ? " depth profile" : "", per_cu, cus, d->lds_total);
     }
     const long long units = (long long)a.B * a.W;
     static const int grid_pct = getenv("SWD_GRID_PCT") ? std::max(1, atoi(getenv("SWD_GRID_PCT"))) : 100; // diagnostics: how does the launch scale with the workgroups per CU?
@@ -601,7 +620,7 @@ int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
         hipLaunchKernelGGL((shot_order_kernel<1024>), dim3(1), dim3(1024), 0, st, (const uint32_t *)wo, a.B, wo + a.B);
         a.order = wo + a.B;
     }
-    hipLaunchKernelGGL((pipeline_kernel<NT, VF, DM, KG, KIND, SF, BIG, VFP>), dim3(grid), dim3(NT), d->lds_total, st, a);
+    hipLaunchKernelGGL((pipeline_kernel<NT, VF, DM, KG, KIND, SF, BIG, VFP, PROF>), dim3(grid), dim3(NT), d->lds_total, st, a);
     SWD_HIP(hipGetLastError());
     return 0;
 }
@@ -618,6 +637,11 @@ void fill_params(const Plan *d, SwdDecodeParams &P, bool hist_is_state, bool his
     int SWD_LAUNCHER_NAME(kind, nt, vf, dm, kg, 0)(Plan *d, const SwdPipeArgs &a, hipStream_t st) { return launch_nt<nt, vf, dm, kg, (kind) == 6 ? 3 : 0, false, true>(d, a, st); }
 #define SWD_DEFINE_LAUNCHER(kind, nt, vf, dm, kg, sf) \
     int SWD_LAUNCHER_NAME(kind, nt, vf, dm, kg, sf)(Plan *d, const SwdPipeArgs &a, hipStream_t st) { return launch_nt<nt, vf, dm, kg, kind, (sf) != 0>(d, a, st); }
+// kind 3 with a depth profile (swd_variants.h, SWD_DEPTH_PROFILES)
+#define SWD_DEPTH_LAUNCHER_NAME(nt, vf, dm, kg) swd_launch_k3_depth_##nt##_##vf##_##dm##_##kg
+#define SWD_DECLARE_DEPTH_LAUNCHER(nt, vf, dm, kg) int SWD_DEPTH_LAUNCHER_NAME(nt, vf, dm, kg)(Plan *, const SwdPipeArgs &, hipStream_t);
+#define SWD_DEFINE_DEPTH_LAUNCHER(nt, vf, dm, kg, ...) \
+    int SWD_DEPTH_LAUNCHER_NAME(nt, vf, dm, kg)(Plan *d, const SwdPipeArgs &a, hipStream_t st) { return launch_nt<nt, vf, dm, kg, 3, false, false, vf, SwdDepthProfile<__VA_ARGS__>>(d, a, st); }
 // large-graph form of the guessing decoders' kernels: kind 8 = kind 1 (serial tree walk), kind 9 = kind 7 (threaded ensemble, tickets);
 // depth-2 register cache for the kept columns (Plan::finalize admits only plans with new_n <= 2 nt)
 #define SWD_DEFINE_BIG_GDG_LAUNCHER(kind, nt, vf, dm, kg) \

@@ -26,6 +26,17 @@
     X(1024, 8, 8, 16, 0, 1, 0, 0)
 #endif
 
+// Depth profiles (optional, per variant; osd_window kind 3): the full-graph node pass serves the nodes in descending-degree order,
+// NT per cache row, and row i of the register cache walks depth[i] edge positions -- a compile-time constant -- instead of DM.
+// A plan whose graphs all fit (every node listed in row i has degree <= depth[i]) launches the profiled instantiation, any other
+// plan the uniform one.  {6,6,3,3,3,3,2}: the three [[144,12,12]] window graphs (at most 504 nodes of degree > 3, 1512 of degree > 2).
+// X(nt, vf, dm, kg, depth[0], ..., depth[vf - 1])
+#if defined(SWD_V7816_ONLY) || defined(SWD_BB288_ONLY)
+#define SWD_DEPTH_PROFILES(X)
+#else
+#define SWD_DEPTH_PROFILES(X) X(256, 7, 6, 9, 6, 6, 3, 3, 3, 3, 2)
+#endif
+
 // Large graphs (row J of the scope table: osd_window on matrices whose fp64 messages do not fit a CU's LDS, e.g. the un-windowed
 // 936 x 8784 detector error model of /root/reference/IBM.ipynb:119): one 1024-thread workgroup per shot, the scratch region of
 // the layout in HBM (pipeline_kernel<..., BIG>).  Chosen when no variant above fits.  X(nt, vf, dm, kg)

@@ -70,6 +70,12 @@ def _as_synd(x, m):
     return np.ascontiguousarray((x.astype(np.int64) & 0xFF).astype(np.uint8))  # C (char) cast, c_util.pyx:6-9
 
 
+def _node_depth(L, name, handle):
+    """1 if the handle's full-graph node pass took the depth-profiled form (a development build may predate the query: uniform)"""
+    f = getattr(L, name, None)
+    return bool(f(handle)) if f is not None and getattr(f, "argtypes", None) else False
+
+
 class osd_window:
     """BP + OSD on a shortened window matrix (reference: src/osd_window.pyx)."""
 
@@ -95,6 +101,8 @@ class osd_window:
         i = [C.c_int32() for _ in range(4)]
         L.swd_osdw_info(self._h, *[C.byref(x) for x in i])
         self.new_n, self.rank = i[2].value, i[3].value
+        # "depth": the full-graph node pass serves the nodes by degree, a fixed depth per cache row (csrc/swd_variants.h); "uniform" otherwise
+        self.node_pass = "depth" if _node_depth(L, "swd_osdw_node_depth", self._h) else "uniform"
         # per-object state the reference keeps between decodes
         self._hist = np.zeros((4, self.n), dtype=np.float64)
         self._last = dict(status=EXIT_PRE, iters=0, min_pm=0.0)
@@ -655,7 +663,7 @@ class SlidingWindowDecoder:
                 self._loop = [cls(w.mat, channel_probs=w.prior, device=self.device,
                                   **{k: v for k, v in kwargs.items() if k != "device"}) for w in plan.windows]
                 self._chk_t = sp.csr_matrix(plan.chk.T.astype(np.int32))
-                self.lds_bytes, self.threads = 0, 1024
+                self.lds_bytes, self.threads, self.node_pass = 0, 1024, "uniform"
                 self.num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
                 self._obs_t = sp.csr_matrix(plan.obs.T.astype(np.int32)) if self.num_obs else None
                 return
@@ -663,6 +671,7 @@ class SlidingWindowDecoder:
         i = [C.c_int32() for _ in range(5)]
         L.swd_pipeline_info(self._h, *[C.byref(x) for x in i])
         self.lds_bytes, self.threads = i[3].value, i[4].value
+        self.node_pass = "depth" if _node_depth(L, "swd_pipeline_node_depth", self._h) else "uniform"  # (as osd_window.node_pass)
         self.num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
         if 0 < self.num_obs <= 32:
             a = sp.csr_matrix(plan.obs)
