@@ -588,6 +588,39 @@ int swd_pipeline_node_depth(const swd_pipeline *pl);
 int swd_graph_node_depth(const swd_graph_desc *g, int32_t pads, int32_t nt, int32_t vf, const int32_t *depth, int32_t *info,
                          uint16_t *vdord, uint32_t *vn_edge_d, double *llr_d, uint32_t *vn_edge, double *llr);
 
+/* diagnostics: which forms of the window kernels (csrc/swd_osdw_kernel.h, pipeline_kernel) a plan takes.  The kernel variant, the
+ * LDS-resident or large-graph form and each window's LDS layout decide which code a launch runs; these calls report the decision,
+ * taken by the code that builds a handle (csrc/swd_plan.h, Plan::select_forms) and by the conditions the kernels themselves test
+ * (swd_osd0_routine, swd_post_form).
+ * plan [SWD_FORM_PLAN_WORDS]:
+ *   [0..3] threads, variable nodes per thread, column-weight bound, groups of four row positions of the variant; [4] the full-graph
+ *   phase splits heavy checks; [5] large-graph form; [6] every window graph fits the variant's depth profile; [7] LDS bytes per
+ *   workgroup; [8] guessing decoders: work-item form available; [9] guessing decoders: depth-2 cache of the shortened graph;
+ *   [10] general form (no window kernel takes the plan: words 0..9 are 0); [11] kernel kind of the most recent launch -- 0 / 3
+ *   osd_window (3: history sum in registers), 5 / 6 the same on large graphs, 1 / 2 / 7 guessing decoders (serial walk, work items,
+ *   threaded ensemble), 8 / 9 serial walk and ensemble on large graphs -- [12] that launch was scheduled as a stream batch, [13] it
+ *   ran the depth-profiled kernel; [11..13] are -1 before the first launch, from swd_window_forms and in the general form.
+ * window [num_windows][SWD_FORM_WINDOW_WORDS] (all -1 in the general form):
+ *   [0] live-slot lists of the post phase: 0 staged in the scratch region, 1 a region of their own, 2 none; [1] post_lds; [2] osd_lds;
+ *   [3] ring entries of the wide column-form elimination (0: none); [4] the higher-order sweep has arrays of its own (1) or lies over
+ *   the sort keys (0); [5] candidates it evaluates at a time; [6] bytes of live mask per check (6 or 8); [7] OSD-0 elimination:
+ *   0 osd0_quad, 1 osd0_wave_reg, 2 osd0_cols, 3 osd0_colsw, 4 osd0_block; [8] post phase: 0 sorted, 1 live-slot lists, 2 no lists,
+ *   3 renumbered (large graphs) -- [7], [8] are -1 under a guessing decoder; [9] T of the heavy-check split and [10..12] checks served
+ *   by one / two / four threads, [13] threads they take together (0 where [4] of the plan is 0); [14] 64-bit words per column of
+ *   the check matrix; [15] pad cells of the graph's slot layout.
+ * Any output may be NULL. */
+#define SWD_FORM_PLAN_WORDS 16
+#define SWD_FORM_WINDOW_WORDS 16
+/* host only (needs no device): the forms a handle built now from these windows would take.  Exactly one of p (osd_window) and gp
+ * (guessing decoders) is given; num_det = rows of the global check matrix of a pipeline, <= 0 for a single-window handle (its
+ * `reserved`, row0, col0 and commit are then 0).  A plan no window kernel takes is reported (plan[10]), not refused. */
+int swd_window_forms(int32_t num_windows, const swd_window_desc *wins, int32_t num_det, const swd_osdw_params *p,
+                     const swd_gdg_params *gp, int32_t *plan, int32_t *window);
+/* the handle's forms and its most recent launch */
+int swd_osdw_last_form(const swd_osdw *h, int32_t *plan, int32_t *window);
+int swd_gdg_last_form(const swd_gdg *h, int32_t *plan, int32_t *window);
+int swd_pipeline_last_form(const swd_pipeline *pl, int32_t *plan, int32_t *window);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,7 +131,12 @@ SYMBOLS = [
     ("swd_graph_node_depth", C.c_int, [C.POINTER(GraphDesc), _i32, _i32, _i32, _vp] + [_vp] * 6),
     ("swd_osdw_node_depth", C.c_int, [_vp]),
     ("swd_pipeline_node_depth", C.c_int, [_vp]),
+    ("swd_window_forms", C.c_int, [_i32, _vp, _i32, C.POINTER(OsdwParams), C.POINTER(GdgParams), _vp, _vp]),
+    ("swd_osdw_last_form", C.c_int, [_vp, _vp, _vp]),
+    ("swd_gdg_last_form", C.c_int, [_vp, _vp, _vp]),
+    ("swd_pipeline_last_form", C.c_int, [_vp, _vp, _vp]),
 ]
+FORM_PLAN_WORDS = FORM_WINDOW_WORDS = 16  # include/swd.h: SWD_FORM_PLAN_WORDS, SWD_FORM_WINDOW_WORDS
 
 STAT_WORDS = 8
 WINDOW_COUNTER_WORDS = 10  # include/swd.h: SWD_WINDOW_COUNTER_WORDS

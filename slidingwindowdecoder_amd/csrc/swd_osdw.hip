@@ -36,7 +36,10 @@ int make_layout(const Graph &g, int new_n, int nt, int kind, SwdLdsLayout &L, bo
     // messages + slot E + one far and one zero slot per wave (swd_osdw_kernel.h, VnCache)
     int scratch = std::max(std::max((E + 1 + 2 * (nt / 64)) * 8, osd_bytes), std::max(rare_bytes, n * 2));
     // post-phase check order (degree histogram + order): behind the staged slot lists when those fit
-    L.off_cord = align_up((g.K * m * 2 <= scratch) ? std::max(L.off_aux, g.K * m * 2) : L.off_aux, 16);
+    // (decided here, once: the region still grows below, and lists admitted by the grown size would lie over the check order and the
+    // staged columns, which were placed for a graph without lists -- m = 48, n = 161, one row of weight 64 decoded wrongly)
+    const bool lists_fit = g.K * m * 2 <= scratch;
+    L.off_cord = align_up(lists_fit ? std::max(L.off_aux, g.K * m * 2) : L.off_aux, 16);
     L.off_rc = align_up(std::max(L.off_cord + 66 * 4 + m * 2, L.off_aux + 3 * 256 * 4), 16); // clear of the select histograms
     L.off_bak = align_up(L.off_rc + E * 2, 16);
     scratch = std::max(scratch, L.off_bak + 10 * m + 2 * n + 8);
@@ -58,13 +61,13 @@ int make_layout(const Graph &g, int new_n, int nt, int kind, SwdLdsLayout &L, bo
     // live mask per check (row weight <= 48), one parity byte per check, no copy of the original check degrees, one
     // "decided" bit per variable node.  Every other kernel: the classic arrays.
     const bool diet = kind == 0 && nt <= SWD_TUNED_NT;
-    L.off_livemask = o; o += (diet && g.K <= 48) ? align_up(m * 6, 4) : m * 8;
+    L.off_livemask = o; o += align_up(m * live_mask_bytes(g, nt, kind), 4);
     L.off_par = o; o += diet ? align_up(m + 1, 4) : (m + 1) * 4; // parities; index m: sink for the dead positions' flips
     L.off_lv = o; o = align_up(o + new_n * 2, 4);
     L.off_jptr = o; o = align_up(o + (g.K + 1) * 2, 4);
     // live-slot lists: osd_window stages them in the (then dead) scratch region; the guessing decoders
     // keep their messages alive across decimation steps and get a dedicated region
-    L.off_lslot = (g.K * m * 2 <= scratch) ? 0 : -1;
+    L.off_lslot = lists_fit ? 0 : -1;
     L.off_gdg = -1;
     if (kind != 0) {
         L.off_gdg = o;
@@ -123,7 +126,7 @@ int make_layout_for_osd(const Graph &g, int nt, SwdLdsLayout &L) { return make_l
 // Static check-to-thread map of the full-graph BP phase for variants that share heavy checks among threads
 // (same rule as cn_assign on the device: smallest T <= cap such that one thread per check of degree <= T,
 // two up to 2T, four up to 4T fit nt threads; lanes are already sorted by decreasing degree).
-bool split_map(const Graph &g, int nt, int cap, std::vector<uint32_t> *map) {
+bool split_map(const Graph &g, int nt, int cap, std::vector<uint32_t> *map, int *form) {
     static const int cand[8] = {3, 4, 6, 8, 12, 16, 24, 32};
     for (int ci = 0; ci < 8; ++ci) {
         const int T = cand[ci];
@@ -136,6 +139,10 @@ bool split_map(const Graph &g, int nt, int cap, std::vector<uint32_t> *map) {
             need += d <= T ? 1 : (d <= 2 * T ? 2 : 4);
         }
         if (!ok || need > nt) continue;
+        if (form) { // T, checks served by one / two / four threads
+            form[0] = T; form[1] = form[2] = form[3] = 0;
+            for (int l = 0; l < g.m; ++l) form[g.row_deg[l] <= T ? 1 : (g.row_deg[l] <= 2 * T ? 2 : 3)]++;
+        }
         if (map) {
             map->assign(nt, 0xFFFFu);
             int t = 0;
@@ -262,6 +269,7 @@ int launch(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
         (void)hipGetLastError(); // ("not ready" is an answer, not an error)
     }
     d->stream_serial = (d->stream_push || overlapped) && a.B >= stream_serial_min; // (the threaded ensemble's launcher reads it too: swd_plan.h, KIND 7)
+    d->last_kind = -1;
     const bool par = d->kind == 1 && d->gdg_parallel && !a.hist && d->variant->launch_par && a.B <= par_max_shots && a.B < SWD_GDG_ITEM_MAX_SHOTS &&
                      !d->stream_serial;
     // osd_window: when the posterior history is only consumed as its slot-order sum (no history in or out, both
@@ -273,6 +281,9 @@ int launch(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
     rc = (d->kind == 0) ? (acc ? (d->depth ? d->depth->launch_acc(d, a, st) : d->variant->launch_acc(d, a, st)) : d->variant->launch(d, a, st))
                         : (ens ? d->variant->launch_ens(d, a, st) : (par ? d->variant->launch_par(d, a, st) : d->variant->launch_gdg(d, a, st)));
     if (rc) return rc;
+    // (what swd_*_last_form reports: the large-graph kernels are kinds 5 / 6 / 8 / 9)
+    d->last_kind = (d->kind == 0) ? (acc ? (d->big ? 6 : 3) : (d->big ? 5 : 0)) : (ens ? (d->big ? 9 : 7) : (par ? 2 : (d->big ? 8 : 1)));
+    d->last_depth = d->kind == 0 && acc && d->depth != nullptr;
     SWD_HIP(hipEventRecord(sl.done, st));
     d->last_done = sl.done; d->last_stream = st;
     if (d->timing) {
@@ -1009,3 +1020,90 @@ extern "C" swd_pipeline *swd_pipeline_create_gdg(int32_t num_windows, const swd_
     if (d->finalize(chk)) { delete d; return nullptr; }
     return (swd_pipeline *)d;
 }
+
+// ------------------------------------------------------------------------------------------
+// diagnostics: which forms of the window kernels a plan takes (include/swd.h)
+// ------------------------------------------------------------------------------------------
+static void plan_record(const Plan *d, int32_t *out) {
+    for (int i = 0; i < SWD_FORM_PLAN_WORDS; ++i) out[i] = 0;
+    out[11] = out[12] = out[13] = -1;
+    if (d->huge || !d->variant) { out[10] = 1; return; }
+    const Variant *v = d->variant;
+    out[0] = v->nt; out[1] = v->vf; out[2] = v->dm; out[3] = v->kg; out[4] = v->sf; out[5] = d->big ? 1 : 0;
+    out[6] = d->depth ? 1 : 0; out[7] = d->lds_total; out[8] = d->gdg_parallel ? 1 : 0; out[9] = d->post_depth2 ? 1 : 0;
+}
+
+static void window_record(const Plan *d, const WindowHost &w, int32_t *out) {
+    const Variant *v = d->variant;
+    const SwdLdsLayout &L = w.L;
+    const Graph &g = *w.g;
+    for (int i = 0; i < SWD_FORM_WINDOW_WORDS; ++i) out[i] = 0;
+    out[0] = L.off_lslot < 0 ? 2 : (L.off_lslot > 0 ? 1 : 0);
+    out[1] = L.post_lds; out[2] = L.osd_lds; out[3] = L.owide_ring; out[4] = L.off_cs != 0 ? 1 : 0; out[5] = L.cs_par;
+    out[6] = live_mask_bytes(g, v->nt, d->kind);
+    out[7] = out[8] = -1;
+    if (d->kind == 0) { // (window_decode: osd_run<NT, DM, !BIG, !BIG, BIG>; the osd_window kernels are built with SWD_OSDW_TUNED)
+        out[7] = swd_osd0_routine(v->nt, v->dm, !d->big, !d->big, d->big, g.wm, L.off_oring, L.off_oslot, L.off_owide);
+        out[8] = swd_post_form(v->nt, v->vf, d->big, true, L.post_lds, L.off_lslot, w.new_n);
+    }
+    if (v->sf) {
+        int form[4] = {0, 0, 0, 0};
+        split_map(g, v->nt, 4 * v->kg, nullptr, form);
+        out[9] = form[0]; out[10] = form[1]; out[11] = form[2]; out[12] = form[3];
+        out[13] = form[1] + 2 * form[2] + 4 * form[3];
+    }
+    out[14] = g.wm; out[15] = g.S - g.E;
+}
+
+extern "C" int swd_window_forms(int32_t num_windows, const swd_window_desc *wins, int32_t num_det, const swd_osdw_params *p,
+                                const swd_gdg_params *gp, int32_t *plan, int32_t *window) {
+    if (!wins || num_windows <= 0 || (p != nullptr) == (gp != nullptr)) {
+        set_error("swd_window_forms: windows and exactly one of the two parameter records"); return -1;
+    }
+    Plan d;
+    d.host_only = true;
+    if (p) {
+        d.p = *p;
+        if (check_params(d.p)) return -1;
+    } else {
+        if (check_gdg_params(*gp)) return -1;
+        d.gp = *gp;
+        d.kind = gp->mode + 1;
+        d.p.pre_max_iter = gp->max_iter; d.p.osd_order = -1; d.p.ms_scaling_factor = gp->ms_scaling_factor;
+    }
+    std::map<std::string, std::shared_ptr<Graph>> cache;
+    bool general = false;
+    for (int i = 0; i < num_windows && !general; ++i) {
+        const swd_window_desc &w = wins[i];
+        if (!w.graph.row_ptr || !w.graph.col_idx || !w.graph.channel_probs) { set_error("swd_window_forms: null graph arrays"); return -1; }
+        general = d.add_window(&w.graph, w.row0, w.col0, w.commit, cache) != 0;
+    }
+    swd_graph_desc chk{};
+    chk.m = num_det; // (select_forms reads the global matrix's dimensions only)
+    if (!general) general = d.select_forms(num_det > 0 ? &chk : nullptr) != 0;
+    if (general) d.variant = nullptr; // no window kernel takes the plan: a handle would go to the general form (single windows) or fail
+    if (plan) plan_record(&d, plan);
+    if (window)
+        for (int i = 0; i < num_windows; ++i) {
+            if (general) { for (int k = 0; k < SWD_FORM_WINDOW_WORDS; ++k) window[i * SWD_FORM_WINDOW_WORDS + k] = -1; }
+            else window_record(&d, d.wins[i], window + i * SWD_FORM_WINDOW_WORDS);
+        }
+    return 0;
+}
+
+// one function for the three handle types: all of them are Plans
+static int plan_last_form(const void *h, int32_t *plan, int32_t *window) {
+    Plan *d = (Plan *)h;
+    if (!d) { set_error("null handle"); return -1; }
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    if (plan) {
+        plan_record(d, plan);
+        if (!d->huge) { plan[11] = d->last_kind; plan[12] = d->last_kind < 0 ? -1 : (d->stream_serial ? 1 : 0); plan[13] = d->last_kind < 0 ? -1 : (d->last_depth ? 1 : 0); }
+    }
+    if (window && !d->huge)
+        for (size_t i = 0; i < d->wins.size(); ++i) window_record(d, d->wins[i], window + i * SWD_FORM_WINDOW_WORDS);
+    return 0;
+}
+extern "C" int swd_osdw_last_form(const swd_osdw *h, int32_t *plan, int32_t *window) { return plan_last_form(h, plan, window); }
+extern "C" int swd_gdg_last_form(const swd_gdg *h, int32_t *plan, int32_t *window) { return plan_last_form(h, plan, window); }
+extern "C" int swd_pipeline_last_form(const swd_pipeline *h, int32_t *plan, int32_t *window) { return plan_last_form(h, plan, window); }

@@ -87,6 +87,44 @@ struct SwdLdsLayout {
     int32_t off_pmsg, pmsg_bytes, post_lds, osd_lds;
 };
 
+// Which code a window runs, as far as the layout and the kernel instantiation decide it: the conditions of osd_run (OSD-0 elimination)
+// and of the post phase, shared by the kernels and by the host's form report (include/swd.h, swd_window_forms).  Arguments that are
+// template parameters at the call sites fold away there.
+//   *_built: the instantiation holds the routine / the form;  *_TAKEN: this window's graph and layout take it.  The run-time tests
+//   are macros: written as functions, however their operands were passed, they changed the code of several kernels (1.9 KB of the
+//   <256, 7, 6, 9> kind-0 kernel alone); as macros the kernels compile to the instruction streams of the open-coded tests.
+enum { SWD_OSD0_QUAD = 0, SWD_OSD0_WAVE_REG = 1, SWD_OSD0_COLS = 2, SWD_OSD0_COLSW = 3, SWD_OSD0_BLOCK = 4 };
+enum { SWD_POST_FORM_SORTED = 0, SWD_POST_FORM_LISTS = 1, SWD_POST_FORM_NOLISTS = 2, SWD_POST_FORM_RENUM = 3 };
+__host__ __device__ constexpr bool swd_osd0_cols_built(int nt, int dm, bool colform) { return colform && nt >= 1024 && dm <= 8; }
+__host__ __device__ constexpr bool swd_osd0_quad_built(int nt, bool quad) { return quad && nt >= 256; }
+__host__ __device__ constexpr bool swd_osd0_colsw_built(int nt, int dm, bool wide) { return wide && nt == 1024 && dm <= 8; }
+#define SWD_OSD0_COLS_TAKEN(wm, off_oslot) ((wm) > 4 && (wm) <= 9 && (off_oslot) >= 0)
+#define SWD_OSD0_QUAD_TAKEN(wm, off_oring) ((wm) <= 4 && (off_oring) >= 0)
+#define SWD_OSD0_WAVE_TAKEN(wm) ((wm) <= 4)
+#define SWD_OSD0_COLSW_TAKEN(wm, off_owide) ((wm) <= 15 && (off_owide) >= 0)
+// (osd_run walks the same chain)
+__host__ __device__ constexpr int swd_osd0_routine(int nt, int dm, bool colform, bool quad, bool wide, int wm, int off_oring, int off_oslot, int off_owide) {
+    if (swd_osd0_quad_built(nt, quad) && SWD_OSD0_QUAD_TAKEN(wm, off_oring)) return SWD_OSD0_QUAD;
+    if (SWD_OSD0_WAVE_TAKEN(wm)) return SWD_OSD0_WAVE_REG;
+    if (swd_osd0_cols_built(nt, dm, colform) && SWD_OSD0_COLS_TAKEN(wm, off_oslot)) return SWD_OSD0_COLS;
+    if (swd_osd0_colsw_built(nt, dm, wide) && SWD_OSD0_COLSW_TAKEN(wm, off_owide)) return SWD_OSD0_COLSW;
+    return SWD_OSD0_BLOCK;
+}
+// tuned: the translation unit's SWD_OSDW_TUNED (the osd_window kernels, kinds 0 / 3 and their large-graph forms)
+__host__ __device__ constexpr bool swd_post_sorted_built(int nt, int vf, bool big, bool tuned) {
+    return (SWD_POST_SORTED & (big ? 4 : ((tuned && nt <= SWD_TUNED_NT) ? 1 : (tuned && nt >= 512 ? 2 : 0)))) != 0 && vf > 2;
+}
+#define SWD_POST_LISTS_TAKEN(off_lslot) ((off_lslot) >= 0)
+#define SWD_POST_SORTED_TAKEN(post_lds, lists, new_n, nt) ((post_lds) != 0 && (lists) && (new_n) <= 2 * (nt))
+#define SWD_POST_RENUM_TAKEN(post_lds, lists) ((post_lds) != 0 && (lists))
+// (the post phase of window_decode walks the same chain; its depth-2 caches are no form of their own)
+__host__ __device__ constexpr int swd_post_form(int nt, int vf, bool big, bool tuned, int post_lds, int off_lslot, int new_n) {
+    const bool lists = SWD_POST_LISTS_TAKEN(off_lslot);
+    if (swd_post_sorted_built(nt, vf, big, tuned) && SWD_POST_SORTED_TAKEN(post_lds, lists, new_n, nt)) return SWD_POST_FORM_SORTED;
+    if (big && SWD_POST_RENUM_TAKEN(post_lds, lists)) return SWD_POST_FORM_RENUM;
+    return lists ? SWD_POST_FORM_LISTS : SWD_POST_FORM_NOLISTS;
+}
+
 // decoder parameters shared by every window of a launch (osd_window.pyx:10-16)
 struct SwdDecodeParams {
     int32_t pre_iter, post_iter, osd_method, osd_order;
@@ -2800,8 +2838,8 @@ __device__ __forceinline__ double osd_run(const SwdGraphDev &g, const SwdLdsLayo
     bool cols = false; // column-form elimination: 256 < m <= 576 on the 1024-thread variants
     // (not in the column-weight-10 variant: its windows -- SHYPS twelve-round, 252 checks -- never need it, and the mere presence
     // of the routine in that kernel cost its BP loops registers: 0.61 -> 0.51 M windows/s)
-    constexpr bool kColForm = COLFORM && NT >= 1024 && DM <= 8;
-    if constexpr (kColForm) cols = g.wm > 4 && g.wm <= 9 && L.off_oslot >= 0;
+    constexpr bool kColForm = swd_osd0_cols_built(NT, DM, COLFORM);
+    if constexpr (kColForm) cols = SWD_OSD0_COLS_TAKEN(g.wm, L.off_oslot);
     const int nst = min(n, (cols ? L.off_oslot : L.npad * 8) / (DM * 2));
     for (int p = tid; p < nst; p += NT) {
         const int v = idx[p];
@@ -2810,16 +2848,16 @@ __device__ __forceinline__ double osd_run(const SwdGraphDev &g, const SwdLdsLayo
         for (int k = 0; k < DM; ++k) crows[p * DM + k] = (k < deg) ? g.vn_row[k * n + v] : (uint16_t)0xFFFF;
     }
     __syncthreads();
-    constexpr bool kQuad = QUAD && NT >= 256;
+    constexpr bool kQuad = swd_osd0_quad_built(NT, QUAD);
     bool quad = false;
-    if constexpr (kQuad) quad = g.wm <= 4 && L.off_oring >= 0;
+    if constexpr (kQuad) quad = SWD_OSD0_QUAD_TAKEN(g.wm, L.off_oring);
     if (quad) {
         if constexpr (kQuad) {
             int npiv = 0;
             const int ra = osd0_quad<NT, DM>(g, s, idx, Tc, Sbuf, piv_col, piv_row, synd, crows, nst, &npiv, s.scratch + L.off_oring);
             if (tid == 0) { s.scal[2] = ra; s.scal[3] = npiv; }
         }
-    } else if (g.wm <= 4) {
+    } else if (SWD_OSD0_WAVE_TAKEN(g.wm)) {
         if (tid < 64) {
             int npiv;
             const int ra = osd0_wave_reg<DM>(g, s, idx, Tc, Sbuf, piv_col, piv_row, synd, crows, nst, &npiv);
@@ -2831,8 +2869,8 @@ __device__ __forceinline__ double osd_run(const SwdGraphDev &g, const SwdLdsLayo
         if constexpr (kColForm) {
             if (cols) { ra = osd0_cols<NT, DM, 9>(g, s, idx, Tc, Sbuf, piv_col, piv_row, synd, crows, nst, &npiv, s.scratch + L.off_oslot); done = true; }
         }
-        if constexpr (WIDE && NT == 1024 && DM <= 8) {
-            if (g.wm <= 15 && L.off_owide >= 0) {
+        if constexpr (swd_osd0_colsw_built(NT, DM, WIDE)) {
+            if (SWD_OSD0_COLSW_TAKEN(g.wm, L.off_owide)) {
                 ra = osd0_colsw<NT, DM, 15>(g, s, idx, Tc, Sbuf, piv_col, piv_row, synd, crows, nst, &npiv, (char *)s.hard - L.off_hard + L.off_owide, L.owide_ring, L.osd_lds != 0);
                 done = true;
             }
@@ -3170,7 +3208,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
         return;
     }
     // ---- compact the live VNs, re-initialise their messages (osd_window.pyx:187)
-    const bool uselist = L.off_lslot >= 0;
+    const bool uselist = SWD_POST_LISTS_TAKEN(L.off_lslot);
     int nlive;
     // live checks are dealt to the threads in order of decreasing live degree (counting sort): a wave's
     // CN pass costs its largest degree, and after shortening the degrees are very uneven
@@ -3182,9 +3220,9 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     // over the dead backup of the peeling step.
     // (SWD_POST_SORTED bit 0: the tuned kernels of up to 256 threads, bit 1: the LDS-resident 1024-thread kernels, bit 2: the large-graph
     // kernels, whose shortened graph lives in the LDS region post_lds names)
-    constexpr bool kSorted = (SWD_POST_SORTED & (BIG ? 4 : (SWD_P16(NT) ? 1 : (SWD_OSDW_TUNED && NT >= 512 ? 2 : 0)))) != 0 && VF > 2;
+    constexpr bool kSorted = swd_post_sorted_built(NT, VF, BIG, SWD_OSDW_TUNED != 0);
     bool sorted = false;
-    if constexpr (kSorted) sorted = L.post_lds != 0 && uselist && g.new_n <= 2 * NT;
+    if constexpr (kSorted) sorted = SWD_POST_SORTED_TAKEN(L.post_lds, uselist, g.new_n, NT);
     uint32_t *deg32 = (uint32_t *)(s.scratch + L.off_bak); // [n] bytes, four per word
     for (int i = tid; i < 65; i += NT) dhist[i] = 0;
     if constexpr (kSorted) {
@@ -3273,7 +3311,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     SwdGraphDev gp = g;
     bool renum = false;
     constexpr bool kRenum = BIG; // (a local constant on purpose: run_post, a generic lambda, captures what it names, and its closure's layout decides two register numbers of the tuned kernels)
-    if constexpr (kRenum) renum = L.post_lds != 0 && uselist;
+    if constexpr (kRenum) renum = SWD_POST_RENUM_TAKEN(L.post_lds, uselist);
     // the post phase proper, for a register cache of any depth: caches, (re)initialised messages, the iterations
     // (renum_tag: compile-time twin of `renum`, so that a BIG kernel's post-phase message pointer is an LDS pointer on every path
     // that reaches the iterations -- ds_read / ds_write instead of flat accesses)

@@ -20,6 +20,8 @@ inline int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 inline int align_up(int x, int a) { return (x + a - 1) / a * a; }
 
 int make_layout(const Graph &g, int new_n, int nt, int kind, SwdLdsLayout &L, bool big = false, int lds_budget = 0);
+// bytes of live mask per check: the tuned osd_window kernels (swd_osdw_kernel.h, DIET) keep 32 + 16 bits while the row weight allows
+inline int live_mask_bytes(const Graph &g, int nt, int kind) { return (kind == 0 && nt <= SWD_TUNED_NT && g.K <= 48) ? 6 : 8; }
 
 struct WindowHost {
     std::shared_ptr<Graph> g;
@@ -104,7 +106,7 @@ struct Variant {
 };
 const Variant *select_variant(const std::vector<WindowHost> &wins, int mmax, int nmax, int dm, int kmax, int kind);
 const Variant *select_big_variant(int mmax, int nmax, int dm, int kmax, int kind = 0); // graphs beyond one CU's LDS: scratch region in HBM
-bool split_map(const Graph &g, int nt, int cap, std::vector<uint32_t> *map);
+bool split_map(const Graph &g, int nt, int cap, std::vector<uint32_t> *map, int *form = nullptr); // form [4], nullable: T, checks on 1 / 2 / 4 threads
 // Depth profile of a variant (swd_variants.h, SWD_DEPTH_PROFILES): the depth of each cache row of the full-graph node pass and the
 // launcher of the kind-3 kernel compiled for it.  A plan whose graphs all fit takes it (Plan::depth), any other the variant's own.
 struct DepthProfile {
@@ -153,6 +155,9 @@ struct Plan {
     int num_det = 0, num_col = 0, nmax = 0, off_det = 0, lds_total = 0;
     bool post_depth2 = false;  // guessing decoders: every window keeps new_n <= 2 nt columns -> depth-2 cache for the shortened graph
     bool big = false;          // large graphs: the layouts' scratch region lives in HBM (big_stride bytes per workgroup)
+    bool host_only = false;    // built by swd_window_forms for its answer alone: select_forms ran, finalize never will
+    int last_kind = -1;        // (under mu) kernel kind of the most recent launch (swd_*_last_form), -1 before the first
+    bool last_depth = false;   // (under mu) ... and whether it went through the depth profile's launcher
     int64_t big_stride = 0;
     DevBuf d_wins, d_chk, d_obs, d_cnmap;
     DevBuf shot;
@@ -194,6 +199,7 @@ struct Plan {
     std::vector<uint16_t> h_rows;
 
     ~Plan() {
+        if (host_only) return; // (a plan of the form report: no device, nothing created on one)
         (void)hipSetDevice(device);
         hstream.reset();
         // stream objects that outlive their pipeline: drain their lanes (they read this plan's buffers) and detach them.  The list is
@@ -274,8 +280,8 @@ struct Plan {
     // where the kernels keep the full graph's messages in LDS (osd_window, not the large-graph form) and the cells cost nothing:
     // launch_nt counts a workgroup's LDS in granules of 1280 B, so the plan may grow up to the granule it ends in, as long as
     // every window layout keeps its form (what lies over what in the scratch region).  SWD_NATURAL_LAYOUT in the environment,
-    // read here, keeps the natural layout (A/B runs, tests).
-    int layout_graphs(int lmax) {
+    // read here, keeps the natural layout (A/B runs, tests).  Host work only: finalize uploads the graphs afterwards.
+    void layout_graphs(int lmax) {
         std::vector<Graph *> uniq;
         for (auto &w : wins)
             if (std::find(uniq.begin(), uniq.end(), w.g.get()) == uniq.end()) uniq.push_back(w.g.get());
@@ -304,12 +310,11 @@ struct Plan {
             off_det = align_up(lmax, 16) + 16;
             lds_total = align_up(lmax, 16) + tail;
         }
-        for (Graph *g : uniq)
-            if (g->upload()) return -1;
-        return 0;
     }
 
-    int finalize(const swd_graph_desc *chk) {
+    // Everything a plan decides about the code its launches run -- variant, LDS-resident or large-graph form, depth profile, the
+    // graphs' slot layout and each window's LDS layout -- without a device call (swd_window_forms runs it alone).
+    int select_forms(const swd_graph_desc *chk) {
         if (kind == 0 && p.osd_method == 1 && p.osd_order > 15) { set_error("osd_e supports osd_order <= 15 on the device"); return -1; }
         if (kind != 0) {
             max_guess = ((1 << gp.max_tree_depth) - 1) * 2 + gp.max_side_depth - gp.max_tree_depth; // bp_guessing_decoder.pyx:181
@@ -390,9 +395,21 @@ struct Plan {
             for (auto &w : wins) fit = fit && w.g->fits_depth(dp->depth, dp->vf, dp->nt);
             if (fit) depth = dp;
         }
-        if (layout_graphs(lmax)) return -1;
+        layout_graphs(lmax);
         post_depth2 = kind != 0 && !getenv("SWD_GDG_NO_DEPTH2");
         for (auto &w : wins) post_depth2 = post_depth2 && w.new_n <= 2 * nt;
+        return 0;
+    }
+
+    int finalize(const swd_graph_desc *chk) {
+        if (select_forms(chk)) return -1;
+        {
+            std::vector<Graph *> uniq;
+            for (auto &w : wins)
+                if (std::find(uniq.begin(), uniq.end(), w.g.get()) == uniq.end()) uniq.push_back(w.g.get());
+            for (Graph *g : uniq)
+                if (g->upload()) return -1;
+        }
         if (kind == 1 && gp.multi_thread == 1) {
             // prefix-tree walk of the ensemble (swd_gdg_kernel.h, gdg_ensemble_tree): behind the 2 + (S - D) mask records come D fork
             // records (masks + message cells: every cell of the window, or -- static tree-walk cache -- VF x DM cells per thread),

@@ -119,6 +119,13 @@ class osd_window:
                 pass
             self._h = None
 
+    @property
+    def last_form(self):
+        """The forms of the window kernels this decoder takes and the kernel kind of its most recent launch (include/swd.h,
+        swd_osdw_last_form): the dict of ``window_forms`` with ``kind`` (-1 before the first launch), ``stream_serial`` and
+        ``depth_launch`` filled in."""
+        return _last_form("swd_osdw_last_form", self._h, 1)
+
     # ---- reference surface -------------------------------------------------------------
     def decode(self, input_vector):
         """One syndrome -> int64[n] (osd_window.pyx:158-199).  The LLR history persists between
@@ -263,6 +270,72 @@ def _gdg_params(kwargs, mode):
                           (2 if kwargs.get("multi_thread", False) == 2 else int(bool(kwargs.get("multi_thread", False)))) if mode == 0 else 0)
 
 
+# ---- which forms of the window kernels a plan takes (include/swd.h, swd_window_forms / swd_*_last_form) ----
+FORM_PLAN_FIELDS = ("nt", "vf", "dm", "kg", "sf", "big", "depth_fit", "lds_total", "gdg_parallel", "post_depth2", "general",
+                    "kind", "stream_serial", "depth_launch")
+FORM_WINDOW_FIELDS = ("lslot", "post_lds", "osd_lds", "owide_ring", "cs_own", "cs_par", "mask_bytes", "osd0", "post",
+                      "split_t", "split_1", "split_2", "split_4", "split_need", "wm", "pads")
+_FORM_NAMES = {"lslot": ("staged", "own", "none"),
+               "osd0": ("osd0_quad", "osd0_wave_reg", "osd0_cols", "osd0_colsw", "osd0_block"),
+               "post": ("sorted", "lists", "no_lists", "renumbered")}
+
+
+def _form_dict(plan, wins):
+    """The int32 records of include/swd.h as a dict with named fields; ``windows`` holds one dict per window (none in the general
+    form).  ``lslot``, ``osd0`` and ``post`` are given by name (None where the record holds -1)."""
+    out = {k: int(v) for k, v in zip(FORM_PLAN_FIELDS, plan)}
+    out["windows"] = []
+    for rec in (wins if not out["general"] else ()):
+        w = {k: int(v) for k, v in zip(FORM_WINDOW_FIELDS, rec)}
+        for k, names in _FORM_NAMES.items():
+            w[k] = names[w[k]] if w[k] >= 0 else None
+        out["windows"].append(w)
+    return out
+
+
+def _last_form(name, handle, nwin):
+    plan = np.zeros(_lib.FORM_PLAN_WORDS, np.int32)
+    wins = np.full((max(nwin, 1), _lib.FORM_WINDOW_WORDS), -1, np.int32)
+    if getattr(_lib.lib(), name)(handle, plan.ctypes.data, wins.ctypes.data):
+        raise RuntimeError(f"{name} failed: {_lib.last_error()}")
+    return _form_dict(plan, wins[:nwin])
+
+
+def window_forms(windows, decoder="osd_window", num_det=0, **kwargs):
+    """Host only (needs no device): the forms a decoder built now would take -- ``last_form`` of that decoder before its first
+    launch (``kind``, ``stream_serial`` and ``depth_launch`` are -1).  ``windows``: a ``windows.WindowPlan`` (a
+    ``SlidingWindowDecoder``), or a list of ``(matrix, channel_probs)`` / ``(matrix, channel_probs, row0, col0, commit)`` with
+    ``num_det`` rows in the global check matrix (0: one window, as ``osd_window`` / ``bpgdg_decoder`` / ``bpgd_decoder`` take it).
+    ``decoder`` and the keyword arguments are those of the decoder.  A plan no window kernel takes reports ``general=1``."""
+    if hasattr(windows, "windows"):
+        num_det = windows.chk.shape[0]
+        windows = [(w.mat, w.prior, w.row0, w.col0, w.commit) for w in windows.windows]
+    if decoder == "osd_window":
+        method, order = _parse_osd_method(kwargs.get("osd_method", "osd_0"), kwargs.get("osd_order", 0))
+        new_n = kwargs.get("new_n", None)
+        p = _lib.OsdwParams(int(kwargs.get("pre_max_iter", 8)), int(kwargs.get("post_max_iter", 100)),
+                            float(kwargs.get("ms_scaling_factor", 1.0)), int(new_n) if new_n else 0, method, order)
+        pp, gp = C.byref(p), None
+    elif decoder in ("bpgdg_decoder", "bpgd_decoder", "bp_history_decoder"):
+        p = _gdg_params(kwargs, {"bpgdg_decoder": 0, "bpgd_decoder": 1, "bp_history_decoder": 2}[decoder])
+        pp, gp = None, C.byref(p)
+    else:
+        raise ValueError(f"unknown window decoder {decoder!r}")
+    keep = []
+    descs = (_lib.WindowDesc * len(windows))()
+    for i, w in enumerate(windows):
+        c = _Csr(w[0], w[1])
+        keep.append(c)
+        descs[i].graph = c.desc
+        if len(w) > 2:
+            descs[i].row0, descs[i].col0, descs[i].commit = int(w[2]), int(w[3]), int(w[4])
+    plan = np.zeros(_lib.FORM_PLAN_WORDS, np.int32)
+    wins = np.full((len(windows), _lib.FORM_WINDOW_WORDS), -1, np.int32)
+    if _lib.lib().swd_window_forms(len(windows), C.cast(descs, C.c_void_p), int(num_det), pp, gp, plan.ctypes.data, wins.ctypes.data):
+        raise ValueError(f"swd_window_forms failed: {_lib.last_error()}")
+    return _form_dict(plan, wins)
+
+
 class bp_history_decoder:
     """Plain min-sum BP with a 4-deep posterior history (reference: src/bp_guessing_decoder.pyx:5-158)
     and base class of the guessing decoders.  ``bpgdg_decoder``: the side branches of a shot's decimation tree run
@@ -326,6 +399,11 @@ class bp_history_decoder:
         self.last_stats, self.last_min_pm = st, pm
         self.last_status = st[:, 0].copy()
         return out
+
+    @property
+    def last_form(self):
+        """As ``osd_window.last_form`` (include/swd.h, swd_gdg_last_form)."""
+        return _last_form("swd_gdg_last_form", self._h, 1)
 
     @property
     def converge(self):
@@ -689,6 +767,12 @@ class SlidingWindowDecoder:
             except Exception:
                 pass
             self._h = None
+
+    @property
+    def last_form(self):
+        """As ``osd_window.last_form``, one entry of ``windows`` per window (include/swd.h, swd_pipeline_last_form); None when the
+        window loop runs on the host over general-form decoders."""
+        return _last_form("swd_pipeline_last_form", self._h, self.W) if self._h else None
 
     def _check_det(self, det_data):
         d = np.asarray(det_data)

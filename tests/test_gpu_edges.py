@@ -56,7 +56,8 @@ def test_empty_batch_pipeline():
 
 @pytest.mark.parametrize("m,n", [(64, 256), (256, 1792), (640, 1600), (600, 2000)])
 def test_largest_matrices_of_a_variant_vs_oracle(m, n):
-    """m and n at the upper edge of a kernel variant (threads x variable nodes per thread)."""
+    """m and n at the upper edge of a kernel variant (threads x variable nodes per thread); the variant, the elimination routine and
+    the post-phase form each shape takes are asserted (the forms at their other bounds: tests/test_gpu_window_forms.py)."""
     from oracle import oracle as O
     from slidingwindowdecoder_amd import osd_window
     rng = np.random.default_rng(m)
@@ -73,6 +74,10 @@ def test_largest_matrices_of_a_variant_vs_oracle(m, n):
     out = dev.decode_batch(synd)
     assert np.array_equal(out, want)
     assert np.array_equal(dev.last_iterations, res["bp_iteration"]) and np.array_equal(dev.last_min_pm, res["min_pm"])
+    f = dev.last_form
+    assert ((f["nt"], f["vf"], f["dm"], f["kg"], f["sf"], f["big"], f["kind"]), f["windows"][0]["osd0"], f["windows"][0]["post"]) == {
+        (64, 256): ((64, 4, 8, 16, 0, 0, 0), "osd0_wave_reg", "sorted"), (256, 1792): ((256, 7, 8, 16, 0, 0, 0), "osd0_quad", "sorted"),
+        (640, 1600): ((1024, 5, 6, 6, 1, 0, 3), "osd0_block", "lists"), (600, 2000): ((1024, 5, 6, 6, 1, 0, 3), "osd0_block", "sorted")}[(m, n)]
 
 
 # (matrices beyond every kernel variant are no longer refused: tests/test_gpu_huge.py)
