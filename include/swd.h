@@ -174,7 +174,17 @@ int swd_gdg_decode_batch_dev(swd_gdg *d, int32_t B, const uint8_t *synd, int64_t
  * graph, where the reference resets it to 0 (bp4_osd.pyx:74-76); osd_order > 0 needs
  * rank(Hx) >= rank(Hz) -- the reference sizes BOTH sweeps with kx = n - rank_x (bp4_osd.pyx:103-104, :284): with
  * rank(Hx) > rank(Hz) its z-basis sweep walks fewer candidate columns than exist, which is reproduced (pinned by
- * tests/golden/bp4_unequal_ranks.npz); with rank(Hx) < rank(Hz) it reads past its column array, which is not. */
+ * tests/golden/bp4_unequal_ranks.npz); with rank(Hx) < rank(Hz) it reads past its column array, which is not.
+ * Further restrictions of the tuned kernels: at most 1024 checks per matrix, row weights within the graph tables, and the messages
+ * of Hx and Hz together within 160 KB of LDS.
+ * GENERAL FORM (swd_bp4_create_ex with SWD_BP4_GENERAL_FORM; csrc/swd_huge_bp4.hip): none of the restrictions on the graph -- any
+ * row and column weight, up to 1 048 576 qubits, 1 048 576 checks per matrix and 67 108 864 edges in Hx and Hz together (the EG
+ * codes [[273,111,17]] and [[1057,571,33]] of Misc.ipynb cell 8, whose every column is above the weight bound; large light codes).
+ * One 1024-thread workgroup per shot (per run of a camel shot), every array in HBM.  It is opt-in and takes ANY graph, one the tuned
+ * kernels would take included; it runs BP only, so like a graph with heavy columns it is created with osd_order = -1 only (with
+ * osd_method 0 the caller's -1 stands), the same results bit for bit.  Every entry point below dispatches on the handle;
+ * swd_bp4_info reports ranks of -1 (no elimination: they are not computed), swd_bp4_heavy_info (0, 0) (no column is special),
+ * swd_bp4_last_form threads = 1024 with the other fields 0. */
 typedef struct swd_bp4_params {
     int32_t max_iter;          /* default 32 */
     double ms_scaling_factor;
@@ -184,6 +194,11 @@ typedef struct swd_bp4_params {
 typedef struct swd_bp4 swd_bp4;
 swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *px, const double *py,
                         const double *pz, const swd_bp4_params *p, int device); /* channel_probs of hx/hz ignored */
+/* swd_bp4_create with flags: bit 0 (SWD_BP4_GENERAL_FORM) = the general form.  swd_bp4_create(...) is swd_bp4_create_ex(..., 0). */
+#define SWD_BP4_GENERAL_FORM 1
+swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *px, const double *py,
+                           const double *pz, const swd_bp4_params *p, int device, int32_t flags);
+int swd_bp4_is_general(const swd_bp4 *d); /* 1: the handle runs the general form, 0: a tuned kernel, -1: null */
 void swd_bp4_destroy(swd_bp4 *d);
 int swd_bp4_info(const swd_bp4 *d, int32_t *mx, int32_t *mz, int32_t *n, int32_t *rank_x, int32_t *rank_z);
 /* Heavy columns of the handle's graphs (both pointers nullable): how many columns the decoder treats as heavy (0: none -- the

@@ -5,17 +5,22 @@
 
 #include <mutex>
 
-#include "swd_host.h"
+#include "swd_plan.h"
 #include "swd_bp4_kernel.h"
 
 namespace swd {
 int make_layout_for_osd(const Graph &g, int nt, SwdLdsLayout &L); // swd_osdw.hip
+const char *last_error();                                          // swd_graph.hip
+// what the refusals of a graph beyond the tuned kernels end with
+#define SWD_BP4_GENERAL_HINT " (bp4_osd(..., general_form=True) takes such a graph: BP only, osd_order=-1 or camel_decode)"
 
 struct Bp4 {
     Graph gx, gz;
     swd_bp4_params p{};
     int device = 0, nt = 256, nt_osd = 256, dm = 4, n = 0;
     int heavy = 0, heavy_deg = 0; // heavy columns (weight above SWD_DMAX in Hx or Hz: the HEAVY instantiation) and the largest of their weights
+    // the general form (swd_huge_bp4.hip; swd_bp4_create_ex flag bit 0): every launch goes to it, gx / gz stay empty
+    std::unique_ptr<HugeBp4Iface> general;
     int nt_split = 0; // > 0: threads of the launch with two threads per qubit (the specialised instantiation; swd_bp4_kernel.h) // nt: threads of the BP kernel (a launch parameter), nt_osd: of the OSD kernel (its layouts)
     SwdLdsLayout Lx{}, Lz{};
     SwdBp4Layout L{};
@@ -41,8 +46,9 @@ struct Bp4 {
     std::mutex mu;
     ~Bp4() { for (auto &sl : slot) if (sl.done) (void)hipEventDestroy(sl.done); }
     // the next slot, ordered behind its previous launch on `st` (call under mu)
-    int take_slot(hipStream_t st, LaunchSlot **out) {
+    int take_slot(hipStream_t st, LaunchSlot **out, int *index = nullptr) {
         LaunchSlot &sl = slot[next_slot];
+        if (index) *index = next_slot;
         next_slot = (next_slot + 1) % kSlots;
         if (!sl.done) SWD_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
         else SWD_HIP(hipStreamWaitEvent(st, sl.done, 0));
@@ -147,6 +153,11 @@ using namespace swd;
 
 extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *px, const double *py,
                                    const double *pz, const swd_bp4_params *p, int device) {
+    return swd_bp4_create_ex(hx, hz, px, py, pz, p, device, 0);
+}
+
+extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *px, const double *py,
+                                      const double *pz, const swd_bp4_params *p, int device, int32_t flags) {
     if (!hx || !hz || !px || !py || !pz || !p) { set_error("null argument"); return nullptr; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: the MI355X decoder has no CPU fallback"); return nullptr; }
@@ -163,6 +174,27 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
     for (int v = 0; v < n; ++v) { qx[v] = px[v] + py[v]; qz[v] = pz[v] + py[v]; }
     swd_graph_desc dx = *hx, dz = *hz;
     dx.channel_probs = qx.data(); dz.channel_probs = qz.data();
+    // channel LLRs (bp4_osd.pyx:127-133)
+    std::vector<double> llr(3 * (size_t)std::max(n, 0));
+    for (int v = 0; v < n; ++v) {
+        double num = px[v] + py[v] + pz[v];
+        num = 1.0 - num;
+        llr[v] = log(num / px[v]); llr[n + v] = log(num / py[v]); llr[2 * n + v] = log(num / pz[v]);
+    }
+    if (flags & SWD_BP4_GENERAL_FORM) {
+        // decided before Graph::build, which is what refuses m > 1024: ANY graph is taken, one a tuned kernel would take included
+        // (how the tests reach this form on the recorded fixtures).  BP only, so like a graph with heavy columns it takes
+        // osd_order = -1 alone, and with osd_method "osd_0" the caller's -1 stands.
+        if (asked_order >= 0) {
+            set_error("OSD in the general form is not supported: create the decoder with osd_order=-1 (decode then returns the BP "
+                      "decisions) or use camel_decode");
+            delete d; return nullptr;
+        }
+        d->p.osd_order = -1;
+        d->general.reset(huge_bp4_create(&dx, &dz, llr.data(), device));
+        if (!d->general) { delete d; return nullptr; }
+        return (swd_bp4 *)d;
+    }
     // Heavy columns: weight above SWD_DMAX in Hx or in Hz (the last qubit of the cycle-assembled and EG codes touches every check).
     // Up to SWD_MAX_HEAVY of them, of any weight (a weight is at most m <= 1024, the lane field of an edge word), leave the ELL tables
     // for a side list; every other column stays within SWD_DMAX.
@@ -181,7 +213,7 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
             for (int v : heavy) ws.push_back(w[v]);
             std::sort(ws.begin(), ws.end(), [](int a, int b) { return a > b; });
             set_error("column weight %d exceeds this build's bound %d (accepted beside it: up to %d heavy columns of any weight up to m <= %d, "
-                      "with osd_order=-1 or camel_decode; this graph has %d columns above the bound)",
+                      "with osd_order=-1 or camel_decode; this graph has %d columns above the bound)" SWD_BP4_GENERAL_HINT,
                       ws[SWD_MAX_HEAVY], SWD_DMAX, SWD_MAX_HEAVY, SWD_MAX_M, (int)heavy.size());
             delete d; return nullptr;
         }
@@ -196,7 +228,12 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
         delete d; return nullptr;
     }
     if (d->heavy) d->p.osd_order = -1;
-    if (d->gx.build(&dx, d->heavy ? &heavy : nullptr) || d->gz.build(&dz, d->heavy ? &heavy : nullptr)) { delete d; return nullptr; }
+    if (d->gx.build(&dx, d->heavy ? &heavy : nullptr) || d->gz.build(&dz, d->heavy ? &heavy : nullptr)) {
+        const std::string why = last_error(); // (more than 1024 checks, a row or a light column past the graph tables: sizes the general form takes)
+        if (why.find("exceeds this build's limit") != std::string::npos || why.find("has weight") != std::string::npos)
+            set_error("%s" SWD_BP4_GENERAL_HINT, why.c_str());
+        delete d; return nullptr;
+    }
     const int kmin = std::min(n - d->gx.rank, n - d->gz.rank);
     if (d->p.osd_order > kmin) { // bp4_osd.pyx:92-98
         set_error("For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", kmin);
@@ -258,14 +295,7 @@ extern "C" swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_des
         L.off_hve = o; o += ((int)d->gx.hv_edge.size() + (int)d->gz.hv_edge.size()) * 4;
     }
     L.total = al(o, 16);
-    if (L.total > 160 * 1024) { set_error("code needs %d bytes of LDS per shot (> 163840)", L.total); delete d; return nullptr; }
-    // channel LLRs (bp4_osd.pyx:127-133)
-    std::vector<double> llr(3 * (size_t)n);
-    for (int v = 0; v < n; ++v) {
-        double num = px[v] + py[v] + pz[v];
-        num = 1.0 - num;
-        llr[v] = log(num / px[v]); llr[n + v] = log(num / py[v]); llr[2 * n + v] = log(num / pz[v]);
-    }
+    if (L.total > 160 * 1024) { set_error("code needs %d bytes of LDS per shot (> 163840)" SWD_BP4_GENERAL_HINT, L.total); delete d; return nullptr; }
     if (d->llr.reserve(llr.size() * 8)) { delete d; return nullptr; }
     if (hipMemcpy(d->llr.p, llr.data(), llr.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy failed"); delete d; return nullptr; }
     d->d_llr_x = d->llr.as<double>(); d->d_llr_y = d->d_llr_x + n; d->d_llr_z = d->d_llr_y + n;
@@ -282,12 +312,19 @@ extern "C" void swd_bp4_destroy(swd_bp4 *h) {
 extern "C" int swd_bp4_info(const swd_bp4 *h, int32_t *mx, int32_t *mz, int32_t *n, int32_t *rank_x, int32_t *rank_z) {
     const Bp4 *d = (const Bp4 *)h;
     if (!d) { set_error("null decoder"); return -1; }
-    if (mx) *mx = d->gx.m;
-    if (mz) *mz = d->gz.m;
+    const bool gen = d->general != nullptr; // (no elimination in the general form: the ranks are not computed, -1)
+    if (mx) *mx = gen ? d->general->mx : d->gx.m;
+    if (mz) *mz = gen ? d->general->mz : d->gz.m;
     if (n) *n = d->n;
-    if (rank_x) *rank_x = d->gx.rank;
-    if (rank_z) *rank_z = d->gz.rank;
+    if (rank_x) *rank_x = gen ? -1 : d->gx.rank;
+    if (rank_z) *rank_z = gen ? -1 : d->gz.rank;
     return 0;
+}
+
+extern "C" int swd_bp4_is_general(const swd_bp4 *h) {
+    const Bp4 *d = (const Bp4 *)h;
+    if (!d) { set_error("null decoder"); return -1; }
+    return d->general ? 1 : 0;
 }
 
 extern "C" int swd_bp4_heavy_info(const swd_bp4 *h, int32_t *count, int32_t *max_degree) {
@@ -326,7 +363,18 @@ extern "C" int swd_bp4_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8_t *sx
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(d->mu);
     Bp4::LaunchSlot *sl = nullptr;
-    if (d->take_slot(st, &sl)) return -1;
+    int slot_index = 0;
+    if (d->take_slot(st, &sl, &slot_index)) return -1;
+    if (d->general) { // no column is special and nothing is queued for an elimination: the slot lends its event and its scratch area
+        HugeBp4Io io{};
+        io.B = B; io.max_iter = d->p.max_iter; io.alpha = d->p.ms_scaling_factor; io.lpr_wanted = lpr ? 1 : 0;
+        io.sx = sx; io.sz = sz; io.out = out; io.osd0 = osd0; io.bp_dec = bp_dec; io.stats = stats; io.lpr = lpr;
+        d->form = {0, 0, 0, 0, 0, 1024, 0, 0};
+        if (d->general->launch(io, slot_index, st)) return -1;
+        SWD_HIP(hipEventRecord(sl->done, st));
+        d->last_done = sl->done; d->last_stream = st;
+        return 0;
+    }
     const bool lpr_wanted = lpr != nullptr;
     if (!lpr) {
         // every slot's buffer at the first launch of this size, not one per launch: the allocations (226 MB each for 65 536 decodes of
@@ -391,7 +439,21 @@ extern "C" int swd_bp4_camel_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(d->mu);
     Bp4::LaunchSlot *sl = nullptr;
-    if (d->take_slot(st, &sl)) return -1;
+    int slot_index = 0;
+    if (d->take_slot(st, &sl, &slot_index)) return -1;
+    if (d->general) { // the four runs of a shot are four units of the general form; the combine step is the one below
+        if (sl->cdec.reserve((size_t)4 * B * 2 * n) || sl->cpm.reserve((size_t)4 * B * 8) || sl->cst.reserve((size_t)4 * B * 2 * 4)) return -1;
+        HugeBp4Io io{};
+        io.B = B; io.camel = 1; io.max_iter = d->p.max_iter; io.alpha = d->p.ms_scaling_factor;
+        io.sx = sx; io.sz = sz;
+        io.camel_dec = sl->cdec.as<uint8_t>(); io.camel_pm = sl->cpm.as<double>(); io.camel_st = sl->cst.as<int32_t>();
+        d->form = {0, 0, 0, 0, 0, 1024, 0, 0};
+        if (d->general->launch(io, slot_index, st)) return -1;
+        hipLaunchKernelGGL(bp4_camel_select, dim3(B), dim3(256), 0, st, (int)n, io.camel_dec, io.camel_pm, io.camel_st, out, stats, min_pm);
+        SWD_HIP(hipGetLastError());
+        SWD_HIP(hipEventRecord(sl->done, st));
+        return 0;
+    }
     if (sl->lpr.reserve((size_t)4 * B * 3 * n * 8) || sl->cdec.reserve((size_t)4 * B * 2 * n) || sl->cpm.reserve((size_t)4 * B * 8) ||
         sl->cst.reserve((size_t)4 * B * 2 * 4))
         return -1;
@@ -419,7 +481,7 @@ extern "C" int swd_bp4_camel_decode_batch(swd_bp4 *h, int32_t B, const uint8_t *
     if (B <= 0) return 0;
     if (!sx || !sz || !out || !stats) { set_error("null output/input pointer"); return -1; }
     SWD_HIP(hipSetDevice(d->device));
-    const size_t n = d->n, mx = d->gx.m, mz = d->gz.m;
+    const size_t n = d->n, mx = d->general ? d->general->mx : d->gx.m, mz = d->general ? d->general->mz : d->gz.m;
     if (d->sx.reserve(B * mx) || d->sz.reserve(B * mz) || d->out.reserve(B * 2 * n) || d->stats.reserve((size_t)B * SWD_STAT_WORDS * 4) ||
         d->pm.reserve((size_t)B * 8))
         return -1;
@@ -443,7 +505,7 @@ static int bp4_decode_batch_direct(swd_bp4 *h, int32_t B, const uint8_t *sx, con
     if (B <= 0) return 0;
     if (!sx || !sz || !out || !stats) { set_error("null output/input pointer"); return -1; }
     SWD_HIP(hipSetDevice(d->device));
-    const size_t n = d->n, mx = d->gx.m, mz = d->gz.m;
+    const size_t n = d->n, mx = d->general ? d->general->mx : d->gx.m, mz = d->general ? d->general->mz : d->gz.m;
     if (d->sx.reserve(B * mx) || d->sz.reserve(B * mz) || d->out.reserve(B * 2 * n) || d->stats.reserve((size_t)B * SWD_STAT_WORDS * 4) ||
         d->lpr.reserve((size_t)B * 3 * n * 8) || d->osd0.reserve(B * 2 * n) || (bp_dec && d->bpd.reserve(B * 2 * n)))
         return -1;
@@ -469,7 +531,7 @@ extern "C" int swd_bp4_decode_batch(swd_bp4 *h, int32_t B, const uint8_t *sx, co
     if (B <= 0) return 0;
     if (!sx || !sz || !out || !stats) { set_error("null output/input pointer"); return -1; }
     SWD_HIP(hipSetDevice(d->device));
-    const size_t n = d->n, mx = d->gx.m, mz = d->gz.m;
+    const size_t n = d->n, mx = d->general ? d->general->mx : d->gx.m, mz = d->general ? d->general->mz : d->gz.m;
     // packed device buffer + pinned mirror: [ sx | sz ] in, [ out | stats | lpr | osd0 | bp_dec ] out, one copy each way
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_sx = 0, o_sz = al(B * mx), o_out = o_sz + al(B * mz), o_stats = o_out + al(B * 2 * n),

@@ -804,7 +804,7 @@ __global__ void __launch_bounds__(NT) bp4_osd_kernel(const SwdBp4Args a) {
 }
 
 // syndrome weight of every decode (both bases), for the start order of a launch: one wave per decode
-__global__ void __launch_bounds__(256) bp4_weight_kernel(const uint8_t *sx, const uint8_t *sz, int mx, int mz, int B, uint32_t *wt) {
+static __global__ void __launch_bounds__(256) bp4_weight_kernel(const uint8_t *sx, const uint8_t *sz, int mx, int mz, int B, uint32_t *wt) {
     const int b = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= B) return;
     const uint8_t *px = sx + (int64_t)b * mx, *pz = sz + (int64_t)b * mz;
@@ -819,7 +819,7 @@ __global__ void __launch_bounds__(256) bp4_weight_kernel(const uint8_t *sx, cons
 // camel_decode's choice among the four runs of a shot: the converged run of smallest path metric, strict < keeps
 // the earliest (bp4_osd.pyx:237-243); converge = min_pm < 9999 (:244-245); bp_iteration = that of the last run.
 // A shot without a converged run returns the zero vectors of a new reference object.
-__global__ void __launch_bounds__(256) bp4_camel_select(int n, const uint8_t *dec, const double *pm, const int32_t *st,
+static __global__ void __launch_bounds__(256) bp4_camel_select(int n, const uint8_t *dec, const double *pm, const int32_t *st,
                                                         uint8_t *out, int32_t *stats, double *min_pm) {
     const int b = blockIdx.x;
     double best = 10000.0;

@@ -132,6 +132,30 @@ HugeIface *huge_create(const swd_graph_desc *g, const swd_osdw_params *p, int de
 // the guessing decoders' general form (swd_huge_gdg.hip): bpgdg_decoder / bpgd_decoder / bp_history_decoder on any such graph
 HugeIface *huge_gdg_create(const swd_graph_desc *g, const swd_gdg_params *p, int device);
 
+// bp4_osd's general form (swd_huge_bp4.hip): quaternary BP without OSD on a pair of graphs of any row and column weight.  What a
+// launch of swd_bp4.hip hands over: the caller's arrays as bp4_kernel takes them, and for camel_decode the per-run arrays of the
+// launch slot that bp4_camel_select combines afterwards.
+struct HugeBp4Io {
+    int32_t B, camel, max_iter, lpr_wanted;
+    double alpha;
+    const uint8_t *sx, *sz;  // [B][mx], [B][mz]
+    uint8_t *out, *osd0, *bp_dec; // [B][2][n]; osd0 / bp_dec nullable; all unused in a camel launch
+    int32_t *stats;          // [B][SWD_STAT_WORDS]
+    double *lpr;             // nullable [B][3][n]
+    uint8_t *camel_dec;      // [4B][2][n]
+    double *camel_pm;        // [4B]
+    int32_t *camel_st;       // [4B][2]
+};
+struct HugeBp4Iface {
+    int mx = 0, mz = 0, n = 0;
+    virtual ~HugeBp4Iface() {}
+    // one launch on `stream` with the scratch area of launch slot `slot` (0 .. 3): the caller has ordered the stream behind the
+    // slot's previous launch
+    virtual int launch(const HugeBp4Io &io, int slot, void *stream) = 0;
+};
+// llr: [3][n] channel LLRs (x, y, z).  NULL with a message naming the bound when the graph is beyond the form.
+HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *llr, int device);
+
 struct Plan {
     std::unique_ptr<HugeIface> huge;
     int m0() const { return huge ? huge->m : wins[0].g->m; }

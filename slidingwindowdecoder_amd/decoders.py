@@ -470,7 +470,13 @@ class bp4_osd:
     any weight): the last qubit of the cycle-assembled and EG codes of Misc.ipynb cells 6-8, H = (H1 | 1), touches every check.
     Such a graph takes ``osd_order=-1`` only (``ValueError`` otherwise): ``camel_decode`` never runs OSD, and ``decode`` returns the
     BP decisions of a shot that did not converge.  With ``osd_method="osd0"`` -- cell 8's spelling -- the reference resets the
-    order to 0; on a graph with heavy columns the caller's -1 stands.  ``heavy_columns`` reports what the decoder found."""
+    order to 0; on a graph with heavy columns the caller's -1 stands.  ``heavy_columns`` reports what the decoder found.
+
+    ``general_form=True`` (default False) takes a graph beyond those bounds -- every column above weight 10 (the EG codes
+    [[273,111,17]] and [[1057,571,33]] of cell 8), more than 1024 checks, rows of any weight, more messages than 160 KB of LDS hold:
+    one 1024-thread workgroup per shot with every array in HBM, the same results bit for bit.  It runs BP only, so like a graph with
+    heavy columns it takes ``osd_order=-1`` (``ValueError`` otherwise) and ``camel_decode``; any graph is taken, one the tuned
+    kernels would take included.  Up to 1 048 576 qubits, 1 048 576 checks per matrix, 67 108 864 edges in all."""
 
     def __init__(self, Hx, Hz, **kwargs):
         L = _lib.lib()
@@ -499,11 +505,13 @@ class bp4_osd:
         if method == 0 and asked < 0:
             order = asked  # (swd_bp4_create resets it to 0 like the reference, except on a graph with heavy columns: include/swd.h)
         p = _lib.Bp4Params(int(kwargs.get("max_iter", 32)), float(kwargs.get("ms_scaling_factor", 1.0)), method, order)
-        self._h = L.swd_bp4_create(C.byref(self._cx.desc), C.byref(self._cz.desc), self._px.ctypes.data,
-                                   self._py.ctypes.data, self._pz.ctypes.data, C.byref(p), self.device)
+        self._h = L.swd_bp4_create_ex(C.byref(self._cx.desc), C.byref(self._cz.desc), self._px.ctypes.data,
+                                      self._py.ctypes.data, self._pz.ctypes.data, C.byref(p), self.device,
+                                      1 if kwargs.get("general_form", False) else 0)
         if not self._h:
             msg = _lib.last_error()
-            if "OSD order" in msg or "invalid" in msg or "blocklength" in msg or "heavy columns" in msg or "column weight" in msg:
+            if "OSD order" in msg or "invalid" in msg or "blocklength" in msg or "heavy columns" in msg or "column weight" in msg \
+                    or "the general form" in msg or "general form limit" in msg:
                 raise ValueError(msg)
             raise RuntimeError(f"swd_bp4_create failed: {msg}")
         i = [C.c_int32() for _ in range(5)]
@@ -566,9 +574,15 @@ class bp4_osd:
         return out, stats
 
     @property
+    def general_form(self):
+        """True when the decoder runs the general form (``general_form=True`` at construction; include/swd.h swd_bp4_is_general)."""
+        return _lib.lib().swd_bp4_is_general(self._h) == 1
+
+    @property
     def heavy_columns(self):
         """(count, largest weight) of the columns the decoder treats as heavy (include/swd.h swd_bp4_heavy_info); (0, 0) for a
-        graph within the column-weight bound, which takes the kernel forms ``last_form`` reports."""
+        graph within the column-weight bound, which takes the kernel forms ``last_form`` reports, and in the general form, where
+        no column is special."""
         c, d = C.c_int32(), C.c_int32()
         if _lib.lib().swd_bp4_heavy_info(self._h, C.byref(c), C.byref(d)):
             raise RuntimeError(f"swd_bp4_heavy_info failed: {_lib.last_error()}")
@@ -1510,7 +1524,8 @@ class CodeCapacityExperiment:
     Pauli errors from ``channel_probs_x / _y / _z`` (``PauliSampler``), ``bp4_osd(Hx, Hz, **decoder_kwargs)``, and the criterion
     ``(dz @ hz_perp.T).any() or (dx @ hx_perp.T).any()`` on the difference of estimate and error.  Cell 8's own codes -- the
     cycle-assembled and EG codes whose last qubit touches every check -- pass as ``(Hx, Hz)`` with ``osd_order=-1``
-    (``bp4_osd``: up to 8 heavy columns); the sampler and the accounting have no degree bound.
+    (``bp4_osd``: up to 8 heavy columns; ``general_form=True`` among the decoder's keyword arguments takes any graph, such as
+    the EG codes [[273,111,17]] and [[1057,571,33]]); the sampler and the accounting have no degree bound.
     ``decoder`` in ``osd_window``, ``bpgdg_decoder``, ``bpgd_decoder``, ``bp_history_decoder`` is the single-basis harness of
     /root/reference/src/simulation.py: errors Bernoulli(``channel_probs``) (``DemSampler`` with ``chk = Hx``), syndrome
     ``err @ hx.T``, ``decoder(Hx, **decoder_kwargs)``, criterion ``(d @ hz_perp.T).any()``.
