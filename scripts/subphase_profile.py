@@ -20,7 +20,7 @@ _, stats, _ = dec.decode_device(d); torch.cuda.synchronize()
 prof = dec.get_profile(shots).astype(np.float64) / 100.0  # us
 cls = stats.cpu().numpy()[..., 0] & 0xFF
 names = {"init": ["ticket + wait + state load", "reset loops", "cache pack / loads", "barrier", "bp_init", "check caches", "rest of the unit after set-up", "epilogue (after the window's decode)"],
-         "shorten": ["(std) init", "livemask rebuild + contradiction test", "backup + peel rounds", "compaction, slot lists, degree histogram", "cn_assign + caches + bp_init", "(std)", "(std)", "(std)"]}[kind]
+         "shorten": ["(std) init", "livemask rebuild + contradiction test", "backup + peel rounds", "compaction, slot lists, degree histogram", "cn_assign + caches + bp_init", "key build + staged columns + column select", "(std)", "(std)"]}[kind]
 sel = np.ones_like(cls, bool) if kind == "init" else (cls != 0)
 for i, nme in enumerate(names):
     print(f"{nme:48s} mean {prof[..., i][sel].mean():8.2f} us over {int(sel.sum())} windows")

@@ -724,8 +724,11 @@ template <bool D = false> __device__ __forceinline__ void lm_set(Lds &s, int l, 
 
 // grp = 1, 2 or 4 threads share a check (adjacent lanes of a quad): thread `sub` walks positions sub, sub + grp, ...
 // (tuned kernels: 48-bit live masks, original degrees from the graph)
-template <int NT, int KG, bool FULL, int SH>
-__device__ __forceinline__ void cn_cache_load(const SwdGraphDev &g, Lds &s, bool uselist, int lc, int sub, int grp, CnCacheP<KG, SH> &cc) {
+// REMAP (sorted form of the shortened graph): the listed slots are old slot numbers, remap[old slot] is the renumbered cell; the far slot
+// of the dead positions is no old slot and stays as it is
+template <int NT, int KG, bool FULL, bool REMAP = false, int SH>
+__device__ __forceinline__ void cn_cache_load(const SwdGraphDev &g, Lds &s, bool uselist, int lc, int sub, int grp, CnCacheP<KG, SH> &cc,
+                                              [[maybe_unused]] const uint16_t *remap = nullptr) {
     constexpr bool DIET = SWD_P16(NT);
     const int m = g.m, dummy = swd_slot_far(g);
     const bool act = (lc >= 0) && (lc < m) && (s.cn_val[lc >= 0 ? lc : 0] >= 0);
@@ -744,8 +747,10 @@ __device__ __forceinline__ void cn_cache_load(const SwdGraphDev &g, Lds &s, bool
     for (int kk = 0; kk < KG * 4; ++kk) {
         const int k = kk * grp + sub;
         int sv = dummy;
-        if (k < cnt && ((lmask >> (k & 63)) & 1ull))
-            sv = bylist ? (int)s.lslot[k * m + l] : (int)s.jptr[k] + l;
+        if (k < cnt && ((lmask >> (k & 63)) & 1ull)) {
+            if constexpr (REMAP) sv = bylist ? (int)remap[s.lslot[k * m + l]] : (int)s.jptr[k] + l;
+            else sv = bylist ? (int)s.lslot[k * m + l] : (int)s.jptr[k] + l;
+        }
         cc.set_slot(kk, sv);
     }
 }
@@ -1263,6 +1268,17 @@ template <bool D = false> __device__ __forceinline__ void vn_decide(Lds &s, int 
     if constexpr (D) atomicOr(&((uint32_t *)s.vn_val)[v >> 5], 1u << (v & 31));
     else s.vn_val[v] = (int8_t)val;
     s.hard[v] = (uint8_t)val;
+}
+// Bit form, peeling rounds without a backup: only the thread that sets the node's bit writes its value -- a second check that forces the
+// same node in the same round either agrees or shows up as a contradiction in the update pass, whichever value stands -- and it notes the
+// node in `set` and the hard decision it replaces in `old`, from which the bad-peel exit undoes the rounds.
+__device__ __forceinline__ void vn_decide_once(Lds &s, int v, int val, uint32_t *old, uint32_t *set) {
+    const uint32_t bit = 1u << (v & 31);
+    if (!(atomicOr(&((uint32_t *)s.vn_val)[v >> 5], bit) & bit)) {
+        atomicOr(&set[v >> 5], bit);
+        if (s.hard[v]) atomicOr(&old[v >> 5], bit);
+        s.hard[v] = (uint8_t)val;
+    }
 }
 template <int NT, bool D = false> __device__ __forceinline__ void vn_reset(Lds &s, int n) {
     if constexpr (D) {
@@ -2931,6 +2947,9 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
                               const uint8_t *synd, double *hist_b, uint8_t *osd0_b, uint8_t *bpdec_b, WinResult &R, const uint32_t *cn_map,
                               VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> &vraw, const bool want_pm) {
     constexpr bool DIET = SWD_P16(NT); // the tuned kernels' LDS forms (decided-node bits, 48-bit live masks, no copy of the check degrees)
+    // The fused passes between the two BP phases (round 12), the tuned kernels of up to 256 threads only: staged columns in 8-byte words,
+    // slot lists renumbered as the check caches read them, no backup in front of the peeling rounds
+    constexpr bool kFuse = DIET && !BIG;
     if constexpr (DIET) s.lm_m = (L.off_par - L.off_livemask < 8 * g.m) ? g.m : 0; // m if the masks are stored in the 48-bit form
     // Tuned kernels: the parity WORDS of the iterations lie over the live masks, which nothing reads while bp_run is running (the full-
     // graph caches never look at them, the shortening step rebuilds them from scratch, the shortened graph's caches are loaded before
@@ -3085,7 +3104,17 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     }
     // columns of the edges, by slot: the shortening step walks them several times
     uint16_t *rc = (uint16_t *)(s.scratch + L.off_rc);
-    for (int e = tid; e < g.E; e += NT) rc[e] = g.row_col[e];
+    if constexpr (kFuse) {
+        // four columns per load and store (the table starts on a 256-byte boundary of the graph's image, off_rc on a 16-byte one); the
+        // last E mod 4 columns one by one
+        const int e4 = g.E >> 2;
+        const uint64_t *src = (const uint64_t *)g.row_col;
+        uint64_t *dst = (uint64_t *)rc;
+        for (int i = tid; i < e4; i += NT) dst[i] = src[i];
+        for (int e = 4 * e4 + tid; e < g.E; e += NT) rc[e] = g.row_col[e];
+    } else {
+        for (int e = tid; e < g.E; e += NT) rc[e] = g.row_col[e];
+    }
     __syncthreads();
     // ---- shortening: decide cols[new_n:] = 0 (osd_window.pyx:178-183)
     if (g.new_n < n) {
@@ -3142,6 +3171,21 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     }
     for (int v = tid; v < n; v += NT)
         if (vn_decided<DIET>(s, v)) s.hard[v] = 0; // (every decided node so far was decided 0)
+    // Tuned kernels of up to 256 threads: no backup of the pre-peel state.  Two bit sets over the nodes, behind the degree bytes of the
+    // sorted form, record what the peeling rounds decide (pk_set) and the hard decision those nodes had before (pk_old); the bad-peel
+    // exit undoes the rounds from them and rebuilds the check state as the mask walk above made it.
+    [[maybe_unused]] uint32_t *pk_old = (uint32_t *)(s.scratch + L.off_bak + ((n + 3) & ~3)), *pk_set = pk_old + (n + 31) / 32;
+    if constexpr (kFuse) {
+        for (int i = tid; i < 2 * ((n + 31) / 32); i += NT) pk_old[i] = 0u;
+        // the degree histogram and the degree bytes of the compaction step are zeroed here, in front of a barrier that is needed anyway:
+        // nothing touches either region (off_cord, off_bak) until the compaction's atomics, which come behind the barriers of the peel
+        int *dh = (int *)(s.scratch + L.off_cord);
+        for (int i = tid; i < 65; i += NT) dh[i] = 0;
+        if (swd_post_sorted_built(NT, VF, BIG, SWD_OSDW_TUNED != 0) && SWD_POST_SORTED_TAKEN(L.post_lds, SWD_POST_LISTS_TAKEN(L.off_lslot), g.new_n, NT)) {
+            uint32_t *dz = (uint32_t *)(s.scratch + L.off_bak);
+            for (int i = tid; i < (n + 3) / 4; i += NT) dz[i] = 0u;
+        }
+    }
     __syncthreads();
     // ---- peel (osd_window.pyx:184-186).  Degree-1 checks force their last VN; the closure of these
     // forced values does not depend on the order they are applied in, and a contradiction shows up
@@ -3150,10 +3194,12 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     // partial result the reference leaves behind depends on that order).
     {
         char *bak = s.scratch + L.off_bak;
-        vn_backup<NT, DIET>(s, n, bak);
-        for (int i = tid; i < m; i += NT) {
-            bak[2 * n + i] = (char)s.cn_val[i]; bak[2 * n + m + i] = (char)s.cn_deg[i];
-            ((uint64_t *)(bak + ((2 * n + 2 * m + 7) & ~7)))[i] = lm_get<DIET>(s, i);
+        if constexpr (!kFuse) {
+            vn_backup<NT, DIET>(s, n, bak);
+            for (int i = tid; i < m; i += NT) {
+                bak[2 * n + i] = (char)s.cn_val[i]; bak[2 * n + m + i] = (char)s.cn_deg[i];
+                ((uint64_t *)(bak + ((2 * n + 2 * m + 7) & ~7)))[i] = lm_get<DIET>(s, i);
+            }
         }
         bool bad = false;
         for (;;) {
@@ -3163,7 +3209,8 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
                     const int j = __ffsll((long long)lm_get<DIET>(s, l)) - 1;
                     const int v = rc[s.jptr[j] + l];
                     const int8_t val = s.cn_val[l];
-                    vn_decide<DIET>(s, v, val);
+                    if constexpr (kFuse) vn_decide_once(s, v, val, pk_old, pk_set);
+                    else vn_decide<DIET>(s, v, val);
                     fired = true;
                 }
             }
@@ -3185,10 +3232,38 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
             if (block_any<NT>(bad, s)) { bad = true; break; }
         }
         if (bad) {
-            vn_restore<NT, DIET>(s, n, bak);
-            for (int i = tid; i < m; i += NT) {
-                s.cn_val[i] = (int8_t)bak[2 * n + i]; s.cn_deg[i] = (uint8_t)bak[2 * n + m + i];
-                lm_set<DIET>(s, i, ((uint64_t *)(bak + ((2 * n + 2 * m + 7) & ~7)))[i]);
+            if constexpr (kFuse) {
+                // back to the state in front of the rounds: the nodes they decided are live again with the hard decision they had, ...
+                for (int i = tid; i < (n + 31) / 32; i += NT) {
+                    uint32_t w = pk_set[i];
+                    const uint32_t o = pk_old[i];
+                    if (w) ((uint32_t *)s.vn_val)[i] &= ~w;
+                    while (w) {
+                        const int b = __ffs((int)w) - 1;
+                        w &= w - 1;
+                        s.hard[32 * i + b] = (uint8_t)((o >> b) & 1u);
+                    }
+                }
+                __syncthreads();
+                // ... and the check state is what the mask walk made of the syndrome and the decided set (no check is empty and unsatisfied)
+                for (int l = tid; l < m; l += NT) {
+                    const int d = g.row_deg[l];
+                    uint64_t mk = 0;
+                    int cntl = 0;
+                    for (int j = 0; j < d; ++j) {
+                        const int v = rc[s.jptr[j] + l];
+                        if (!vn_decided<DIET>(s, v)) { mk |= 1ull << j; ++cntl; }
+                    }
+                    int cv = synd[g.perm[l]] ? 1 : 0;
+                    if (cntl == 0 && cv == 0) cv = -1;
+                    lm_set<DIET>(s, l, mk); s.cn_deg[l] = (uint8_t)cntl; s.cn_val[l] = (int8_t)cv;
+                }
+            } else {
+                vn_restore<NT, DIET>(s, n, bak);
+                for (int i = tid; i < m; i += NT) {
+                    s.cn_val[i] = (int8_t)bak[2 * n + i]; s.cn_deg[i] = (uint8_t)bak[2 * n + m + i];
+                    lm_set<DIET>(s, i, ((uint64_t *)(bak + ((2 * n + 2 * m + 7) & ~7)))[i]);
+                }
             }
             __syncthreads();
             if (tid < 64) {
@@ -3224,12 +3299,14 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     bool sorted = false;
     if constexpr (kSorted) sorted = SWD_POST_SORTED_TAKEN(L.post_lds, uselist, g.new_n, NT);
     uint32_t *deg32 = (uint32_t *)(s.scratch + L.off_bak); // [n] bytes, four per word
-    for (int i = tid; i < 65; i += NT) dhist[i] = 0;
-    if constexpr (kSorted) {
-        if (sorted)
-            for (int i = tid; i < (n + 3) / 4; i += NT) deg32[i] = 0u;
+    if constexpr (!kFuse) { // (kFuse: both were zeroed in front of the peeling rounds, whose barriers stand between those stores and the atomics below)
+        for (int i = tid; i < 65; i += NT) dhist[i] = 0;
+        if constexpr (kSorted) {
+            if (sorted)
+                for (int i = tid; i < (n + 3) / 4; i += NT) deg32[i] = 0u;
+        }
+        __syncthreads(); // the histogram (and the degree bytes) are zero before the first atomic below
     }
-    __syncthreads(); // the histogram (and the degree bytes) are zero before the first atomic below
     {
         int lc = 0, le = 0;
         for (int l = tid; l < m; l += NT)
@@ -3323,14 +3400,21 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
             gp.E = g.D * nlive;
             if constexpr (BIG) s.msg = (double *)(s.hard - L.off_hard + L.off_pmsg); // the LDS block starts off_hard bytes below s.hard
             vn_cache_load_compact<NT, VFX, DM>(gp, s, nlive, vcx, remap, kc);
-            __syncthreads();
-            for (int l = tid; l < m; l += NT)
-                if (s.cn_val[l] >= 0) {
-                    const int d = s.cn_deg[l];
-                    for (int k = 0; k < d; ++k) s.lslot[k * m + l] = remap[s.lslot[k * m + l]];
-                }
-            __syncthreads();
-            cn_cache_load<NT, KGX, false>(gp, s, uselist, clc, csub, cgrp, cnx);
+            __syncthreads(); // remap[] is written by the nodes' threads and read below by the checks' threads
+            if constexpr (kFuse) {
+                // The slot lists are renumbered as they are read: the rewrite pass and the barrier behind it are gone.  Hazard: the lists were
+                // written by the compaction pass (barriers since), only this thread reads the list of the check it serves, and the barrier
+                // below still orders every read of lslot[] / remap[] before bp_init overwrites the region.
+                cn_cache_load<NT, KGX, false, true>(gp, s, uselist, clc, csub, cgrp, cnx, remap);
+            } else {
+                for (int l = tid; l < m; l += NT)
+                    if (s.cn_val[l] >= 0) {
+                        const int d = s.cn_deg[l];
+                        for (int k = 0; k < d; ++k) s.lslot[k * m + l] = remap[s.lslot[k * m + l]];
+                    }
+                __syncthreads();
+                cn_cache_load<NT, KGX, false>(gp, s, uselist, clc, csub, cgrp, cnx);
+            }
             __syncthreads(); // every lane has read its slot list before the messages are re-initialised
             bp_init<VFX, DM>(s, vcx);
             __syncthreads();
@@ -3966,6 +4050,7 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
                 for (int k = 0; k < 8; ++k) { pr[k] = s.scal[20 + k]; s.scal[20 + k] = 0; }
 #endif
 #ifdef SWD_SHPROF
+                pr[5] = R.t[3] ? R.t[3] - R.t[2] : 0; // (the column select, which the four words below overwrite)
                 pr[1] = s.scal[20]; pr[2] = s.scal[21]; pr[3] = s.scal[22]; pr[4] = s.scal[23];
                 if (tid == 0) { s.scal[20] = s.scal[21] = s.scal[22] = s.scal[23] = 0; }
 #endif
