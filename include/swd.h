@@ -603,6 +603,25 @@ int swd_pipeline_node_depth(const swd_pipeline *pl);
 int swd_graph_node_depth(const swd_graph_desc *g, int32_t pads, int32_t nt, int32_t vf, const int32_t *depth, int32_t *info,
                          uint16_t *vdord, uint32_t *vn_edge_d, double *llr_d, uint32_t *vn_edge, double *llr);
 
+/* Cache image (csrc/swd_graph.h, SwdGraphDev::img_*): the osd_window kernels of up to 256 threads load the full graph's register
+ * caches ready-made, packed once per graph when a handle is created.  diagnostics, host only: the image of graph g as a pipeline that
+ * launches the kernel variant <nt, vf, dm, kg> would build it with up to `pads` pad cells -- depth NULL: the uniform node part (row i of
+ * thread role t serves column t + i * nt over dm positions), else depth[vf]: the node part of that depth profile (listed node
+ * t + i * nt of the depth order over depth[i] positions; the graph must fit) and the layout of such a plan.  In 16-byte chunks,
+ * chunk-major and role-minor: word w of role t is at ((w / 4) * nt + t) * 4 + w % 4.
+ *   node part, words of a role in order: the prior of each row (low word, high word; +0.0 for a row without a node); then for each row
+ *   its edge positions two per word (low half first) as byte offsets of their message cells, slot << 3; then for each row the
+ *   positions' checks as lane << 2.  A row takes its depth rounded up to whole pairs; a position without an edge holds the byte
+ *   offset of cell slots + 1 + nt / 64 + t / 64 and the check m << 2.
+ *   check part, role t = lane t: positions 0 .. 4 kg - 1 two per word as byte offsets (jptr[k] + t) << 3, beyond the check's
+ *   degree (and for t >= m) the offset of cell slots + 1 + t / 64; then one word (t, or 0xFFFF for t >= m) | degree << 16 | degree << 24.
+ * info[8] = { slots, K, D, chunks of the node part, chunks of the check part, pad cells used, 0, 0 }; img_vn [chunks * nt * 4], img_cn
+ * likewise, and the tables the image was packed from: jptr [K + 1], row_deg [m] by lane, vn_edge [D * n] / llr [n] in the order the
+ * node part serves (columns, or the depth order).  Any array may be NULL: call once with NULL arrays for the sizes. */
+int swd_graph_cache_image(const swd_graph_desc *g, int32_t pads, int32_t nt, int32_t vf, int32_t dm, int32_t kg, const int32_t *depth,
+                          int32_t *info, uint32_t *img_vn, uint32_t *img_cn, uint16_t *jptr, uint8_t *row_deg, uint32_t *vn_edge,
+                          double *llr);
+
 /* diagnostics: which forms of the window kernels (csrc/swd_osdw_kernel.h, pipeline_kernel) a plan takes.  The kernel variant, the
  * LDS-resident or large-graph form and each window's LDS layout decide which code a launch runs; these calls report the decision,
  * taken by the code that builds a handle (csrc/swd_plan.h, Plan::select_forms) and by the conditions the kernels themselves test

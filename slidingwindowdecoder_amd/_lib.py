@@ -131,6 +131,7 @@ SYMBOLS = [
     ("swd_diag_occupy",C.c_int, [C.c_int, _i32, _i32, _i32, _i32, _vp]),
     ("swd_graph_layout", C.c_int, [C.POINTER(GraphDesc), _i32] + [_vp] * 9),
     ("swd_graph_node_depth", C.c_int, [C.POINTER(GraphDesc), _i32, _i32, _i32, _vp] + [_vp] * 6),
+    ("swd_graph_cache_image", C.c_int, [C.POINTER(GraphDesc), _i32, _i32, _i32, _i32, _i32, _vp] + [_vp] * 7),
     ("swd_osdw_node_depth", C.c_int, [_vp]),
     ("swd_pipeline_node_depth", C.c_int, [_vp]),
     ("swd_window_forms", C.c_int, [_i32, _vp, _i32, C.POINTER(OsdwParams), C.POINTER(GdgParams), _vp, _vp]),

@@ -49,6 +49,13 @@ struct SwdGraphDev {
     const uint16_t *vdord;     // [n]
     const uint32_t *vn_edge_d; // [D*n]
     const double *llr_d;       // [n]
+    // Cache image (graphs of plans that launch the tuned osd_window kernels of up to SWD_TUNED_NT threads; null otherwise): the full
+    // graph's register caches as those kernels hold them after their set-up, packed once on the host (swd_graph.hip, Graph::fill_image;
+    // the word order is SwdCacheImg's, swd_osdw_kernel.h).  In 16-byte chunks, chunk-major and role-minor: chunk q of thread role r
+    // is words (q * nt + r) * 4 .. + 3, so a wave loads a chunk from consecutive addresses.
+    const uint32_t *img_vn;    // node part by role vtid, uniform depth: columns vtid + i * nt
+    const uint32_t *img_vn_d;  // ... of the plan's depth profile: listed nodes vtid + i * nt (null without a profile)
+    const uint32_t *img_cn;    // check part by role ctid: the check of lane ctid
 };
 
 // Heavy columns (weight above what the ELL tables hold; asked for by swd_bp4_create only): a side list beside the tables above,

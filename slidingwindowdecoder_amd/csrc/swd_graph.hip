@@ -136,6 +136,56 @@ bool Graph::fits_depth(const int *depth, int vf, int nt) const {
     return true;
 }
 
+// The cache image (swd_graph.h): per thread role exactly the registers the tuned osd_window kernel <nt, vf, dm, kg> holds when its
+// set-up built them from the tables -- VnCacheP<vf, dm, 0, false>::llr / edp / par (byte offsets of the message cells, parity-word
+// byte offsets lane << 2, m << 2 for a dead position) and CnCacheP<kg>::slp with cnt / live / l in one word behind them.  A dead node
+// position points at the zero slot of the role's wave, cell S + 1 + nt / 64 + (role >> 6), a dead check position at its far slot,
+// cell S + 1 + (role >> 6).  Word order: SwdCacheImg (swd_osdw_kernel.h).
+void Graph::fill_image(int nt, int vf, int dm, int kg, const int *depth) {
+    const int waves = nt / 64;
+    auto node_part = [&](const std::vector<uint32_t> &et, const std::vector<double> &lt, const int *dep, std::vector<uint32_t> &out) {
+        int pw = 0; // words of edp[][] = words of par[][] per thread: row i keeps its depth in whole pairs
+        for (int i = 0; i < vf; ++i) pw += (std::min(dep ? dep[i] : dm, dm) + 1) / 2;
+        const int chunks = (2 * vf + 2 * pw + 3) / 4;
+        out.assign((size_t)chunks * nt * 4, 0u);
+        std::vector<uint32_t> w((size_t)chunks * 4);
+        for (int t = 0; t < nt; ++t) {
+            std::fill(w.begin(), w.end(), 0u);
+            const uint32_t dead = (uint32_t)(S + 1 + waves + (t >> 6)) << 3, nopar = (uint32_t)m << 2;
+            int at = 2 * vf;
+            for (int i = 0; i < vf; ++i) {
+                const int idx = t + i * nt, kd = std::min(dep ? dep[i] : dm, dm);
+                const bool valid = idx < n;
+                const double l = valid ? lt[idx] : 0.0;
+                uint64_t lb;
+                memcpy(&lb, &l, 8);
+                w[2 * i] = (uint32_t)lb; w[2 * i + 1] = (uint32_t)(lb >> 32);
+                for (int k = 0; k < ((kd + 1) & ~1); ++k) {
+                    const uint32_t e = (valid && k < kd && k < D) ? et[(size_t)k * n + idx] : SWD_PAD_EDGE;
+                    const uint32_t ed = (e != SWD_PAD_EDGE) ? swd_edge_slot(e) << 3 : dead, ph = (e != SWD_PAD_EDGE) ? swd_edge_lane(e) << 2 : nopar;
+                    w[at + (k >> 1)] |= ed << (16 * (k & 1));
+                    w[at + pw + (k >> 1)] |= ph << (16 * (k & 1));
+                }
+                at += (kd + 1) / 2;
+            }
+            for (int q = 0; q < chunks; ++q) memcpy(&out[((size_t)q * nt + t) * 4], &w[(size_t)q * 4], 16);
+        }
+    };
+    node_part(vn_edge, llr, nullptr, img_vn);
+    if (depth) node_part(vn_edge_d, llr_d, depth, img_vn_d); else img_vn_d.clear();
+    const int chunks = (2 * kg + 1 + 3) / 4;
+    img_cn.assign((size_t)chunks * nt * 4, 0u);
+    std::vector<uint32_t> w((size_t)chunks * 4);
+    for (int t = 0; t < nt; ++t) {
+        std::fill(w.begin(), w.end(), 0u);
+        const int cnt = (t < m) ? (int)row_deg[t] : 0;
+        const uint32_t far = (uint32_t)(S + 1 + (t >> 6)) << 3;
+        for (int k = 0; k < 4 * kg; ++k) w[k >> 1] |= ((k < cnt) ? (uint32_t)(jptr[k] + t) << 3 : far) << (16 * (k & 1));
+        w[2 * kg] = ((t < m) ? (uint32_t)t : 0xFFFFu) | ((uint32_t)cnt << 16) | ((uint32_t)cnt << 24);
+        for (int q = 0; q < chunks; ++q) memcpy(&img_cn[((size_t)q * nt + t) * 4], &w[(size_t)q * 4], 16);
+    }
+}
+
 // LDS-array cycles of one variable-node pass over the full graph, from the tables: thread t serves column t (listed: the node at
 // position t of the depth order -- 32 resp. 16 consecutive listed positions make a group), edge index k, one 8-byte cell per lane.  ds_read_b64 is served in aligned groups of 32 lanes, bank = cell mod 32; ds_write_b64 in aligned groups
 // of 16 lanes, bank = cell mod 16.  A group costs the largest number of (distinct) cells on one bank.
@@ -370,7 +420,10 @@ int Graph::upload() {
     size_t o_vdord = al(o_llr + llr.size() * 8);
     size_t o_vnedge_d = al(o_vdord + vdord.size() * 2);
     size_t o_llr_d = al(o_vnedge_d + vn_edge_d.size() * 4);
-    size_t total = al(o_llr_d + llr_d.size() * 8);
+    size_t o_imgvn = al(o_llr_d + llr_d.size() * 8);
+    size_t o_imgvnd = al(o_imgvn + img_vn.size() * 4);
+    size_t o_imgcn = al(o_imgvnd + img_vn_d.size() * 4);
+    size_t total = al(o_imgcn + img_cn.size() * 4);
     // (the side list of heavy columns behind everything else, only when there is one: the other graphs' images are unchanged)
     const size_t nh = hv_id.size();
     const size_t o_hvid = total, o_hvdeg = al(o_hvid + nh * 4), o_hvptr = al(o_hvdeg + nh * 4), o_hvedge = al(o_hvptr + (nh + 1) * 4);
@@ -394,6 +447,9 @@ int Graph::upload() {
     memcpy(&h[o_vdord], vdord.data(), vdord.size() * 2);
     memcpy(&h[o_vnedge_d], vn_edge_d.data(), vn_edge_d.size() * 4);
     memcpy(&h[o_llr_d], llr_d.data(), llr_d.size() * 8);
+    if (!img_vn.empty()) memcpy(&h[o_imgvn], img_vn.data(), img_vn.size() * 4);
+    if (!img_vn_d.empty()) memcpy(&h[o_imgvnd], img_vn_d.data(), img_vn_d.size() * 4);
+    if (!img_cn.empty()) memcpy(&h[o_imgcn], img_cn.data(), img_cn.size() * 4);
     if (dev.reserve(total)) return -1;
     SWD_HIP(hipMemcpy(dev.p, h.data(), total, hipMemcpyHostToDevice));
     char *b = (char *)dev.p;
@@ -410,6 +466,9 @@ int Graph::upload() {
     d.vdord = (const uint16_t *)(b + o_vdord);
     d.vn_edge_d = (const uint32_t *)(b + o_vnedge_d);
     d.llr_d = (const double *)(b + o_llr_d);
+    d.img_vn = img_vn.empty() ? nullptr : (const uint32_t *)(b + o_imgvn);
+    d.img_vn_d = img_vn_d.empty() ? nullptr : (const uint32_t *)(b + o_imgvnd);
+    d.img_cn = img_cn.empty() ? nullptr : (const uint32_t *)(b + o_imgcn);
     hv = SwdHeavyDev{};
     if (nh) {
         hv.count = (int32_t)nh; hv.edges = (int32_t)hv_edge.size();
@@ -467,6 +526,33 @@ extern "C" int swd_graph_node_depth(const swd_graph_desc *g, int32_t pads, int32
     if (llr_d) memcpy(llr_d, G.llr_d.data(), G.llr_d.size() * 8);
     if (vn_edge) memcpy(vn_edge, G.vn_edge.data(), G.vn_edge.size() * 4);
     if (llr) memcpy(llr, G.llr.data(), G.llr.size() * 8);
+    return 0;
+}
+
+extern "C" int swd_graph_cache_image(const swd_graph_desc *g, int32_t pads, int32_t nt, int32_t vf, int32_t dm, int32_t kg, const int32_t *depth,
+                                     int32_t *info, uint32_t *img_vn, uint32_t *img_cn, uint16_t *jptr, uint8_t *row_deg, uint32_t *vn_edge,
+                                     double *llr) {
+    swd::Graph G;
+    if (G.build(g)) return -1;
+    if (nt < 64 || nt % 64 || vf <= 0 || vf > 64 || dm <= 0 || dm % 2 || kg <= 0) { swd::set_error("swd_graph_cache_image: nt a multiple of 64, 0 < vf <= 64, dm even, kg > 0"); return -1; }
+    if (G.m > nt || G.n > (long)nt * vf || G.D > dm || G.K > 4 * kg) { swd::set_error("swd_graph_cache_image: the graph does not fit a <%d, %d, %d, %d> kernel", nt, vf, dm, kg); return -1; }
+    int dep[64];
+    for (int i = 0; i < vf && depth; ++i) dep[i] = depth[i];
+    if (depth && !G.fits_depth(dep, vf, nt)) { swd::set_error("swd_graph_cache_image: the graph does not fit the depth profile"); return -1; }
+    if (!swd::natural_layout_requested()) G.optimize_layout(pads, depth != nullptr);
+    if ((G.S + 1 + 2 * (nt / 64)) * 8 > 65536) { swd::set_error("swd_graph_cache_image: %d message slots exceed 16-bit byte offsets", G.S); return -1; }
+    G.fill_image(nt, vf, dm, kg, depth ? dep : nullptr);
+    const std::vector<uint32_t> &vn = depth ? G.img_vn_d : G.img_vn;
+    if (info) {
+        const int32_t v[8] = {G.S, G.K, G.D, (int32_t)(vn.size() / ((size_t)nt * 4)), (int32_t)(G.img_cn.size() / ((size_t)nt * 4)), G.S - G.E, 0, 0};
+        memcpy(info, v, sizeof v);
+    }
+    if (img_vn) memcpy(img_vn, vn.data(), vn.size() * 4);
+    if (img_cn) memcpy(img_cn, G.img_cn.data(), G.img_cn.size() * 4);
+    if (jptr) memcpy(jptr, G.jptr.data(), G.jptr.size() * 2);
+    if (row_deg) memcpy(row_deg, G.row_deg.data(), G.row_deg.size());
+    if (vn_edge) memcpy(vn_edge, (depth ? G.vn_edge_d : G.vn_edge).data(), G.vn_edge.size() * 4);
+    if (llr) memcpy(llr, (depth ? G.llr_d : G.llr).data(), G.llr.size() * 8);
     return 0;
 }
 

@@ -113,6 +113,10 @@ struct Graph {
     void fill_depth();
     // every listed node i * nt .. (i + 1) * nt - 1 that exists has degree <= depth[i], for each of the vf cache rows
     bool fits_depth(const int *depth, int vf, int nt) const;
+    // cache image of the graph for the tuned osd_window kernel <nt, vf, dm, kg> (swd_graph.h, SwdGraphDev::img_*): after the layout is
+    // final, before upload().  depth (nullable): the plan's depth profile -- both node parts are then built, the uniform one alone otherwise
+    std::vector<uint32_t> img_vn, img_vn_d, img_cn;
+    void fill_image(int nt, int vf, int dm, int kg, const int *depth);
     int upload();                          // hipMalloc + copy, fills d
 };
 

@@ -418,101 +418,76 @@ struct VnCacheP {
 __device__ __forceinline__ int swd_slot_far(const SwdGraphDev &g) { return g.E + 1 + (int)(threadIdx.x >> 6); }
 template <int NT>
 __device__ __forceinline__ int swd_slot_zero(const SwdGraphDev &g) { return g.E + 1 + NT / 64 + (int)(threadIdx.x >> 6); }
+// The two slots as the routines of a register cache with shift SH number them.  SH == 0 -- the byte-offset caches, which only the tuned
+// osd_window kernels of up to SWD_TUNED_NT threads hold -- numbers them by the wave's ROLE: those kernels take the full graph's caches
+// from the graph's host-packed image (SwdCacheImg below), whose rows belong to roles, not to physical waves -- the zero slot goes with
+// the node part (vtid), the far slot with the check part (ctid).  Any bijection of the waves is correct: a wave only ever touches its
+// own slot in the pass that uses it.  Every other cache keeps the physical wave.
+template <int SH>
+__device__ __forceinline__ int swd_slot_far_of(const SwdGraphDev &g, const Lds &s) {
+    if constexpr (SH == 0) return g.E + 1 + (s.ctid >> 6);
+    else return swd_slot_far(g);
+}
+template <int NT, int SH>
+__device__ __forceinline__ int swd_slot_zero_of(const SwdGraphDev &g, const Lds &s) {
+    if constexpr (SH == 0) return g.E + 1 + NT / 64 + (s.vtid >> 6);
+    else return swd_slot_zero<NT>(g);
+}
 
 // remap != nullptr (shortened graph, BIG kernels with the post-phase messages in LDS): the messages are renumbered one column of
 // cells per live variable node -- cell(k, i) = k * nlive + i for edge position k of the i-th live node, so that the threads of a
 // wave touch consecutive cells in the variable-node pass -- and remap[old slot] = cell for the check side (g.E = D * nlive here).
 // All global loads are issued unconditionally and before anything depends on them (the edge table is padded with SWD_PAD_EDGE
 // beyond a column's degree, rows beyond g.D do not exist: clamped): one memory latency per call instead of two per variable node.
-// Full graph, in two halves: vn_cache_issue starts every load (raw edge words + priors), vn_cache_pack builds the cache from them --
-// whatever the caller does in between runs while the loads are in flight.
-template <int NT, int VF, int DM>
-struct VnRaw { uint32_t ev[VF][DM]; double llr[VF]; };
-template <int NT, int VF, int DM>
-__device__ __forceinline__ void vn_cache_issue(const SwdGraphDev &g, const Lds &s, VnRaw<NT, VF, DM> &r) {
-    const int n = g.n, D = g.D;
-    const uint32_t *et = g.vn_edge;
-    const double *lt = g.llr;
-#pragma unroll
-    for (int i = 0; i < VF; ++i) {
-        const int idx = s.vtid + i * NT;
-        const int v = (idx < n) ? idx : 0;
-        r.llr[i] = (n > 0) ? lt[v] : 0.0;
-#pragma unroll
-        for (int k = 0; k < DM; ++k) r.ev[i][k] = (n > 0) ? et[max(min(k, D - 1), 0) * n + v] : SWD_PAD_EDGE;
-    }
-}
-template <int NT, int VF, int DM, int SH, bool PB>
-__device__ __forceinline__ void vn_cache_pack(const SwdGraphDev &g, const Lds &s, const VnRaw<NT, VF, DM> &r, VnCacheP<VF, DM, SH, PB> &c) {
-    const int n = g.n, D = g.D;
-    const uint32_t dead = (uint32_t)swd_slot_zero<NT>(g) << 3;
-#pragma unroll
-    for (int i = 0; i < VF; ++i) {
-        const int idx = s.vtid + i * NT;
-        const bool valid = idx < n;
-        c.llr[i] = valid ? r.llr[i] : 0.0;
-#pragma unroll
-        for (int k = 0; k < DM; ++k) c.set_ed(i, k, dead);
-        constexpr int PS = VnCacheP<VF, DM, SH, PB>::par_shift;
-#pragma unroll
-        for (int k = 0; k < (DM + 1) / 2; ++k) c.par[i][k] = ((uint32_t)g.m << PS) * 0x10001u;
-#pragma unroll
-        for (int k = 0; k < DM; ++k) {
-            const uint32_t e = r.ev[i][k];
-            if (valid && k < D && e != SWD_PAD_EDGE) {
-                c.set_ed(i, k, swd_edge_slot(e) << 3);
-                c.par[i][k >> 1] = (k & 1) ? ((c.par[i][k >> 1] & 0xFFFFu) | ((swd_edge_lane(e) << PS) << 16))
-                                           : ((c.par[i][k >> 1] & 0xFFFF0000u) | (swd_edge_lane(e) << PS));
-            }
-        }
-    }
-}
-
 // f(integral_constant<int, I>) for I = 0 .. N - 1: the rows of a register cache with the row number as a compile-time constant
 template <int I, int N, class F>
 __device__ __forceinline__ void swd_rows(F &&f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); swd_rows<I + 1, N>(f); }
 }
 
-// The two halves for a depth profile PROF: entry idx is the idx-th node of the graph's depth order, read from the tables in that order;
-// row i asks for and packs its first PROF::depth(i) positions only (a plan launches a profiled kernel only on graphs that fit: no
-// node listed in row i has an edge beyond them).  The other positions of the cache do not exist for the profiled routines.
-template <class PROF, int NT, int VF, int DM>
-__device__ __forceinline__ void vn_cache_issue_depth(const SwdGraphDev &g, const Lds &s, VnRaw<NT, VF, DM> &r) {
-    const int n = g.n, D = g.D;
-    const uint32_t *et = g.vn_edge_d;
-    const double *lt = g.llr_d;
-    swd_rows<0, VF>([&](auto i_tag) {
-        constexpr int i = decltype(i_tag)::value, KD = PROF::template depth<DM>(i);
-        const int idx = s.vtid + i * NT;
-        const int v = (idx < n) ? idx : 0;
-        r.llr[i] = (n > 0) ? lt[v] : 0.0;
-#pragma unroll
-        for (int k = 0; k < KD; ++k) r.ev[i][k] = (n > 0) ? et[max(min(k, D - 1), 0) * n + v] : SWD_PAD_EDGE;
-    });
+// Full graph, tuned kernels of up to SWD_TUNED_NT threads: both register caches are the same bits for every unit of a graph, so the
+// host packs them once per graph (swd_graph.hip, Graph::fill_image; include/swd.h, swd_graph_cache_image) and a unit loads them
+// ready-made -- 16-byte loads of consecutive addresses, chunk q of role r at word (q * NT + r) * 4 -- instead of building them from
+// the raw edge words, s.jptr and s.cn_deg.  swd_cache_img_issue starts every load; whatever the caller does before it moves the words
+// into the caches (swd_cache_img_vn / swd_cache_img_cn) runs while they are in flight.
+//   node part of role vtid (g.img_vn, or g.img_vn_d for a depth profile PROF: the nodes in the graph's depth order), words in order:
+//     llr[i] (low word, high word) for every row i; edp[i][0 .. KD2(i) / 2) for every row i; par[i][0 .. KD2(i) / 2) for every row i,
+//     KD2(i) = PROF::depth(i) rounded up to whole pairs (uniform: DM) -- the other positions of a profiled cache do not exist
+//   check part of role ctid (g.img_cn, one thread per check): slp[0 .. 2 KG), then one word l & 0xFFFF | cnt << 16 | live << 24
+typedef uint32_t swd_u32x4r __attribute__((ext_vector_type(4)));
+template <class PROF, int VF, int DM>
+constexpr int swd_img_kd2(int i) { return (PROF::template depth<DM>(i) + 1) & ~1; }
+template <class PROF, int VF, int DM>
+constexpr int swd_img_edp_at(int i) { // first edp word of row i; the par words lie swd_img_edp_at(VF) - 2 VF words behind
+    int w = 2 * VF;
+    for (int r = 0; r < i; ++r) w += swd_img_kd2<PROF, VF, DM>(r) / 2;
+    return w;
 }
-template <class PROF, int NT, int VF, int DM, int SH, bool PB>
-__device__ __forceinline__ void vn_cache_pack_depth(const SwdGraphDev &g, const Lds &s, const VnRaw<NT, VF, DM> &r, VnCacheP<VF, DM, SH, PB> &c) {
-    const int n = g.n, D = g.D;
-    const uint32_t dead = (uint32_t)swd_slot_zero<NT>(g) << 3;
+template <class PROF, int VF, int DM, int KG>
+struct SwdCacheImg {
+    static constexpr int PW = swd_img_edp_at<PROF, VF, DM>(VF) - 2 * VF; // edp words = par words
+    static constexpr int CV = (2 * VF + 2 * PW + 3) / 4, CC = (2 * KG + 1 + 3) / 4;
+    swd_u32x4r v[CV], c[CC];
+};
+struct SwdNoCacheImg {};
+template <class PROF, int NT, int VF, int DM, int KG>
+__device__ __forceinline__ void swd_cache_img_issue(const SwdGraphDev &g, const Lds &s, SwdCacheImg<PROF, VF, DM, KG> &im) {
+    const swd_u32x4r *pv = (const swd_u32x4r *)(PROF::on ? g.img_vn_d : g.img_vn) + s.vtid, *pc = (const swd_u32x4r *)g.img_cn + s.ctid;
+#pragma unroll
+    for (int q = 0; q < SwdCacheImg<PROF, VF, DM, KG>::CV; ++q) im.v[q] = pv[q * NT];
+#pragma unroll
+    for (int q = 0; q < SwdCacheImg<PROF, VF, DM, KG>::CC; ++q) im.c[q] = pc[q * NT];
+}
+template <class PROF, int VF, int DM, int KG>
+__device__ __forceinline__ void swd_cache_img_vn(const SwdCacheImg<PROF, VF, DM, KG> &im, VnCacheP<VF, DM, 0, false> &c) {
+    constexpr int PW = SwdCacheImg<PROF, VF, DM, KG>::PW;
     swd_rows<0, VF>([&](auto i_tag) {
-        constexpr int i = decltype(i_tag)::value, KD = PROF::template depth<DM>(i), KD2 = (KD + 1) & ~1; // (whole pairs)
-        const int idx = s.vtid + i * NT;
-        const bool valid = idx < n;
-        c.llr[i] = valid ? r.llr[i] : 0.0;
+        constexpr int i = decltype(i_tag)::value, at = swd_img_edp_at<PROF, VF, DM>(i);
+        c.llr[i] = __longlong_as_double((long long)(((uint64_t)im.v[(2 * i + 1) >> 2][(2 * i + 1) & 3] << 32) | im.v[(2 * i) >> 2][(2 * i) & 3]));
 #pragma unroll
-        for (int k = 0; k < KD2; ++k) c.set_ed(i, k, dead);
-        constexpr int PS = VnCacheP<VF, DM, SH, PB>::par_shift;
-#pragma unroll
-        for (int k = 0; k < KD2 / 2; ++k) c.par[i][k] = ((uint32_t)g.m << PS) * 0x10001u;
-#pragma unroll
-        for (int k = 0; k < KD; ++k) {
-            const uint32_t e = r.ev[i][k];
-            if (valid && k < D && e != SWD_PAD_EDGE) {
-                c.set_ed(i, k, swd_edge_slot(e) << 3);
-                c.par[i][k >> 1] = (k & 1) ? ((c.par[i][k >> 1] & 0xFFFFu) | ((swd_edge_lane(e) << PS) << 16))
-                                           : ((c.par[i][k >> 1] & 0xFFFF0000u) | (swd_edge_lane(e) << PS));
-            }
+        for (int k = 0; k < swd_img_kd2<PROF, VF, DM>(i) / 2; ++k) {
+            c.edp[i][k] = im.v[(at + k) >> 2][(at + k) & 3];
+            c.par[i][k] = im.v[(at + PW + k) >> 2][(at + PW + k) & 3];
         }
     });
 }
@@ -522,7 +497,7 @@ __device__ __forceinline__ void vn_cache_pack_depth(const SwdGraphDev &g, const 
 template <int NT, int VF, int DM, bool FULL, bool ALLEDGES = false, bool JPACK = false, int SH, bool PB>
 __device__ __forceinline__ void vn_cache_load(const SwdGraphDev &g, Lds &s, int nlive, VnCacheP<VF, DM, SH, PB> &c, uint16_t *remap = nullptr) {
     const int n = g.n, cnt = FULL ? n : nlive;
-    const uint32_t dead = (uint32_t)swd_slot_zero<NT>(g) << 3;
+    const uint32_t dead = (uint32_t)swd_slot_zero_of<NT, SH>(g, s) << 3;
     const int D = g.D;
     const uint32_t *et = g.vn_edge;
     const double *lt = g.llr;
@@ -571,7 +546,7 @@ template <int NT, int VF, int DM, int SH, bool PB>
 __device__ __forceinline__ void vn_cache_load_compact(const SwdGraphDev &g, Lds &s, int nlive, VnCacheP<VF, DM, SH, PB> &c, uint16_t *remap, int (&kc)[VF]) {
     const int n = g.n, D = g.D;
     constexpr int PS = VnCacheP<VF, DM, SH, PB>::par_shift;
-    const uint32_t dead = (uint32_t)swd_slot_zero<NT>(g) << 3;
+    const uint32_t dead = (uint32_t)swd_slot_zero_of<NT, SH>(g, s) << 3;
     uint32_t ev[VF][DM];
 #pragma unroll
     for (int i = 0; i < VF; ++i) {
@@ -612,7 +587,6 @@ __device__ __forceinline__ void vn_cache_load_compact(const SwdGraphDev &g, Lds 
 }
 
 __device__ __forceinline__ double &swd_msg_at(Lds &s, uint32_t ed) { return *(double *)((char *)s.msg + ed); }
-typedef uint32_t swd_u32x4r __attribute__((ext_vector_type(4)));
 // Hybrid store, explicit form: a FLAT access is worked through the texture addresser lane by lane whichever memory it ends in -- and the
 // scattered 8-byte accesses of the variable-node pass are bound by exactly that unit -- so the two memories get an instruction each
 // (ds_read / ds_write for the lanes in LDS, global_load / global_store for the rest, disjoint exec masks).
@@ -699,6 +673,18 @@ struct CnCacheP {
     }
     int cnt, live, l, sub, grp;
 };
+// the full graph's check cache from the graph's image (SwdCacheImg): what cn_cache_load<NT, KG, true> builds for one thread per check
+template <class PROF, int VF, int DM, int KG>
+__device__ __forceinline__ void swd_cache_img_cn(const SwdCacheImg<PROF, VF, DM, KG> &im, CnCacheP<KG, 0> &cc) {
+#pragma unroll
+    for (int k = 0; k < 2 * KG; ++k) cc.slp[k] = im.c[k >> 2][k & 3];
+    const uint32_t w = im.c[(2 * KG) >> 2][(2 * KG) & 3];
+    cc.l = (int)(int16_t)(w & 0xFFFFu); // (-1: no check)
+    cc.cnt = (int)((w >> 16) & 0xFFu);
+    cc.live = (int)(w >> 24);
+    cc.sub = 0;
+    cc.grp = 1;
+}
 
 // Live-position masks of the checks: 64 bits per check, or -- tuned osd_window kernels (D) on graphs with row weight <= 48
 // (s.lm_m != 0) -- 32 + 16 bits in two arrays.
@@ -730,7 +716,7 @@ template <int NT, int KG, bool FULL, bool REMAP = false, int SH>
 __device__ __forceinline__ void cn_cache_load(const SwdGraphDev &g, Lds &s, bool uselist, int lc, int sub, int grp, CnCacheP<KG, SH> &cc,
                                               [[maybe_unused]] const uint16_t *remap = nullptr) {
     constexpr bool DIET = SWD_P16(NT);
-    const int m = g.m, dummy = swd_slot_far(g);
+    const int m = g.m, dummy = swd_slot_far_of<SH>(g, s);
     const bool act = (lc >= 0) && (lc < m) && (s.cn_val[lc >= 0 ? lc : 0] >= 0);
     const int l = act ? lc : 0;
     cc.l = act ? lc : -1;
@@ -875,7 +861,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
 #endif
     // largest number of threads sharing a check in this wave (uniform): waves whose checks all have a thread of their own skip the merge
     [[maybe_unused]] const int gmax = __builtin_amdgcn_readfirstlane(wave_max(cn.grp));
-    const int farslot = swd_slot_far(g), zeroslot = swd_slot_zero<NT>(g);
+    const int farslot = swd_slot_far_of<SH>(g, s), zeroslot = swd_slot_zero_of<NT, SH>(g, s);
     constexpr int K4 = KG * 4;
     constexpr int NR = (K4 + 31) / 32;       // sign shift registers
     iters_done = 0;
@@ -2938,14 +2924,13 @@ __device__ __forceinline__ void lds_bind(Lds &s, char *smem, const SwdLdsLayout 
 
 // osd_window.decode (osd_window.pyx:158-199) for one syndrome `synd` (LDS bytes, original check
 // order).  On return s.hard[0..n) is the vector decode() returns.
-// vraw (kernels that split the cache load): where the raw edge words and priors of the variable nodes go
 // want_pm (uniform over the launch): the caller gave min_pm a destination.  Without one the PRE and POST exits leave R.pm at 0 and skip
 // ordered_pm -- a scan, three barriers and a serial sum on one wave that nothing reads; the OSD exit needs the metric itself.
 // PROF: depth profile of the full-graph phase (kind 3 only); the post phase keeps its own list and tiers
 template <int NT, int VF, int DM, int KG, bool SF, bool HACC, bool BIG = false, class PROF = SwdUniformDepth>
 __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLdsLayout &L, const SwdDecodeParams &P, Lds &s,
                               const uint8_t *synd, double *hist_b, uint8_t *osd0_b, uint8_t *bpdec_b, WinResult &R, const uint32_t *cn_map,
-                              VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> &vraw, const bool want_pm) {
+                              const bool want_pm) {
     constexpr bool DIET = SWD_P16(NT); // the tuned kernels' LDS forms (decided-node bits, 48-bit live masks, no copy of the check degrees)
     // The fused passes between the two BP phases (round 12), the tuned kernels of up to 256 threads only: staged columns in 8-byte words,
     // slot lists renumbered as the check caches read them, no backup in front of the peeling rounds
@@ -2962,18 +2947,20 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     for (int i = 0; i < 9; ++i) R.t[i] = 0;
     R.t[0] = wall_clock64();
 
-    // kernels of up to 256 threads: the cache's loads are in flight during the reset loops (headline 9.95 -> 9.84 ms per launch at
-    // order 0; the 1024-thread kernels lose by it -- [[288]] 63.2 -> 64.0 ms -- and load where they always did)
+    // kernels of up to 256 threads: the full graph's caches come ready-made from the graph's image (SwdCacheImg), and its loads are in
+    // flight during the reset loops (headline 9.95 -> 9.84 ms per launch at order 0 when the raw edge words were loaded this way; the
+    // 1024-thread kernels lose by it -- [[288]] 63.2 -> 64.0 ms -- and load and pack where they always did)
     constexpr bool kSplitLoad = NT <= SWD_TUNED_NT;
-    // (memory loads return in order: what the reset loops need from the graph is asked for BEFORE the cache's 7 x DM + 7 loads, so
-    // that the loops run while those are in flight instead of behind them)
+    static_assert(!kSplitLoad || (SWD_P16(NT) && !BIG && !SF), "the cache image: byte-offset caches, one thread per check, messages in LDS");
+    // (memory loads return in order: what the reset loops need from the graph is asked for BEFORE the image's loads, so that the loops
+    // run while those are in flight instead of behind them)
     [[maybe_unused]] int d_first = 0, p_first = 0, j_first = 0;
+    [[maybe_unused]] std::conditional_t<kSplitLoad, SwdCacheImg<PROF, VF, DM, KG>, SwdNoCacheImg> img;
     if constexpr (kSplitLoad) {
         if (tid < m) { d_first = g.row_deg[tid]; p_first = g.perm[tid]; }
         if (tid <= g.K) j_first = g.jptr[tid];
         __builtin_amdgcn_sched_barrier(0); // (issued here)
-        if constexpr (PROF::on) vn_cache_issue_depth<PROF, NT, VF, DM>(g, s, vraw);
-        else vn_cache_issue<NT, VF, DM>(g, s, vraw);
+        swd_cache_img_issue<PROF, NT>(g, s, img);
     }
     // reset (osd_window.pyx:288-303)
     for (int l = tid; l < m; l += NT) {
@@ -2999,10 +2986,8 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     bool rec_on = false;
     if constexpr (kRec) rec_on = L.off_pmsg >= 0 && m <= 1023 && L.pmsg_bytes >= (m + 1) * 32 + 4096;
     static_assert(!PROF::on || (kSplitLoad && HACC && !BIG && !SF && PROF::rows == VF), "depth profiles: the tuned kind-3 kernels, a depth per cache row");
-    if constexpr (kSplitLoad) {
-        if constexpr (PROF::on) vn_cache_pack_depth<PROF, NT, VF, DM>(g, s, vraw, vc);
-        else vn_cache_pack<NT, VF, DM>(g, s, vraw, vc);
-    } else if constexpr (kTbl) { // (no cache)
+    if constexpr (kSplitLoad) swd_cache_img_vn(img, vc);
+    else if constexpr (kTbl) { // (no cache)
     } else {
         if (kRec && rec_on) { if constexpr (kRec) vn_cache_load<NT, VF, DM, true, false, true>(g, s, n, vc); }
         else vn_cache_load<NT, VF, DM, true>(g, s, n, vc);
@@ -3012,7 +2997,8 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     const long long ip1 = wall_clock64();
 #endif
     // the check state and jptr written above are read below by OTHER threads (a check is served by the thread
-    // whose ctid equals its lane number, which need not be the thread that initialised it)
+    // whose ctid equals its lane number, which need not be the thread that initialised it; with the check cache taken from the image the
+    // first reader is bp_run, behind the second barrier -- this one is kept as it was, its removal is a measurement of its own)
     __syncthreads();
 #ifdef SWD_INITPROF
     const long long ip2 = wall_clock64();
@@ -3041,12 +3027,15 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     const long long ip3 = wall_clock64();
 #endif
     std::conditional_t<SWD_P16(NT), CnCacheP<KG>, CnCacheP<KG, 3>> cn;
-    if constexpr (SF) { // heavy checks are shared by 2 or 4 threads in the full-graph phase too (host-built map)
+    if constexpr (kSplitLoad) swd_cache_img_cn(img, cn);
+    else if constexpr (SF) { // heavy checks are shared by 2 or 4 threads in the full-graph phase too (host-built map)
         const uint32_t e = cn_map[s.ctid];
         cn_cache_load<NT, KG, true>(g, s, false, (e & 0xFFFFu) == 0xFFFFu ? -1 : (int)(e & 0xFFFFu), (int)((e >> 16) & 3u), (int)(e >> 18), cn);
     } else {
         cn_cache_load<NT, KG, true>(g, s, false, s.ctid < m ? s.ctid : -1, 0, 1, cn);
     }
+    // (stays with the image: the messages bp_init stored and the check values of the reset loops are read by OTHER threads in the
+    // first check pass of bp_run, which has no barrier of its own in front of it)
     __syncthreads();
 
     int it = 0;
@@ -3847,9 +3836,8 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
             R.exit_class = SWD_EXIT_SCHED_FAULT;
         } else if constexpr (KIND == 0 || KIND == 3) // 3: osd_window with the posterior history accumulated in registers (bp_run, ACC)
         {
-            VnRaw<NT, (NT <= SWD_TUNED_NT) ? VF : 1, DM> vraw;
             decode_window<NT, VF, DM, KG, SF, KIND == 3, BIG, PROF>(g, L, a.P, s, sdet + (w.row0 - dbase), hist_b, a.osd0 ? a.osd0 + (int64_t)b * g.n : nullptr,
-                                                         a.bp_dec ? a.bp_dec + (int64_t)b * g.n : nullptr, R, w.cn_map, vraw, a.min_pm != nullptr);
+                                                         a.bp_dec ? a.bp_dec + (int64_t)b * g.n : nullptr, R, w.cn_map, a.min_pm != nullptr);
         }
         else {
             uint8_t *snap_b = a.snap + (int64_t)sidx * a.snap_stride;

@@ -431,8 +431,13 @@ struct Plan {
             std::vector<Graph *> uniq;
             for (auto &w : wins)
                 if (std::find(uniq.begin(), uniq.end(), w.g.get()) == uniq.end()) uniq.push_back(w.g.get());
-            for (Graph *g : uniq)
+            // the tuned osd_window kernels of up to SWD_TUNED_NT threads take the full graph's register caches from the graph's image
+            // (a profiled plan still launches the uniform kernel when a posterior history is asked for: both node parts)
+            const bool image = kind == 0 && !big && nt <= SWD_TUNED_NT && !variant->sf;
+            for (Graph *g : uniq) {
+                if (image) g->fill_image(nt, vf, variant->dm, variant->kg, depth ? depth->depth : nullptr);
                 if (g->upload()) return -1;
+            }
         }
         if (kind == 1 && gp.multi_thread == 1) {
             // prefix-tree walk of the ensemble (swd_gdg_kernel.h, gdg_ensemble_tree): behind the 2 + (S - D) mask records come D fork
