@@ -76,8 +76,25 @@ def _node_depth(L, name, handle):
     return bool(f(handle)) if f is not None and getattr(f, "argtypes", None) else False
 
 
-class osd_window:
+class _Handle:
+    """Owner of one library handle ``_h`` that the C function named ``_destroy`` releases."""
+    _h = _destroy = None
+
+    def _release(self):
+        h = getattr(self, "_h", None)  # (a constructor that raised early has not set it)
+        if h:
+            try:
+                getattr(_lib.lib(), self._destroy)(h)
+            except Exception:  # interpreter shutdown: the module globals may be gone already
+                pass
+            self._h = None
+
+    __del__ = _release
+
+
+class osd_window(_Handle):
     """BP + OSD on a shortened window matrix (reference: src/osd_window.pyx)."""
+    _destroy = "swd_osdw_destroy"
 
     def __init__(self, parity_check_matrix, **kwargs):
         L = _lib.lib()
@@ -109,15 +126,6 @@ class osd_window:
         self._bp_decoding = np.zeros(self.n, dtype=np.int64)
         self._osdw_decoding = np.zeros(self.n, dtype=np.int64)
         self._osd0_decoding = np.zeros(self.n, dtype=np.int64)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.lib().swd_osdw_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
     @property
     def last_form(self):
@@ -336,7 +344,7 @@ def window_forms(windows, decoder="osd_window", num_det=0, **kwargs):
     return _form_dict(plan, wins)
 
 
-class bp_history_decoder:
+class bp_history_decoder(_Handle):
     """Plain min-sum BP with a 4-deep posterior history (reference: src/bp_guessing_decoder.pyx:5-158)
     and base class of the guessing decoders.  ``bpgdg_decoder``: the side branches of a shot's decimation tree run
     concurrently on different workgroups; with ``multi_thread=False`` (default) the result is that of the reference's
@@ -348,7 +356,7 @@ class bp_history_decoder:
     returned (a re-used reference object returns its previous decode's ``min_pm_error``, bpgd.cpp:583, 619-625), and each thread's
     posterior history starts from zeros (a re-used reference thread keeps its own stale slots when ``max_iter_per_step < 4``);
     ``hypotheses=H`` is this package's own ensemble over every leaf of gdg()'s tree with H leaves (no reference counterpart)."""
-    _mode = 2
+    _mode, _destroy = 2, "swd_gdg_destroy"
 
     def __init__(self, parity_check_matrix, **kwargs):
         L = _lib.lib()
@@ -361,15 +369,6 @@ class bp_history_decoder:
             raise RuntimeError(f"swd_gdg_create failed: {_lib.last_error()}")
         self._hist = np.zeros((4, self.n), dtype=np.float64)
         self._last = dict(status=0, iters=0, min_pm=0.0)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.lib().swd_gdg_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
     def decode(self, input_vector):
         s = _as_synd(input_vector, self.m)
@@ -462,7 +461,7 @@ class bpgd_decoder(bp_history_decoder):
     _mode = 1
 
 
-class bp4_osd:
+class bp4_osd(_Handle):
     """Quaternary BP + OSD (reference: src/bp4_osd.pyx).  ``decode(sx, sz)`` returns the int64 array of
     shape (2, n) the reference returns (row 0: X string, row 1: Z string).
 
@@ -477,6 +476,7 @@ class bp4_osd:
     one 1024-thread workgroup per shot with every array in HBM, the same results bit for bit.  It runs BP only, so like a graph with
     heavy columns it takes ``osd_order=-1`` (``ValueError`` otherwise) and ``camel_decode``; any graph is taken, one the tuned
     kernels would take included.  Up to 1 048 576 qubits, 1 048 576 checks per matrix, 67 108 864 edges in all."""
+    _destroy = "swd_bp4_destroy"
 
     def __init__(self, Hx, Hz, **kwargs):
         L = _lib.lib()
@@ -521,15 +521,6 @@ class bp4_osd:
         self._lpr = np.zeros((3, n))
         self._osd0 = np.zeros((2, n), np.int64)
         self._out = np.zeros((2, n), np.int64)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.lib().swd_bp4_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
     def decode_batch(self, synd_x, synd_z, return_llr=False, details=True):
         """[B, mx], [B, mz] -> uint8 [B, 2, n] (X string, Z string per decode).  ``details=False`` leaves the posteriors, the OSD-0
@@ -704,13 +695,14 @@ class _HostPool:
         return base[...]
 
 
-class SlidingWindowDecoder:
+class SlidingWindowDecoder(_Handle):
     """The (W,F) sliding-window loop of the reference harness (/root/reference/osd.py:130-179) for
     a whole batch of shots in ONE launch: a workgroup carries a shot through all its windows,
     committing ``commit`` columns per window and folding them back into the residual syndrome.
 
     ``plan`` is a ``windows.WindowPlan``; decoder kwargs are those of ``osd_window`` and apply to
     every window like in osd.py:152-161."""
+    _destroy = "swd_pipeline_destroy"
 
     def __init__(self, plan, device=0, decoder="osd_window", **kwargs):
         L = _lib.lib()
@@ -772,15 +764,6 @@ class SlidingWindowDecoder:
             od = _lib.GraphDesc(a.shape[0], a.shape[1], int(rp[-1]), rp.ctypes.data, ci.ctypes.data, None)
             if L.swd_pipeline_set_observables(self._h, C.byref(od)):
                 raise RuntimeError(f"swd_pipeline_set_observables failed: {_lib.last_error()}")
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.lib().swd_pipeline_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
     @property
     def last_form(self):
@@ -953,10 +936,11 @@ class SlidingWindowDecoder:
         return ms.value, k.value
 
 
-class SlidingWindowStream:
+class SlidingWindowStream(_Handle):
     """Two-lane stream of a ``SlidingWindowDecoder`` (C ABI: swd_pipeline_stream_*).  Host form: ``push(det)`` returns at once,
     ``pop()`` waits for the oldest batch in flight -> (total_e_hat, stats, min_pm, obs_flips, flagged).  Device form:
     ``push_device`` launches on the next lane with the caller's CUDA tensors (keep one set of outputs per lane), ``wait()`` joins."""
+    _destroy = "swd_pipeline_stream_destroy"
 
     def __init__(self, dec, max_shots, packed=False, want_stats=True):
         self.dec, self.packed, self.want_stats = dec, bool(packed), bool(want_stats)
@@ -967,16 +951,7 @@ class SlidingWindowStream:
             raise RuntimeError(f"swd_pipeline_stream_create failed: {_lib.last_error()}")
         self._sizes = []
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.lib().swd_pipeline_stream_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    __del__ = close
+    close = _Handle._release
 
     @property
     def pending(self):
@@ -1035,20 +1010,10 @@ class SlidingWindowStream:
             raise RuntimeError(f"swd_pipeline_stream_wait_last failed: {_lib.last_error()}")
 
 
-class _SessionBase:
+class _SessionBase(_Handle):
     """What ``SlidingWindowSession`` and ``RollingSession`` share: the handle's life, ``begin`` and the checks of arriving rows.
     ``_C``: the prefix of the form's C symbols."""
-
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                getattr(_lib.lib(), self._C + "_destroy")(h)
-            except Exception:
-                pass
-            self._h = None
-
-    __del__ = close
+    close = _Handle._release
 
     def begin(self, B):
         """Zero state for a batch of ``B <= max_shots`` shots; also restarts a session that has been used."""
@@ -1080,7 +1045,7 @@ class SlidingWindowSession(_SessionBase):
     total_e_hat and the observable accumulators of one batch on the device; ``push`` takes the next rows of every shot (any
     number, in row order) and returns the windows they completed, each decoded on the rows received so far and committed --
     bit-identical to ``decode`` of the whole experiment, whatever the chunking."""
-    _C = "swd_pipeline_session"
+    _C, _destroy = "swd_pipeline_session", "swd_pipeline_session_destroy"
 
     def __init__(self, dec, max_shots):
         self.dec, self.max_shots, self.B = dec, int(max_shots), 0
@@ -1182,7 +1147,7 @@ class RollingSession(_SessionBase):
     One thread at a time per session at this layer: ``push`` sizes its output arrays from a state query made before the call, so
     two threads pushing on one session would size them for the wrong state (the library then refuses the call, it does not
     overrun).  The C ABI itself may be called from any thread."""
-    _C = "swd_pipeline_rolling"
+    _C, _destroy = "swd_pipeline_rolling", "swd_pipeline_rolling_destroy"
 
     def __init__(self, dec, max_shots):
         from .windows import rolling_template
@@ -1321,11 +1286,12 @@ class RollingSession(_SessionBase):
         return t, faults, stats, pm, shot[:, 0], shot[:, 1]
 
 
-class DemSampler:
+class DemSampler(_Handle):
     """Samples shots of a detector error model on the device: ``det, obs = sampler.sample(shots)`` is what
     ``dem.compile_sampler().sample(shots)`` gives the reference harness (/root/reference/osd.py:124-125).
     Faults are Bernoulli(priors) per column from a Philox4x32-10 stream that is a pure function of
     (seed, shot number, column): batches and ranks can be cut anywhere (``first_shot``)."""
+    _destroy = "swd_sampler_destroy"
 
     def __init__(self, chk, obs, priors, device=0):
         L = _lib.lib()
@@ -1348,14 +1314,6 @@ class DemSampler:
         if not self._h:
             raise RuntimeError(f"swd_sampler_create failed: {_lib.last_error()}")
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            try:
-                _lib.lib().swd_sampler_destroy(self._h)
-            except Exception:  # interpreter shutdown: the module globals may be gone already
-                pass
-            self._h = None
-
     def sample(self, shots, seed=20240318, first_shot=0, return_faults=False):
         """-> det uint8 [shots, num_det], obs uint8 [shots, num_obs] (, faults uint8 [shots, num_col])."""
         det = np.zeros((shots, self.num_det), np.uint8)
@@ -1367,25 +1325,31 @@ class DemSampler:
         obs = ((flips[:, None] >> np.arange(self.num_obs, dtype=np.uint32)) & 1).astype(np.uint8)
         return (det, obs, faults) if return_faults else (det, obs)
 
-    def sample_device(self, shots, seed=20240318, first_shot=0):
-        """-> torch tensors on the device: det uint8 [shots, num_det], observable-flip bit masks int32 [shots]."""
+    def sample_device(self, shots, seed=20240318, first_shot=0, out=None, stream=None, faults=None):
+        """-> torch tensors on the device: det uint8 [shots, num_det], observable-flip bit masks int32 [shots]; asynchronous on the
+        current (or given) torch stream.  ``out`` = (det, flips) tensors to fill (contiguous, at least ``shots`` rows; ``flips`` None:
+        the masks are not computed and None is returned for them); ``faults``: uint8 [>= shots, num_col], contiguous, receives the
+        sampled faults."""
         import torch
         dev = torch.device("cuda", self.device)
-        det = torch.empty((shots, self.num_det), dtype=torch.uint8, device=dev)
-        flips = torch.empty((shots,), dtype=torch.int32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        if _lib.lib().swd_sampler_sample_dev(self._h, shots, int(seed), int(first_shot), det.data_ptr(), 0, flips.data_ptr(),
-                                             None, 0, st):
+        if out is None:
+            out = (torch.empty((shots, self.num_det), dtype=torch.uint8, device=dev), torch.empty((shots,), dtype=torch.int32, device=dev))
+        det, flips = out
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        if _lib.lib().swd_sampler_sample_dev(self._h, shots, int(seed), int(first_shot), det.data_ptr(), 0,
+                                             flips.data_ptr() if flips is not None else None,
+                                             faults.data_ptr() if faults is not None else None, 0, st.cuda_stream):
             raise RuntimeError(f"swd_sampler_sample_dev failed: {_lib.last_error()}")
-        return det, flips
+        return det[:shots], flips[:shots] if flips is not None else None
 
 
-class PauliSampler:
+class PauliSampler(_Handle):
     """Samples Pauli errors of a CSS code and their syndromes on the device: what the first lines of the reference's data-noise
     cells compute with ``np.random.uniform`` and two dense products (/root/reference/Misc.ipynb cell 2:
     ``err_x = noise < px+py``, ``err_z = px < noise < px+py+pz``, ``syndrome_x = err_z @ hx.T``, ``syndrome_z = err_x @ hz.T``).
     The stream is Philox4x32-10, a pure function of (seed, shot number, qubit) (include/swd.h; tests/pauli_ref.py restates it):
     batches, lanes and ranks can be cut anywhere with ``first_shot``."""
+    _destroy = "swd_pauli_sampler_destroy"
 
     def __init__(self, Hx, Hz, channel_probs_x, channel_probs_y, channel_probs_z, device=0):
         L = _lib.lib()
@@ -1410,14 +1374,6 @@ class PauliSampler:
             if "probabilit" in msg or "exceeds 1" in msg or "out of range" in msg:
                 raise ValueError(msg)
             raise RuntimeError(f"swd_pauli_sampler_create failed: {msg}")
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            try:
-                _lib.lib().swd_pauli_sampler_destroy(self._h)
-            except Exception:  # interpreter shutdown: the module globals may be gone already
-                pass
-            self._h = None
 
     def sample(self, shots, seed=20240318, first_shot=0):
         """-> err uint8 [shots, 2, n] (row 0 the X string, row 1 the Z string), sx uint8 [shots, mx] = Hx err_z,
@@ -1446,8 +1402,9 @@ class PauliSampler:
         return err[:shots], sx[:shots], sz[:shots]
 
 
-class _CssAccount:
+class _CssAccount(_Handle):
     """swd_css_account handle: ``cx`` = [Hx; Lx] on the Z string, ``cz`` = [Hz; Lz] on the X string, either None."""
+    _destroy = "swd_css_account_destroy"
 
     def __init__(self, cx, stab_x, cz, stab_z, device):
         self._keep, descs = [], []
@@ -1467,14 +1424,6 @@ class _CssAccount:
         if not self._h:
             raise RuntimeError(f"swd_css_account_create failed: {_lib.last_error()}")
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            try:
-                _lib.lib().swd_css_account_destroy(self._h)
-            except Exception:
-                pass
-            self._h = None
-
     def account(self, B, est, err, stats, result, counters, stream):
         """torch tensors (rows may be strided); ``stats`` / ``result`` / ``counters`` may be None."""
         if _lib.lib().swd_css_account_dev(self._h, B, est.data_ptr(), est.stride(0), err.data_ptr(), err.stride(0),
@@ -1484,16 +1433,8 @@ class _CssAccount:
             raise RuntimeError(f"swd_css_account_dev failed: {_lib.last_error()}")
 
 
-class CodeCapacityResult:
-    """Counters of a code-capacity run.  ``logical_errors``: shots whose correction leaves a logical error by the reference's
-    criterion (a residual syndrome counts: it is not in ker(h) either); ``residual_syndromes``: those among them whose correction
-    does not even reproduce the syndrome; ``not_converged``: shots with ``converge`` = 0 (the notebooks' "flagged");
-    ``osd0_logical_errors``: logical errors of the OSD-0 solutions, None unless asked for."""
-
-    def __init__(self, shots, logical_errors, residual_syndromes, not_converged, osd0_logical_errors=None):
-        self.shots, self.logical_errors, self.residual_syndromes = int(shots), int(logical_errors), int(residual_syndromes)
-        self.not_converged = int(not_converged)
-        self.osd0_logical_errors = None if osd0_logical_errors is None else int(osd0_logical_errors)
+class _ErrorRate:
+    """``ler`` and its standard error from a result's ``logical_errors`` and ``shots``."""
 
     @property
     def ler(self):
@@ -1504,6 +1445,18 @@ class CodeCapacityResult:
         """binomial standard error of ``ler``"""
         p = self.ler
         return float(np.sqrt(p * (1.0 - p) / self.shots)) if self.shots else float("nan")
+
+
+class CodeCapacityResult(_ErrorRate):
+    """Counters of a code-capacity run.  ``logical_errors``: shots whose correction leaves a logical error by the reference's
+    criterion (a residual syndrome counts: it is not in ker(h) either); ``residual_syndromes``: those among them whose correction
+    does not even reproduce the syndrome; ``not_converged``: shots with ``converge`` = 0 (the notebooks' "flagged");
+    ``osd0_logical_errors``: logical errors of the OSD-0 solutions, None unless asked for."""
+
+    def __init__(self, shots, logical_errors, residual_syndromes, not_converged, osd0_logical_errors=None):
+        self.shots, self.logical_errors, self.residual_syndromes = int(shots), int(logical_errors), int(residual_syndromes)
+        self.not_converged = int(not_converged)
+        self.osd0_logical_errors = None if osd0_logical_errors is None else int(osd0_logical_errors)
 
     def _fields(self):
         return (self.shots, self.logical_errors, self.residual_syndromes, self.not_converged, self.osd0_logical_errors)
@@ -1516,7 +1469,56 @@ class CodeCapacityResult:
                 "osd0_logical_errors={})".format(*self._fields()))
 
 
-class CodeCapacityExperiment:
+def _run_batches(shots, batch, lanes, first_shot, max_errors, enqueue, sync_lanes, logical_errors):
+    """Which shots an experiment's ``run`` sends where, and when it may stop: batch j is ``min(batch, shots left)`` shots numbered
+    from ``first_shot`` on, on lane ``j % lanes``.  With ``max_errors`` the count is read after every WHOLE round of lanes, once
+    those lanes have been joined (a final partial round is not checked), and the loop stops at ``>= max_errors``.  The experiment
+    supplies ``enqueue(lane, B, first shot of the batch)``, ``sync_lanes(lanes)`` and ``logical_errors()`` (the device counter);
+    nothing here touches torch or the library.  -> shots enqueued."""
+    start, k = 0, 0
+    while start < shots:
+        B = min(batch, shots - start)
+        enqueue(k % lanes, B, first_shot + start)
+        start, k = start + B, k + 1
+        if max_errors is not None and k % lanes == 0:
+            sync_lanes(lanes)
+            if logical_errors() >= max_errors:
+                break
+    return start
+
+
+class _LaneExperiment:
+    """What the experiments share: the lanes -- a torch stream and buffers of its own each, ``dict(cap=, stream=, ...)`` -- and the
+    frame of ``run``.  An experiment supplies ``_alloc(ln, cap, want)``, what a lane of ``cap`` shots holds (``want``: the buffer
+    only some runs ask for), and ``_stale(ln, want)``, whether a lane that is large enough has to be set up again all the same."""
+
+    def _stale(self, ln, want):
+        return False
+
+    def _lane(self, k, cap, want=False):
+        import torch
+        while len(self._lanes) <= k:  # (streams of both priorities: streams of one priority may share a hardware queue and then run back to back)
+            self._lanes.append(dict(cap=0, stream=torch.cuda.Stream(torch.device("cuda", self.device), priority=-(len(self._lanes) & 1))))
+        ln = self._lanes[k]
+        if ln["cap"] < cap or self._stale(ln, want):
+            ln["stream"].synchronize()  # (the buffers it replaces may still be in use)
+            cap = max(cap, ln["cap"])
+            ln.update(self._alloc(ln, cap, want), cap=cap)
+        return ln
+
+    def _sync_lanes(self, lanes=None):
+        for ln in self._lanes[:lanes]:
+            ln["stream"].synchronize()
+
+    def _run(self, shots, batch, lanes, first_shot, max_errors, enqueue, logical_errors):
+        """the caller has zeroed its device counters on the current stream; they are final when this returns"""
+        import torch
+        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()  # the lanes add into zeroed counters
+        _run_batches(shots, batch, lanes, first_shot, max_errors, enqueue, self._sync_lanes, logical_errors)
+        self._sync_lanes()
+
+
+class CodeCapacityExperiment(_LaneExperiment):
     """The reference's data-noise (code-capacity) Monte Carlo on the device: sample, decode, account, count -- only counters come
     back to the host.
 
@@ -1563,23 +1565,19 @@ class CodeCapacityExperiment:
         self._lanes = []
 
     # ---- one batch on one lane: sample, decode, account, all enqueued on the lane's stream -----------------------------------
-    def _lane_buffers(self, k, B, osd0):
+    def _stale(self, ln, osd0):
+        return osd0 and ln.get("osd0") is None
+
+    def _alloc(self, ln, cap, osd0):
         import torch
-        while len(self._lanes) <= k:  # (streams of both priorities: streams of one priority may share a hardware queue and then run back to back)
-            self._lanes.append(dict(cap=0, stream=torch.cuda.Stream(torch.device("cuda", self.device), priority=-(len(self._lanes) & 1))))
-        ln = self._lanes[k]
-        if ln["cap"] < B or (osd0 and ln.get("osd0") is None):
-            dev, u8 = torch.device("cuda", self.device), torch.uint8
-            ln["stream"].synchronize()  # (the buffers it replaces may still be in use)
-            cap = max(B, ln["cap"])
-            width = (2, self.n) if self.decoder_name == "bp4_osd" else (self.n,)
-            ln.update(cap=cap, err=torch.empty((cap,) + width, dtype=u8, device=dev), est=torch.empty((cap,) + width, dtype=u8, device=dev),
-                      sx=torch.empty((cap, self.mx), dtype=u8, device=dev), sz=torch.empty((cap, self.mz), dtype=u8, device=dev),
-                      stats=torch.empty((cap, _lib.STAT_WORDS), dtype=torch.int32, device=dev),
-                      result=torch.empty((cap,), dtype=torch.int32, device=dev), result0=torch.empty((cap,), dtype=torch.int32, device=dev),
-                      min_pm=torch.empty((cap,), dtype=torch.float64, device=dev),
-                      osd0=torch.empty((cap,) + width, dtype=u8, device=dev) if osd0 else None)
-        return ln
+        dev, u8 = torch.device("cuda", self.device), torch.uint8
+        width = (2, self.n) if self.decoder_name == "bp4_osd" else (self.n,)
+        return dict(err=torch.empty((cap,) + width, dtype=u8, device=dev), est=torch.empty((cap,) + width, dtype=u8, device=dev),
+                    sx=torch.empty((cap, self.mx), dtype=u8, device=dev), sz=torch.empty((cap, self.mz), dtype=u8, device=dev),
+                    stats=torch.empty((cap, _lib.STAT_WORDS), dtype=torch.int32, device=dev),
+                    result=torch.empty((cap,), dtype=torch.int32, device=dev), result0=torch.empty((cap,), dtype=torch.int32, device=dev),
+                    min_pm=torch.empty((cap,), dtype=torch.float64, device=dev),
+                    osd0=torch.empty((cap,) + width, dtype=u8, device=dev) if osd0 else None)
 
     def _enqueue(self, ln, B, seed, first_shot, osd0, counters, counters0):
         import torch
@@ -1597,9 +1595,7 @@ class CodeCapacityExperiment:
                     rc = L.swd_bp4_decode_batch_dev(d._h, B, ln["sx"].data_ptr(), ln["sz"].data_ptr(), ln["est"].data_ptr(),
                                                     ln["stats"].data_ptr(), None, ln["osd0"].data_ptr() if osd0 else None, None, s)
             else:
-                if L.swd_sampler_sample_dev(self.sampler._h, B, int(seed), int(first_shot), ln["sx"].data_ptr(), 0, None,
-                                            ln["err"].data_ptr(), 0, s):
-                    raise RuntimeError(f"swd_sampler_sample_dev failed: {_lib.last_error()}")
+                self.sampler.sample_device(B, seed, first_shot, out=(ln["sx"], None), stream=st, faults=ln["err"])
                 if self.decoder_name == "osd_window":
                     rc = L.swd_osdw_decode_batch_dev(d._h, B, ln["sx"].data_ptr(), 0, ln["est"].data_ptr(), 0, ln["stats"].data_ptr(),
                                                      ln["min_pm"].data_ptr(), None, 0, None, None, s)
@@ -1628,22 +1624,10 @@ class CodeCapacityExperiment:
         if shots < 0 or batch <= 0 or lanes <= 0:
             raise ValueError("shots >= 0, batch > 0, lanes > 0")
         self._check_osd0(osd0)
-        dev = torch.device("cuda", self.device)
-        counters = torch.zeros((2, 4), dtype=torch.int64, device=dev)
-        torch.cuda.current_stream(dev).synchronize()  # the lanes add into zeroed counters
-        start, k = 0, 0
-        while start < shots:
-            B = min(batch, shots - start)
-            ln = self._lane_buffers(k % lanes, min(batch, shots), osd0)
-            self._enqueue(ln, B, seed, first_shot + start, osd0, counters[0], counters[1] if osd0 else None)
-            start, k = start + B, k + 1
-            if max_errors is not None and k % lanes == 0:
-                for l2 in self._lanes[:lanes]:
-                    l2["stream"].synchronize()
-                if int(counters[0, 1].item()) >= max_errors:
-                    break
-        for l2 in self._lanes:
-            l2["stream"].synchronize()
+        counters = torch.zeros((2, 4), dtype=torch.int64, device=torch.device("cuda", self.device))
+        self._run(shots, batch, lanes, first_shot, max_errors,
+                  lambda k, B, s: self._enqueue(self._lane(k, min(batch, shots), osd0), B, seed, s, osd0, counters[0], counters[1] if osd0 else None),
+                  lambda: int(counters[0, 1].item()))
         c = counters.cpu().numpy()
         return CodeCapacityResult(c[0, 0], c[0, 1], c[0, 2], c[0, 3], c[1, 1] if osd0 else None)
 
@@ -1654,7 +1638,7 @@ class CodeCapacityExperiment:
         ``result_osd0``."""
         self._check_osd0(osd0)
         B = int(B)
-        ln = self._lane_buffers(0, B, osd0)
+        ln = self._lane(0, B, osd0)
         self._enqueue(ln, B, seed, int(first_shot), osd0, None, None)
         ln["stream"].synchronize()
         keys = ["err", "sx", "est", "stats", "result"] + (["sz"] if self.decoder_name == "bp4_osd" else [])
@@ -1749,7 +1733,7 @@ def group_account_device(shot_result, true_flips, masks, counters, stream=None):
         raise RuntimeError(f"swd_group_account_dev failed: {_lib.last_error()}")
 
 
-class MemoryResult:
+class MemoryResult(_ErrorRate):
     """Counters of a memory experiment under sliding windows -- what the reference's ``sliding_window_decoder`` prints
     (/root/reference/osd.py:181-194).  ``logical_errors``: shots that are flagged or whose predicted observable flips differ from
     the true ones ("Logical Errors"); ``flagged``: shots whose residual syndrome is not zero ("Overall Flagged Errors");
@@ -1771,16 +1755,6 @@ class MemoryResult:
         self.failed_shots_complete = (len(self.failed_shots) == self.logical_errors) if failed_shots_complete is None \
             else bool(failed_shots_complete)
         self.group_errors = {k: int(v) for k, v in (group_errors or {}).items()}
-
-    @property
-    def ler(self):
-        return self.logical_errors / self.shots if self.shots else float("nan")
-
-    @property
-    def ler_stderr(self):
-        """binomial standard error of ``ler``"""
-        p = self.ler
-        return float(np.sqrt(p * (1.0 - p) / self.shots)) if self.shots else float("nan")
 
     def ler_per_round(self, num_repeat):
         """osd.py:190-191: ``1 - (1 - ler) ** (1 / num_repeat)``"""
@@ -1824,17 +1798,13 @@ class MemoryResult:
         return s + f", failed_shots={len(self.failed_shots)}{'' if self.failed_shots_complete else ' (incomplete)'})"
 
 
-class MemoryExperiment:
-    """The reference's ``sliding_window_decoder(N, p, num_repeat, num_shots, W, F, ...)`` (/root/reference/osd.py:123-194, guessing.py)
-    on the device: sample the detector error model (``DemSampler``), run the (W, F) window loop (``SlidingWindowDecoder``), compare
-    the predicted observable flips with the true ones and reduce the per-window records -- only counters come back to the host.
-
-    ``plan``: a ``windows.WindowPlan`` with 1..32 observables that the one-launch pipeline takes; ``decoder`` and the keyword
-    arguments are those of ``SlidingWindowDecoder``."""
+class _MemoryLaneExperiment(_LaneExperiment):
+    """What ``MemoryExperiment`` and ``RollingMemoryExperiment`` share beyond the lanes: the window decoder of a plan with 1..32
+    observables, the device counters of a run and the result they make, and the frame of ``run_batch``."""
 
     observable_groups = None  # what ``run`` counts per group when it is not told (``phenomenological(basis="both")`` sets it)
 
-    def __init__(self, plan, decoder="osd_window", device=0, **decoder_kwargs):
+    def __init__(self, plan, decoder, device, decoder_kwargs):
         num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
         if num_obs == 0:
             raise ValueError("a memory experiment needs observables: plan.obs is empty")
@@ -1842,10 +1812,70 @@ class MemoryExperiment:
             raise ValueError(f"a memory experiment carries at most 32 observables per shot, plan.obs has {num_obs}")
         self.plan, self.device = plan, int(device)
         self.decoder = SlidingWindowDecoder(plan, device=self.device, decoder=decoder, **decoder_kwargs)
-        self.decoder._no_loop("MemoryExperiment")
+        self.decoder._no_loop(type(self).__name__)
+        self._lanes = []
+
+    def _groups(self, observable_groups):
+        """-> (names, (masks, zeroed device counters)) of ``observable_groups`` (None: the experiment's own), or (None, None)"""
+        import torch
+        g = _observable_groups(self.observable_groups if observable_groups is None else observable_groups, self.plan.obs.shape[0])
+        if g is None:
+            return None, None
+        return g[0], (g[1], torch.zeros((len(g[1]),), dtype=torch.int64, device=torch.device("cuda", self.device)))
+
+    @staticmethod
+    def _group_errors(gnames, groups):
+        return dict(zip(gnames, groups[1].cpu().tolist())) if groups is not None else None
+
+    def _counters(self, window_rows, keep):
+        """zeroed device counters of a run: shots, rows of window counters (0: none), numbers of failing shots to keep (0: none)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        return (torch.zeros((4,), dtype=torch.int64, device=dev),
+                torch.zeros((window_rows, _lib.WINDOW_COUNTER_WORDS), dtype=torch.int64, device=dev) if window_rows else None,
+                torch.zeros((1 + keep,), dtype=torch.int64, device=dev) if keep else None)
+
+    def _result(self, counters, wc, failed, keep, gnames, groups):
+        """after the lanes were joined: the pipeline's status is checked, the device counters are read once -> (args, kwargs) of
+        ``MemoryResult``"""
+        self.decoder.check_status()
+        c = counters.cpu().numpy()
+        w = wc.cpu().numpy() if wc is not None else None
+        kept = failed.cpu().numpy().view(np.uint64) if failed is not None else np.zeros(1, np.uint64)
+        return (c[0], c[1], c[2], c[3]) + ((w[:, :8], w[:, 8], w[:, 9]) if w is not None else (None, None, None)), \
+            dict(failed_shots=kept[1:1 + min(int(kept[0]), keep)], failed_shots_complete=int(c[1]) <= keep,
+                 group_errors=self._group_errors(gnames, groups))
+
+    def _run_one_batch(self, B, observable_groups, enqueue, keys, want=False):
+        """the frame of ``run_batch``: ``enqueue(ln, groups)`` on lane 0, then ``keys`` of the lane and the true flips on the host"""
+        import torch
+        gnames, groups = self._groups(observable_groups)
+        if groups is not None:
+            torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()  # the lane adds into zeroed counters
+        ln = self._lane(0, B, want)
+        enqueue(ln, groups)
+        ln["stream"].synchronize()
+        self.decoder.check_status()
+        out = {key: ln[key][:B].cpu().numpy() for key in keys}
+        out["true_flips"] = ln["flips"][:B].cpu().numpy().view(np.uint32)
+        if groups is not None:
+            out["group_errors"] = self._group_errors(gnames, groups)
+        return out
+
+
+class MemoryExperiment(_MemoryLaneExperiment):
+    """The reference's ``sliding_window_decoder(N, p, num_repeat, num_shots, W, F, ...)`` (/root/reference/osd.py:123-194, guessing.py)
+    on the device: sample the detector error model (``DemSampler``), run the (W, F) window loop (``SlidingWindowDecoder``), compare
+    the predicted observable flips with the true ones and reduce the per-window records -- only counters come back to the host.
+
+    ``plan``: a ``windows.WindowPlan`` with 1..32 observables that the one-launch pipeline takes; ``decoder`` and the keyword
+    arguments are those of ``SlidingWindowDecoder``."""
+
+    def __init__(self, plan, decoder="osd_window", device=0, **decoder_kwargs):
+        super().__init__(plan, decoder, device, decoder_kwargs)
         self.sampler = DemSampler(plan.chk, plan.obs, plan.priors, device=self.device)
         self.W = self.decoder.W
-        self._stream, self._lanes = None, []
+        self._stream = None
 
     @classmethod
     def bb(cls, N, p, num_repeat, W, F, method=1, z_basis=True, decoder="osd_window", **kw):
@@ -1881,28 +1911,22 @@ class MemoryExperiment:
     __del__ = close
 
     # ---- one batch on one lane: sample, window loop, account, all ordered on the lane's torch stream ---------------------------
-    def _lane(self, k, cap, window_stats):
+    def _stale(self, ln, window_stats):
+        return window_stats and ln.get("stats") is None
+
+    def _alloc(self, ln, cap, window_stats):
         import torch
-        dev = torch.device("cuda", self.device)
-        while len(self._lanes) <= k:  # (streams of both priorities: streams of one priority may share a hardware queue)
-            self._lanes.append(dict(cap=0, stats=None, stream=torch.cuda.Stream(dev, priority=-(len(self._lanes) & 1))))
-        ln, d = self._lanes[k], self.decoder
-        if ln["cap"] < cap or (window_stats and ln["stats"] is None):
-            ln["stream"].synchronize()  # (the buffers it replaces may still be in use)
-            cap, i32 = max(cap, ln["cap"]), torch.int32
-            ln.update(cap=cap, det=torch.empty((cap, d.num_det), dtype=torch.uint8, device=dev), flips=torch.empty((cap,), dtype=i32, device=dev),
-                      total=torch.empty((cap, d.num_col), dtype=torch.uint8, device=dev), shot_result=torch.empty((cap, 2), dtype=i32, device=dev),
-                      result=torch.empty((cap,), dtype=i32, device=dev),
-                      stats=torch.empty((cap, self.W, _lib.STAT_WORDS), dtype=i32, device=dev) if window_stats or ln["stats"] is not None else None)
-        return ln
+        dev, d, i32 = torch.device("cuda", self.device), self.decoder, torch.int32
+        return dict(det=torch.empty((cap, d.num_det), dtype=torch.uint8, device=dev), flips=torch.empty((cap,), dtype=i32, device=dev),
+                    total=torch.empty((cap, d.num_col), dtype=torch.uint8, device=dev), shot_result=torch.empty((cap, 2), dtype=i32, device=dev),
+                    result=torch.empty((cap,), dtype=i32, device=dev),
+                    stats=torch.empty((cap, self.W, _lib.STAT_WORDS), dtype=i32, device=dev) if window_stats or ln.get("stats") is not None else None)
 
     def _enqueue(self, ln, B, seed, first_shot, streamed, window_stats, counters, window_counters, failed, groups=None):
         """``groups``: (masks, counters int64 [len(masks)]) or None"""
         st, d = ln["stream"], self.decoder
-        det, total, shot, stats = ln["det"][:B], ln["total"][:B], ln["shot_result"][:B], ln["stats"][:B] if window_stats else None
-        if _lib.lib().swd_sampler_sample_dev(self.sampler._h, B, int(seed), int(first_shot), det.data_ptr(), 0, ln["flips"].data_ptr(),
-                                             None, 0, st.cuda_stream):
-            raise RuntimeError(f"swd_sampler_sample_dev failed: {_lib.last_error()}")
+        total, shot, stats = ln["total"][:B], ln["shot_result"][:B], ln["stats"][:B] if window_stats else None
+        det = self.sampler.sample_device(B, seed, first_shot, out=(ln["det"], ln["flips"]), stream=st)[0]
         if streamed:  # the stream object's lane starts behind the sampler; the accounting waits for that lane alone
             self._stream.push_device(det, total, stats=stats, min_pm=None, shot_result=shot, after=st)
             self._stream.wait_last(st)
@@ -1911,14 +1935,6 @@ class MemoryExperiment:
         shot_account_device(shot, ln["flips"][:B], stats, first_shot, ln["result"], counters, window_counters, failed, stream=st)
         if groups is not None:
             group_account_device(shot, ln["flips"][:B], groups[0], groups[1], stream=st)
-
-    def _groups(self, observable_groups, dev):
-        """-> (names, (masks, zeroed device counters)) of ``observable_groups`` (None: the experiment's own), or (None, None)"""
-        import torch
-        g = _observable_groups(self.observable_groups if observable_groups is None else observable_groups, self.plan.obs.shape[0])
-        if g is None:
-            return None, None
-        return g[0], (g[1], torch.zeros((len(g[1]),), dtype=torch.int64, device=dev))
 
     def run(self, shots, batch=4096, seed=20240318, first_shot=0, lanes=2, max_errors=None, keep_failures=0, window_stats=True,
             observable_groups=None):
@@ -1932,72 +1948,41 @@ class MemoryExperiment:
         out (the window loop then writes none).  ``observable_groups``: name -> observable mask or list of observable indices, at
         most 4; ``result.group_errors[name]`` then counts the shots with a wrong observable inside the group, in one more small launch
         per batch (none without groups; ``{}`` switches the experiment's own groups off).  -> ``MemoryResult``."""
-        import torch
         shots, batch, lanes, keep = int(shots), int(batch), int(lanes), int(keep_failures)
         if shots < 0 or batch <= 0 or lanes not in (1, 2) or keep < 0:
             raise ValueError("shots >= 0, batch > 0, lanes 1 or 2 (a stream object has two), keep_failures >= 0")
-        dev = torch.device("cuda", self.device)
-        gnames, groups = self._groups(observable_groups, dev)
+        gnames, groups = self._groups(observable_groups)
         cap = max(1, min(batch, shots))
         if lanes == 2 and (self._stream is None or self._stream.max_shots < cap):
-            for ln in self._lanes:
-                ln["stream"].synchronize()
+            self._sync_lanes()
             self.close()
             self._stream = self.decoder.stream(cap, want_stats=window_stats)
-        counters = torch.zeros((4,), dtype=torch.int64, device=dev)
-        wc = torch.zeros((self.W, _lib.WINDOW_COUNTER_WORDS), dtype=torch.int64, device=dev) if window_stats else None
-        failed = torch.zeros((1 + keep,), dtype=torch.int64, device=dev) if keep else None
-        torch.cuda.current_stream(dev).synchronize()  # the lanes add into zeroed counters
-        start, k = 0, 0
-        while start < shots:
-            B = min(batch, shots - start)
-            ln = self._lane(k % lanes, cap, window_stats)
-            self._enqueue(ln, B, seed, first_shot + start, lanes == 2, window_stats, counters, wc, failed, groups)
-            start, k = start + B, k + 1
-            if max_errors is not None and k % lanes == 0:
-                for l2 in self._lanes[:lanes]:
-                    l2["stream"].synchronize()
-                if int(counters[1].item()) >= max_errors:
-                    break
-        for l2 in self._lanes:
-            l2["stream"].synchronize()
-        self.decoder.check_status()
-        c = counters.cpu().numpy()
-        w = wc.cpu().numpy() if wc is not None else None
-        kept = failed.cpu().numpy().view(np.uint64) if failed is not None else np.zeros(1, np.uint64)
-        return MemoryResult(c[0], c[1], c[2], c[3], *((w[:, :8], w[:, 8], w[:, 9]) if w is not None else (None, None, None)),
-                            failed_shots=kept[1:1 + min(int(kept[0]), keep)], failed_shots_complete=int(c[1]) <= keep,
-                            group_errors=dict(zip(gnames, groups[1].cpu().tolist())) if groups is not None else None)
+        counters, wc, failed = self._counters(self.W if window_stats else 0, keep)
+        self._run(shots, batch, lanes, first_shot, max_errors,
+                  lambda k, B, s: self._enqueue(self._lane(k, cap, window_stats), B, seed, s, lanes == 2, window_stats, counters, wc, failed, groups),
+                  lambda: int(counters[1].item()))
+        args, kw = self._result(counters, wc, failed, keep, gnames, groups)
+        return MemoryResult(*args, **kw)
 
     def run_batch(self, B, seed=20240318, first_shot=0, observable_groups=None):
         """One batch with the per-shot arrays on the host (tests and debugging): dict with ``det`` [B, num_det], ``true_flips`` uint32
         [B], ``total`` [B, num_col], ``stats`` [B, W, 8], ``shot_result`` [B, 2] and ``result`` (the words of include/swd.h: bit 0
         logical error, bit 1 flagged, bit 2 observable mismatch); with ``observable_groups`` (as in ``run``) also ``group_errors``."""
-        import torch
         B = int(B)
         if B <= 0:
             raise ValueError("B > 0")
-        dev = torch.device("cuda", self.device)
-        gnames, groups = self._groups(observable_groups, dev)
-        if groups is not None:
-            torch.cuda.current_stream(dev).synchronize()  # the lane adds into zeroed counters
-        ln = self._lane(0, B, True)
-        self._enqueue(ln, B, seed, int(first_shot), False, True, None, None, None, groups)
-        ln["stream"].synchronize()
-        self.decoder.check_status()
-        out = {key: ln[key][:B].cpu().numpy() for key in ("det", "total", "stats", "shot_result", "result")}
-        out["true_flips"] = ln["flips"][:B].cpu().numpy().view(np.uint32)
-        if groups is not None:
-            out["group_errors"] = dict(zip(gnames, groups[1].cpu().tolist()))
-        return out
+        return self._run_one_batch(B, observable_groups,
+                                   lambda ln, groups: self._enqueue(ln, B, seed, int(first_shot), False, True, None, None, None, groups),
+                                   ("det", "total", "stats", "shot_result", "result"), want=True)
 
 
-class RollingDemSampler:
+class RollingDemSampler(_Handle):
     """Samples the detector rows of a memory experiment of ANY number of rounds from a template of R0 rounds, a few row blocks (of
     ``n_half`` rows) per call and bit-identical to ``DemSampler`` on the model of that many rounds (C ABI: swd_rolling_sampler_*;
     ``windows.extend_template`` with the Philox stream on the global column number is the executable specification).  Its device
     memory is the template's.  ``template_plan``: a ``windows.WindowPlan`` that ``windows.rolling_template`` accepts, or the
     ``RollingTemplate`` itself; ``from_blocks`` takes any periodic model."""
+    _destroy = "swd_rolling_sampler_destroy"
 
     def __init__(self, template_plan, device=0):
         from .windows import _as_template, template_blocks
@@ -2038,14 +2023,6 @@ class RollingDemSampler:
         info = (C.c_int32 * 8)()
         L.swd_rolling_sampler_info(self._h, info, -1, 0, 0, None, None)
         self.n_half, self.num_obs, self.R0, self.min_rounds = int(info[0]), int(info[2]), int(info[3]), int(info[6])
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            try:
-                _lib.lib().swd_rolling_sampler_destroy(self._h)
-            except Exception:  # interpreter shutdown: the module globals may be gone already
-                pass
-            self._h = None
 
     def _check_rounds(self, rounds):
         if int(rounds) < self.min_rounds:
@@ -2136,7 +2113,27 @@ class RollingMemoryResult(MemoryResult):
         return "Rolling" + super().__repr__()[:-1] + f", rounds={self.rounds})"
 
 
-class RollingMemoryExperiment:
+def _smallest_rolling_template(num_repeat, W, F, make_plan, short_form):
+    """The plan of the least ``R0 = num_repeat (mod F)``, ``W <= R0 <= num_repeat``, that ``windows.rolling_template`` accepts.
+    ``make_plan(R0)`` -> (plan of R0 rounds, whatever else the caller wants back with it); ``short_form``: the constructor to
+    recommend when there is none.  -> what ``make_plan`` returned for that R0; ValueError relays the last refusal."""
+    from . import windows
+    num_repeat, why = int(num_repeat), "none was tried"
+    R0 = W + (num_repeat - W) % F
+    while R0 <= num_repeat:
+        plan, extras = make_plan(R0)
+        try:
+            windows.rolling_template(plan)
+        except ValueError as e:
+            why, R0 = f"R0 = {R0}: {e}", R0 + F
+            continue
+        return plan, extras
+    raise ValueError(f"no rolling template serves {num_repeat} rounds with (W, F) = ({W}, {F}): it needs R0 = {num_repeat} (mod {F}), "
+                     f"R0 <= {num_repeat}, periodic between its first and its last window, and {why}.  Use {short_form} for "
+                     f"an experiment this short")
+
+
+class RollingMemoryExperiment(_MemoryLaneExperiment):
     """``MemoryExperiment`` for experiments of any length: the reference's ``sliding_window_decoder(N, p, num_repeat, ...)`` swept over
     ``num_repeat`` from ONE template plan of R0 rounds, in device memory that does not depend on the length.  Per batch and lane:
     ``RollingSession.begin``; per window the rows it still needs from ``RollingDemSampler`` and one window step of the session;
@@ -2145,27 +2142,15 @@ class RollingMemoryExperiment:
     / tail.  ``template_plan``: a ``windows.WindowPlan`` with 1..32 observables that the one-launch pipeline takes and
     ``windows.rolling_template`` accepts; it serves ``rounds = R0 (mod F)``, ``rounds >= min_rounds``."""
 
-    observable_groups = None  # as in ``MemoryExperiment``
-    _groups = MemoryExperiment._groups
-
     def __init__(self, template_plan, decoder="osd_window", device=0, **decoder_kwargs):
         from .windows import rolling_template
-        plan = template_plan
-        num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
-        if num_obs == 0:
-            raise ValueError("a memory experiment needs observables: plan.obs is empty")
-        if num_obs > 32:
-            raise ValueError(f"a memory experiment carries at most 32 observables per shot, plan.obs has {num_obs}")
-        self.plan, self.device = plan, int(device)
-        self.decoder = SlidingWindowDecoder(plan, device=self.device, decoder=decoder, **decoder_kwargs)
-        self.decoder._no_loop("RollingMemoryExperiment")
-        self.template = rolling_template(plan)  # ValueError names what is not periodic
+        super().__init__(template_plan, decoder, device, decoder_kwargs)
+        self.template = rolling_template(template_plan)  # ValueError names what is not periodic
         self.sampler = RollingDemSampler(self.template, device=self.device)
         T = self.template
         self.rounds = int(T.R0)  # the default length of run()
         # row blocks a step hands over at most: the head's W, a body window's F, what finish takes
         self._step_blocks = max(T.W, T.F, (T.tail.row1 - T.tail.row0) // T.n_half - (T.W - T.F))
-        self._lanes = []
 
     @classmethod
     def bb(cls, N, p, num_repeat, W, F, method=1, z_basis=True, decoder="osd_window", **kw):
@@ -2174,24 +2159,15 @@ class RollingMemoryExperiment:
         accepts.  ``run()`` then defaults to ``num_repeat`` rounds."""
         from .circuit import bb_dem
         from .codes import bb_code
-        from .windows import plan_windows, rolling_template
+        from .windows import plan_windows
         code, A, B = bb_code(N)
-        num_repeat, why = int(num_repeat), "none was tried"
-        R0 = W + (num_repeat - W) % F
-        while R0 <= num_repeat:
+
+        def make_plan(R0):
             dem = bb_dem(code, A, B, p, R0, z_basis=z_basis)
-            plan = plan_windows(dem.chk, dem.obs, dem.priors, N // 2, W, F, method, z_basis)
-            try:
-                rolling_template(plan)
-            except ValueError as e:
-                why, R0 = f"R0 = {R0}: {e}", R0 + F
-                continue
-            exp = cls(plan, decoder=decoder, **kw)
-            exp.rounds = num_repeat
-            return exp
-        raise ValueError(f"no rolling template serves {num_repeat} rounds with (W, F) = ({W}, {F}): it needs R0 = {num_repeat} (mod {F}), "
-                         f"R0 <= {num_repeat}, periodic between its first and its last window, and {why}.  Use MemoryExperiment.bb for "
-                         f"an experiment this short")
+            return plan_windows(dem.chk, dem.obs, dem.priors, N // 2, W, F, method, z_basis), None
+        exp = cls(_smallest_rolling_template(num_repeat, W, F, make_plan, "MemoryExperiment.bb")[0], decoder=decoder, **kw)
+        exp.rounds = int(num_repeat)
+        return exp
 
     @classmethod
     def phenomenological(cls, code_or_matrices, p, num_repeat, W, F, q=None, basis="z", noise="bitflip", decoder="osd_window", **kw):
@@ -2199,28 +2175,21 @@ class RollingMemoryExperiment:
         template that serves ``num_repeat`` -- the model of the least ``R0 = num_repeat (mod F)``, ``R0 <= num_repeat``, that
         ``rolling_template`` accepts.  ``run()`` then defaults to ``num_repeat`` rounds."""
         from .phenomenological import experiment_model
-        from .windows import plan_windows, rolling_template
-        num_repeat, why = int(num_repeat), "none was tried"
-        R0 = W + (num_repeat - W) % F
-        while R0 <= num_repeat:
+        from .windows import plan_windows
+
+        def make_plan(R0):
             dem, n_half, groups = experiment_model(code_or_matrices, p, R0, q, basis, noise)
-            plan = plan_windows(dem.chk, dem.obs, dem.priors, n_half, W, F, method=0)
-            try:
-                rolling_template(plan)
-            except ValueError as e:
-                why, R0 = f"R0 = {R0}: {e}", R0 + F
-                continue
-            exp = cls(plan, decoder=decoder, **kw)
-            exp.rounds, exp.observable_groups = num_repeat, groups
-            return exp
-        raise ValueError(f"no rolling template serves {num_repeat} rounds with (W, F) = ({W}, {F}): it needs R0 = {num_repeat} (mod {F}), "
-                         f"R0 <= {num_repeat}, periodic between its first and its last window, and {why}.  Use "
-                         f"MemoryExperiment.phenomenological for an experiment this short")
+            return plan_windows(dem.chk, dem.obs, dem.priors, n_half, W, F, method=0), groups
+        plan, groups = _smallest_rolling_template(num_repeat, W, F, make_plan, "MemoryExperiment.phenomenological")
+        exp = cls(plan, decoder=decoder, **kw)
+        exp.rounds, exp.observable_groups = int(num_repeat), groups
+        return exp
 
     def close(self):
         for ln in getattr(self, "_lanes", []):
             ln["stream"].synchronize()
-            ln["session"].close()
+            if ln.get("session") is not None:
+                ln["session"].close()
         self._lanes = []
 
     __del__ = close
@@ -2233,22 +2202,15 @@ class RollingMemoryExperiment:
                    for ln in self._lanes)
 
     # ---- one batch on one lane: per window sample + step (+ its counts), then the tail and the accounting, all on the lane's stream ---
-    def _lane(self, k, cap):
+    def _alloc(self, ln, cap, want):
         import torch
-        dev = torch.device("cuda", self.device)
-        while len(self._lanes) <= k:
-            self._lanes.append(dict(cap=0, session=None, stream=torch.cuda.Stream(dev, priority=-(len(self._lanes) & 1))))
-        ln = self._lanes[k]
-        if ln["cap"] < cap:
-            ln["stream"].synchronize()  # (the buffers it replaces may still be in use)
-            if ln["session"] is not None:
-                ln["session"].close()
-            i32 = torch.int32
-            ln.update(cap=cap, session=self.decoder.rolling_session(cap),
-                      rows=torch.empty((cap, self._step_blocks * self.template.n_half), dtype=torch.uint8, device=dev),
-                      flips=torch.empty((cap,), dtype=i32, device=dev), shot_result=torch.empty((cap, 2), dtype=i32, device=dev),
-                      result=torch.empty((cap,), dtype=i32, device=dev), stats=torch.empty((cap, _lib.STAT_WORDS), dtype=i32, device=dev))
-        return ln
+        dev, i32 = torch.device("cuda", self.device), torch.int32
+        if ln.get("session") is not None:  # a session serves the shots it was opened for: a larger lane opens another
+            ln["session"].close()
+        return dict(session=self.decoder.rolling_session(cap),
+                    rows=torch.empty((cap, self._step_blocks * self.template.n_half), dtype=torch.uint8, device=dev),
+                    flips=torch.empty((cap,), dtype=i32, device=dev), shot_result=torch.empty((cap, 2), dtype=i32, device=dev),
+                    result=torch.empty((cap,), dtype=i32, device=dev), stats=torch.empty((cap, _lib.STAT_WORDS), dtype=i32, device=dev))
 
     def _enqueue(self, ln, B, rounds, sched, seed, first_shot, window_stats, counters, window_counters, failed, det=None, stats_all=None,
                  groups=None):
@@ -2303,38 +2265,18 @@ class RollingMemoryExperiment:
         once at the end; the result is a pure function of (seed, first_shot, shots, rounds), whatever ``batch`` and ``lanes``.
         ``max_errors``, ``keep_failures``, ``window_stats`` and ``observable_groups`` as in ``MemoryExperiment.run``.  ValueError, before anything is
         launched, when the template does not serve ``rounds``.  -> ``RollingMemoryResult``."""
-        import torch
         shots, batch, lanes, keep = int(shots), int(batch), int(lanes), int(keep_failures)
         if shots < 0 or batch <= 0 or lanes not in (1, 2) or keep < 0:
             raise ValueError("shots >= 0, batch > 0, lanes 1 or 2, keep_failures >= 0")
         rounds, sched = self._schedule(rounds)
-        dev = torch.device("cuda", self.device)
         cap = max(1, min(batch, shots))
-        gnames, groups = self._groups(observable_groups, dev)
-        counters = torch.zeros((4,), dtype=torch.int64, device=dev)
-        wc = torch.zeros((3, _lib.WINDOW_COUNTER_WORDS), dtype=torch.int64, device=dev) if window_stats else None
-        failed = torch.zeros((1 + keep,), dtype=torch.int64, device=dev) if keep else None
-        torch.cuda.current_stream(dev).synchronize()  # the lanes add into zeroed counters
-        start, k = 0, 0
-        while start < shots:
-            B = min(batch, shots - start)
-            self._enqueue(self._lane(k % lanes, cap), B, rounds, sched, seed, first_shot + start, window_stats, counters, wc, failed,
-                          groups=groups)
-            start, k = start + B, k + 1
-            if max_errors is not None and k % lanes == 0:
-                for l2 in self._lanes[:lanes]:
-                    l2["stream"].synchronize()
-                if int(counters[1].item()) >= max_errors:
-                    break
-        for l2 in self._lanes:
-            l2["stream"].synchronize()
-        self.decoder.check_status()
-        c = counters.cpu().numpy()
-        w = wc.cpu().numpy() if wc is not None else None
-        kept = failed.cpu().numpy().view(np.uint64) if failed is not None else np.zeros(1, np.uint64)
-        return RollingMemoryResult(rounds, len(sched), c[0], c[1], c[2], c[3], *((w[:, :8], w[:, 8], w[:, 9]) if w is not None else (None, None, None)),
-                                   failed_shots=kept[1:1 + min(int(kept[0]), keep)], failed_shots_complete=int(c[1]) <= keep,
-                                   group_errors=dict(zip(gnames, groups[1].cpu().tolist())) if groups is not None else None)
+        gnames, groups = self._groups(observable_groups)
+        counters, wc, failed = self._counters(3 if window_stats else 0, keep)
+        self._run(shots, batch, lanes, first_shot, max_errors,
+                  lambda k, B, s: self._enqueue(self._lane(k, cap), B, rounds, sched, seed, s, window_stats, counters, wc, failed, groups=groups),
+                  lambda: int(counters[1].item()))
+        args, kw = self._result(counters, wc, failed, keep, gnames, groups)
+        return RollingMemoryResult(rounds, len(sched), *args, **kw)
 
     def run_batch(self, B, rounds=None, seed=20240318, first_shot=0, observable_groups=None):
         """One batch with the per-shot arrays on the host (tests and debugging; unlike ``run`` it holds the whole experiment's rows):
@@ -2346,20 +2288,15 @@ class RollingMemoryExperiment:
         if B <= 0:
             raise ValueError("B > 0")
         rounds, sched = self._schedule(rounds)
-        dev = torch.device("cuda", self.device)
-        gnames, groups = self._groups(observable_groups, dev)
-        if groups is not None:
-            torch.cuda.current_stream(dev).synchronize()  # the lane adds into zeroed counters
-        ln = self._lane(0, B)
-        with torch.cuda.stream(ln["stream"]):
-            det = torch.empty((B, (rounds + 1) * self.template.n_half), dtype=torch.uint8, device=dev)
-            stats = torch.empty((len(sched), B, _lib.STAT_WORDS), dtype=torch.int32, device=dev)
-        self._enqueue(ln, B, rounds, sched, seed, int(first_shot), True, None, None, None, det=det, stats_all=stats, groups=groups)
-        ln["stream"].synchronize()
-        self.decoder.check_status()
-        out = {key: ln[key][:B].cpu().numpy() for key in ("shot_result", "result")}
-        if groups is not None:
-            out["group_errors"] = dict(zip(gnames, groups[1].cpu().tolist()))
-        out.update(det=det.cpu().numpy(), stats=np.ascontiguousarray(stats.cpu().numpy().transpose(1, 0, 2)),
-                   true_flips=ln["flips"][:B].cpu().numpy().view(np.uint32))
+        own = {}  # the whole experiment's rows and every window's records: this call's own arrays, not the lane's
+
+        def enqueue(ln, groups):
+            dev = torch.device("cuda", self.device)
+            with torch.cuda.stream(ln["stream"]):
+                own["det"] = torch.empty((B, (rounds + 1) * self.template.n_half), dtype=torch.uint8, device=dev)
+                own["stats"] = torch.empty((len(sched), B, _lib.STAT_WORDS), dtype=torch.int32, device=dev)
+            self._enqueue(ln, B, rounds, sched, seed, int(first_shot), True, None, None, None, det=own["det"], stats_all=own["stats"],
+                          groups=groups)
+        out = self._run_one_batch(B, observable_groups, enqueue, ("shot_result", "result"))
+        out.update(det=own["det"].cpu().numpy(), stats=np.ascontiguousarray(own["stats"].cpu().numpy().transpose(1, 0, 2)))
         return out
