@@ -556,6 +556,51 @@ int swd_pipeline_rolling_finish_dev(swd_rolling *s, int32_t nrows, const uint8_t
 int swd_pipeline_rolling_state(swd_rolling *s, int64_t *rows_received, int64_t *windows_done, int32_t *frame_fill, int32_t *info,
                                int64_t *device_bytes);
 
+/* ---- detector front end: raw measurement records in, detector rows out ------------------------------
+ * A running experiment produces measurement outcomes; the sessions above take detector rows.  Every detector of a memory
+ * experiment is the parity of measurements of its own round and of the round before it, and the rounds after the first are
+ * translates of one another, so three templates state the whole map (measurements.py, MeasurementMap.blocks, builds and checks them):
+ *     head, body  [n_half x 2 meas_per_round]             CSR over [previous round's measurements | this round's measurements]: round 0
+ *                                                         (no entry in the first half) and every later syndrome round
+ *     tail        [n_half x (meas_per_round + meas_final)] CSR over [last syndrome round | final block]: the detectors of the final block
+ *     obs_tail    [(<= 32) x the same]                     the observables (nullable: none)
+ * (channel_probs of the descriptors is ignored.)  A front end owns, for one batch of shots, the last complete round's outcomes and
+ * the bits of the round under way: 2 meas_per_round bytes per shot, whatever the length of the experiment, so it serves fixed and
+ * rolling sessions alike.  Refused at create: 2 meas_per_round + meas_final > 32768 (what one launch stages), a template of another
+ * shape, an entry outside its columns.
+ *   begin       zero state for a batch of B <= max_shots shots; also restarts a used front end
+ *   push_dev    the next nbits measurement bits of every shot, any number, 0 included; a chunk may end inside a round and inside a
+ *               byte.  packed = 0: one byte per bit (non-zero = 1); packed = 1: bit (i & 7) of byte (i >> 3) of the chunk -- every
+ *               chunk starts at bit 0 of its own buffer.  stride = bytes between the shots' buffers (0 = dense: nbits, or
+ *               (nbits + 7) / 8 packed); buffers that are 8-byte aligned (pointer and stride) are read with 8-byte loads.  Writes
+ *               the detector rows of every round the bits completed, det_rows [B][*rows_out] (det_stride = bytes between shots, 0 =
+ *               *rows_out), the layout swd_pipeline_session_push_dev and swd_pipeline_rolling_push_dev read.  *rows_out (nullable) =
+ *               ((bits of the round under way + nbits) / meas_per_round) n_half is computed on the host: the caller sizes det_rows by
+ *               the same rule from `state`; nothing is read back from the device.  One launch (more when a push is longer than a
+ *               launch stages), asynchronous on `stream`; calls on different streams are ordered by the front end.
+ *               EVERY bit handed to push counts as a bit of a syndrome round: the final block goes to finish.
+ *   finish_dev  the rest of the syndrome round under way, if any (whole further rounds are taken too), then the final block: writes
+ *               the remaining detector rows, the final block's n_half among them, and raw_obs [B]: bit k = the parity of observable
+ *               k's measurements.  Fails, with the state unchanged, unless the bits complete the last syndrome round exactly, bring
+ *               the whole final block and at least one syndrome round has been seen.  After finish: begin.
+ *   push/finish the same with host pointers, dense, synchronous
+ *   state       bits received and syndrome rounds completed since begin; info[8] = { meas_per_round, meas_final, n_half, observables,
+ *               bits of the round under way, final block taken, B, max_shots }; bytes of device memory owned; all nullable */
+typedef struct swd_frontend swd_frontend;
+swd_frontend *swd_frontend_create(const swd_graph_desc *head, const swd_graph_desc *body, const swd_graph_desc *tail,
+                                  const swd_graph_desc *obs_tail, int32_t meas_per_round, int32_t meas_final, int32_t n_half,
+                                  int32_t max_shots, int device);
+void swd_frontend_destroy(swd_frontend *fe);
+int swd_frontend_begin(swd_frontend *fe, int32_t B);
+int swd_frontend_state(swd_frontend *fe, int64_t *bits_received, int64_t *rounds_done, int32_t *info, int64_t *device_bytes);
+int swd_frontend_push_dev(swd_frontend *fe, int32_t nbits, const uint8_t *meas, int64_t stride, int32_t packed, uint8_t *det_rows,
+                          int64_t det_stride, int32_t *rows_out, void *stream);
+int swd_frontend_finish_dev(swd_frontend *fe, int32_t nbits, const uint8_t *final_meas, int64_t stride, int32_t packed,
+                            uint8_t *det_rows, int64_t det_stride, int32_t *rows_out, uint32_t *raw_obs, void *stream);
+int swd_frontend_push(swd_frontend *fe, int32_t nbits, const uint8_t *meas, int32_t packed, uint8_t *det_rows, int32_t *rows_out);
+int swd_frontend_finish(swd_frontend *fe, int32_t nbits, const uint8_t *final_meas, int32_t packed, uint8_t *det_rows,
+                        int32_t *rows_out, uint32_t *raw_obs);
+
 /* Threading and streams: every entry point may be called from any host thread.  Launches of ONE decoder /
  * pipeline handle are serialised on the host while they are prepared; on the device, launches on different streams
  * run concurrently -- each launch takes its scheduling scratch from a ring of four launch slots, and a fifth launch

@@ -103,6 +103,14 @@ SYMBOLS = [
     ("swd_pipeline_rolling_finish", C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     ("swd_pipeline_rolling_finish_dev", C.c_int, [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("swd_pipeline_rolling_state", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)]),
+    ("swd_frontend_create", _vp, [C.POINTER(GraphDesc)] * 4 + [_i32, _i32, _i32, _i32, C.c_int]),
+    ("swd_frontend_destroy", None, [_vp]),
+    ("swd_frontend_begin", C.c_int, [_vp, _i32]),
+    ("swd_frontend_state", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64)]),
+    ("swd_frontend_push_dev", C.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _i64, C.POINTER(_i32), _vp]),
+    ("swd_frontend_finish_dev", C.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _i64, C.POINTER(_i32), _vp, _vp]),
+    ("swd_frontend_push", C.c_int, [_vp, _i32, _vp, _i32, _vp, C.POINTER(_i32)]),
+    ("swd_frontend_finish", C.c_int, [_vp, _i32, _vp, _i32, _vp, C.POINTER(_i32), _vp]),
     ("swd_pipeline_status", C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     ("swd_pipeline_set_profiling", C.c_int, [_vp, _i32]),
     ("swd_pipeline_get_profile", C.c_int, [_vp, _i32, _vp]),
@@ -144,6 +152,7 @@ FORM_PLAN_WORDS = FORM_WINDOW_WORDS = 16  # include/swd.h: SWD_FORM_PLAN_WORDS, 
 STAT_WORDS = 8
 WINDOW_COUNTER_WORDS = 10  # include/swd.h: SWD_WINDOW_COUNTER_WORDS
 MAX_OBSERVABLE_GROUPS = 4  # include/swd.h: SWD_MAX_OBSERVABLE_GROUPS
+FRONTEND_STAGE_BYTES = 32768  # include/swd.h, swd_frontend_create: what one launch of the front end stages
 STREAM_PACKED,STREAM_NO_STATS = 1, 2
 STREAM_NO_DEPENDENCY = C.c_void_p(-1).value  # include/swd.h: SWD_STREAM_NO_DEPENDENCY
 

@@ -850,6 +850,17 @@ class SlidingWindowDecoder(_Handle):
         self._no_loop("rolling_session()")
         return RollingSession(self, max_shots)
 
+    def measurement_session(self, max_shots, mmap):
+        """Online form fed with the raw measurement record (``MeasurementSession``): ``mmap`` is the experiment's
+        ``measurements.MeasurementMap``; a device front end turns the arriving bits into detector rows in front of ``session``'s
+        merge, and ``finish`` returns the corrected logical readout.  ValueError if the map does not fit the plan."""
+        return MeasurementSession(self, max_shots, mmap)
+
+    def rolling_measurement_session(self, max_shots, mmap):
+        """Rolling form fed with the raw measurement record (``RollingMeasurementSession``); ``mmap`` is the map of the template's
+        own R0 rounds."""
+        return RollingMeasurementSession(self, max_shots, mmap)
+
     def decode_stream(self, batches, packed=False, want_stats=True):
         """Generator over an iterable of host batches [B_k, num_det]: yields (total_e_hat, stats, min_pm, obs_flips, flagged) per
         batch, in order, keeping two batches in flight (the deployment form of the shots loop of /root/reference/osd.py:130-191)."""
@@ -1284,6 +1295,302 @@ class RollingSession(_SessionBase):
                                                       faults.data_ptr(), stats.data_ptr(), pm.data_ptr(), shot.data_ptr(), st.cuda_stream):
             raise RuntimeError(f"swd_pipeline_rolling_finish_dev failed: {_lib.last_error()}")
         return t, faults, stats, pm, shot[:, 0], shot[:, 1]
+
+
+def _template_desc(a, keep):
+    """CSR descriptor of a measurement template (no priors); the arrays are appended to ``keep``"""
+    a = sp.csr_matrix(a)
+    a.sort_indices()
+    rp, ci = np.ascontiguousarray(a.indptr, np.int32), np.ascontiguousarray(a.indices, np.int32)
+    keep += [rp, ci]
+    return _lib.GraphDesc(a.shape[0], a.shape[1], int(rp[-1]), rp.ctypes.data, ci.ctypes.data, None)
+
+
+class MeasurementFrontEnd(_Handle):
+    """Detector front end (C ABI: swd_frontend_*): turns the raw measurement record of a batch of shots, arriving in pieces of any
+    size, into detector rows on the device -- ``measurements.MeasurementMap.blocks(n_half)`` applied push by push.  Per shot it
+    keeps the last complete round's outcomes and the bits of the round under way (``device_bytes`` depends on the map and
+    ``max_shots`` only).  ``push`` / ``push_device`` take bits of the SYNDROME rounds and return the rows of the rounds they
+    completed; ``finish`` / ``finish_device`` take the rest of the last syndrome round and the final block and return the remaining
+    rows and the raw observable parities (uint32 masks).  ``packed=True``: bit ``i & 7`` of byte ``i >> 3`` of every chunk
+    (``np.packbits(chunk, axis=1, bitorder="little")``)."""
+    _destroy = "swd_frontend_destroy"
+    close = _Handle._release
+
+    def __init__(self, mmap, n_half, max_shots, device=0):
+        blk = mmap.blocks(n_half)  # ValueError names what does not fit
+        self.blocks, self.max_shots, self.device, self.B = blk, int(max_shots), int(device), 0
+        self.n_half, self.meas_per_round, self.meas_final, self.num_obs = blk.n_half, blk.meas_per_round, blk.meas_final, blk.obs_tail.shape[0]
+        # what the library refuses about the map and the batch is checked here: a failing create is then the device's
+        if self.num_obs > 32:
+            raise ValueError(f"at most 32 observables, the map has {self.num_obs}")
+        if self.max_shots <= 0:
+            raise ValueError("max_shots must be positive")
+        if 2 * blk.meas_per_round + blk.meas_final > _lib.FRONTEND_STAGE_BYTES:
+            raise ValueError(f"two rounds of {blk.meas_per_round} measurements and a final block of {blk.meas_final} exceed the "
+                             f"{_lib.FRONTEND_STAGE_BYTES} bytes a launch of the front end stages")
+        keep = []
+        d = [_template_desc(t, keep) for t in (blk.head, blk.body, blk.tail, blk.obs_tail)]
+        self._h = _lib.lib().swd_frontend_create(C.byref(d[0]), C.byref(d[1]), C.byref(d[2]), C.byref(d[3]) if self.num_obs else None,
+                                                 blk.meas_per_round, blk.meas_final, blk.n_half, self.max_shots, self.device)
+        if not self._h:
+            raise RuntimeError(f"swd_frontend_create failed: {_lib.last_error()}")
+
+    def begin(self, B):
+        if _lib.lib().swd_frontend_begin(self._h, int(B)):
+            raise RuntimeError(f"swd_frontend_begin failed: {_lib.last_error()}")
+        self.B = int(B)
+
+    def _state(self):
+        bits, rounds, info, nbytes = C.c_int64(), C.c_int64(), (C.c_int32 * 8)(), C.c_int64()
+        if _lib.lib().swd_frontend_state(self._h, C.byref(bits), C.byref(rounds), info, C.byref(nbytes)):
+            raise RuntimeError(f"swd_frontend_state failed: {_lib.last_error()}")
+        return bits.value, rounds.value, int(info[4]), bool(info[5]), nbytes.value
+
+    @property
+    def bits_received(self):
+        return self._state()[0]
+
+    @property
+    def rounds_done(self):
+        return self._state()[1]
+
+    @property
+    def device_bytes(self):
+        return self._state()[4]
+
+    def rows_for(self, nbits, final=False):
+        """detector rows a push (``final``: the finish) of ``nbits`` bits completes; ValueError if a finish of that many bits does
+        not complete the last syndrome round and bring the whole final block"""
+        bits, rounds, fill, finished = self._state()[:4]
+        nbits = int(nbits)
+        if not final:
+            return (fill + nbits) // self.meas_per_round * self.n_half
+        pre = nbits - self.meas_final
+        if self.B and (finished or pre < 0 or (fill + pre) % self.meas_per_round or rounds + (fill + pre) // self.meas_per_round < 1):
+            raise ValueError(f"finish: {nbits} bits after {bits} received ({rounds} whole rounds of {self.meas_per_round}, {fill} bits of the "
+                             f"next) do not complete the last syndrome round and bring the final block of {self.meas_final}")
+        return ((fill + pre) // self.meas_per_round + 1) * self.n_half
+
+    def _host_bits(self, meas, packed):
+        """[B, k] host chunk -> (C-contiguous uint8 array, number of bits).  A packed chunk is [B, ceil(k / 8)] bytes and carries
+        8 bits per byte unless ``packed`` is the bit count itself."""
+        d = np.asarray(meas)
+        if d.ndim != 2 or d.shape[0] != self.B:
+            raise ValueError(f"meas must have shape [{self.B}, k]")
+        if d.dtype != np.uint8:
+            if _is_packed(packed):
+                if ((d < 0) | (d > 255)).any():
+                    raise ValueError("a packed chunk holds bytes: values 0..255")
+                d = d.astype(np.uint8)
+            else:
+                d = (d != 0).astype(np.uint8)  # any non-zero value is a 1, as on the device
+        return np.ascontiguousarray(d), _chunk_bits(d.shape[1], packed)
+
+    def _check_device_bits(self, meas, packed):
+        import torch
+        if meas.dtype != torch.uint8 or meas.dim() != 2 or meas.shape[0] != self.B or not meas.is_cuda or (meas.shape[1] > 1 and meas.stride(1) != 1):
+            raise ValueError(f"meas must be a uint8 CUDA tensor [{self.B}, k] with unit column stride")
+        if meas.device.index != self.device:
+            raise ValueError(f"meas lives on {meas.device}, the front end on cuda:{self.device}")
+        return _chunk_bits(meas.shape[1], packed)
+
+    def push(self, meas, packed=False):
+        """meas [B, k] (host): the next bits of the syndrome rounds -> det_rows uint8 [B, rows completed]"""
+        d, nbits = self._host_bits(meas, packed)
+        rows = np.empty((self.B, self.rows_for(nbits) if self.B else 0), np.uint8)
+        n = C.c_int32()
+        if _lib.lib().swd_frontend_push(self._h, nbits, d.ctypes.data, _is_packed(packed), rows.ctypes.data, C.byref(n)):
+            raise RuntimeError(f"swd_frontend_push failed: {_lib.last_error()}")
+        assert n.value == rows.shape[1]
+        return rows
+
+    def finish(self, final_meas, packed=False):
+        """final_meas [B, k] (host): the rest of the last syndrome round, then the final block -> (det_rows uint8 [B, rows],
+        raw_obs uint32 [B]).  ValueError, with the state unchanged, if the bits do not end the experiment."""
+        d, nbits = self._host_bits(final_meas, packed)
+        rows = np.empty((self.B, self.rows_for(nbits, final=True) if self.B else 0), np.uint8)
+        raw, n = np.zeros(self.B, np.uint32), C.c_int32()
+        if _lib.lib().swd_frontend_finish(self._h, nbits, d.ctypes.data, _is_packed(packed), rows.ctypes.data, C.byref(n), raw.ctypes.data):
+            raise RuntimeError(f"swd_frontend_finish failed: {_lib.last_error()}")
+        return rows, raw
+
+    def push_device(self, meas, packed=False, out=None, stream=None):
+        """torch uint8 CUDA tensor [B, k] with unit column stride; one launch queued on ``stream`` (default: the current torch
+        stream).  ``out``: optional uint8 CUDA tensor [B, >= rows] with unit column stride to write into.  -> det_rows [B, rows]."""
+        import torch
+        nbits = self._check_device_bits(meas, packed)
+        st = torch.cuda.current_stream(meas.device) if stream is None else stream
+        rows = self.rows_for(nbits) if self.B else 0
+        if out is None:
+            with torch.cuda.stream(st):
+                out = torch.empty((self.B, rows), dtype=torch.uint8, device=meas.device)
+        elif out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != self.B or out.shape[1] < rows or out.device != meas.device or \
+                (out.shape[1] > 1 and out.stride(1) != 1):
+            raise ValueError(f"out must be a uint8 CUDA tensor [{self.B}, >= {rows}] with unit column stride on {meas.device}")
+        n = C.c_int32()
+        if _lib.lib().swd_frontend_push_dev(self._h, nbits, meas.data_ptr() if nbits else None, meas.stride(0) if nbits else 0, _is_packed(packed),
+                                            out.data_ptr() if rows else None, out.stride(0) if rows else 0, C.byref(n), st.cuda_stream):
+            raise RuntimeError(f"swd_frontend_push_dev failed: {_lib.last_error()}")
+        return out[:, :rows] if out.shape[1] != rows else out
+
+    def finish_device(self, final_meas, packed=False, stream=None):
+        """``finish`` with a CUDA tensor, queued on ``stream`` -> (det_rows [B, rows] uint8, raw_obs [B] int32 bit masks), CUDA tensors"""
+        import torch
+        nbits = self._check_device_bits(final_meas, packed)
+        rows = self.rows_for(nbits, final=True)
+        st = torch.cuda.current_stream(final_meas.device) if stream is None else stream
+        with torch.cuda.stream(st):
+            out = torch.empty((self.B, rows), dtype=torch.uint8, device=final_meas.device)
+            raw = torch.empty(self.B, dtype=torch.int32, device=final_meas.device)
+        n = C.c_int32()
+        if _lib.lib().swd_frontend_finish_dev(self._h, nbits, final_meas.data_ptr(), final_meas.stride(0), _is_packed(packed), out.data_ptr(),
+                                              out.stride(0), C.byref(n), raw.data_ptr(), st.cuda_stream):
+            raise RuntimeError(f"swd_frontend_finish_dev failed: {_lib.last_error()}")
+        return out, raw
+
+
+def _is_packed(packed):
+    return 0 if packed is False or packed is None else 1
+
+
+def _chunk_bits(width, packed):
+    """bits of a chunk that is ``width`` bytes wide: ``packed`` False -> one per byte; True -> 8 per byte; an int -> that many bits
+    of ceil(bits / 8) bytes (a packed chunk that ends inside a byte)"""
+    if packed is False or packed is None:
+        return int(width)
+    if packed is True:
+        return 8 * int(width)
+    nbits = int(packed)
+    if nbits < 0 or (nbits + 7) // 8 != width:
+        raise ValueError(f"a packed chunk of {nbits} bits is {(nbits + 7) // 8} bytes wide, got {width}")
+    return nbits
+
+
+class _MeasurementSessionBase:
+    """A ``MeasurementFrontEnd`` in front of a session: ``push`` takes measurement bits instead of detector rows and returns what
+    the session's ``push`` returns for the rounds the bits completed."""
+
+    def __init__(self, dec, session, mmap, max_shots, rows_per_round, num_obs):
+        self.dec, self.session, self.frontend, self.B = dec, session, None, 0
+        try:
+            if mmap.n_half is not None and mmap.n_half != rows_per_round:
+                raise ValueError(f"the map has {mmap.n_half} detector rows per round, the plan {rows_per_round}")
+            if mmap.obs.shape[0] != num_obs:
+                raise ValueError(f"the map has {mmap.obs.shape[0]} observables, the plan {num_obs}")
+            self.frontend = MeasurementFrontEnd(mmap, rows_per_round, max_shots, dec.device)
+        except Exception:
+            session.close()
+            raise
+
+    def close(self):
+        for x in (self.frontend, self.session):
+            if x is not None:
+                x.close()
+
+    def begin(self, B):
+        self.session.begin(B)
+        self.frontend.begin(B)
+        self.B = int(B)
+
+    @property
+    def bits_received(self):
+        return self.frontend.bits_received
+
+    def _check_push(self, nbits):
+        pass  # (a rolling experiment has no length until it ends)
+
+    def push(self, meas, packed=False):
+        """meas [B, k] (host): the next bits of the syndrome rounds, any number; ``packed``: False = one byte per bit, True = 8 bits
+        per byte, an int = that many bits in ceil(bits / 8) bytes.  Returns what the session's ``push`` returns for the detector rows
+        of the rounds these bits completed."""
+        fe = self.frontend
+        d, nbits = fe._host_bits(meas, packed)
+        self._check_push(nbits)
+        return self.session.push(fe.push(d, packed))
+
+    def push_device(self, meas, packed=False, stream=None, **kw):
+        """The same with a uint8 CUDA tensor: the front end's launch, then the session's merge, decode and commit, are queued on
+        ``stream`` (default: the current torch stream).  Returns what the session's ``push_device`` returns."""
+        import torch
+        fe = self.frontend
+        nbits = fe._check_device_bits(meas, packed)
+        self._check_push(nbits)
+        st = torch.cuda.current_stream(meas.device) if stream is None else stream
+        # the rows are a tensor of this push, allocated on its stream: a buffer kept from push to push would need an order of its
+        # own when the stream changes (the front end's event is recorded before the session's merge has read the rows)
+        return self.session.push_device(fe.push_device(meas, packed, stream=st), stream=st, **kw)
+
+
+class MeasurementSession(_MeasurementSessionBase):
+    """``SlidingWindowDecoder.measurement_session``: an online session (``SlidingWindowSession``) fed with the raw measurement record.
+    ``push`` takes the bits of the syndrome rounds in pieces of any size; ``finish`` takes the rest of the last syndrome round and
+    the final block, pushes the remaining detector rows -- the windows they complete are left in ``last_events``, in the form
+    ``push`` returns them -- and returns the session's ``finish`` with the corrected readout."""
+
+    def __init__(self, dec, max_shots, mmap):
+        dec._no_loop("measurement_session()")
+        if mmap.det.shape[0] != dec.num_det:
+            raise ValueError(f"the map has {mmap.det.shape[0]} detectors, the plan {dec.num_det}")
+        super().__init__(dec, dec.session(max_shots), mmap, max_shots, dec.plan.n_half, dec.num_obs)
+        self.total_bits = self.frontend.blocks.rounds * self.frontend.meas_per_round
+        self.last_events = []
+
+    def _check_push(self, nbits):
+        got = self.frontend.bits_received if self.B else 0
+        if self.B and got + nbits > self.total_bits:
+            raise ValueError(f"{nbits} bits after {got} received: the syndrome rounds of this experiment have {self.total_bits} "
+                             f"(the final block of {self.frontend.meas_final} goes to finish)")
+
+    def _check_finish(self, nbits):
+        fe = self.frontend
+        got = fe.bits_received if self.B else 0
+        if self.B and got + nbits != self.total_bits + fe.meas_final:
+            raise ValueError(f"finish: {nbits} bits after {got} received; the experiment has {self.total_bits} bits of syndrome rounds and a "
+                             f"final block of {fe.meas_final}: finish takes the {self.total_bits + fe.meas_final - got} that are left")
+
+    def finish(self, final_meas, packed=False):
+        """final_meas [B, k] (host): the rest of the last syndrome round, if any, then the final block.  Returns ``(total_e_hat,
+        stats, min_pm, obs_flips, flagged, raw_obs, logical_values)``: the first five as ``SlidingWindowSession.finish`` and
+        ``decode`` leave them, ``raw_obs`` uint32 [B] = the observables' parities of the data measurement as read, and
+        ``logical_values = raw_obs ^ obs_flips``, the corrected logical readout.  ValueError, with the state unchanged, unless the
+        bits are exactly those the experiment still lacks."""
+        fe = self.frontend
+        d, nbits = fe._host_bits(final_meas, packed)
+        self._check_finish(nbits)
+        rows, raw = fe.finish(d, packed)
+        self.last_events = self.session.push(rows)
+        out = self.session.finish()
+        return out + (raw, raw ^ out[3])
+
+
+class RollingMeasurementSession(_MeasurementSessionBase):
+    """``SlidingWindowDecoder.rolling_measurement_session``: a rolling session (``RollingSession``) fed with the raw measurement
+    record of an experiment of any length the template serves; the map is that of the template's own R0 rounds.  The final block
+    goes to ``finish``, with the rest of the last syndrome round if any: the rows of that round are pushed first -- the windows
+    they complete are left in ``last_events``, in the form ``push`` returns them -- and the final block closes the experiment."""
+
+    def __init__(self, dec, max_shots, mmap):
+        dec._no_loop("rolling_measurement_session()")
+        ses = dec.rolling_session(max_shots)
+        super().__init__(dec, ses, mmap, max_shots, ses.template.n_half, dec.num_obs)
+        self.last_events = []
+
+    def finish(self, final_meas, packed=False):
+        """final_meas [B, k] (host): the rest of the last syndrome round, if any, then the final block.  Returns ``(t, tail_faults,
+        stats, min_pm, obs_flips, flagged, raw_obs, logical_values)``: the first six as ``RollingSession.finish`` returns them, then
+        the raw observable parities and ``logical_values = raw_obs ^ obs_flips``.  ValueError, with the state unchanged, if the bits
+        do not end the round under way and bring the final block, or the rounds are not a length the template serves."""
+        fe, T = self.frontend, self.session.template
+        d, nbits = fe._host_bits(final_meas, packed)
+        ahead = fe.rows_for(nbits, final=True) - T.n_half  # rows of syndrome rounds the call completes
+        rounds, rem = divmod(self.session.rows_received + ahead, T.n_half)
+        if self.B and (rem or not T.serves(rounds)):
+            raise ValueError(f"finish: the experiment would end after {rounds} syndrome rounds; this template serves {T.lengths()}")
+        rows, raw = fe.finish(d, packed)
+        self.last_events = self.session.push(rows[:, :ahead]) if ahead else []
+        out = self.session.finish(rows[:, ahead:])
+        return out + (raw, raw ^ out[4])
 
 
 class DemSampler(_Handle):
