@@ -169,7 +169,8 @@ int swd_gdg_decode_batch_dev(swd_gdg *d, int32_t B, const uint8_t *synd, int64_t
  * posterior LLRs, decisions and OSD orderings are bit-identical to a reference run on an FMA-capable x86-64.
  * Restrictions (swd_bp4_create fails with a message): column weight of Hx / Hz <= 10, except for up to 8 HEAVY columns
  * (weight above 10 in Hx or Hz, any position, any weight up to m <= 1024: the last qubit of the cycle-assembled and EG codes of
- * Misc.ipynb cells 6-8, H = (H1 | 1), touches every check), which are accepted with osd_order = -1 only (decode returns the BP
+ * Misc.ipynb cells 6-8, H = (H1 | 1), touches every check), which are accepted with osd_order = -1 only unless the handle is
+ * created with SWD_BP4_GENERAL_OSD (below) (decode returns the BP
  * decisions of a shot that did not converge; camel_decode never runs OSD) -- with osd_method 0 the caller's -1 stands on such a
  * graph, where the reference resets it to 0 (bp4_osd.pyx:74-76); osd_order > 0 needs
  * rank(Hx) >= rank(Hz) -- the reference sizes BOTH sweeps with kx = n - rank_x (bp4_osd.pyx:103-104, :284): with
@@ -181,10 +182,21 @@ int swd_gdg_decode_batch_dev(swd_gdg *d, int32_t B, const uint8_t *synd, int64_t
  * row and column weight, up to 1 048 576 qubits, 1 048 576 checks per matrix and 67 108 864 edges in Hx and Hz together (the EG
  * codes [[273,111,17]] and [[1057,571,33]] of Misc.ipynb cell 8, whose every column is above the weight bound; large light codes).
  * One 1024-thread workgroup per shot (per run of a camel shot), every array in HBM.  It is opt-in and takes ANY graph, one the tuned
- * kernels would take included; it runs BP only, so like a graph with heavy columns it is created with osd_order = -1 only (with
- * osd_method 0 the caller's -1 stands), the same results bit for bit.  Every entry point below dispatches on the handle;
- * swd_bp4_info reports ranks of -1 (no elimination: they are not computed), swd_bp4_heavy_info (0, 0) (no column is special),
- * swd_bp4_last_form threads = 1024 with the other fields 0. */
+ * kernels would take included; on its own it runs BP only, so like a graph with heavy columns it is created with osd_order = -1
+ * only (with osd_method 0 the caller's -1 stands; SWD_BP4_GENERAL_OSD below lifts both), the same results bit for bit.  Every entry point below dispatches on the handle;
+ * swd_bp4_info reports the host GF(2) ranks (-1 only without the elimination on a graph whose dense rows would pass 1 GiB, where
+ * they are not computed), swd_bp4_heavy_info (0, 0) (no column is special), swd_bp4_last_form threads = 1024 with the other fields 0.
+ * GENERAL OSD (swd_bp4_create_ex with SWD_BP4_GENERAL_OSD; huge_bp4_osd_kernel, csrc/swd_huge_bp4.hip): the elimination and the
+ * osd_e / osd_cs sweep in HBM, one 1024-thread workgroup per unconverged decode, no bound on a column's weight.  Opt-in.  With the
+ * bit set osd_order >= 0 is taken on a graph with heavy columns (the tuned BP kernel queues for it), with SWD_BP4_GENERAL_FORM
+ * beside it on any graph (the general BP kernel queues for it), and on any other graph too (BP in whatever tuned form the graph
+ * takes, the elimination in this kernel instead of the tuned one); osd_method 0 resets the order to 0 as the reference does, so
+ * Misc.ipynb cell 8's (osd0, -1) runs OSD-0 inside decode like the reference; -1 with methods 1 and 2 stays "no OSD".  The rules
+ * above carry over (osd_order <= min(n - rank_x, n - rank_z); osd_order > 0 needs rank(Hx) >= rank(Hz) and walks kx candidates
+ * in the z basis; osd_e order <= 15).  Its own bounds, refused at create with a message that names them: at most 4096 checks per
+ * matrix (64 words per column of the transform matrix), and one workgroup's elimination arrays within the 8 GiB of a launch
+ * slot's area (the grid shrinks to fit first).  Results are those of the reference bit for bit; statistics word 0 is SWD_EXIT_OSD,
+ * word 7 the row additions of both bases as the general form of osd_window counts them (not comparable with the tuned kernels'). */
 typedef struct swd_bp4_params {
     int32_t max_iter;          /* default 32 */
     double ms_scaling_factor;
@@ -194,11 +206,14 @@ typedef struct swd_bp4_params {
 typedef struct swd_bp4 swd_bp4;
 swd_bp4 *swd_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *px, const double *py,
                         const double *pz, const swd_bp4_params *p, int device); /* channel_probs of hx/hz ignored */
-/* swd_bp4_create with flags: bit 0 (SWD_BP4_GENERAL_FORM) = the general form.  swd_bp4_create(...) is swd_bp4_create_ex(..., 0). */
+/* swd_bp4_create with flags: bit 0 (SWD_BP4_GENERAL_FORM) = the general form, bit 1 (SWD_BP4_GENERAL_OSD) = the general
+ * elimination.  swd_bp4_create(...) is swd_bp4_create_ex(..., 0). */
 #define SWD_BP4_GENERAL_FORM 1
+#define SWD_BP4_GENERAL_OSD 2
 swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *px, const double *py,
                            const double *pz, const swd_bp4_params *p, int device, int32_t flags);
 int swd_bp4_is_general(const swd_bp4 *d); /* 1: the handle runs the general form, 0: a tuned kernel, -1: null */
+int swd_bp4_is_general_osd(const swd_bp4 *d); /* 1: created with SWD_BP4_GENERAL_OSD, 0: not, -1: null */
 void swd_bp4_destroy(swd_bp4 *d);
 int swd_bp4_info(const swd_bp4 *d, int32_t *mx, int32_t *mz, int32_t *n, int32_t *rank_x, int32_t *rank_z);
 /* Heavy columns of the handle's graphs (both pointers nullable): how many columns the decoder treats as heavy (0: none -- the

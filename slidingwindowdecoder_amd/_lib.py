@@ -63,6 +63,7 @@ SYMBOLS = [
     ("swd_bp4_create", _vp, [C.POINTER(GraphDesc), C.POINTER(GraphDesc), _vp, _vp, _vp, C.POINTER(Bp4Params), C.c_int]),
     ("swd_bp4_create_ex", _vp, [C.POINTER(GraphDesc), C.POINTER(GraphDesc), _vp, _vp, _vp, C.POINTER(Bp4Params), C.c_int, _i32]),
     ("swd_bp4_is_general", C.c_int, [_vp]),
+    ("swd_bp4_is_general_osd", C.c_int, [_vp]),
     ("swd_bp4_destroy", None, [_vp]),
     ("swd_bp4_info", C.c_int, [_vp] + [C.POINTER(_i32)] * 5),
     ("swd_bp4_heavy_info", C.c_int, [_vp] + [C.POINTER(_i32)] * 2),

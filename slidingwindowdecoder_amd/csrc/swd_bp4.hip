@@ -13,6 +13,8 @@ int make_layout_for_osd(const Graph &g, int nt, SwdLdsLayout &L); // swd_osdw.hi
 const char *last_error();                                          // swd_graph.hip
 // what the refusals of a graph beyond the tuned kernels end with
 #define SWD_BP4_GENERAL_HINT " (bp4_osd(..., general_form=True) takes such a graph: BP only, osd_order=-1 or camel_decode)"
+// what the refusals of an OSD the tuned elimination kernel cannot run end with
+#define SWD_BP4_GENERAL_OSD_HINT "; bp4_osd(..., general_osd=True) runs the OSD of such a graph in the general elimination kernel"
 
 struct Bp4 {
     Graph gx, gz;
@@ -21,6 +23,13 @@ struct Bp4 {
     int heavy = 0, heavy_deg = 0; // heavy columns (weight above SWD_DMAX in Hx or Hz: the HEAVY instantiation) and the largest of their weights
     // the general form (swd_huge_bp4.hip; swd_bp4_create_ex flag bit 0): every launch goes to it, gx / gz stay empty
     std::unique_ptr<HugeBp4Iface> general;
+    // the general elimination (huge_bp4_osd_kernel, swd_huge_bp4.hip; flag bit 1): the decodes a BP kernel queues are finished there,
+    // not in bp4_osd_kernel.  With the general form beside it `general` itself (one device copy of the graphs), otherwise an object
+    // of its own that runs no BP.  NULL when the handle runs no OSD (osd_order = -1).
+    std::unique_ptr<HugeBp4Iface> elim_own;
+    HugeBp4Iface *elim = nullptr;
+    bool general_osd = false; // the flag as given, whatever the order
+    int cur_slot = 0;         // (under mu) the launch slot of the launch being prepared: the elimination's scratch area
     int nt_split = 0; // > 0: threads of the launch with two threads per qubit (the specialised instantiation; swd_bp4_kernel.h) // nt: threads of the BP kernel (a launch parameter), nt_osd: of the OSD kernel (its layouts)
     SwdLdsLayout Lx{}, Lz{};
     SwdBp4Layout L{};
@@ -80,10 +89,15 @@ static int bp4_launch(Bp4 *d, const SwdBp4Args &a0, hipStream_t st, int nt) {
         slots_lds[d->device & 63] = d->L.total; slots_nt[d->device & 63] = nt;
     }
     const int units = a.camel ? 4 * a.B : a.B;
-    const bool with_osd = !HEAVY && !a.camel && a.osd_order >= 0; // (graphs with heavy columns are created with osd_order = -1 only)
+    // (graphs with heavy columns are created with osd_order = -1, or with the general elimination: no Lx / Lz layouts)
+    const bool with_osd = (!HEAVY || d->elim) && !a.camel && a.osd_order >= 0;
     if (with_osd || a.ticket) SWD_HIP(hipMemsetAsync(a.osd_count, 0, 4 * sizeof(uint32_t), st)); // (queue counter, ticket counter)
     hipLaunchKernelGGL((bp4_kernel<WMAX, DM, FAST, LAZY, HEAVY>), dim3(std::min(units, slots[d->device & 63])), dim3(nt), d->L.total, st, a);
     SWD_HIP(hipGetLastError());
+    if (with_osd && d->elim) { // the queue length stays on the device: no host synchronise between the two kernels
+        HugeBp4OsdIo io{a.B, a.sx, a.sz, a.out, a.osd0, a.stats, a.lpr, a.osd_list, a.osd_count};
+        return d->elim->launch_osd(io, d->cur_slot, st);
+    }
     if constexpr (!HEAVY) if (with_osd) { // the queue of unconverged decodes (often empty: its workgroups then read the count and leave)
         static int lds_limit2[64] = {0}, slots2[64] = {0}, slots2_lds[64] = {0};
         if (d->L.total > lds_limit2[d->device & 63]) {
@@ -167,6 +181,7 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
     d->device = device; d->p = *p; d->n = hx->n;
     const int n = hx->n;
     const int asked_order = d->p.osd_order;
+    d->general_osd = (flags & SWD_BP4_GENERAL_OSD) != 0;
     if (d->p.osd_method == 0) d->p.osd_order = 0;
     if (d->p.osd_method < 0 || d->p.osd_method > 2) { set_error("ERROR: OSD method '%d' invalid.", d->p.osd_method); delete d; return nullptr; }
     // OSD path metrics use prior_llr_x = log((1-(px+py))/(px+py)), prior_llr_z = log((1-(pz+py))/(pz+py)) (bp4_osd.pyx:134-137)
@@ -185,14 +200,17 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
         // decided before Graph::build, which is what refuses m > 1024: ANY graph is taken, one a tuned kernel would take included
         // (how the tests reach this form on the recorded fixtures).  BP only, so like a graph with heavy columns it takes
         // osd_order = -1 alone, and with osd_method "osd_0" the caller's -1 stands.
-        if (asked_order >= 0) {
+        // With SWD_BP4_GENERAL_OSD beside it the order is the reference's (osd_method 0 resets it to 0) and the queued decodes go
+        // to the general elimination, which shares the graphs.
+        if (!d->general_osd && asked_order >= 0) {
             set_error("OSD in the general form is not supported: create the decoder with osd_order=-1 (decode then returns the BP "
-                      "decisions) or use camel_decode");
+                      "decisions) or use camel_decode" SWD_BP4_GENERAL_OSD_HINT);
             delete d; return nullptr;
         }
-        d->p.osd_order = -1;
-        d->general.reset(huge_bp4_create(&dx, &dz, llr.data(), device));
+        if (!d->general_osd) d->p.osd_order = -1;
+        d->general.reset(huge_bp4_create(&dx, &dz, llr.data(), device, true, d->p.osd_order >= 0 ? &d->p : nullptr));
         if (!d->general) { delete d; return nullptr; }
+        if (d->p.osd_order >= 0) d->elim = d->general.get();
         return (swd_bp4 *)d;
     }
     // Heavy columns: weight above SWD_DMAX in Hx or in Hz (the last qubit of the cycle-assembled and EG codes touches every check).
@@ -219,15 +237,15 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
         }
     }
     d->heavy = (int)heavy.size();
-    if (d->heavy && asked_order >= 0) {
+    if (d->heavy && !d->general_osd && asked_order >= 0) {
         // (the elimination kernel's ELL column tables hold light columns only; with osd_method "osd_0" the reference resets the order to
         // 0, bp4_osd.pyx:74-76, which its camel_decode never looks at -- here the caller's -1 stands, and decode returns the BP
         // decisions of a shot that did not converge, as the reference does for the other methods with osd_order = -1)
         set_error("OSD on a graph with heavy columns (%d of weight above %d, up to %d) is not supported: create the decoder with "
-                  "osd_order=-1 (decode then returns the BP decisions) or use camel_decode", d->heavy, SWD_DMAX, d->heavy_deg);
+                  "osd_order=-1 (decode then returns the BP decisions) or use camel_decode" SWD_BP4_GENERAL_OSD_HINT, d->heavy, SWD_DMAX, d->heavy_deg);
         delete d; return nullptr;
     }
-    if (d->heavy) d->p.osd_order = -1;
+    if (d->heavy && !d->general_osd) d->p.osd_order = -1;
     if (d->gx.build(&dx, d->heavy ? &heavy : nullptr) || d->gz.build(&dz, d->heavy ? &heavy : nullptr)) {
         const std::string why = last_error(); // (more than 1024 checks, a row or a light column past the graph tables: sizes the general form takes)
         if (why.find("exceeds this build's limit") != std::string::npos || why.find("has weight") != std::string::npos)
@@ -266,7 +284,12 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
     // are pivots, so at least kx are not: the first kx non-pivot columns of the whole order always lie among them, whatever their rank
     // (pinned by tests/golden/bp4_unequal_prefix.npz, where that prefix is rank-deficient on every OSD shot).
     if (d->p.osd_order > 0 && d->gx.rank > d->gz.rank) d->gz.d.new_n = n - d->gx.rank + d->gz.rank;
-    if (!d->heavy) { // (no OSD on a graph with heavy columns: no elimination scratch)
+    if (d->general_osd && d->p.osd_order >= 0) { // the elimination alone: the tuned BP kernel of this graph queues for it
+        d->elim_own.reset(huge_bp4_create(&dx, &dz, llr.data(), device, false, &d->p));
+        if (!d->elim_own) { delete d; return nullptr; }
+        d->elim = d->elim_own.get();
+    }
+    if (!d->heavy && !d->elim) { // (no OSD in bp4_osd_kernel: no elimination scratch in LDS)
         make_layout_for_osd(d->gx, d->nt_osd, d->Lx);
         make_layout_for_osd(d->gz, d->nt_osd, d->Lz);
     }
@@ -312,12 +335,12 @@ extern "C" void swd_bp4_destroy(swd_bp4 *h) {
 extern "C" int swd_bp4_info(const swd_bp4 *h, int32_t *mx, int32_t *mz, int32_t *n, int32_t *rank_x, int32_t *rank_z) {
     const Bp4 *d = (const Bp4 *)h;
     if (!d) { set_error("null decoder"); return -1; }
-    const bool gen = d->general != nullptr; // (no elimination in the general form: the ranks are not computed, -1)
+    const bool gen = d->general != nullptr;
     if (mx) *mx = gen ? d->general->mx : d->gx.m;
     if (mz) *mz = gen ? d->general->mz : d->gz.m;
     if (n) *n = d->n;
-    if (rank_x) *rank_x = gen ? -1 : d->gx.rank;
-    if (rank_z) *rank_z = gen ? -1 : d->gz.rank;
+    if (rank_x) *rank_x = gen ? d->general->rank_x : d->gx.rank; // (general form: -1 where the host rank was not computed)
+    if (rank_z) *rank_z = gen ? d->general->rank_z : d->gz.rank;
     return 0;
 }
 
@@ -325,6 +348,12 @@ extern "C" int swd_bp4_is_general(const swd_bp4 *h) {
     const Bp4 *d = (const Bp4 *)h;
     if (!d) { set_error("null decoder"); return -1; }
     return d->general ? 1 : 0;
+}
+
+extern "C" int swd_bp4_is_general_osd(const swd_bp4 *h) {
+    const Bp4 *d = (const Bp4 *)h;
+    if (!d) { set_error("null decoder"); return -1; }
+    return d->general_osd ? 1 : 0;
 }
 
 extern "C" int swd_bp4_heavy_info(const swd_bp4 *h, int32_t *count, int32_t *max_degree) {
@@ -365,12 +394,26 @@ extern "C" int swd_bp4_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8_t *sx
     Bp4::LaunchSlot *sl = nullptr;
     int slot_index = 0;
     if (d->take_slot(st, &sl, &slot_index)) return -1;
-    if (d->general) { // no column is special and nothing is queued for an elimination: the slot lends its event and its scratch area
+    d->cur_slot = slot_index;
+    if (d->general) { // no column is special: the slot lends its event, its scratch areas and, with the elimination, its queue
         HugeBp4Io io{};
         io.B = B; io.max_iter = d->p.max_iter; io.alpha = d->p.ms_scaling_factor; io.lpr_wanted = lpr ? 1 : 0;
         io.sx = sx; io.sz = sz; io.out = out; io.osd0 = osd0; io.bp_dec = bp_dec; io.stats = stats; io.lpr = lpr;
+        io.osd_order = d->elim ? d->p.osd_order : -1;
+        if (io.osd_order >= 0) {
+            for (auto &s2 : d->slot) if (s2.osd_q.reserve((size_t)B * 4 + 16)) return -1;
+            io.osd_count = sl->osd_q.as<uint32_t>(); io.osd_list = sl->osd_q.as<int32_t>() + 4;
+            if (!lpr) { // the posteriors of the queued decodes: the slot's buffer, as on the tuned path
+                for (auto &s2 : d->slot) if (s2.lpr.reserve((size_t)B * 3 * d->n * 8)) return -1;
+                io.lpr = sl->lpr.as<double>();
+            }
+        }
         d->form = {0, 0, 0, 0, 0, 1024, 0, 0};
         if (d->general->launch(io, slot_index, st)) return -1;
+        if (io.osd_order >= 0) {
+            HugeBp4OsdIo oio{B, sx, sz, out, osd0, stats, io.lpr, io.osd_list, io.osd_count};
+            if (d->elim->launch_osd(oio, slot_index, st)) return -1;
+        }
         SWD_HIP(hipEventRecord(sl->done, st));
         d->last_done = sl->done; d->last_stream = st;
         return 0;
@@ -444,7 +487,7 @@ extern "C" int swd_bp4_camel_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8
     if (d->general) { // the four runs of a shot are four units of the general form; the combine step is the one below
         if (sl->cdec.reserve((size_t)4 * B * 2 * n) || sl->cpm.reserve((size_t)4 * B * 8) || sl->cst.reserve((size_t)4 * B * 2 * 4)) return -1;
         HugeBp4Io io{};
-        io.B = B; io.camel = 1; io.max_iter = d->p.max_iter; io.alpha = d->p.ms_scaling_factor;
+        io.B = B; io.camel = 1; io.max_iter = d->p.max_iter; io.alpha = d->p.ms_scaling_factor; io.osd_order = -1;
         io.sx = sx; io.sz = sz;
         io.camel_dec = sl->cdec.as<uint8_t>(); io.camel_pm = sl->cpm.as<double>(); io.camel_st = sl->cst.as<int32_t>();
         d->form = {0, 0, 0, 0, 0, 1024, 0, 0};

@@ -55,20 +55,6 @@ __device__ int huge_set_value(const SwdHugeArgs &a, const HugeView &v, int x, in
     return 0;
 }
 
-// the member columns (indices into the candidate columns) of candidate l in the reference's order: osd_cs -- k of weight one, then the
-// pairs i < j < order (osd_window.pyx:134-155); osd_e -- every pattern of the first `order` columns, pattern l = the binary digits
-// of l (:128-132).  Returns how many.
-__device__ int huge_cand_members(int osd_method, int w, int k, long long l, int *mem) {
-    int nm = 0;
-    if (osd_method == 2) {
-        if (l < k) mem[nm++] = (int)l;
-        else { long long q = l - k; int i = 0; while (q >= w - 1 - i) { q -= w - 1 - i; ++i; } mem[nm++] = i; mem[nm++] = i + 1 + (int)q; }
-    } else {
-        for (int bit = 0; bit < w; ++bit) if ((l >> bit) & 1) mem[nm++] = bit;
-    }
-    return nm;
-}
-
 __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
     __shared__ HugeLds s;
     const int tid = threadIdx.x, m = a.g.m, n = a.g.n, wm = a.wm;
@@ -218,6 +204,8 @@ __global__ void __launch_bounds__(HNT) huge_kernel(const SwdHugeArgs a) {
         }
         if (exit_class < 0) {
             // ---- OSD (osd_window.pyx:201-284) ----
+            // (the text from the transform matrix to the end of the sweep is also huge_osd of swd_huge_common.h, which bp4_osd's general
+            // elimination calls; this kernel keeps its inlined copy: through the function it needs 460 instead of 352 B/lane of scratch)
             exit_class = SWD_EXIT_OSD;
             if (a.bp_dec) for (int x = tid; x < n; x += HNT) a.bp_dec[(int64_t)b * n + x] = v.hard[x];
             huge_history_order(v.hist, n, a.npad, v.vn, v.key, v.idx); // idx = orig_cols

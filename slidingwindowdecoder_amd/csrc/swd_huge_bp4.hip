@@ -3,8 +3,9 @@
 // Misc.ipynb cell 8, large light codes.  The reference has no size limit (src/include/mod2sparse.c:52-80).  The form of swd_huge.hip
 // and swd_huge_gdg.hip: one 1024-thread workgroup per unit -- a shot of decode, one of the four runs of a shot of camel_decode -- a
 // grid of at most one workgroup per CU that loops over the units, both graphs in HBM as CSR + CSC, every per-unit array in the
-// workgroup's slice of an HBM buffer, LDS only for block-wide flags (and the scan behind cal_pm).  BP only: the reference runs these
-// codes with osd_order = -1 or camel_decode, neither of which reaches the elimination.
+// workgroup's slice of an HBM buffer, LDS only for block-wide flags (and the scan behind cal_pm).  huge_bp4_kernel runs BP; with
+// osd_order >= 0 (a handle created with SWD_BP4_GENERAL_OSD) the decodes it leaves unconverged are queued for huge_bp4_osd_kernel
+// below, the elimination in HBM that also finishes the queue of the tuned BP kernels on graphs with heavy columns.
 // Restated from /root/reference/src/bp4_osd.pyx, bit for bit (exp / log1p of swd_libm.h through bp4_log1pexp / bp4_logaddexp):
 //   reset 371-386, vn_set_value 389-423, bp_init 425-442, bp4_decode_llr 444-481, cn_update_all 483-529, vn_update 533-589,
 //   cal_pm 250-259.
@@ -197,6 +198,7 @@ __global__ void __launch_bounds__(HNT) huge_bp4_kernel(const SwdHugeBp4Args a) {
             continue;
         }
         uint8_t *out_b = a.io.out + (int64_t)b * 2 * n;
+        const bool to_osd = !conv && a.io.osd_order >= 0; // finished by huge_bp4_osd_kernel from the posteriors stored below
         for (int v = tid; v < n; v += HNT) { out_b[v] = decx[v]; out_b[n + v] = decz[v]; }
         if (a.io.bp_dec)
             for (int v = tid; v < n; v += HNT) { a.io.bp_dec[(int64_t)b * 2 * n + v] = decx[v]; a.io.bp_dec[(int64_t)b * 2 * n + n + v] = decz[v]; }
@@ -208,9 +210,71 @@ __global__ void __launch_bounds__(HNT) huge_bp4_kernel(const SwdHugeBp4Args a) {
         }
         if (tid == 0) {
             int32_t *st = a.io.stats + (int64_t)b * SWD_STAT_WORDS;
-            st[0] = (conv ? SWD_EXIT_PRE : SWD_EXIT_NO_OSD) | (conv ? SWD_STATUS_CONVERGE : 0);
+            st[0] = (conv ? SWD_EXIT_PRE : (to_osd ? SWD_EXIT_OSD : SWD_EXIT_NO_OSD)) | (conv ? SWD_STATUS_CONVERGE : 0);
             st[1] = iters; st[2] = iters; st[3] = 0; st[4] = n; st[5] = mx + mz; st[6] = Ex + Ez; st[7] = 0;
+            if (to_osd) a.io.osd_list[atomicAdd(a.io.osd_count, 1u)] = b;
         }
+    }
+}
+
+// ---- the elimination (bp4_osd.pyx:261-368) ----
+
+// The decodes a BP kernel queued -- huge_bp4_kernel above, or a tuned bp4_kernel (swd_bp4_kernel.h) of a handle created with
+// SWD_BP4_GENERAL_OSD -- one per workgroup at a time: osd('x') on Hx, synd_x gives the Z string, osd('z') on Hz, synd_z the X string
+// (bp4_osd.decode :212-219).  Per basis: ordering keys from the stored posteriors (:280 / :297), the stable ascending order
+// (huge_f2key + huge_sort), then huge_osd (swd_huge_common.h) -- the elimination over all n sorted columns, the OSD-0 solution, the
+// osd_e / osd_cs sweep with path metrics from prior_llr_x / prior_llr_z (gx.llr / gz.llr).  No bound on a column's weight, up to 4096
+// checks per matrix; T and the candidate columns are sized for the larger basis and used by the two in turn.
+struct SwdHugeBp4OsdArgs {
+    HugeGraphDev gx, gz;                 // llr: prior_llr_x (px + py), prior_llr_z (pz + py)  (bp4_osd.pyx:134-137)
+    int32_t rank_x, rank_z, new_n_x, new_n_z; // new_n_z: n, or n - rank_x + rank_z -- the z sweep walks kx candidates (swd_bp4.hip)
+    int32_t npad, osd_method, osd_order;
+    HugeBp4OsdIo io;
+    uint8_t *scratch; int64_t stride;    // a workgroup's slice: scratch + blockIdx.x * stride
+    int64_t o_key, o_idx, o_T, o_ycand, o_pm, o_pc, o_pr, o_rowof, o_plist, o_ht, o_lv, o_lc, o_best, o_bak, o_hard;
+};
+
+__global__ void __launch_bounds__(HNT) huge_bp4_osd_kernel(const SwdHugeBp4OsdArgs a) {
+    __shared__ HugeLds s;
+    const int tid = threadIdx.x, n = a.gx.n;
+    uint8_t *base = a.scratch + (int64_t)blockIdx.x * a.stride;
+    uint64_t *key = (uint64_t *)(base + a.o_key);
+    int32_t *idx = (int32_t *)(base + a.o_idx);
+    HugeOsdView v;
+    v.T = (uint64_t *)(base + a.o_T); v.ycand = (uint64_t *)(base + a.o_ycand); v.pm = (double *)(base + a.o_pm);
+    v.pc = (int32_t *)(base + a.o_pc); v.pr = (int32_t *)(base + a.o_pr); v.rowof = (int32_t *)(base + a.o_rowof);
+    v.plist = (int32_t *)(base + a.o_plist); v.ht = (int32_t *)(base + a.o_ht); v.lv = (int32_t *)(base + a.o_lv);
+    v.lc = (int32_t *)(base + a.o_lc); v.best = (int32_t *)(base + a.o_best); v.bak = base + a.o_bak; v.hard = base + a.o_hard;
+    const int count = min((int)*a.io.osd_count, a.io.B);
+    for (int q = blockIdx.x; q < count; q += gridDim.x) {
+        const int b = a.io.osd_list[q];
+        const double *lpr_b = a.io.lpr + (int64_t)b * 3 * n;
+        uint8_t *out_b = a.io.out + (int64_t)b * 2 * n;
+        int rowadds = 0;
+        for (int basis = 0; basis < 2; ++basis) {
+            const HugeGraphDev g = basis == 0 ? a.gx : a.gz;
+            const uint8_t *synd = basis == 0 ? a.io.sx + (int64_t)b * g.m : a.io.sz + (int64_t)b * g.m;
+            __syncthreads(); // the previous basis (or decode) is done with the slice
+            for (int i = tid; i < a.npad; i += HNT) {
+                if (i < n) {
+                    const double lx = lpr_b[i], ly = lpr_b[n + i], lz = lpr_b[2 * (int64_t)n + i];
+                    const double post = basis == 0 ? hb_log1pexp(-1. * lx) - hb_logaddexp(-1. * ly, -1. * lz)
+                                                   : hb_log1pexp(-1. * lz) - hb_logaddexp(-1. * ly, -1. * lx);
+                    key[i] = huge_f2key(post);
+                    idx[i] = i;
+                } else { key[i] = ~0ull; idx[i] = 0x7FFFFFFF; }
+            }
+            __syncthreads();
+            huge_sort(key, idx, a.npad);
+            uint8_t *o0 = a.io.osd0 ? a.io.osd0 + (int64_t)b * 2 * n + (basis == 0 ? n : 0) : nullptr;
+            double min_pm;
+            const uint8_t *ret = huge_osd(g, (g.m + 63) >> 6, basis == 0 ? a.rank_x : a.rank_z, basis == 0 ? a.new_n_x : a.new_n_z,
+                                          a.osd_method, a.osd_order, idx, synd, o0, v, s, rowadds, min_pm);
+            __syncthreads();
+            uint8_t *dst = out_b + (basis == 0 ? n : 0);
+            for (int x = tid; x < n; x += HNT) dst[x] = ret[x];
+        }
+        if (tid == 0) a.io.stats[(int64_t)b * SWD_STAT_WORDS + 7] = rowadds; // (word 0 is the BP kernel's: SWD_EXIT_OSD, no converge bit)
     }
 }
 
@@ -219,16 +283,22 @@ __global__ void __launch_bounds__(HNT) huge_bp4_kernel(const SwdHugeBp4Args a) {
 struct HugeBp4 : HugeBp4Iface {
     static constexpr int kSlots = 4;             // Bp4::kSlots (swd_bp4.hip)
     static constexpr int64_t kSlotBytes = 8ll << 30; // a launch slot's scratch area never exceeds this: the grid shrinks to fit
-    int device = 0, grid_max = 1;
-    DevBuf graph, scratch[kSlots];
+    int device = 0, grid_max = 1, osd_grid_max = 1;
+    bool has_bp = false, has_osd = false;
+    // one device copy of the graphs for BP and the elimination; per launch slot one area for each of the two kernels, so that four
+    // launches of a handle run side by side
+    DevBuf graph, scratch[kSlots], osd_scratch[kSlots];
     int64_t stride = 0;
     SwdHugeBp4Args tmpl{};
+    SwdHugeBp4OsdArgs otmpl{};
 
     static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
     int64_t take(size_t bytes) { const int64_t at = stride; stride += (int64_t)al(bytes); return at; }
 
     int launch(const HugeBp4Io &io, int slot, void *stream) override {
         if (slot < 0 || slot >= kSlots) { set_error("launch slot %d out of range", slot); return -1; }
+        if (!has_bp) { set_error("this handle runs the elimination only"); return -1; }
+        if (!io.camel && io.osd_order >= 0 && (!has_osd || !io.lpr || !io.osd_list || !io.osd_count)) { set_error("OSD launch without its queue"); return -1; }
         SWD_HIP(hipSetDevice(device));
         const int64_t units = io.camel ? 4 * (int64_t)io.B : io.B;
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(units, grid_max));
@@ -236,14 +306,34 @@ struct HugeBp4 : HugeBp4Iface {
         if (scratch[slot].reserve((size_t)grid * (size_t)stride)) return -1;
         SwdHugeBp4Args a = tmpl;
         a.io = io;
+        if (io.camel) a.io.osd_order = -1;
         a.scratch = scratch[slot].as<uint8_t>();
+        if (a.io.osd_order >= 0) SWD_HIP(hipMemsetAsync(io.osd_count, 0, sizeof(uint32_t), (hipStream_t)stream));
         hipLaunchKernelGGL(huge_bp4_kernel, dim3(grid), dim3(HNT), 0, (hipStream_t)stream, a);
+        SWD_HIP(hipGetLastError());
+        return 0;
+    }
+
+    int launch_osd(const HugeBp4OsdIo &io, int slot, void *stream) override {
+        if (slot < 0 || slot >= kSlots) { set_error("launch slot %d out of range", slot); return -1; }
+        if (!has_osd) { set_error("this handle was created without the elimination"); return -1; }
+        if (!io.sx || !io.sz || !io.out || !io.stats || !io.lpr || !io.osd_list || !io.osd_count) { set_error("null pointer in the OSD launch"); return -1; }
+        SWD_HIP(hipSetDevice(device));
+        // the queue length is only known on the device: as many workgroups as the batch could queue, at most one per CU -- those
+        // beyond the queue read the count and leave
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(io.B, osd_grid_max));
+        if (osd_scratch[slot].reserve((size_t)grid * (size_t)otmpl.stride)) return -1;
+        SwdHugeBp4OsdArgs a = otmpl;
+        a.io = io;
+        a.scratch = osd_scratch[slot].as<uint8_t>();
+        hipLaunchKernelGGL(huge_bp4_osd_kernel, dim3(grid), dim3(HNT), 0, (hipStream_t)stream, a);
         SWD_HIP(hipGetLastError());
         return 0;
     }
 };
 
-HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *llr, int device) {
+HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *llr, int device, bool bp,
+                              const swd_bp4_params *osd) {
     if (HugeHost::check_desc(hx) || HugeHost::check_desc(hz)) return nullptr;
     if (hx->n != hz->n) { set_error("Hx, Hz blocklength does not match!"); return nullptr; }
     const int n = hx->n;
@@ -255,8 +345,14 @@ HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz
         set_error("%lld edges exceed bp4_osd's general form limit of 67108864 edges in Hx and Hz together", (long long)hx->nnz + hz->nnz);
         return nullptr;
     }
+    if (osd)
+        for (const swd_graph_desc *g : {hx, hz})
+            if (g->m > 4096) {
+                set_error("m=%d exceeds the general OSD's limit of 4096 checks per matrix (64 words per column of the elimination's transform matrix)", g->m);
+                return nullptr;
+            }
     std::unique_ptr<HugeBp4> h(new HugeBp4());
-    h->device = device; h->mx = hx->m; h->mz = hz->m; h->n = n;
+    h->device = device; h->mx = hx->m; h->mz = hz->m; h->n = n; h->has_bp = bp; h->has_osd = osd != nullptr;
     if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return nullptr; }
     CsrHost c[2];
     std::vector<int32_t> node[2];
@@ -270,7 +366,23 @@ HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz
         node[i].resize((size_t)g->nnz);
         for (int v = 0; v < n; ++v) for (int k = c[i].col_ptr[v]; k < c[i].col_ptr[v + 1]; ++k) node[i][k] = v;
     }
-    // one buffer of 256-byte aligned arrays: per graph row_ptr, col_idx, col_ptr, row_idx, c2r, r2c, node; then the channel LLRs
+    // the reference's rules that need the ranks (bp4_osd.pyx:92-104), with the tuned path's messages (swd_bp4.hip)
+    // (gf2_rank works on dense rows: without the elimination, a graph whose rows would pass 1 GiB keeps -1, "not computed")
+    if (osd || (size_t)std::max(hx->m, hz->m) * (size_t)((n + 63) / 64) * 8 <= ((size_t)1 << 30)) {
+        h->rank_x = gf2_rank(hx->m, n, c[0].row_ptr, c[0].col_idx);
+        h->rank_z = gf2_rank(hz->m, n, c[1].row_ptr, c[1].col_idx);
+    }
+    if (osd) {
+        const int kmin = std::min(n - h->rank_x, n - h->rank_z);
+        if (osd->osd_order > kmin) { set_error("For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", kmin); return nullptr; }
+        if (osd->osd_order > 0 && h->rank_x < h->rank_z) {
+            set_error("higher-order OSD with rank(Hx) < rank(Hz) is undefined in the reference (kz = n - rank_x: it reads past its column array) and not supported");
+            return nullptr;
+        }
+        if (osd->osd_method == 1 && osd->osd_order > 15) { set_error("osd_e supports osd_order <= 15 on the device"); return nullptr; }
+    }
+    // one buffer of 256-byte aligned arrays: per graph row_ptr, col_idx, col_ptr, row_idx, c2r, r2c, node; then the channel LLRs and
+    // the two prior LLR arrays of the OSD's path metrics
     struct Seg { const void *src; size_t bytes; };
     std::vector<Seg> seg;
     for (int i = 0; i < 2; ++i) {
@@ -280,6 +392,7 @@ HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz
         seg.push_back({c[i].c2r.data(), E * 4}); seg.push_back({c[i].r2c.data(), E * 4}); seg.push_back({node[i].data(), E * 4});
     }
     seg.push_back({llr, (size_t)3 * n * 8});
+    seg.push_back({c[0].llr.data(), (size_t)n * 8}); seg.push_back({c[1].llr.data(), (size_t)n * 8});
     std::vector<size_t> off(seg.size() + 1, 0);
     for (size_t i = 0; i < seg.size(); ++i) off[i + 1] = off[i] + HugeBp4::al(seg[i].bytes);
     if (h->graph.reserve(off.back())) return nullptr;
@@ -288,22 +401,53 @@ HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz
         if (hipMemcpy(d + off[i], seg[i].src, seg[i].bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy of the graph failed"); return nullptr; }
     SwdHugeBp4Args &a = h->tmpl;
     auto ip = [&](int i) { return (const int32_t *)(d + off[i]); };
-    a.gx = HugeGraphDev{hx->m, n, ip(0), ip(1), ip(2), ip(3), ip(4), nullptr}; a.r2cx = ip(5); a.nodex = ip(6);
-    a.gz = HugeGraphDev{hz->m, n, ip(7), ip(8), ip(9), ip(10), ip(11), nullptr}; a.r2cz = ip(12); a.nodez = ip(13);
+    a.gx = HugeGraphDev{hx->m, n, ip(0), ip(1), ip(2), ip(3), ip(4), (const double *)(d + off[15])}; a.r2cx = ip(5); a.nodex = ip(6);
+    a.gz = HugeGraphDev{hz->m, n, ip(7), ip(8), ip(9), ip(10), ip(11), (const double *)(d + off[16])}; a.r2cz = ip(12); a.nodez = ip(13);
     a.llr_x = (const double *)(d + off[14]); a.llr_y = a.llr_x + n; a.llr_z = a.llr_y + n;
     a.Ex = hx->nnz; a.Ez = hz->nnz;
-    const size_t Ex = (size_t)hx->nnz, Ez = (size_t)hz->nnz;
-    a.o_b2cx = h->take(Ex * 8); a.o_c2bx = h->take(Ex * 8); a.o_b2cz = h->take(Ez * 8); a.o_c2bz = h->take(Ez * 8);
-    a.o_inix = h->take((size_t)n * 8); a.o_iniz = h->take((size_t)n * 8);
-    a.o_tx = h->take((size_t)n * 8); a.o_ty = h->take((size_t)n * 8); a.o_tz = h->take((size_t)n * 8);
-    a.o_numx = h->take((size_t)n * 8); a.o_numz = h->take((size_t)n * 8);
-    a.o_decx = h->take((size_t)n); a.o_decz = h->take((size_t)n); a.o_cnx = h->take((size_t)hx->m); a.o_cnz = h->take((size_t)hz->m);
-    a.o_list = h->take((size_t)n * 4);
-    a.stride = h->stride;
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 64;
-    // one workgroup per CU, fewer when their slices would pass the slot's bound (the largest graph: 1.1 GB per slice)
-    h->grid_max = (int)std::max<int64_t>(1, std::min<int64_t>(std::max(1, cus), HugeBp4::kSlotBytes / h->stride));
+    if (bp) {
+        const size_t Ex = (size_t)hx->nnz, Ez = (size_t)hz->nnz;
+        a.o_b2cx = h->take(Ex * 8); a.o_c2bx = h->take(Ex * 8); a.o_b2cz = h->take(Ez * 8); a.o_c2bz = h->take(Ez * 8);
+        a.o_inix = h->take((size_t)n * 8); a.o_iniz = h->take((size_t)n * 8);
+        a.o_tx = h->take((size_t)n * 8); a.o_ty = h->take((size_t)n * 8); a.o_tz = h->take((size_t)n * 8);
+        a.o_numx = h->take((size_t)n * 8); a.o_numz = h->take((size_t)n * 8);
+        a.o_decx = h->take((size_t)n); a.o_decz = h->take((size_t)n); a.o_cnx = h->take((size_t)hx->m); a.o_cnz = h->take((size_t)hz->m);
+        a.o_list = h->take((size_t)n * 4);
+        a.stride = h->stride;
+        // one workgroup per CU, fewer when their slices would pass the slot's bound (the largest graph: 1.1 GB per slice)
+        h->grid_max = (int)std::max<int64_t>(1, std::min<int64_t>(std::max(1, cus), HugeBp4::kSlotBytes / h->stride));
+    }
+    if (osd) {
+        SwdHugeBp4OsdArgs &o = h->otmpl;
+        o.gx = a.gx; o.gz = a.gz;
+        o.rank_x = h->rank_x; o.rank_z = h->rank_z;
+        o.osd_method = osd->osd_method; o.osd_order = osd->osd_order;
+        // rank(Hx) > rank(Hz): the z-basis sweep walks the first kx = n - rank_x non-pivot columns like the reference's (swd_bp4.hip)
+        o.new_n_x = n; o.new_n_z = (osd->osd_order > 0 && h->rank_x > h->rank_z) ? n - h->rank_x + h->rank_z : n;
+        int npad = 2; while (npad < n) npad <<= 1;
+        o.npad = npad;
+        // a slice of the elimination: every array sized for the larger of the two bases
+        const int mm = std::max(hx->m, hz->m), wm = (mm + 63) / 64;
+        const int kx = std::max(o.new_n_x - h->rank_x, 0), kz = std::max(o.new_n_z - h->rank_z, 0), k = std::max(kx, kz);
+        const int nyc = osd->osd_order <= 0 ? 0 : (osd->osd_method == 2 ? k : std::min(k, osd->osd_order));
+        const int rk = std::max(h->rank_x, h->rank_z);
+        int64_t st = 0;
+        auto tk = [&](size_t bytes) { const int64_t at = st; st += (int64_t)HugeBp4::al(bytes); return at; };
+        o.o_key = tk((size_t)npad * 8); o.o_idx = tk((size_t)npad * 4);
+        o.o_T = tk((size_t)wm * mm * 8); o.o_ycand = tk((size_t)std::max(nyc, 1) * wm * 8); o.o_pm = tk((size_t)(2 * wm + 4) * 8);
+        o.o_pc = tk((size_t)(rk + 1) * 4); o.o_pr = tk((size_t)(rk + 1) * 4); o.o_rowof = tk((size_t)n * 4);
+        o.o_plist = tk((size_t)std::max(n, mm) * 4); o.o_ht = tk((size_t)(k + 1) * 4); o.o_lv = tk((size_t)n * 4);
+        o.o_lc = tk((size_t)std::max(mm, n) * 4); o.o_best = tk(64); o.o_bak = tk((size_t)n); o.o_hard = tk((size_t)n);
+        o.stride = st;
+        if (st > HugeBp4::kSlotBytes) {
+            set_error("the elimination needs %lld bytes per workgroup, which exceeds the general OSD's limit of %lld bytes (8 GiB) per launch slot",
+                      (long long)st, (long long)HugeBp4::kSlotBytes);
+            return nullptr;
+        }
+        h->osd_grid_max = (int)std::max<int64_t>(1, std::min<int64_t>(std::max(1, cus), HugeBp4::kSlotBytes / st));
+    }
     return h.release();
 }
 

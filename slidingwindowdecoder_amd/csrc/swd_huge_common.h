@@ -206,6 +206,201 @@ __device__ inline int huge_minsum(const HugeGraphDev &g, double alpha, double *b
     return 0;
 }
 
+// the member columns (indices into the candidate columns) of candidate l in the reference's order: osd_cs -- k of weight one, then the
+// pairs i < j < order (osd_window.pyx:134-155); osd_e -- every pattern of the first `order` columns, pattern l = the binary digits
+// of l (:128-132).  Returns how many.
+__device__ inline int huge_cand_members(int osd_method, int w, int k, long long l, int *mem) {
+    int nm = 0;
+    if (osd_method == 2) {
+        if (l < k) mem[nm++] = (int)l;
+        else { long long q = l - k; int i = 0; while (q >= w - 1 - i) { q -= w - 1 - i; ++i; } mem[nm++] = i; mem[nm++] = i + 1 + (int)q; }
+    } else {
+        for (int bit = 0; bit < w; ++bit) if ((l >> bit) & 1) mem[nm++] = bit;
+    }
+    return nm;
+}
+
+// The arrays of the elimination and the sweep (huge_osd) in a workgroup's scratch slice, for a matrix of m checks (wm = words per
+// column of T), n columns, rank pivots, k = new_n - rank candidate columns:
+//   T [wm * m] words, ycand [max(reduced candidate columns, 1) * wm] words, pm [2 * wm + 4] doubles, pc / pr [rank + 1], rowof [n],
+//   plist [max(n, m)], ht [k + 1], lv [n], lc [max(m, new_n)], best 64 bytes, bak [n] (the OSD-0 solution), hard [n] (the sweep's winner)
+struct HugeOsdView {
+    uint64_t *T, *ycand;
+    double *pm;
+    int32_t *pc, *pr, *rowof, *plist, *ht, *lv, *lc, *best;
+    uint8_t *bak, *hard;
+};
+
+// OSD on one matrix (osd_window.pyx:201-284 == bp4_osd.pyx:299-368; mod2sparse_decomp_osd / LU_forward_backward_solve,
+// src/include/mod2sparse_extra.cpp:78-376) with every array in HBM: the elimination over all n columns in the order idx[] lists them,
+// the OSD-0 solution (also into osd0 when given), and with osd_order > 0 the osd_e / osd_cs sweep over the first new_n - rank
+// non-pivot columns among the first new_n sorted ones, path metrics from g.llr.  One body for osd_window's general form
+// (huge_kernel) and bp4_osd's (huge_bp4_osd_kernel).  Returns the solution (v.bak or v.hard; behind a barrier only: the caller
+// synchronises before reading it), its path metric in min_pm; adds the row additions to rowadds.
+__device__ __forceinline__ const uint8_t *huge_osd(const HugeGraphDev &g, int wm, int rank, int new_n, int osd_method, int osd_order,
+                                                  const int32_t *idx, const uint8_t *synd, uint8_t *osd0, const HugeOsdView &v,
+                                                  HugeLds &s, int &rowadds, double &min_pm) {
+    const int tid = threadIdx.x, m = g.m, n = g.n;
+    const uint8_t *ret;
+    // transform matrix T (word-major: T[w * m + j] = word w of column j), identity
+    for (int i = tid; i < wm * m; i += HNT) { const int w = i / m, j = i - w * m; v.T[i] = (j >> 6) == w ? (1ull << (j & 63)) : 0ull; }
+    for (int x = tid; x < n; x += HNT) v.rowof[x] = -1;
+    uint64_t *pivmask = (uint64_t *)v.pm; // [wm] (the path metrics are not needed before the sweep)
+    for (int w = tid; w < wm; w += HNT) pivmask[w] = 0ull;
+    __syncthreads();
+    // greedy first-independent columns in sorted order; pivot row = lowest unpivoted row with a 1 (mod2sparse_extra.cpp:113-376).
+    // Sixteen columns are reduced against T at a time (one wave each); the first of them with a pivot is applied, the scan
+    // resumes behind it (the reduced forms of the later ones are stale then).
+    int np = 0, kcol = 0;
+    const int wv = tid >> 6, lane = tid & 63;
+    while (np < rank && kcol < n) {
+        {
+            const int kk = kcol + wv;
+            uint64_t y = 0ull;
+            if (kk < n && lane < wm) {
+                const int col = idx[kk];
+                for (int k = g.col_ptr[col]; k < g.col_ptr[col + 1]; ++k) y ^= v.T[(size_t)lane * m + g.row_idx[k]];
+            }
+            s.y[wv * 64 + lane] = y;
+            const uint64_t cand = (lane < wm) ? (y & ~pivmask[lane]) : 0ull;
+            const unsigned long long bal = __ballot(cand != 0ull);
+            if (lane == 0) s.piv[wv] = -1;
+            if (bal) {
+                const int w0 = __ffsll((long long)bal) - 1;
+                const uint64_t cw = __shfl(cand, w0, 64);
+                if (lane == 0) s.piv[wv] = w0 * 64 + (__ffsll((long long)cw) - 1);
+            }
+        }
+        __syncthreads();
+        int first = -1;
+        for (int q = 0; q < 16; ++q) if (s.piv[q] >= 0) { first = q; break; }
+        if (first < 0) { kcol += 16; __syncthreads(); continue; }
+        const int r = s.piv[first], col = idx[kcol + first];
+        // Gauss-Jordan step in transform form: every column j of T with bit r set takes S = y with bit r cleared
+        const unsigned long long *yv = &s.y[first * 64];
+        for (int j = tid; j < m; j += HNT) {
+            if ((v.T[(size_t)(r >> 6) * m + j] >> (r & 63)) & 1ull) {
+                for (int w = 0; w < wm; ++w) {
+                    uint64_t sv = (uint64_t)yv[w];
+                    if (w == (r >> 6)) sv &= ~(1ull << (r & 63));
+                    if (sv) v.T[(size_t)w * m + j] ^= sv;
+                }
+            }
+        }
+        if (tid == 0) {
+            v.pc[np] = col; v.pr[np] = r; v.rowof[col] = r;
+            pivmask[r >> 6] |= 1ull << (r & 63);
+            int ra = 0;
+            for (int w = 0; w < wm; ++w) ra += __popcll((unsigned long long)yv[w]);
+            s.flag[3] = ra - 1;
+        }
+        __syncthreads();
+        rowadds += s.flag[3];
+        ++np;
+        kcol += first + 1;
+        __syncthreads();
+    }
+    // base = T * syndrome; the OSD-0 solution: pivot column i takes bit pr[i] of it, every other column 0
+    uint64_t *basev = (uint64_t *)(v.pm) + wm; // [wm]
+    {
+        const int cnt = huge_compact(m, v.plist, s, [&](int c) { return synd[c] != 0; });
+        for (int w = tid; w < wm; w += HNT) {
+            uint64_t y = 0ull;
+            for (int i = 0; i < cnt; ++i) y ^= v.T[(size_t)w * m + v.plist[i]];
+            basev[w] = y;
+        }
+        __syncthreads();
+    }
+    uint8_t *o0 = v.bak; // [n] osd0_decoding
+    for (int x = tid; x < n; x += HNT) { const int r = v.rowof[x]; o0[x] = (r >= 0 && ((basev[r >> 6] >> (r & 63)) & 1ull)) ? 1 : 0; }
+    __syncthreads();
+    const int npiv = huge_compact(n, v.plist, s, [&](int x) { return v.rowof[x] >= 0; }); // pivot columns, ascending
+    {
+        const int cnt = huge_compact(n, v.lv, s, [&](int x) { return o0[x] != 0; });
+        if (tid == 0) v.best[2] = cnt, ((double *)v.best)[2] = huge_ordered_sum(v.lv, cnt, g.llr);
+        __syncthreads();
+    }
+    min_pm = ((double *)v.best)[2];
+    if (osd0) for (int x = tid; x < n; x += HNT) osd0[x] = o0[x];
+    ret = o0;
+    if (osd_order > 0) {
+        // candidate columns: the first k = new_n - rank non-pivot columns among the first new_n of the sorted order (:243-256)
+        const int k = new_n - rank;
+        int nht = huge_compact(new_n, v.lc, s, [&](int i) { return v.rowof[idx[i]] < 0; }); // positions in sorted order
+        nht = min(nht, k);
+        for (int j = tid; j < nht; j += HNT) v.ht[j] = idx[v.lc[j]];
+        __syncthreads();
+        const int nyc = (osd_method == 2) ? nht : min(nht, osd_order); // columns whose reduced form the sweep needs
+        for (int j = wv; j < nyc; j += 16) {
+            uint64_t y = 0ull;
+            if (lane < wm) { const int col = v.ht[j]; for (int q = g.col_ptr[col]; q < g.col_ptr[col + 1]; ++q) y ^= v.T[(size_t)lane * m + g.row_idx[q]]; }
+            if (lane < wm) v.ycand[(size_t)j * wm + lane] = y;
+        }
+        __syncthreads();
+        const int w = osd_order;
+        const long long ncand = (osd_method == 2) ? (long long)k + (long long)w * (w - 1) / 2 : (1ll << w);
+        double bpm = min_pm;
+        long long bidx = -1;
+        for (long long l = tid; l < ncand; l += HNT) {
+            int mem[16];
+            const int nm = huge_cand_members(osd_method, w, k, l, mem);
+            // members beyond the candidate columns that exist contribute nothing (enc rows are k long: they cannot occur)
+            int nmv = 0;
+            int memc[16];
+            for (int q = 0; q < nm; ++q) if (mem[q] < nht) { mem[nmv] = mem[q]; memc[nmv] = v.ht[mem[q]]; ++nmv; }
+            // candidate columns in ascending column order for the ordered sum
+            for (int p = 1; p < nmv; ++p) { const int cc = memc[p], mm2 = mem[p]; int q = p - 1; while (q >= 0 && memc[q] > cc) { memc[q + 1] = memc[q]; mem[q + 1] = mem[q]; --q; } memc[q + 1] = cc; mem[q + 1] = mm2; }
+            double pm = 0.0;
+            int nx = 0;
+            for (int i = 0; i < npiv; ++i) {
+                const int col = v.plist[i], r = v.rowof[col];
+                while (nx < nmv && memc[nx] < col) pm += g.llr[memc[nx++]];
+                uint64_t bit = (basev[r >> 6] >> (r & 63)) & 1ull;
+                for (int q = 0; q < nmv; ++q) bit ^= (v.ycand[(size_t)mem[q] * wm + (r >> 6)] >> (r & 63)) & 1ull;
+                if (bit) pm += g.llr[col];
+            }
+            while (nx < nmv) pm += g.llr[memc[nx++]];
+            if (pm < bpm) { bpm = pm; bidx = l; } // (ascending l per thread: strict < keeps the earliest)
+        }
+        // block minimum of (pm, index): the reference keeps the first candidate that is strictly better than everything before
+        for (int o = 32; o > 0; o >>= 1) {
+            const double op = __shfl_xor(bpm, o, 64);
+            const long long oi = __shfl_xor(bidx, o, 64);
+            if (oi >= 0 && (bidx < 0 || op < bpm || (op == bpm && oi < bidx))) { bpm = op; bidx = oi; }
+        }
+        __syncthreads();
+        if (lane == 0) { s.red[wv] = (unsigned long long)__double_as_longlong(bpm); ((long long *)s.y)[wv] = bidx; }
+        __syncthreads();
+        bpm = min_pm; bidx = -1;
+        for (int q = 0; q < HNT / 64; ++q) {
+            const double op = __longlong_as_double((long long)s.red[q]);
+            const long long oi = ((long long *)s.y)[q];
+            if (oi >= 0 && (bidx < 0 || op < bpm || (op == bpm && oi < bidx))) { bpm = op; bidx = oi; }
+        }
+        __syncthreads();
+        if (bidx >= 0 && bpm < min_pm) {
+            min_pm = bpm;
+            int mem[16];
+            const int nm = huge_cand_members(osd_method, w, k, bidx, mem);
+            uint8_t *ow = v.hard; // (the BP decisions went out before)
+            for (int x = tid; x < n; x += HNT) {
+                const int r = v.rowof[x];
+                uint64_t bit = 0;
+                if (r >= 0) {
+                    bit = (basev[r >> 6] >> (r & 63)) & 1ull;
+                    for (int q = 0; q < nm; ++q) if (mem[q] < nht) bit ^= (v.ycand[(size_t)mem[q] * wm + (r >> 6)] >> (r & 63)) & 1ull;
+                }
+                ow[x] = (uint8_t)bit;
+            }
+            __syncthreads();
+            if (tid == 0) for (int q = 0; q < nm; ++q) if (mem[q] < nht) ow[v.ht[mem[q]]] = 1;
+            __syncthreads();
+            ret = ow;
+        }
+    }
+    return ret;
+}
+
 // ---- host side ----
 
 // What both general forms own and do alike; each derives its handle from this and adds its argument template and kernel launch.

@@ -145,16 +145,38 @@ struct HugeBp4Io {
     uint8_t *camel_dec;      // [4B][2][n]
     double *camel_pm;        // [4B]
     int32_t *camel_st;       // [4B][2]
+    // osd_order >= 0 (a handle with the elimination): a decode that did not converge leaves its posteriors in lpr (not NULL then),
+    // is appended to osd_list with one atomic add on osd_count (zeroed by the launch) and exits as SWD_EXIT_OSD
+    int32_t osd_order;
+    int32_t *osd_list;       // [B]
+    uint32_t *osd_count;
+};
+// what the elimination kernel (huge_bp4_osd_kernel) takes from a launch: the queue a BP kernel -- the general one or a tuned one --
+// filled on the same stream, the posteriors it stored, the caller's arrays
+struct HugeBp4OsdIo {
+    int32_t B;
+    const uint8_t *sx, *sz;  // [B][mx], [B][mz]
+    uint8_t *out, *osd0;     // [B][2][n]; osd0 nullable
+    int32_t *stats;          // [B][SWD_STAT_WORDS]: word 7 takes the row additions
+    const double *lpr;       // [B][3][n]
+    const int32_t *osd_list; // [B]
+    const uint32_t *osd_count;
 };
 struct HugeBp4Iface {
     int mx = 0, mz = 0, n = 0;
+    int rank_x = -1, rank_z = -1; // host GF(2) ranks
     virtual ~HugeBp4Iface() {}
     // one launch on `stream` with the scratch area of launch slot `slot` (0 .. 3): the caller has ordered the stream behind the
     // slot's previous launch
     virtual int launch(const HugeBp4Io &io, int slot, void *stream) = 0;
+    // the elimination of the queued decodes, behind a BP launch on the same stream and slot (a handle created with osd)
+    virtual int launch_osd(const HugeBp4OsdIo &io, int slot, void *stream) = 0;
 };
-// llr: [3][n] channel LLRs (x, y, z).  NULL with a message naming the bound when the graph is beyond the form.
-HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *llr, int device);
+// llr: [3][n] channel LLRs (x, y, z); the descriptions' channel_probs: px + py / pz + py (the OSD's path metrics).  bp: the handle
+// runs BP (the general form); osd (nullable): it runs the elimination with these settings (osd_order >= 0, the reference's rules
+// already applied to it except those that need the ranks).  NULL with a message naming the bound when the graph is beyond the form.
+HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *llr, int device, bool bp,
+                              const swd_bp4_params *osd);
 
 struct Plan {
     std::unique_ptr<HugeIface> huge;

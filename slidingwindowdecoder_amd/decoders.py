@@ -467,15 +467,24 @@ class bp4_osd(_Handle):
 
     Columns of Hx / Hz have weight <= 10, except for up to 8 HEAVY columns (weight above 10 in Hx or in Hz, at any position, of
     any weight): the last qubit of the cycle-assembled and EG codes of Misc.ipynb cells 6-8, H = (H1 | 1), touches every check.
-    Such a graph takes ``osd_order=-1`` only (``ValueError`` otherwise): ``camel_decode`` never runs OSD, and ``decode`` returns the
-    BP decisions of a shot that did not converge.  With ``osd_method="osd0"`` -- cell 8's spelling -- the reference resets the
-    order to 0; on a graph with heavy columns the caller's -1 stands.  ``heavy_columns`` reports what the decoder found.
+    Without ``general_osd=True`` (below) such a graph takes ``osd_order=-1`` only (``ValueError`` otherwise): ``camel_decode``
+    never runs OSD, and ``decode`` returns the BP decisions of a shot that did not converge.  With ``osd_method="osd0"`` -- cell
+    8's spelling -- the reference resets the order to 0; on a graph with heavy columns the caller's -1 then stands.
+    ``heavy_columns`` reports what the decoder found.
 
     ``general_form=True`` (default False) takes a graph beyond those bounds -- every column above weight 10 (the EG codes
     [[273,111,17]] and [[1057,571,33]] of cell 8), more than 1024 checks, rows of any weight, more messages than 160 KB of LDS hold:
     one 1024-thread workgroup per shot with every array in HBM, the same results bit for bit.  It runs BP only, so like a graph with
     heavy columns it takes ``osd_order=-1`` (``ValueError`` otherwise) and ``camel_decode``; any graph is taken, one the tuned
-    kernels would take included.  Up to 1 048 576 qubits, 1 048 576 checks per matrix, 67 108 864 edges in all."""
+    kernels would take included.  Up to 1 048 576 qubits, 1 048 576 checks per matrix, 67 108 864 edges in all.
+
+    ``general_osd=True`` (default False) lifts both ``osd_order=-1`` restrictions: the shots BP leaves unconverged are finished by
+    an elimination kernel that keeps its arrays in HBM (one 1024-thread workgroup per shot, no bound on a column's weight), on a
+    graph with heavy columns behind the tuned BP kernel, with ``general_form=True`` beside it behind the general one, and on any
+    other graph too (in place of the tuned elimination kernel) -- OSD-0, ``osd_e`` and ``osd_cs`` with the reference's results bit
+    for bit.  ``osd_method="osd0"`` then resets the order to 0 as the reference does, so cell 8's ``("osd0", -1)`` runs OSD-0
+    inside ``decode``; ``osd_order=-1`` with the other methods stays "no OSD".  Bounds (``ValueError``): at most 4096 checks per
+    matrix, and one shot's elimination arrays within 8 GiB.  ``rank_x`` / ``rank_z`` are the host GF(2) ranks."""
     _destroy = "swd_bp4_destroy"
 
     def __init__(self, Hx, Hz, **kwargs):
@@ -503,15 +512,17 @@ class bp4_osd(_Handle):
         self.device = int(kwargs.get("device", 0))
         asked = int(kwargs.get("osd_order", 0))
         if method == 0 and asked < 0:
-            order = asked  # (swd_bp4_create resets it to 0 like the reference, except on a graph with heavy columns: include/swd.h)
+            # (swd_bp4_create resets it to 0 like the reference, except on a graph with heavy columns or in the general form without
+            # general_osd=True: include/swd.h)
+            order = asked
         p = _lib.Bp4Params(int(kwargs.get("max_iter", 32)), float(kwargs.get("ms_scaling_factor", 1.0)), method, order)
         self._h = L.swd_bp4_create_ex(C.byref(self._cx.desc), C.byref(self._cz.desc), self._px.ctypes.data,
                                       self._py.ctypes.data, self._pz.ctypes.data, C.byref(p), self.device,
-                                      1 if kwargs.get("general_form", False) else 0)
+                                      (1 if kwargs.get("general_form", False) else 0) | (2 if kwargs.get("general_osd", False) else 0))
         if not self._h:
             msg = _lib.last_error()
             if "OSD order" in msg or "invalid" in msg or "blocklength" in msg or "heavy columns" in msg or "column weight" in msg \
-                    or "the general form" in msg or "general form limit" in msg:
+                    or "the general form" in msg or "general form limit" in msg or "general OSD" in msg:
                 raise ValueError(msg)
             raise RuntimeError(f"swd_bp4_create failed: {msg}")
         i = [C.c_int32() for _ in range(5)]
@@ -568,6 +579,12 @@ class bp4_osd(_Handle):
     def general_form(self):
         """True when the decoder runs the general form (``general_form=True`` at construction; include/swd.h swd_bp4_is_general)."""
         return _lib.lib().swd_bp4_is_general(self._h) == 1
+
+    @property
+    def general_osd(self):
+        """True when the decoder was created with ``general_osd=True``: its OSD runs in the general elimination kernel
+        (include/swd.h swd_bp4_is_general_osd)."""
+        return _lib.lib().swd_bp4_is_general_osd(self._h) == 1
 
     @property
     def heavy_columns(self):
@@ -1834,7 +1851,8 @@ class CodeCapacityExperiment(_LaneExperiment):
     ``(dz @ hz_perp.T).any() or (dx @ hx_perp.T).any()`` on the difference of estimate and error.  Cell 8's own codes -- the
     cycle-assembled and EG codes whose last qubit touches every check -- pass as ``(Hx, Hz)`` with ``osd_order=-1``
     (``bp4_osd``: up to 8 heavy columns; ``general_form=True`` among the decoder's keyword arguments takes any graph, such as
-    the EG codes [[273,111,17]] and [[1057,571,33]]); the sampler and the accounting have no degree bound.
+    the EG codes [[273,111,17]] and [[1057,571,33]]; ``general_osd=True`` runs ``decode`` with OSD on them); the sampler and the
+    accounting have no degree bound.
     ``decoder`` in ``osd_window``, ``bpgdg_decoder``, ``bpgd_decoder``, ``bp_history_decoder`` is the single-basis harness of
     /root/reference/src/simulation.py: errors Bernoulli(``channel_probs``) (``DemSampler`` with ``chk = Hx``), syndrome
     ``err @ hx.T``, ``decoder(Hx, **decoder_kwargs)``, criterion ``(d @ hz_perp.T).any()``.
