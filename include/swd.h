@@ -636,6 +636,14 @@ int swd_pipeline_get_timing(swd_pipeline *pl, double *total_ms, int64_t *launche
  * residency (tests/test_gpu_forward_progress.py: blocks that each take more than half a CU's LDS hold one CU apiece). */
 int swd_diag_occupy(int device, int32_t blocks, int32_t threads, int32_t lds_bytes, int32_t microseconds, void *stream);
 
+/* diagnostics: evaluates one routine of the quaternary decoder's arithmetic element by element, out[i] = f(x[i]) (ops 4 and 6:
+ * f(x[i], y[i]); y may be NULL otherwise), on n fp64 DEVICE arrays with an ordinary grid-stride kernel on `stream` -- the device
+ * build of csrc/swd_libm.h and of the composites on top of it, which tests/test_gpu_libm.py holds to a host build of the same header
+ * bit for bit.  op: 0 swd_exp (constant table); 1 swd_exp_from with the table copied to LDS as bp4_kernel copies it; 2 swd_log1p;
+ * 3 bp4_log1pexp and 4 bp4_logaddexp (csrc/swd_bp4_kernel.h, LDS table, the forms of the BP loops); 5 / 6 the general form's
+ * called copies hb_log1pexp / hb_logaddexp, launched from the translation unit that owns them (csrc/swd_huge_bp4.hip). */
+int swd_diag_libm(int device, int32_t op, int64_t n, const double *x, const double *y, double *out, void *stream);
+
 /* diagnostics, host only (needs no device): the message-slot layout of graph g as a pipeline built now would lay it out with up to
  * `pads` pad cells -- the bank-conflict-aware layout, or with SWD_NATURAL_LAYOUT set in the environment the natural one (positions
  * in column order, no pads).  info[8] = { slots, K, D, model cost of the loads, of the stores, the natural layout's two costs,

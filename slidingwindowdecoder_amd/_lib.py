@@ -138,6 +138,7 @@ SYMBOLS = [
     ("swd_shot_account_dev", C.c_int, [C.c_int, _i32, _i32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _i32, _vp]),
     ("swd_group_account_dev", C.c_int, [C.c_int, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     ("swd_diag_occupy",C.c_int, [C.c_int, _i32, _i32, _i32, _i32, _vp]),
+    ("swd_diag_libm", C.c_int, [C.c_int, _i32, _i64, _vp, _vp, _vp, _vp]),
     ("swd_graph_layout", C.c_int, [C.POINTER(GraphDesc), _i32] + [_vp] * 9),
     ("swd_graph_node_depth", C.c_int, [C.POINTER(GraphDesc), _i32, _i32, _i32, _vp] + [_vp] * 6),
     ("swd_graph_cache_image", C.c_int, [C.POINTER(GraphDesc), _i32, _i32, _i32, _i32, _i32, _vp] + [_vp] * 7),

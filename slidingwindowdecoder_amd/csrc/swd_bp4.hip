@@ -603,3 +603,42 @@ extern "C" int swd_bp4_decode_batch(swd_bp4 *h, int32_t B, const uint8_t *sx, co
     if (bp_dec) memcpy(bp_dec, hs + o_bpd, B * 2 * n);
     return 0;
 }
+
+// ---- diagnostics: the device's exp / log1p and the two composites of the node update, element by element (include/swd.h:
+// swd_diag_libm; tests/test_gpu_libm.py holds them to a host build of swd_libm.h bit for bit) ----
+namespace swd {
+__global__ void __launch_bounds__(256) diag_libm_kernel(int op, int64_t n, const double *x, const double *y, double *out) {
+    // the table in LDS exactly as bp4_kernel copies it (swd_bp4_kernel.h)
+    __shared__ __attribute__((aligned(16))) uint64_t s_exptab[256];
+    const int NT = (int)blockDim.x;
+    for (int i = threadIdx.x; i < 256; i += NT) s_exptab[i] = swd_exp_tab_dev[i];
+    __syncthreads();
+    const uint64_t *const xt = s_exptab;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = x[i];
+        double r;
+        switch (op) {
+        case 0: r = swd_exp(v); break;
+        case 1: r = swd_exp_from(v, xt); break;
+        case 2: r = swd_log1p(v); break;
+        case 3: r = bp4_log1pexp(v, xt); break;
+        default: r = bp4_logaddexp(v, y[i], xt); break;
+        }
+        out[i] = r;
+    }
+}
+} // namespace swd
+
+extern "C" int swd_diag_libm(int device, int32_t op, int64_t n, const double *x, const double *y, double *out, void *stream) {
+    if (op < 0 || op > 6 || n < 0 || (n > 0 && (!x || !out || ((op == 4 || op == 6) && !y)))) {
+        swd::set_error("swd_diag_libm: op 0..6, n >= 0, x and out (and y for ops 4 and 6) device arrays of n doubles");
+        return -1;
+    }
+    if (n == 0) return 0;
+    SWD_HIP(hipSetDevice(device));
+    if (op >= 5) return swd::huge_bp4_diag_libm(op, n, x, y, out, stream);
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(swd::diag_libm_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (int)op, n, x, y, out);
+    SWD_HIP(hipGetLastError());
+    return 0;
+}

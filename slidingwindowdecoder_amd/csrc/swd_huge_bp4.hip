@@ -451,4 +451,17 @@ HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz
     return h.release();
 }
 
+// ---- diagnostics (include/swd.h: swd_diag_libm, ops 5 / 6): the noinline copies above, one argument (pair) per element ----
+__global__ void __launch_bounds__(256) huge_bp4_diag_libm_kernel(int op, int64_t n, const double *x, const double *y, double *out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = (op == 5) ? hb_log1pexp(x[i]) : hb_logaddexp(x[i], y[i]);
+}
+
+int huge_bp4_diag_libm(int op, int64_t n, const double *x, const double *y, double *out, void *stream) {
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(huge_bp4_diag_libm_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, op, n, x, y, out);
+    SWD_HIP(hipGetLastError());
+    return 0;
+}
+
 } // namespace swd

@@ -177,6 +177,9 @@ struct HugeBp4Iface {
 // already applied to it except those that need the ranks).  NULL with a message naming the bound when the graph is beyond the form.
 HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *llr, int device, bool bp,
                               const swd_bp4_params *osd);
+// swd_diag_libm's ops 5 / 6 (include/swd.h): hb_log1pexp / hb_logaddexp element by element, launched from the translation unit that
+// owns them, so the copies evaluated are the ones huge_bp4_kernel calls
+int huge_bp4_diag_libm(int op, int64_t n, const double *x, const double *y, double *out, void *stream);
 
 struct Plan {
     std::unique_ptr<HugeIface> huge;

@@ -344,6 +344,33 @@ def window_forms(windows, decoder="osd_window", num_det=0, **kwargs):
     return _form_dict(plan, wins)
 
 
+def diag_libm(op, x, y=None, device=0):
+    """Diagnostics (include/swd.h swd_diag_libm): one routine of the quaternary decoder's arithmetic on the device, element by
+    element.  ``op``: 0 exp, 1 exp with its table in LDS, 2 log1p, 3 log1pexp, 4 logaddexp(x, y), 5 / 6 the general form's copies of
+    3 / 4.  ``x`` (and ``y`` for ops 4 and 6): float64 numpy arrays -- copied to ``device`` and back, a numpy array returns -- or
+    contiguous float64 CUDA tensors, evaluated on their device and the current stream, a tensor returns."""
+    import torch
+    host = not isinstance(x, torch.Tensor)
+    binary = op in (4, 6)
+    if binary and y is None:
+        raise ValueError("ops 4 and 6 take x and y")
+    if host:
+        dev = torch.device("cuda", int(device))
+        xt = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
+        yt = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev) if binary else None
+    else:
+        xt, yt = x, (y if binary else None)
+    for t in (xt, yt):
+        if t is not None and (t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.shape != xt.shape or t.device != xt.device):
+            raise ValueError("x and y must be contiguous float64 CUDA tensors of one shape on one device")
+    out = torch.empty_like(xt)
+    rc = _lib.lib().swd_diag_libm(xt.device.index, int(op), xt.numel(), xt.data_ptr(), yt.data_ptr() if binary else None, out.data_ptr(),
+                                  torch.cuda.current_stream(xt.device).cuda_stream)
+    if rc:
+        raise ValueError(f"swd_diag_libm failed: {_lib.last_error()}")
+    return out.cpu().numpy() if host else out
+
+
 class bp_history_decoder(_Handle):
     """Plain min-sum BP with a 4-deep posterior history (reference: src/bp_guessing_decoder.pyx:5-158)
     and base class of the guessing decoders.  ``bpgdg_decoder``: the side branches of a shot's decimation tree run

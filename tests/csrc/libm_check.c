@@ -1,5 +1,8 @@
 /* Test helper (CPU): holds slidingwindowdecoder_amd/csrc/swd_libm.h to the host C library, bit for bit.
- * Built by tests/test_libm_restatement.py with gcc; returns the number of arguments where the results differ. */
+ * Built by tests/test_libm_restatement.py with gcc; returns the number of arguments where the results differ.
+ * swd_eval_header / swd_eval_libm (below) evaluate the ops of swd_diag_libm (include/swd.h) on arrays: the host build of the header
+ * that tests/test_gpu_libm.py holds the device build to, and the C library's own exp / log1p under the same composites. */
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -60,4 +63,45 @@ long swd_check_log1p(long n, uint64_t seed, double *first_bad) {
     for (unsigned i = 0; i < sizeof special / sizeof special[0]; ++i)
         if (!same(log1p(special[i]), swd_log1p(special[i]))) { if (!bad && first_bad) *first_bad = special[i]; ++bad; }
     return bad;
+}
+
+/* log1pexp / logaddexp in the BRANCHING form of the reference (src/include/bpgd.cpp:399-416, oracle/swd_oracle.c log1pexp_ /
+ * logaddexp_), over the header's exp / log1p: what the device's branch-free bp4_log1pexp / bp4_logaddexp must equal */
+static double hdr_log1pexp(double x) {
+    if (x > 36.04365338911715) return x + swd_log1p(swd_exp(-x));
+    return swd_log1p(swd_exp(x));
+}
+static double hdr_logaddexp(double x, double y) {
+    double const tmp = x - y;
+    if (x == y) return x + M_LN2;
+    if (tmp > 0) return x + hdr_log1pexp(-tmp);
+    else if (tmp <= 0) return y + hdr_log1pexp(tmp);
+    return tmp;
+}
+/* the same two over the C library, the threshold spelled as the reference spells it */
+static double libm_log1pexp(double x) {
+    if (x > -log(DBL_EPSILON)) return x + log1p(exp(-x));
+    return log1p(exp(x));
+}
+static double libm_logaddexp(double x, double y) {
+    double const tmp = x - y;
+    if (x == y) return x + M_LN2;
+    if (tmp > 0) return x + libm_log1pexp(-tmp);
+    else if (tmp <= 0) return y + libm_log1pexp(tmp);
+    return tmp;
+}
+
+/* ops of swd_diag_libm: 0 / 1 exp, 2 log1p, 3 / 5 log1pexp, 4 / 6 logaddexp(x, y) (the device's ops 1, 5, 6 are other COPIES of
+ * the same functions); y is read by ops 4 and 6 only.  Returns -1 for an unknown op. */
+int swd_eval_header(int op, long n, const double *x, const double *y, double *out) {
+    if (op < 0 || op > 6) return -1;
+    for (long i = 0; i < n; ++i)
+        out[i] = op <= 1 ? swd_exp(x[i]) : op == 2 ? swd_log1p(x[i]) : (op == 3 || op == 5) ? hdr_log1pexp(x[i]) : hdr_logaddexp(x[i], y[i]);
+    return 0;
+}
+int swd_eval_libm(int op, long n, const double *x, const double *y, double *out) {
+    if (op < 0 || op > 6) return -1;
+    for (long i = 0; i < n; ++i)
+        out[i] = op <= 1 ? exp(x[i]) : op == 2 ? log1p(x[i]) : (op == 3 || op == 5) ? libm_log1pexp(x[i]) : libm_logaddexp(x[i], y[i]);
+    return 0;
 }
