@@ -25,6 +25,38 @@ extern "C" {
 
 #define SWD_ABI_VERSION 4
 
+/* Environment variables (test hooks and diagnostics)
+ *
+ * The library reads these nineteen variables and nothing else from the environment (csrc/swd_env.h holds the table and the only
+ * getenv).  None changes a result; each demands a kernel form or a scheduling that the library would otherwise choose by itself, so a
+ * production process sets none of them.
+ * Read: P = at its first use, then cached for the process; C = by every handle creation; L = by every launch.
+ * Kind: set = on when set to anything, "0" included; nonzero = on when set to anything but "0"; int; text.
+ *
+ *   variable                   read  kind     effect
+ *   SWD_FORCE_HUGE             C     set      swd_osdw_create, swd_gdg_create: the general form (every array in HBM) on any graph
+ *   SWD_NATURAL_LAYOUT         C     set      graphs keep the natural message-slot layout (also read by swd_graph_layout and the other
+ *                                             host-only layout calls)
+ *   SWD_UNIFORM_DEPTH          C     nonzero  osd_window handles keep the uniform node pass where a depth profile would fit
+ *   SWD_OWIDE_RING             C     int      large graphs: ring entries of the wide column-form elimination (at least 4; default 64 or 32)
+ *   SWD_GRID_PCT               P     int      persistent grid of that percentage of the resident workgroup slots (at least 1; default 100)
+ *   SWD_GDG_SERIAL             C     set      guessing decoders: the serial tree walk, never work items
+ *   SWD_GDG_STREAM_SERIAL_MIN  L     int      guessing decoders: shots from which a batch with another one in flight walks serially (3072)
+ *   SWD_GDG_PAR_MAX_SHOTS      P     int      guessing decoders: shots up to which a launch takes the work-item form (5120)
+ *   SWD_GDG_INFLIGHT           P     int      work-item form: side branches of a tree queued or running at a time (at least 1; default 4)
+ *   SWD_GDG_SHOTS_PCT          P     int      work-item form: shots admitted up front in percent of the grid (at least 1; default 100 / 400)
+ *   SWD_ENS_TICKETS            L     set      threaded ensemble: ticket scheduling instead of the work-item ring
+ *   SWD_ENS_NO_TASKS           L     set      threaded ensemble on the ring: every thread body on the unit's workgroup
+ *   SWD_BP4_NT                 C     int      bp4_osd: threads of the BP kernel (a multiple of 64 in 64..1024; anything else is ignored)
+ *   SWD_BP4_SKEW               P     text     bp4_osd: even | odd -- waves of that index parity sleep before every message-storing node
+ *                                             pass of a split launch; anything else is off
+ *   SWD_BP4_OVERLAPPED         P     set      bp4_osd: every launch is taken as one with another launch in flight
+ *   SWD_BP4_NOSPLIT            C     set      bp4_osd: one thread per qubit also for small codes
+ *   SWD_BP4_NO_LAZY            P     set      bp4_osd: the fused node update only
+ *   SWD_BP4_GENERIC            L     set      bp4_osd: the generic instantiation instead of the specialised one
+ *   SWD_BP4_SPLIT_MAX          C     int      bp4_osd: two threads per qubit up to this value of 2 n (default 256, at most 512)
+ */
+
 /* exit class of one window decode, low byte of status[]; bit 8 = converge flag */
 enum {
     SWD_EXIT_PRE = 0,       /* pre-processing BP converged    osd_window.pyx:166-170 */
@@ -150,7 +182,7 @@ typedef struct swd_gdg swd_gdg;
  * statistics words.  Its bounds, each an error at construction: 4096 checks, 4194304 columns, 4096 snapshots per shot
  * (max_guess, or S - D + 2 for the threaded ensemble); multi_thread = 2 is refused there; modes 0 and 1 refuse a check of weight
  * >= 128 (the reference keeps check degrees in char, bpgd.hpp:23: they wrap, no answer is pinned), mode 2 takes it.
- * Test hook of both constructors: with the environment variable SWD_FORCE_HUGE set, swd_osdw_create and swd_gdg_create build
+ * Test hook of both constructors: SWD_FORCE_HUGE ("Environment variables" above) makes swd_osdw_create and swd_gdg_create build
  * the general form on any graph.  swd_pipeline_create_gdg refuses windows beyond every pipeline kernel. */
 swd_gdg *swd_gdg_create(const swd_graph_desc *g, const swd_gdg_params *p, int device);
 void swd_gdg_destroy(swd_gdg *d);
@@ -222,7 +254,7 @@ int swd_bp4_heavy_info(const swd_bp4 *d, int32_t *count, int32_t *max_degree);
 /* The form of the BP kernel the handle's most recent launch took (diagnostics and tests; every pointer nullable):
  * split 1 = two threads per qubit, lazy 1 = the two-half node update, fast 1 = the specialised instantiation (0: generic),
  * wmax / dm = the instantiation's most waves per workgroup and column-weight bound, threads = the workgroup size, skew = the
- * SWD_BP4_SKEW wave stagger (0 off, 1 even, 2 odd), overlapped 1 = taken as a launch with another one in flight.
+ * SWD_BP4_SKEW wave stagger (0 off, 1 even, 2 odd; "Environment variables" above), overlapped 1 = taken as a launch with another one in flight.
  * Returns -1 before the first launch. */
 int swd_bp4_last_form(const swd_bp4 *d, int32_t *split, int32_t *lazy, int32_t *fast, int32_t *wmax, int32_t *dm,
                       int32_t *threads, int32_t *skew, int32_t *overlapped);
@@ -645,8 +677,8 @@ int swd_diag_occupy(int device, int32_t blocks, int32_t threads, int32_t lds_byt
 int swd_diag_libm(int device, int32_t op, int64_t n, const double *x, const double *y, double *out, void *stream);
 
 /* diagnostics, host only (needs no device): the message-slot layout of graph g as a pipeline built now would lay it out with up to
- * `pads` pad cells -- the bank-conflict-aware layout, or with SWD_NATURAL_LAYOUT set in the environment the natural one (positions
- * in column order, no pads).  info[8] = { slots, K, D, model cost of the loads, of the stores, the natural layout's two costs,
+ * `pads` pad cells -- the bank-conflict-aware layout, or under SWD_NATURAL_LAYOUT ("Environment variables" above) the natural one
+ * (positions in column order, no pads).  info[8] = { slots, K, D, model cost of the loads, of the stores, the natural layout's two costs,
  * pad cells used }; the arrays (any of them may be NULL) are sized jptr [K + 1], row_col [slots], perm / iperm / row_deg [m],
  * vn_edge / vn_edge_s [D * n], vperm [n]: call once with NULL arrays for the sizes.  The cost is in LDS-array cycles of one
  * variable-node pass over the full graph (csrc/swd_graph.hip, Graph::layout_cost). */
@@ -657,8 +689,8 @@ int swd_graph_layout(const swd_graph_desc *g, int32_t pads, int32_t *info, uint1
  * a depth profile and whose window graphs all fit it serves the full graph's nodes in descending-degree order, a fixed number of
  * edge positions per row of the register cache; every other handle keeps the uniform pass over the variant's column-weight bound.
  * Both compute the same results.  1: profiled, 0: uniform (the launches of such a handle that write a posterior history keep the
- * uniform kernel).  Test hook: with SWD_UNIFORM_DEPTH set in the environment (to anything but 0) when a handle is created, the
- * handle keeps the uniform form (A/B runs, tests), as SWD_NATURAL_LAYOUT keeps the natural message-slot layout. */
+ * uniform kernel).  Test hook: SWD_UNIFORM_DEPTH ("Environment variables" above) keeps the uniform form, as SWD_NATURAL_LAYOUT
+ * keeps the natural message-slot layout. */
 int swd_osdw_node_depth(const swd_osdw *h);
 int swd_pipeline_node_depth(const swd_pipeline *pl);
 

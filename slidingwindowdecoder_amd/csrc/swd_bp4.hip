@@ -128,7 +128,7 @@ static int bp4_dispatch_nt(Bp4 *d, const SwdBp4Args &a, hipStream_t st, int nt) 
     // BP kernel: one thread per qubit (two in the specialised launch) while the waves fit a workgroup; OSD kernel: the workgroups its
     // layouts were made for.  The two-half node update (LAZY, swd_bp4_kernel.h) where it was measured to pay: every launch with one thread
     // per qubit (profiles/r06_bp4_lazy.log; the two-threads-per-qubit launches of the small codes keep the fused update); SWD_BP4_NO_LAZY: never
-    static const bool lazy_ok = getenv("SWD_BP4_NO_LAZY") == nullptr;
+    const bool lazy_ok = !env::on(env::BP4_NO_LAZY);
     if constexpr (FAST) {
         // (two threads per qubit: the fused form one launch at a time, the two-half form when another launch is in flight beside this one --
         // SHYPS r = 3, two streams: 33.2 -> 40.8 M decodes/s, [[72]] 70.7 / 70.0; one at a time it loses 5-7 %)
@@ -143,11 +143,8 @@ static int bp4_dispatch_nt(Bp4 *d, const SwdBp4Args &a, hipStream_t st, int nt) 
 // SWD_BP4_SKEW=even|odd (diagnostics): the waves of that index parity sleep before every node pass of a split launch that stores messages
 // (bp4_skew, swd_bp4_kernel.h) -- the two threads of a qubit must not depend on running in step
 static int bp4_skew_switch() {
-    static const int v = [] {
-        const char *e = getenv("SWD_BP4_SKEW");
-        return !e ? 0 : (!strcmp(e, "even") ? 1 : (!strcmp(e, "odd") ? 2 : 0));
-    }();
-    return v;
+    const char *e = env::str(env::BP4_SKEW);
+    return !e ? 0 : (!strcmp(e, "even") ? 1 : (!strcmp(e, "odd") ? 2 : 0));
 }
 static int bp4_dispatch(Bp4 *d, const SwdBp4Args &a, hipStream_t st) {
     // the specialised instantiation: a thread per qubit and per check, no camel run (swd_bp4_kernel.h); two threads per qubit for
@@ -157,7 +154,7 @@ static int bp4_dispatch(Bp4 *d, const SwdBp4Args &a, hipStream_t st) {
         return d->nt <= 256 ? bp4_launch<4, 256, SWD_DMAX, false, false, true>(d, a, st, d->nt)
                             : (d->nt <= 512 ? bp4_launch<8, 256, SWD_DMAX, false, false, true>(d, a, st, d->nt)
                                             : bp4_launch<16, 256, SWD_DMAX, false, false, true>(d, a, st, d->nt));
-    const bool fast = !a.camel && d->n <= d->nt && d->gx.m + d->gz.m <= d->nt && !getenv("SWD_BP4_GENERIC");
+    const bool fast = !a.camel && d->n <= d->nt && d->gx.m + d->gz.m <= d->nt && !env::on(env::BP4_GENERIC);
     if (fast) return bp4_dispatch_nt<true>(d, a, st, d->nt_split ? d->nt_split : d->nt);
     return bp4_dispatch_nt<false>(d, a, st, d->nt);
 }
@@ -269,12 +266,12 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
     d->dm = d->heavy ? SWD_DMAX : (D <= 4 ? 4 : (D <= 8 ? 8 : SWD_DMAX)); // SHYPS stabiliser matrices reach column weight 9
     d->nt_osd = n <= 3072 ? 256 : 1024;
     d->nt = n <= 1024 ? std::max(64, (n + 63) / 64 * 64) : 1024;
-    if (const char *e = getenv("SWD_BP4_NT")) { const int v = atoi(e); if (v >= 64 && v <= 1024 && v % 64 == 0) d->nt = v; } // (diagnostics)
+    if (const int v = env::num(env::BP4_NT, 0); v >= 64 && v <= 1024 && v % 64 == 0) d->nt = v; // (diagnostics)
     // two threads per qubit while the workgroup stays within four waves (measured, profiles/r06_bp4_split.log: [[72]] 43.8 -> 46.9 M
     // decodes/s, SHYPS r = 3 23.9 -> 24.9 M; [[144]] on five waves 35.9 -> 28.0 M, so larger codes keep one thread per qubit;
     // SWD_BP4_SPLIT_MAX overrides the bound on 2 n for experiments)
-    const int split_max = getenv("SWD_BP4_SPLIT_MAX") ? atoi(getenv("SWD_BP4_SPLIT_MAX")) : 256;
-    d->nt_split = (!d->heavy && 2 * n <= std::min(split_max, 512) && !getenv("SWD_BP4_NOSPLIT")) ? std::max(64, (2 * n + 63) / 64 * 64) : 0;
+    const int split_max = env::num(env::BP4_SPLIT_MAX, 256);
+    d->nt_split = (!d->heavy && 2 * n <= std::min(split_max, 512) && !env::on(env::BP4_NOSPLIT)) ? std::max(64, (2 * n + 63) / 64 * 64) : 0;
     if (d->gx.upload() || d->gz.upload()) { delete d; return nullptr; }
     d->gx.d.new_n = n; d->gz.d.new_n = n;
     // rank(Hx) > rank(Hz): the z-basis sweep walks the first kx = n - rank_x non-pivot columns like the reference's (not the n - rank_z
@@ -435,35 +432,30 @@ extern "C" int swd_bp4_decode_batch_dev(swd_bp4 *h, int32_t B, const uint8_t *sx
     // [ OSD queue counter | ticket counter | - | - | OSD queue [B] | weights [B] | start order [B] ]
     for (auto &s2 : d->slot) if (s2.osd_q.reserve((size_t)B * 12 + 16)) return -1;
     a.osd_count = sl->osd_q.as<uint32_t>(); a.osd_list = sl->osd_q.as<int32_t>() + 4;
-    static const bool static_units = getenv("SWD_BP4_STATIC") != nullptr; // (diagnostics: the static shares of rounds 4-5)
     d->overlapped = false;
-    if (!static_units) {
-        a.ticket = a.osd_count + 1;
-        // start order: heaviest syndrome first.  The decodes that run all max_iter iterations are NOT the heaviest ones ([[144]]: weights 5-25
-        // around a median of 10, spread over ranks 0.07-0.89 of the order: profiles/r06_bp4_heavy.log), so the order does not move the tail of
-        // a launch; it still pays where the iteration count follows the weight -- SHYPS r = 3 18.8 -> 24.9 M decodes/s, [[72]] 40.0 -> 45.9,
-        // [[144]] 35.1 -> 36.2; [[288]] .. [[756]] lose 2-3 % to the two small kernels (profiles/r06_bp4_order.log).  SWD_BP4_NO_ORDER: off
-        // ... and not when another launch of this handle is still running on a DIFFERENT stream (a caller that keeps two launches in
-        // flight): whatever tail this launch has, the other launch's grid fills it, and the two small kernels are 6 % of a step
-        // ([[144]], two streams in turn: 55.4 -> 58.7 M decodes/s without them)
-        static const bool by_weight = getenv("SWD_BP4_NO_ORDER") == nullptr;
-        static const bool always = getenv("SWD_BP4_ORDER_ALWAYS") != nullptr;
-        // SWD_BP4_OVERLAPPED (diagnostics): every launch takes the path of a launch with another one in flight -- the two-half (LAZY)
-        // form for two threads per qubit, no start order -- so that the tests reach that form without depending on timing
-        static const bool force_overlap = getenv("SWD_BP4_OVERLAPPED") != nullptr;
-        bool overlapped = force_overlap;
-        if (!force_overlap && !always && d->last_done && d->last_stream != st) {
-            overlapped = hipEventQuery(d->last_done) == hipErrorNotReady;
-            (void)hipGetLastError(); // ("not ready" is an answer, not an error: it must not be what the launch checks below pick up)
-        }
-        d->overlapped = overlapped;
-        if (by_weight && !overlapped) {
-            uint32_t *wt = sl->osd_q.as<uint32_t>() + 4 + B, *ord = wt + B;
-            hipLaunchKernelGGL(bp4_weight_kernel, dim3((B + 3) / 4), dim3(256), 0, st, sx, sz, d->gx.m, d->gz.m, B, wt);
-            hipLaunchKernelGGL((shot_order_kernel<1024>), dim3(1), dim3(1024), 0, st, (const uint32_t *)wt, B, ord);
-            SWD_HIP(hipGetLastError());
-            a.order = ord;
-        }
+    a.ticket = a.osd_count + 1; // (the static shares of rounds 4-5, a null ticket, are what the camel launches below still take)
+    // start order: heaviest syndrome first.  The decodes that run all max_iter iterations are NOT the heaviest ones ([[144]]: weights 5-25
+    // around a median of 10, spread over ranks 0.07-0.89 of the order: profiles/r06_bp4_heavy.log), so the order does not move the tail of
+    // a launch; it still pays where the iteration count follows the weight -- SHYPS r = 3 18.8 -> 24.9 M decodes/s, [[72]] 40.0 -> 45.9,
+    // [[144]] 35.1 -> 36.2; [[288]] .. [[756]] lose 2-3 % to the two small kernels (profiles/r06_bp4_order.log)
+    // ... and not when another launch of this handle is still running on a DIFFERENT stream (a caller that keeps two launches in
+    // flight): whatever tail this launch has, the other launch's grid fills it, and the two small kernels are 6 % of a step
+    // ([[144]], two streams in turn: 55.4 -> 58.7 M decodes/s without them)
+    // SWD_BP4_OVERLAPPED (diagnostics): every launch takes the path of a launch with another one in flight -- the two-half (LAZY)
+    // form for two threads per qubit, no start order -- so that the tests reach that form without depending on timing
+    const bool force_overlap = env::on(env::BP4_OVERLAPPED);
+    bool overlapped = force_overlap;
+    if (!force_overlap && d->last_done && d->last_stream != st) {
+        overlapped = hipEventQuery(d->last_done) == hipErrorNotReady;
+        (void)hipGetLastError(); // ("not ready" is an answer, not an error: it must not be what the launch checks below pick up)
+    }
+    d->overlapped = overlapped;
+    if (!overlapped) {
+        uint32_t *wt = sl->osd_q.as<uint32_t>() + 4 + B, *ord = wt + B;
+        hipLaunchKernelGGL(bp4_weight_kernel, dim3((B + 3) / 4), dim3(256), 0, st, sx, sz, d->gx.m, d->gz.m, B, wt);
+        hipLaunchKernelGGL((shot_order_kernel<1024>), dim3(1), dim3(1024), 0, st, (const uint32_t *)wt, B, ord);
+        SWD_HIP(hipGetLastError());
+        a.order = ord;
     }
     if (bp4_dispatch(d, a, st)) return -1;
     SWD_HIP(hipEventRecord(sl->done, st));

@@ -478,7 +478,7 @@ int Graph::upload() {
     return 0;
 }
 
-bool natural_layout_requested() { return getenv("SWD_NATURAL_LAYOUT") != nullptr; }
+bool natural_layout_requested() { return env::on(env::NATURAL_LAYOUT); }
 
 } // namespace swd
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "swd.h"
+#include "swd_env.h"
 #include "swd_graph.h"
 
 namespace swd {
@@ -120,7 +121,7 @@ struct Graph {
     int upload();                          // hipMalloc + copy, fills d
 };
 
-// SWD_NATURAL_LAYOUT in the environment (diagnostics, A/B runs): plans keep the natural layout of their graphs
+// SWD_NATURAL_LAYOUT in the environment (swd_env.h): plans keep the natural layout of their graphs
 bool natural_layout_requested();
 
 int gf2_rank(int m, int n, const std::vector<int32_t> &row_ptr, const std::vector<int32_t> &col_idx);

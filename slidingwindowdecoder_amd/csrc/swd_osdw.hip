@@ -85,7 +85,7 @@ int make_layout(const Graph &g, int new_n, int nt, int kind, SwdLdsLayout &L, bo
     // large graphs: what fits beside the state goes back into LDS -- the messages of the shortened graph (one column of cells per
     // live variable node: D x new_n cells + the sink, far and zero slots) and the arrays of the OSD phase that start at off_aux
     L.off_pmsg = -1; L.pmsg_bytes = 0; L.post_lds = 0; L.osd_lds = 0;
-    if (big && kind == 0 && !getenv("SWD_BIG_NO_LDS")) {
+    if (big && kind == 0) {
         const int post_b = align_up((g.D * new_n + 1 + 2 * (nt / 64)) * 8, 16);
         // (transform matrix, pivots; the ordered list behind them stays in the scratch region -- osd_run)
         const int aux_b = align_up(std::max(std::max(osd_bytes_at_aux - n * 2, rare_bytes) - L.off_aux, L.off_hs + n * 8 - L.off_aux), 16);
@@ -100,18 +100,17 @@ int make_layout(const Graph &g, int new_n, int nt, int kind, SwdLdsLayout &L, bo
     }
     // large graphs, 256 < m <= 960: ring (64 or 32 entries of 16 words), pivoted-row mask and control words of osd0_colsw
     L.off_owide = -1; L.owide_ring = 0;
-    if (big && kind == 0 && nt == 1024 && wm > 4 && wm <= 15 && !getenv("SWD_NO_OSD_WIDE")) {
-        const char *rq = getenv("SWD_OWIDE_RING"); // (tests: a smaller ring, so that batches close early)
-        for (int ring = rq ? std::max(atoi(rq), 4) : 64; ring >= (rq ? 4 : 32); ring >>= 1) {
+    if (big && kind == 0 && nt == 1024 && wm > 4 && wm <= 15) {
+        const int rq = env::num(env::OWIDE_RING, 0, 4); // (tests: a smaller ring, so that batches close early)
+        for (int ring = rq ? rq : 64; ring >= (rq ? 4 : 32); ring >>= 1) {
             const int bytes = align_up(ring * 16 * 8 + 16 * 8 + 64, 16);
             if (o + bytes <= lds_budget) { L.off_owide = o; L.owide_ring = ring; o += bytes; break; }
         }
     }
     // sorted form of the shortened graph (round 5): the production form of the tuned kernels' post phase whenever the renumbered cells
-    // fit in front of the staged column table, which becomes the old-slot -> cell table; SWD_NO_POST_SORTED=1 in the environment keeps
-    // the round-4 form
+    // fit in front of the staged column table, which becomes the old-slot -> cell table
     // (diet kernels keep cell BYTE offsets in 16 bits, the 1024-thread osd_window kernels cell numbers)
-    if (kind == 0 && !big && !getenv("SWD_NO_POST_SORTED") && L.off_lslot == 0 && (g.D * new_n + 1 + 2 * (nt / 64)) * 8 <= L.off_rc &&
+    if (kind == 0 && !big && L.off_lslot == 0 && (g.D * new_n + 1 + 2 * (nt / 64)) * 8 <= L.off_rc &&
         g.D * new_n + 1 + 2 * (nt / 64) <= (diet ? 8191 : 65535) && (diet || nt >= 512))
         L.post_lds = 1;
     L.total = align_up(o, 16);
@@ -188,7 +187,7 @@ const DepthProfile *find_depth_profile(const Variant *v) {
     return nullptr;
 }
 
-bool uniform_depth_requested() { const char *e = getenv("SWD_UNIFORM_DEPTH"); return e && strcmp(e, "0") != 0; }
+bool uniform_depth_requested() { return env::on(env::UNIFORM_DEPTH); }
 
 #define X(nt, vf, dm, kg) SWD_DECLARE_LAUNCHER(5, nt, vf, dm, kg, 0) SWD_DECLARE_LAUNCHER(6, nt, vf, dm, kg, 0) SWD_DECLARE_LAUNCHER(8, nt, vf, dm, kg, 0) SWD_DECLARE_LAUNCHER(9, nt, vf, dm, kg, 0)
 SWD_BIG_VARIANTS(X)
@@ -255,8 +254,8 @@ int launch(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
     int rc;
     // guessing decoders: the parallel form (side branches as work items) shortens the critical path of a batch that
     // cannot fill the device with whole shots; large batches keep the serial walk (no speculation, no queue traffic)
-    static const int par_max_shots = getenv("SWD_GDG_PAR_MAX_SHOTS") ? atoi(getenv("SWD_GDG_PAR_MAX_SHOTS")) : 5120; // measured, [[144]] GDG windows (work items with 64 contexts vs serial, round 6): 4096 shots 36.9 vs 41.3 ms, 5120 shots 44.2 vs 45.2, 6144 shots 50.3 vs 47.5, 8192 shots 66.6 vs 55.9 (round 5, every context handed out: 4608)
-    const int stream_serial_min = getenv("SWD_GDG_STREAM_SERIAL_MIN") ? atoi(getenv("SWD_GDG_STREAM_SERIAL_MIN")) : 3072; // (read per launch: the tests switch it)
+    const int par_max_shots = env::num(env::GDG_PAR_MAX_SHOTS, 5120); // measured, [[144]] GDG windows (work items with 64 contexts vs serial, round 6): 4096 shots 36.9 vs 41.3 ms, 5120 shots 44.2 vs 45.2, 6144 shots 50.3 vs 47.5, 8192 shots 66.6 vs 55.9 (round 5, every context handed out: 4608)
+    const int stream_serial_min = env::num(env::GDG_STREAM_SERIAL_MIN, 3072); // (read per launch: the tests switch it)
     // ... and so do the batches of a stream object from 3072 shots (round 6): the work-item form shortens ONE launch's critical path at the price of
     // queue traffic and idle polling; with two batches in flight the next launch's grid fills the tail the serial walk leaves --
     // [[144]] GDG windows, 4096 shots per batch: 1.19 M windows/s one launch at a time (work items), 1.21 M streamed with work items,
@@ -275,7 +274,7 @@ int launch(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
     // osd_window: when the posterior history is only consumed as its slot-order sum (no history in or out, both
     // iteration caps multiples of four) the kernel that accumulates the sum in registers runs: no 4 x n ring in HBM
     const bool acc = d->kind == 0 && d->variant->launch_acc && !a.hist && !a.P.record_all && !a.P.hist_is_state && !a.P.zero_hist &&
-                     a.P.pre_iter >= 4 && a.P.pre_iter % 4 == 0 && a.P.post_iter >= 4 && a.P.post_iter % 4 == 0 && !getenv("SWD_NO_HACC");
+                     a.P.pre_iter >= 4 && a.P.pre_iter % 4 == 0 && a.P.post_iter >= 4 && a.P.post_iter % 4 == 0;
     const bool ens = d->kind == 1 && d->gp.multi_thread == 1; // the reference's threaded ensemble: its own kernel (kind 7)
     // (a plan whose graphs fit the variant's depth profile: the profiled kind-3 kernel; its kind-0 launches keep the uniform pass)
     rc = (d->kind == 0) ? (acc ? (d->depth ? d->depth->launch_acc(d, a, st) : d->variant->launch_acc(d, a, st)) : d->variant->launch(d, a, st))
@@ -349,7 +348,7 @@ extern "C" swd_osdw *swd_osdw_create(const swd_graph_desc *g, const swd_osdw_par
     d->p = *p;
     std::map<std::string, std::shared_ptr<Graph>> cache;
     if (check_params(d->p)) { delete d; return nullptr; }
-    if (getenv("SWD_FORCE_HUGE") /* tests: the general form on graphs a variant would take */ || d->add_window(g, 0, 0, 0, cache) || d->finalize(nullptr)) {
+    if (env::on(env::FORCE_HUGE) /* tests: the general form on graphs a variant would take */ || d->add_window(g, 0, 0, 0, cache) || d->finalize(nullptr)) {
         // no kernel variant takes this graph (more than 1024 checks, 9216 columns, 65 535 edges, row weight 64 or column weight 10):
         // the general form, every array in HBM (swd_huge.hip) -- the reference's mod2sparse has no size limit
         d->wins.clear();
@@ -686,7 +685,7 @@ static int stream_alloc_lane(HostStream *hs, StreamLane &l) {
 static int stream_lane_init(StreamLane &l, bool high_priority) {
     if (!l.st) {
         int least = 0, greatest = 0;
-        if (high_priority && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest < least && !getenv("SWD_STREAM_SAME_PRIORITY"))
+        if (high_priority && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest < least)
             SWD_HIP(hipStreamCreateWithPriority(&l.st, hipStreamNonBlocking, greatest));
         else SWD_HIP(hipStreamCreateWithFlags(&l.st, hipStreamNonBlocking));
     }
@@ -800,11 +799,9 @@ static int pipeline_decode_host(Plan *d, int32_t B, const uint8_t *det, uint8_t 
                                 int32_t *shot_result, int packed) {
     std::lock_guard<std::recursive_mutex> lk(d->mu);
     SWD_HIP(hipSetDevice(d->device));
-    static const int split_min = getenv("SWD_HOST_SPLIT_MIN") ? atoi(getenv("SWD_HOST_SPLIT_MIN")) : 2048; // shots from which a call is cut
     // (measured, 4096 shots of the headline workload, OSD-CS 10: one part 13.8 ms per call, two 17.5, four 22.1, eight 27.1 -- a launch of
     // 1024 shots is bound by its longest shot's chain of eleven windows, not by the device; only calls of 16384 shots and more are cut)
-    static const int want_parts = getenv("SWD_HOST_PARTS") ? std::max(1, atoi(getenv("SWD_HOST_PARTS"))) : 0;
-    int parts = want_parts ? ((B >= split_min) ? want_parts : 1) : std::max(1, B / 8192);
+    int parts = std::max(1, B / 8192);
     while (parts > 1 && B / parts < 512) --parts; // (a part keeps the device busy)
     const int per = (B + parts - 1) / parts;
     if (!d->hstream || d->hstream->max_shots < per) {
@@ -983,7 +980,7 @@ extern "C" swd_gdg *swd_gdg_create(const swd_graph_desc *g, const swd_gdg_params
     d->kind = gp->mode + 1;
     d->p.pre_max_iter = gp->max_iter; d->p.osd_order = -1; d->p.ms_scaling_factor = gp->ms_scaling_factor;
     std::map<std::string, std::shared_ptr<Graph>> cache;
-    if (getenv("SWD_FORCE_HUGE") /* tests: the general form on graphs a variant would take */ || d->add_window(g, 0, 0, 0, cache) || d->finalize(nullptr)) {
+    if (env::on(env::FORCE_HUGE) /* tests: the general form on graphs a variant would take */ || d->add_window(g, 0, 0, 0, cache) || d->finalize(nullptr)) {
         // no kernel variant takes this graph: the guessing decoders' general form, every array in HBM (swd_huge_gdg.hip)
         d->wins.clear();
         d->huge.reset(huge_gdg_create(g, gp, device));

@@ -376,7 +376,7 @@ struct Plan {
             }
             // (... and a tree of at most SWD_GDG_SLOTS snapshots: deeper trees take the serial walk)
             gdg_parallel = kind == 1 && gp.multi_thread != 1 && max_guess <= SWD_GDG_SLOTS && gp.max_side_branch_step <= SWD_GDG_MAXSTEP && gp.max_step < 200 && gp.max_side_depth < 200 &&
-                           wins.size() <= SWD_GDG_ITEM_MAX_WINDOWS && !getenv("SWD_GDG_SERIAL");
+                           wins.size() <= SWD_GDG_ITEM_MAX_WINDOWS && !env::on(env::GDG_SERIAL);
             for (auto &w : wins) new_n_max = std::max(new_n_max, w.new_n);
             size_snapshots();
         }
@@ -445,7 +445,7 @@ struct Plan {
             if (fit) depth = dp;
         }
         layout_graphs(lmax);
-        post_depth2 = kind != 0 && !getenv("SWD_GDG_NO_DEPTH2");
+        post_depth2 = kind != 0;
         for (auto &w : wins) post_depth2 = post_depth2 && w.new_n <= 2 * nt;
         return 0;
     }
@@ -550,10 +550,9 @@ int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
         while (per_cu > 1 && (long long)per_cu * align_up(d->lds_total, 1280) > 160 * 1024) --per_cu;
         slots[d->device & 63] = std::max(1, per_cu) * std::max(1, cus);
         slots_lds[d->device & 63] = d->lds_total;
-        if (getenv("SWD_DEBUG")) fprintf(stderr, "[swd] pipeline_kernel<%d,%d,%d,%d,%d>%s: %d workgroups per CU x %d CUs, %d B LDS\n", NT, VF, DM, KG, KIND, PROF::on ? " depth profile" : "", per_cu, cus, d->lds_total);
     }
     const long long units = (long long)a.B * a.W;
-    static const int grid_pct = getenv("SWD_GRID_PCT") ? std::max(1, atoi(getenv("SWD_GRID_PCT"))) : 100; // diagnostics: how does the launch scale with the workgroups per CU?
+    const int grid_pct = env::num(env::GRID_PCT, 100, 1); // diagnostics: how does the launch scale with the workgroups per CU?
     const unsigned grid = (unsigned)std::min<long long>(units, std::max(1, slots[d->device & 63] * grid_pct / 100));
     if constexpr (KIND == 7) {
         // The threaded ensemble on the work-item ring (sliding-window launches): UNIT items (a window is queued when its predecessor has
@@ -565,9 +564,9 @@ int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
         // (a stream object's batches of 3072 shots or more: tickets, every thread body on the unit's workgroup -- the ring's workgroups poll
         // until the launch ends, the ticket-scheduled ones leave their slots to the next batch: 64 hypotheses, 4096 shots per batch 77.9 ->
         // 75.7 ms per step, 16 384 shots 0.62 -> 0.68 M windows/s; one launch at a time the ring wins, 80 against 119 ms)
-        if (!BIG && a.W > 1 && a.B < SWD_GDG_ITEM_MAX_SHOTS && a.W <= SWD_GDG_ITEM_MAX_WINDOWS && !getenv("SWD_ENS_TICKETS") && !d->stream_serial) {
+        if (!BIG && a.W > 1 && a.B < SWD_GDG_ITEM_MAX_SHOTS && a.W <= SWD_GDG_ITEM_MAX_WINDOWS && !env::on(env::ENS_TICKETS) && !d->stream_serial) {
             a.slot_scratch = 1;
-            const bool tasks = Dp >= 1 && !getenv("SWD_ENS_NO_TASKS");
+            const bool tasks = Dp >= 1 && !env::on(env::ENS_NO_TASKS);
             unsigned nctx = 64;
             while (nctx < 2 * grid) nctx <<= 1;
             const int nh = 1 + ((1 << Dp) - 1) + NS, nforks = Dp >= 1 ? (1 << (Dp - 1)) : 0;
@@ -611,16 +610,15 @@ int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
     }
     if constexpr (KIND == 2) { // work-item ring + contexts of parked trees (swd_gdg_kernel.h); items need per-workgroup scratch
         a.slot_scratch = 1;
-        static const int inflight = getenv("SWD_GDG_INFLIGHT") ? std::max(1, atoi(getenv("SWD_GDG_INFLIGHT"))) : 4; // (4096 shots: 3, 4: 1.202 M windows/s; 6: 1.191; 8: 1.179; 12: 1.175 -- every branch is queued anyway while workgroups wait)
+        const int inflight = env::num(env::GDG_INFLIGHT, 4, 1); // (4096 shots: 3, 4: 1.202 M windows/s; 6: 1.191; 8: 1.179; 12: 1.175 -- every branch is queued anyway while workgroups wait)
         unsigned nctx = 64;
-        static const unsigned nctx_mult = getenv("SWD_GDG_NCTX_MULT") ? (unsigned)std::max(1, atoi(getenv("SWD_GDG_NCTX_MULT"))) : 2u; // diagnostics
-        while (nctx < nctx_mult * grid) nctx <<= 1;
+        while (nctx < 2u * grid) nctx <<= 1;
         // shots admitted at a time, in percent of the workgroups of the grid (a finished shot admits the next): every queued item
         // waits behind the whole ring, so a shot's chain of dependent items (unit -> side branches -> final -> next window)
         // finishes the sooner the fewer other shots are under way -- as long as the side branches keep the grid busy
         // (measured, [[144]] GDG windows: 2048 shots 43.1 ms at 400 %, 37.1 at 100 %, 36.2 at 75 %, 39.6 at 50 %, 65 at 25 %;
         // 4096 shots 70.8 ms at 100 %, 68.1 at 400 %)
-        static const int shots_pct_env = getenv("SWD_GDG_SHOTS_PCT") ? std::max(1, atoi(getenv("SWD_GDG_SHOTS_PCT"))) : 0;
+        const int shots_pct_env = env::num(env::GDG_SHOTS_PCT, 0, 1);
         const int shots_pct = shots_pct_env ? shots_pct_env : (a.B <= 4 * grid ? 100 : 400);
         a.gdgp.shots_inflight = (int)std::min<long long>(a.B, std::max<long long>(1, (long long)grid * shots_pct / 100));
         unsigned cap = 1024;
@@ -639,7 +637,7 @@ int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
         // most of the launch walks most trees serially (no speculative branches, no queue traffic) and spreads only a few at a time
         // (measured, [[144]] GDG windows, ms per launch with 16 / 64 / 256 / all contexts: 256 shots 10.7 / 9.2 / 8.0 / 8.1, 1024 shots
         // 16.2 / 15.0 / 14.0 / 13.4, 2048 shots 25.1 / 24.0 / 24.0 / 22.9, 4096 shots 36.5 / 36.5 / 37.3 / 38.7; profiles/r06_gdg_stream.log)
-        const unsigned navail = getenv("SWD_GDG_NCTX") ? std::min<unsigned>(nctx, (unsigned)atoi(getenv("SWD_GDG_NCTX"))) : (a.B > 3072 ? std::min(nctx, 64u) : nctx);
+        const unsigned navail = a.B > 3072 ? std::min(nctx, 64u) : nctx;
         if (sl.gfree_n != (int)nctx || sl.gfree_avail != (int)navail) { // template of the free ring: ids 0..navail-1 in order
             std::vector<uint64_t> tmpl(2 + nctx, 0);
             tmpl[0] = (uint64_t)navail << 32; tmpl[1] = 0; // head 0, tail = contexts available
@@ -653,10 +651,9 @@ int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
         a.gdgp.fq = sl.gfq.as<uint32_t>(); a.gdgp.fmask = nctx - 1;
         a.gdgp.ctx = sl.gctx.as<uint8_t>(); a.gdgp.csnap = sl.gsnap.as<uint8_t>();
         a.gdgp.ensemble = d->gp.multi_thread == 2 ? 1 : 0;
-        static const bool adaptive = !(getenv("SWD_GDG_ADAPTIVE") && atoi(getenv("SWD_GDG_ADAPTIVE")) == 0);
-        a.gdgp.inflight_max = adaptive ? inflight : -inflight;
+        a.gdgp.inflight_max = inflight; // (the kernel's negative form -- the bound kept even while workgroups wait -- has no host entry left)
         a.gdgp.nctx = (int)nctx; a.gdgp.chk_status = d->status.as<uint32_t>();
-        a.gdgp.static_bound = getenv("SWD_GDG_STATIC_BOUND") ? 1 : 0;
+        a.gdgp.static_bound = 0; // (nor has the pruning bound frozen at launch time)
         SWD_HIP(hipMemsetAsync(a.gdgp.q, 0, qbytes, st));
         SWD_HIP(hipMemcpyAsync(a.gdgp.fq, sl.gfree_tmpl.p, fbytes, hipMemcpyDeviceToDevice, st));
     }
@@ -681,8 +678,7 @@ int launch_nt(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
     // once): [[144]] GDG windows, 4096 shots 0.79 -> 0.92 M windows/s, 2048 shots 0.71 -> 0.76 M, 16384 shots (serial form) +1.5 %.
     // The osd_window kernels gain nothing from it (their launches end with the last ROUND of windows, not with the last shots;
     // ordering that round by the weight of the last window's rows: no gain either) and keep the natural order.
-    static const int order_env = getenv("SWD_SHOT_ORDER") ? atoi(getenv("SWD_SHOT_ORDER")) : -1; // diagnostics: 0 off, 1 on for every kernel kind
-    const bool want_order = order_env >= 0 ? order_env != 0 : (KIND == 1 || KIND == 2 || KIND == 7);
+    const bool want_order = KIND == 1 || KIND == 2 || KIND == 7;
     a.order = nullptr;
     if (want_order && a.W > 1 && (unsigned)a.B > grid && a.det) {
         if (d->cur->order.reserve((size_t)a.B * 8)) return -1;
