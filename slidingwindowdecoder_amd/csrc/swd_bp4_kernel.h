@@ -58,20 +58,15 @@ struct SwdBp4Args {
 
 namespace swd {
 
-#ifdef SWD_BP4_CALLS
-#define SWD_BP4_FN __device__ __attribute__((noinline))
-#else
-#define SWD_BP4_FN __device__ __forceinline__
-#endif
 // (bpgd.cpp:399-416.  Written without branches: the reference's two cases of each routine differ in the ARGUMENT of one and the same
 // evaluation, so a lane selects the argument, evaluates once and selects the result -- the same operations on the same values per
 // lane, and a wave whose lanes disagree about the case no longer walks both inlined copies of exp / log1p, four per logaddexp.)
-SWD_BP4_FN double bp4_log1pexp(double x, const uint64_t *tab = nullptr) {
+__device__ __forceinline__ double bp4_log1pexp(double x, const uint64_t *tab = nullptr) {
     const bool big = x > 36.04365338911715; // -log(DBL_EPSILON)
     const double r = swd_log1p(swd_exp_from(big ? -x : x, tab));
     return big ? x + r : r;
 }
-SWD_BP4_FN double bp4_logaddexp(double x, double y, const uint64_t *tab = nullptr) {
+__device__ __forceinline__ double bp4_logaddexp(double x, double y, const uint64_t *tab = nullptr) {
     const double tmp = x - y;
     const bool gt = tmp > 0, le = tmp <= 0;
     const double r = (gt ? x : y) + bp4_log1pexp(gt ? -tmp : tmp, tab);
@@ -142,9 +137,6 @@ __device__ __forceinline__ void bp4_skew(int skew) {
         for (int i = 0; i < 8; ++i) __builtin_amdgcn_s_sleep(127);
 }
 
-#ifndef SWD_BP4_OWN_CHECK
-#define SWD_BP4_OWN_CHECK 1
-#endif
 // one check of the plain min-sum CN pass (bp4_osd.pyx:483-529): true when its parity word was still set
 __device__ __forceinline__ bool bp4_cn_one(double *msg, const uint16_t *jptr, const int8_t *cn, uint32_t *par, int l, int deg, int it, double alpha) {
     bool unsat = false;
@@ -211,26 +203,20 @@ __device__ __forceinline__ bool bp4_cn_pass(int nthreads, const SwdGraphDev &g, 
     return unsat;
 }
 
-#ifndef SWD_BP4_ROLLED
-#define SWD_BP4_ROLLED 1 // the variable-node update's per-edge loops as loops (one helper body per basis; SHYPS r = 3 +10 %, the BB codes unchanged, half the compile time)
-#endif
-#ifndef SWD_BP4_LAZY_MSG
-#define SWD_BP4_LAZY_MSG 1 // the node update's message half runs only when another check pass follows (round 6; needs SWD_BP4_ROLLED)
-#endif
-#ifndef SWD_BP4_LAZY_ITS
-#define SWD_BP4_LAZY_ITS 3 // ... in a decode's first iterations (the iterations of the decodes that stop early)
-#endif
-#ifndef SWD_BP4_PRIO_IT
-#define SWD_BP4_PRIO_IT 3 // iteration from which a decode's waves run at raised priority (-1: never)
-#endif
-#ifndef SWD_BP4_WAVES
-// waves per SIMD the register allocation leaves room for (kernels of up to 256 / up to 512 threads).  Round 4 (static shares of the
+// LAZY instantiation (below): the node update's message half runs only when another check pass follows, in a decode's first
+// kBp4LazyIts iterations (the iterations of the decodes that stop early)
+constexpr int kBp4LazyIts = 3;
+constexpr int kBp4PrioIt = 3; // iteration from which a decode's waves run at raised priority
+// Waves per SIMD the register allocation leaves room for (__launch_bounds__ of bp4_kernel), by the most waves of a workgroup and the
+// form of the node update.  The fused form, kernels of up to 256 / up to 512 threads: five / six.  Round 4 (static shares of the
 // units): 1 / 2 / 3 / 4 / 6 / 8 -> 6.9 / 10.0 / 13.4 / 15.3 / 15.4 / 15.0 M decodes/s on [[144,12,12]].  Round 6 (ticket-scheduled units,
 // gpurun_out/r06e -> profiles/r06_bp4_codes_rate.log): 4 / 5 / 6 -> [[144]] 35.2 / 36.4 / 35.7 M, [[72]] 44.8 / 43.5 / 41.4, SHYPS r = 3
-// 26.4 / 24.8 / 23.8 (all one- to three-wave workgroups: five); [[288]] 16.9 / 19.8 / 20.2, [[360]] 15.3 / 14.6 / 15.9 (up to eight waves: six)
-#define SWD_BP4_WAVES(wmax) ((wmax) <= 4 ? 5 : 6)
-#endif
-// WMAX: the most waves a workgroup of this instantiation is launched with (4 / 8: up to 256 / 512 threads, SWD_BP4_WAVES waves per SIMD;
+// 26.4 / 24.8 / 23.8 (all one- to three-wave workgroups: five); [[288]] 16.9 / 19.8 / 20.2, [[360]] 15.3 / 14.6 / 15.9 (up to eight waves: six).
+// The LAZY form: three / four (measurements with the instantiations below).  Up to 1024 threads: one (128 registers).
+constexpr int bp4_waves_per_simd(int wmax, bool lazy) {
+    return wmax > 8 ? 1 : lazy ? (wmax <= 4 ? 3 : 4) : (wmax <= 4 ? 5 : 6);
+}
+// WMAX: the most waves a workgroup of this instantiation is launched with (4 / 8: up to 256 / 512 threads, bp4_waves_per_simd waves per SIMD;
 // 16: up to 1024 threads, 128 registers).  The workgroup size itself is a launch parameter: ceil(n / 64) waves while that is at most 16, so that every qubit has
 // a thread of its own and the node's edges / LLRs / bp_init messages stay in registers.
 // FAST (round 6): the launch of the notebooks' codes -- every qubit has a thread (n <= NT), every check of both graphs has a thread
@@ -251,14 +237,11 @@ __device__ __forceinline__ bool bp4_cn_pass(int nthreads, const SwdGraphDev &g, 
 // instantiation has, the per-edge outputs num - logaddexp(..) -- independent of each other, each reads and overwrites its own slot --
 // and their parity flips are spread over all threads.  The decided qubit of a camel run, when heavy, has no update: the spread pass
 // puts its bp_init messages back into the slots the check pass overwrote.
-#ifndef SWD_BP4_WAVES_LAZY
-#define SWD_BP4_WAVES_LAZY 3
-#endif
+// ... and the LAZY instantiation of five to eight waves for four (128 registers, 96 B; six: 80 registers, the fused form's choice): [[288]]
+// 19.6 -> 22.8 M decodes/s one launch at a time, 26.8 -> 32.0 M with two in flight; [[360]] 15.7 -> 20.7, 20.5 -> 27.7 (three waves: 15.4 / 19.9,
+// 14.1 / 18.3)
 template <int WMAX, int DM, bool FAST, bool LAZY = false, bool HEAVY = false>
-#ifndef SWD_BP4_WAVES_LAZY8
-#define SWD_BP4_WAVES_LAZY8 4 // ... and the five- to eight-wave ones for four (128 registers, 96 B; six: 80 registers, the fused form's choice): [[288]] 19.6 -> 22.8 M decodes/s one launch at a time, 26.8 -> 32.0 M with two in flight; [[360]] 15.7 -> 20.7, 20.5 -> 27.7 (three waves: 15.4 / 19.9, 14.1 / 18.3)
-#endif
-__global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? SWD_BP4_WAVES_LAZY : SWD_BP4_WAVES_LAZY8) : SWD_BP4_WAVES(WMAX)) : 1)) bp4_kernel(const SwdBp4Args a) {
+__global__ void __launch_bounds__(WMAX * 64, bp4_waves_per_simd(WMAX, LAZY)) bp4_kernel(const SwdBp4Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // glibc's exp table (swd_libm.h) in LDS: tail and scale of an entry are one aligned 16-byte read
     __shared__ __attribute__((aligned(16))) uint64_t s_exptab[256];
@@ -354,7 +337,7 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
     // of Hx and the start of Hz walked both: 2x the others, which waited for it at the barrier), and neither the pass nor the
     // reset waits for a load of the graph's tables any more.
     const int mtot = mx + mz;
-    const bool own = FAST || (SWD_BP4_OWN_CHECK && mtot <= NT);
+    const bool own = FAST || mtot <= NT;
     int o_l = -1, o_deg = 0, o_perm = 0;
     bool o_z = false;
     if (own) {
@@ -370,13 +353,9 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
     const uint16_t *const o_jp = o_z ? jpz : jpx;
     int8_t *const o_cn = o_z ? cnz : cnx;
     uint32_t *const o_par = o_z ? parz : parx;
-#ifdef SWD_BP4PROF // diagnostic build: cycles (s_memtime) per region of a decode, summed over the units of this workgroup
-    long long q_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, q0_ = clock64();
-    long long q_iters = 0, q_units = 0;
-#define BP4T(i) { const long long t_ = clock64(); q_[i] += t_ - q0_; q0_ = t_; }
-#else
-#define BP4T(i)
-#endif
+    // diagnostic build: cycles (s_memtime) per region of a decode, summed over the units of this workgroup (BP4T(i) closes region i)
+    SWD_IF_BP4PROF(long long q_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, q0_ = clock64();
+        long long q_iters = 0, q_units = 0;)
     uint32_t tk_next = 0; // (thread 0) the ticket drawn for the workgroup's next unit
     auto next_unit = [&](uint32_t tk) -> uint32_t {
         if (!a.ticket) return tk + gridDim.x;
@@ -446,7 +425,7 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
     // bp4_decode_llr (bp4_osd.pyx:444-481)
     int conv = 0, iters = 0;
     const int lane0z = (mx + mz <= NT) ? mx : 0; // Hz checks on the lanes after the Hx ones when both fit
-    // Round 6: in a decode's first SWD_BP4_LAZY_ITS iterations the variable-node update runs in two halves with the convergence test between them.  Half A is what the test and the outputs
+    // Round 6: in a decode's first kBp4LazyIts iterations the variable-node update runs in two halves with the convergence test between them.  Half A is what the test and the outputs
     // need -- sums of the check messages, the three posteriors, the hard decision, its parity flips; half B, the new bit-to-check
     // messages (a log1pexp and a logaddexp per edge: most of a decode's arithmetic), only feeds the NEXT check pass and is skipped when the
     // decode stops here -- for the notebooks' noise rates after the first update in three decodes out of four.  Outputs are those of
@@ -454,9 +433,8 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
     // A decode that is still running after those iterations is one of the few that run for long: it goes on with the fused update of
     // rounds 4-5 (two barriers per iteration instead of four; the test of an update is made by the next check pass).
     for (int it = 0; it < a.max_iter; ++it) {
-#if SWD_BP4_LAZY_MSG && SWD_BP4_ROLLED
-        if constexpr (LAZY) if (it < SWD_BP4_LAZY_ITS) {
-        if (SWD_BP4_PRIO_IT >= 0 && it == SWD_BP4_PRIO_IT) __builtin_amdgcn_s_setprio(2);
+        if constexpr (LAZY) if (it < kBp4LazyIts) {
+        if (it == kBp4PrioIt) __builtin_amdgcn_s_setprio(2);
         if (own) {
             if (o_l >= 0) (void)bp4_cn_one(o_msg, o_jp, o_cn, o_par, o_l, o_deg, 0, a.alpha);
         } else {
@@ -523,9 +501,7 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
         }
         const bool any = bp4_block_any(unsat, s, NT >> 6);
         BP4T(7)
-#ifdef SWD_BP4PROF
-        ++q_iters;
-#endif
+        SWD_IF_BP4PROF(++q_iters;)
         if (!any) { conv = 1; iters = it + 1; break; }
         if (it + 1 >= a.max_iter) break; // (the messages of the last update feed no check pass)
         if (split) bp4_skew(a.skew);
@@ -553,10 +529,9 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
         __syncthreads();
             continue;
         }
-#endif
         // a decode that is still running after a few iterations is one of the few that will run for long: its waves issue ahead of
         // the others on their SIMDs from here on (what ends a launch is the last of these decodes, not the device's throughput)
-        if (SWD_BP4_PRIO_IT >= 0 && it == SWD_BP4_PRIO_IT) __builtin_amdgcn_s_setprio(2);
+        if (it == kBp4PrioIt) __builtin_amdgcn_s_setprio(2);
         bool unsat = false;
         if (own) {
             if (o_l >= 0) unsat = bp4_cn_one(o_msg, o_jp, o_cn, o_par, o_l, o_deg, it, a.alpha);
@@ -634,28 +609,12 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
             const int bx = idx & 1, bz = idx >> 1;
             if (hsel & 1) { decx[v] = (uint8_t)bx; decz[v] = (uint8_t)bz; }
             BP4T(3) // node: message loads, sums, posteriors, decision
-#if SWD_BP4_ROLLED // one body of the edge loop for both halves (bp4_split_edges): the edge word is picked by a select chain, the message re-read from LDS
+            // one body of the edge loop for both halves (bp4_split_edges): the edge word is picked by a select chain, the message re-read from LDS
+            // (against per-edge loops unrolled per basis: SHYPS r = 3 +10 %, the BB codes unchanged, half the compile time;
+            // scripts/experiments/bp4_kernel_switches.patch)
             for (int h = (hsel & 1) ? 0 : 1; h <= ((hsel & 2) ? 1 : 0); ++h)
                 bp4_split_edges<DM>(h == 0, ex, ez, dx, dz, llrx_hx, llry_all, llrz_hz, msgx, msgz, parx, parz, h == 0 ? bz : bx, xt);
             BP4T(6) // edges: log1pexp, then logaddexp + store + parity flip each
-#else
-            const double num_hx = (hsel & 1) ? bp4_log1pexp(-1. * llrx_hx, xt) : 0.0;
-#pragma unroll
-            for (int k = 0; k < DM; ++k)
-                if (k < dx && (hsel & 1)) {
-                    const double aa = llrz_hz - cx[k], bb = llry_all - cx[k];
-                    msgx[swd_edge_slot(ex[k])] = num_hx - bp4_logaddexp(-1. * aa, -1. * bb, xt);
-                    if (bz) atomicXor(&parx[swd_edge_lane(ex[k])], 1u); // Hx * z-string
-                }
-            const double num_hz = bp4_log1pexp(-1. * llrz_hz, xt);
-#pragma unroll
-            for (int k = 0; k < DM; ++k)
-                if (k < dz && (hsel & 2)) {
-                    const double aa = llrx_hx - cz[k], bb = llry_all - cz[k];
-                    msgz[swd_edge_slot(ez[k])] = num_hz - bp4_logaddexp(-1. * aa, -1. * bb, xt);
-                    if (bx) atomicXor(&parz[swd_edge_lane(ez[k])], 1u); // Hz * x-string
-                }
-#endif
         }
         if constexpr (HEAVY) { // the spread pass: every edge of a heavy node on a thread of its own (bp4_osd.pyx:571-589, as bp4_split_edges)
             __syncthreads(); // the heavy nodes' sums and decisions are in LDS; nothing has overwritten their check messages yet
@@ -679,11 +638,9 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
         }
         __syncthreads();
         BP4T(7) // barrier behind the node pass
-#ifdef SWD_BP4PROF
-        ++q_iters;
-#endif
+        SWD_IF_BP4PROF(++q_iters;)
         }
-    if (SWD_BP4_PRIO_IT >= 0) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     // the next unit's ticket: drawn as soon as this decode's iterations are over, so that the atomic's round trip overlaps the stores below
     if (a.ticket && tid == 0) tk_next = gridDim.x + atomicAdd(a.ticket, 1u);
     if (!conv) {
@@ -735,15 +692,11 @@ __global__ void __launch_bounds__(WMAX * 64, (WMAX <= 8 ? (LAZY ? (WMAX <= 4 ? S
         st[1] = iters; st[2] = iters; st[3] = 0; st[4] = n; st[5] = mx + mz; st[6] = gx.E + gz.E; st[7] = 0;
     }
     BP4T(8) // exit test, result stores
-#ifdef SWD_BP4PROF
-    ++q_units;
-#endif
+    SWD_IF_BP4PROF(++q_units;)
     } // next unit
-#ifdef SWD_BP4PROF
-    if ((tid & 63) == 0 && (blockIdx.x % 97) == 0)
-        printf("bp4prof block %d wave %d: units %lld node passes %lld | reset+init %lld | check passes %lld | flags+barrier %lld | node head %lld | log1pexp x2 %lld | Hx edges %lld | Hz edges %lld | end barrier %lld | tail %lld cycles\n",
-               (int)blockIdx.x, tid >> 6, q_units, q_iters, q_[0], q_[1], q_[2], q_[3], q_[4], q_[5], q_[6], q_[7], q_[8]);
-#endif
+    SWD_IF_BP4PROF(if ((tid & 63) == 0 && (blockIdx.x % 97) == 0)
+            printf("bp4prof block %d wave %d: units %lld node passes %lld | reset+init %lld | check passes %lld | flags+barrier %lld | node head %lld | log1pexp x2 %lld | Hx edges %lld | Hz edges %lld | end barrier %lld | tail %lld cycles\n",
+                   (int)blockIdx.x, tid >> 6, q_units, q_iters, q_[0], q_[1], q_[2], q_[3], q_[4], q_[5], q_[6], q_[7], q_[8]);)
 }
 
 // The decodes the BP kernel queued (bp4_osd.pyx:212-219: osd('x') and osd('z') when BP did not converge), one per workgroup at a time:

@@ -91,24 +91,6 @@ __device__ __forceinline__ GdgCtx gdg_ctx(const SwdGdgPar &gp, int id) {
 }
 __device__ __forceinline__ uint32_t *gdg_rec(const GdgCtx &c, int slot) { return c.rec + slot * (SWD_GDG_REC_BYTES / 4); }
 
-#ifdef SWD_GDG_DEBUG // diagnostic build: counters in the decoder's status array (words 1..)
-#define GDG_COUNT(word, v) atomicAdd(&dbg_status[word], (uint32_t)(v))
-#else
-#define GDG_COUNT(word, v) do { } while (0)
-#endif
-#ifdef SWD_SELPROF // diagnostic build: 100 MHz ticks inside select_vn / the cache rebuild, summed per unit in s.scal[20..27]
-#define SEL_T0() long long sel_t_ = wall_clock64()
-#define SEL_T(k) do { const long long sel_n_ = wall_clock64(); if (threadIdx.x == 0) s.scal[20 + (k)] += (int)(sel_n_ - sel_t_); sel_t_ = sel_n_; } while (0)
-#else
-#define SEL_T0() do { } while (0)
-#define SEL_T(k) do { } while (0)
-#endif
-#ifdef SWD_GDG_CHECKS // diagnostic build: invariant violations are reported in the status word (bits 8..) instead of followed
-#define GDG_CHECK(cond, code) do { if (!(cond)) atomicOr(chk_status, 1u << (8 + (code))); } while (0)
-#else
-#define GDG_CHECK(cond, code) do { } while (0)
-#endif
-
 // multi-producer multi-consumer ring: r[0] head, r[1] tail, r[2], r[3] free for the user, then (sequence << 32 | payload)
 __device__ __forceinline__ void ring_push(uint32_t *r, uint32_t mask, uint32_t payload) { // one thread
     const uint32_t t = atomicAdd(&r[1], 1u);
@@ -367,9 +349,7 @@ __device__ __forceinline__ int gdg_build_caches(const SwdGraphDev &g, Lds &s, co
     __syncthreads();
     SEL_T(5);
     vn_cache_load<NT, VF, DM, false>(g, s, nlive, vc);
-#ifdef SWD_SELPROF
-    asm volatile("" : "+v"(vc.edp[0][0]), "+v"(vc.llr[0]));
-#endif
+    SWD_IF_SELPROF(asm volatile("" : "+v"(vc.edp[0][0]), "+v"(vc.llr[0]));)
     SEL_T(6);
     gdg_cn_cache_from_mask<NT>(g, s, mp, cn);
     __syncthreads();
@@ -760,9 +740,7 @@ __device__ __forceinline__ bool gdg_sched_step(const SwdGdgPar &gp, const SwdDec
     int launched = (int)ag_ld(&h[18]);
     unsigned long long lmask = (unsigned long long)ag_ld(&h[20]) | ((unsigned long long)ag_ld(&h[21]) << 32);
     const int finalp = (int)ag_ld(&h[22]), mcd0 = (int)ag_ld(&h[23]);
-#ifdef SWD_GDG_CHECKS
-    uint32_t *chk_status = gp.chk_status;
-#endif
+    SWD_IF_GDG_CHECKS(uint32_t *chk_status = gp.chk_status;)
     GDG_CHECK(!finalp, 0);                                  // scheduler run after the FINAL item was queued
     GDG_CHECK(nseq >= 0 && nseq <= SWD_GDG_SLOTS && i >= 0 && i <= nseq, 1);
     GDG_CHECK(launched >= (int)ag_ld(&h[19]), 2);
@@ -861,20 +839,16 @@ __device__ __forceinline__ void gdg_run_task(const SwdPipeArgs &a, char *smem, u
     const int tid = threadIdx.x;
     const SwdGdgPar &gp = a.gdgp;
     const int ctxid = (int)((payload >> 8) & 0x3FFFFFu), slot = (int)(payload & 0xFFu);
-#ifdef SWD_GDG_DEBUG
-    uint32_t *dbg_status = gp.chk_status;
-    const long long dbg_t0 = wall_clock64();
-#endif
+    SWD_IF_GDG_DEBUG(uint32_t *dbg_status = gp.chk_status;
+        const long long dbg_t0 = wall_clock64();)
     GdgSpec sp;
     sp.ctx = gdg_ctx(gp, ctxid);
-#ifdef SWD_GDG_CHECKS
-    uint32_t *chk_status = gp.chk_status;
-    GDG_CHECK(ctxid >= 0 && ctxid < gp.nctx && slot < SWD_GDG_SLOTS, 5);
-    GDG_CHECK(ag_ld(&sp.ctx.hdr[1]) == 1u, 6);             // the context is owned by a parked tree
-    GDG_CHECK((int)ag_ld(&sp.ctx.hdr[4]) < a.W && (int)ag_ld(&sp.ctx.hdr[5]) < a.B, 7);
-    GDG_CHECK((ag_ld(&gdg_rec(sp.ctx, slot)[1]) & 2u) == 0u, 8); // this branch has not run before
-    if (!(ctxid >= 0 && ctxid < gp.nctx && slot < SWD_GDG_SLOTS && (int)ag_ld(&sp.ctx.hdr[4]) < a.W)) return;
-#endif
+    SWD_IF_GDG_CHECKS(uint32_t *chk_status = gp.chk_status;
+        GDG_CHECK(ctxid >= 0 && ctxid < gp.nctx && slot < SWD_GDG_SLOTS, 5);
+        GDG_CHECK(ag_ld(&sp.ctx.hdr[1]) == 1u, 6);             // the context is owned by a parked tree
+        GDG_CHECK((int)ag_ld(&sp.ctx.hdr[4]) < a.W && (int)ag_ld(&sp.ctx.hdr[5]) < a.B, 7);
+        GDG_CHECK((ag_ld(&gdg_rec(sp.ctx, slot)[1]) & 2u) == 0u, 8); // this branch has not run before
+        if (!(ctxid >= 0 && ctxid < gp.nctx && slot < SWD_GDG_SLOTS && (int)ag_ld(&sp.ctx.hdr[4]) < a.W)) return;)
     const int wi = (int)ag_ld(&sp.ctx.hdr[4]);
     const bool dead_unsat = ag_ld(&sp.ctx.hdr[6]) != 0u;
     const SwdWindowDev &w = a.wins[wi];
@@ -970,13 +944,9 @@ __device__ __forceinline__ void gdg_run_task(const SwdPipeArgs &a, char *smem, u
     if (tid == 0) {
         ag_st(&rec[1], (start_failed ? 1u : 0u) | 2u | (pruned ? 4u : 0u) | ((uint32_t)nsteps << 8) | ((uint32_t)(conv_step + 1) << 16));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // ... before the record reads "done"
-#ifdef SWD_GDG_DEBUG
-        const long long dbg_t1 = wall_clock64();
-#endif
+        SWD_IF_GDG_DEBUG(const long long dbg_t1 = wall_clock64();)
         gdg_sched(gp, P, sp.ctx, ctxid, true);
-#ifdef SWD_GDG_DEBUG
-        GDG_COUNT(1, 1); GDG_COUNT(2, dbg_t1 - dbg_t0); GDG_COUNT(3, wall_clock64() - dbg_t1); GDG_COUNT(4, nsteps); GDG_COUNT(5, pruned ? 1 : 0);
-#endif
+        SWD_IF_GDG_DEBUG(GDG_COUNT(1, 1); GDG_COUNT(2, dbg_t1 - dbg_t0); GDG_COUNT(3, wall_clock64() - dbg_t1); GDG_COUNT(4, nsteps); GDG_COUNT(5, pruned ? 1 : 0);)
     }
     __syncthreads();
 }
@@ -1183,12 +1153,7 @@ __device__ __forceinline__ void gdg_ensemble_tree(int ROLE, const SwdGraphDev *g
     bool saved = false;                  // tree thread on its own: masks saved at depth D
     double own_pm = 10000.0;
     int bk_pos = NONE, bk_val = 0;
-#ifdef SWD_GDGPROF
-    long long gp_t_ = wall_clock64();
-#define EPT(k) do { const long long gp_n_ = wall_clock64(); R.gp[k] += gp_n_ - gp_t_; gp_t_ = gp_n_; } while (0)
-#else
-#define EPT(k) do { } while (0)
-#endif
+    GPT0();
     R.post_it = (ROLE == 0) ? R.post_it : 0;
     const int nforks = Dp >= 1 ? (1 << (Dp - 1)) : 0;
     if (ROLE == 2 && task_p <= T) { // tree thread task_p: from the fork at depth D - 1 above it, through the child its last direction bit names
@@ -1210,7 +1175,7 @@ __device__ __forceinline__ void gdg_ensemble_tree(int ROLE, const SwdGraphDev *g
         }
     };
     for (;;) {
-        EPT(4);
+        GPT(4);
         if (ROLE == 2 && (adv == ADV_LEAF || adv == ADV_SIDE)) break; // the thread's walk is over
         if (want_main_end) { // the vector returned if nothing converges (bpgd.cpp:677-682)
             if (!main_conv) { gdg_store_err<NT>(s, G, new_n, ROLE == 1 ? (uint32_t *)(ec->vec + (int64_t)ec->nh * ec->vecb) : main_fb); ag_publish_barrier(); have_main_fb = true; }
@@ -1273,7 +1238,7 @@ __device__ __forceinline__ void gdg_ensemble_tree(int ROLE, const SwdGraphDev *g
                 continue;
             }
         }
-        EPT(3);
+        GPT(3);
         // loop bounds of the thread bodies
         if (mode == M_DESC) {
             if (p == 0 && main_alive && d >= P.max_step) { // (max_step <= D: the main thread's loop is over, the tree threads go on)
@@ -1297,10 +1262,10 @@ __device__ __forceinline__ void gdg_ensemble_tree(int ROLE, const SwdGraphDev *g
             const int nlive = gdg_caches<NT, VF, DM, KG>(g, s, G, st, vc, cn, cmap);
             if (first) { bp_init<VF, DM>(s, vc); __syncthreads(); }
             first = false;
-            EPT(0);
+            GPT(0);
             cv = bp_run<NT, VF, DM, KG, false, false, false, !std::is_same_v<ST, GdgNoStatic>>(g, P, s, P.max_iter_per_step, nlive, vc, cn, hist_b, it, P.gdg_factor, dead_unsat, nullptr, h4, with_main);
             blocks += share; R.post_it += it * share; // counted once per thread of the ensemble that runs this block
-            EPT(1);
+            GPT(1);
         }
         // ... the scan (the main thread scans BEFORE its convergence test, bpgd.cpp:630-633; the others only go on when the block failed)
         double pm_t = 0.0;
@@ -1318,7 +1283,7 @@ __device__ __forceinline__ void gdg_ensemble_tree(int ROLE, const SwdGraphDev *g
             const bool sidethr = !(mode == M_MAIN || (desc && p == 0)); // thresholds (0, -10) once an unfavoured branch has been taken
             rc = gdg_select_core<NT>(g, P, s, G, hist_b, sidethr ? 0.0 : -3.0, sidethr ? -10.0 : (d == 0 ? -16.0 : -12.0), d, gpos, favor, st, h4);
         }
-        EPT(2);
+        GPT(2);
         if (cv) { // ---- a converged block: the strict-< offers, in the order main, tree threads by id, side threads
             const double pm = gdg_get_pm<NT>(g, s, G);
             int who = 0, count = 1;
@@ -1466,17 +1431,6 @@ __device__ __forceinline__ void gdg_ens_finalize(const SwdGraphDev &g, const Swd
     R.live_vn = 1 + T + (int)ag_ld(&c.hdr[10]); R.live_cn = (int)ag_ld(&c.hdr[8]); R.live_e = winner; R.osd_rowadds = ties;
 }
 
-// bpgdg_decoder.decode / bpgd_decoder.decode / bp_history_decoder for one syndrome.  On return
-// s.hard[0..n) is the returned vector.
-// par != nullptr (parallel form): a tree with side branches is parked in a context and its side branches are queued;
-// then R.exit_class = -2 on return and the result arrives later as a FINAL item (gdg_finalize).
-#ifdef SWD_GDGPROF // diagnostic build (scripts/gdg_phase_profile.py): 100 MHz ticks per kind of work inside a tree walk
-#define GPT0() long long gp_t_ = wall_clock64()
-#define GPT(k) do { const long long gp_n_ = wall_clock64(); R.gp[k] += gp_n_ - gp_t_; gp_t_ = gp_n_; } while (0)
-#else
-#define GPT0() do { } while (0)
-#define GPT(k) do { } while (0)
-#endif
 // The window's edge columns (row_col) and check order (perm) staged in LDS, in the slot-list region the guessing decoders no
 // longer use: the reset after the sort chases slot -> column for every position of every check and the peeling sweeps look both
 // up for every check they fire -- from L2 that was one memory latency per look-up.  gl: the graph descriptor the tree walk uses
@@ -1498,6 +1452,10 @@ __device__ __forceinline__ void gdg_staged_graph(SwdGraphDev &gl, const SwdGraph
     if ((Ee + g.m) * 2 <= g.K * g.m * 2) { gl.row_col = s.lslot; gl.perm = s.lslot + Ee; }
 }
 
+// bpgdg_decoder.decode / bpgd_decoder.decode / bp_history_decoder for one syndrome.  On return
+// s.hard[0..n) is the returned vector.
+// par != nullptr (parallel form): a tree with side branches is parked in a context and its side branches are queued;
+// then R.exit_class = -2 on return and the result arrives later as a FINAL item (gdg_finalize).
 // ENS (kernel kind 7): bpgdg_decoder(multi_thread=True) -- the post-processing is the reference's threaded ensemble
 // (gdg_ensemble_tree, run by the caller) instead of gdg()'s tree walk.
 template <int NT, int VF, int DM, int KG, bool ENS = false, int VFP = VF>
@@ -1511,9 +1469,7 @@ __device__ __forceinline__ void decode_window_gdg(const SwdGraphDev &g_in, const
     gdg_bind(G, gdg_lds_base(s, L), L, n, new_n);
 #pragma unroll
     for (int i = 0; i < 9; ++i) R.t[i] = 0;
-#ifdef SWD_GDGPROF
-    for (int i = 0; i < 5; ++i) R.gp[i] = 0;
-#endif
+    SWD_IF_GDGPROF(for (int i = 0; i < 5; ++i) R.gp[i] = 0;)
     R.t[0] = wall_clock64();
     for (int l = tid; l < m; l += NT) {
         const int d = g.row_deg[l];
@@ -1660,14 +1616,12 @@ __device__ __forceinline__ void decode_window_gdg(const SwdGraphDev &g_in, const
         __syncthreads();
         ctxid = (int)acc[1];
         if (ctxid >= 0) { ctx = gdg_ctx(par->gdgp, ctxid); snap_b = ctx.snap; }
-#ifdef SWD_GDG_CHECKS
-        if (ctxid >= 0 && tid == 0) {
+        SWD_IF_GDG_CHECKS(if (ctxid >= 0 && tid == 0) {
             uint32_t *chk_status = par->gdgp.chk_status;
             GDG_CHECK(ctxid < par->gdgp.nctx, 13);
             const uint32_t st = atomicExch(&ctx.hdr[1], 3u);
             GDG_CHECK(st != 1u && st != 3u, 14); // a context handed out while a parked tree or another main branch owns it
-        }
-#endif
+        })
     }
     // ---- phase 1: main branch
     GPT0();
@@ -1784,9 +1738,7 @@ __device__ __forceinline__ void decode_window_gdg(const SwdGraphDev &g_in, const
         for (int j = tid; j < new_n; j += NT) s.hard[G.pos_lv[j]] = G.best_err[j];
         __syncthreads();
     }
-#ifdef SWD_GDG_CHECKS
-    if (ctxid >= 0 && tid == 0) { uint32_t *chk_status = par->gdgp.chk_status; GDG_CHECK(atomicExch(&ctx.hdr[1], 0u) == 3u, 15); }
-#endif
+    SWD_IF_GDG_CHECKS(if (ctxid >= 0 && tid == 0) { uint32_t *chk_status = par->gdgp.chk_status; GDG_CHECK(atomicExch(&ctx.hdr[1], 0u) == 3u, 15); })
     if (ctxid >= 0 && tid == 0) ring_push(par->gdgp.fq, par->gdgp.fmask, (uint32_t)ctxid); // walked here after all: the context goes back
     R.conv = converge; R.pm = min_pm; R.total_it = R.pre_it + R.post_it;
     R.live_vn = used_guess; R.live_cn = blocks; R.live_e = min_converge_depth;

@@ -13,12 +13,12 @@
 
 #include "swd.h"
 #include "swd_graph.h"
+#include "swd_diag.h"
 
 #define SWD_DMAX 10 // largest column degree any kernel variant of this build supports
 
-// Build switches of this header -- every preprocessor conditional below tests one of these (DESIGN.md section 4 has the same table),
-// apart from five experiment switches whose folding changes the emitted code and which therefore stay for now, each where it is
-// used: SWD_POST_SORTED, SWD_POST_KGP (below), SWD_BIG_TBL, SWD_BIG_REC (in front of the OSD), SWD_QUAD_LAZY (osd0_quad).
+// Build switches of this header -- every preprocessor conditional below tests one of the ten named here (DESIGN.md section 4 has the
+// table of all build switches; tests/test_build_switches.py holds both to the source).
 // Per translation unit (swd_kernels_k0 / k3 set them; the host reads SWD_TUNED_NT):
 //   SWD_OSDW_TUNED       the osd_window kernels of up to SWD_TUNED_NT threads keep the BP register caches packed (VnCache / CnCache,
 //                        P16) and -- variants with at most twelve groups of check positions -- are built for three waves per SIMD
@@ -28,14 +28,14 @@
 //                        occupancy API accepts: scripts/residency_check.py)
 //   SWD_TUNED_NT         largest workgroup of the tuned osd_window kernels (16-bit LDS offsets, LDS diet); the host uses the same bound
 //   SWD_POST_DEPTH2      the shortened graph's register cache of the [[288,12,18]] variants (swd_kernels_k0 / k3)
-// Development variant lists (swd_variants.h, scripts/devbuild.sh): SWD_HEADLINE_ONLY, SWD_BB288_ONLY, SWD_V7816_ONLY
-// Diagnostic builds (scripts/*_profile.py, *_timeline.py, gdg_debug.py, residency_check.py read what they record; SWD_OSDPROF and
-// SWD_GDG_CHECKS have no script of their own):
-//   SWD_BPPROF  SWD_OSDPROF  SWD_INITPROF  SWD_SHPROF  SWD_TSPROF  SWD_SELPROF  SWD_GDGPROF   cycle counters of a phase
-//   SWD_GDG_DEBUG  SWD_GDG_CHECKS   checksums / invariant checks of the guessing decoders
-//   SWD_RESIDENCY                   resident workgroups per launch
+// Five experiment switches whose folding changes the emitted code and which therefore stay for now, each where it is used:
+//   SWD_POST_SORTED  SWD_POST_KGP (below)   SWD_BIG_TBL  SWD_BIG_REC (in front of the OSD)   SWD_QUAD_LAZY (osd0_quad)
 // A/B builds of the structurizer flag (Makefile, STRUCT_FLAG; docs/history/DESIGN_rounds_1-5.md section 8):
 //   SWD_NO_SCALAR_ANY  SWD_NO_SCALAR_WMAX   block_any / the walk bound as vector values
+// Development variant lists are chosen in swd_variants.h (scripts/devbuild.sh): SWD_HEADLINE_ONLY, SWD_BB288_ONLY, SWD_V7816_ONLY.
+// Diagnostic builds (cycle counters of a phase, checksums and invariant checks of the guessing decoders, resident workgroups): the
+// SWD_IF_<switch>(...) lines of this header, of swd_gdg_kernel.h and of swd_bp4_kernel.h.  swd_diag.h defines them, says what each
+// switch records and which script reads it, and is the only file that tests one.
 #ifndef SWD_OSDW_TUNED
 #define SWD_OSDW_TUNED 0
 #endif
@@ -869,9 +869,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
     // VNs this wave walks (wave-uniform): entries vtid + i*NT < vcnt for some lane
     const int wbase = s.vtid & ~63;
     const int nch = __builtin_amdgcn_readfirstlane((vcnt > wbase) ? min(VF, (vcnt - wbase + NT - 1) / NT) : 0);
-#ifdef SWD_BPPROF
-    if (!FULL && (tid & 63) == 0) ((uint8_t *)&s.scal[28])[tid >> 6] = (uint8_t)wmax;
-#endif
+    SWD_IF_BPPROF(if (!FULL && (tid & 63) == 0) ((uint8_t *)&s.scal[28])[tid >> 6] = (uint8_t)wmax;)
     swd_msg_st<HYB>(s, (uint32_t)farslot << 3, 64.0);
     swd_msg_st<HYB>(s, (uint32_t)zeroslot << 3, 0.0);
     char *const parb = (char *)s.par;
@@ -883,13 +881,8 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
 #pragma unroll
         for (int i = 0; i < VF; ++i) { const int idx = s.vtid + i * NT; vnode[i] = (idx < vcnt) ? (int)s.lv[idx] : n; }
     }
-#ifdef SWD_BPPROF
-    long long tc0, tc1, tc2, tc3;
-    long long acc_cn = 0, acc_any = 0, acc_vn = 0, acc_bar = 0;
-#define BPT(x) x = clock64()
-#else
-#define BPT(x)
-#endif
+    SWD_IF_BPPROF(long long tc0, tc1, tc2, tc3;
+        long long acc_cn = 0, acc_any = 0, acc_vn = 0, acc_bar = 0;)
     static_assert(!TBL || (FULL && !TIER && !REC && !SPARSE && !PB), "table form: the full graph of the large-graph kernels");
     static_assert(!PROF::on || (FULL && ACC && !SPARSE && !TIER && !HYB && !REC && !TBL && VF <= 32), "depth profiles: the full graph of the kind-3 kernels (no history stores, deferred hard decisions)");
     [[maybe_unused]] uint32_t tbe[3][DM]; // edge words of rows i, i + 1, i + 2 (asked for two rows ahead)
@@ -1074,10 +1067,8 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
         const bool any = __builtin_amdgcn_readfirstlane(anyr) != 0; // the same on every lane: a scalar branch
 #endif
         BPT(tc2);
-#ifdef SWD_BPPROF
-        acc_cn += tc1 - tc0; acc_any += tc2 - tc1;
-        if (it > 0 && !any && !FULL && tid == 0) { s.scal[24] += (int)acc_cn; s.scal[25] += (int)acc_any; s.scal[26] += (int)acc_vn; s.scal[27] += (int)acc_bar; }
-#endif
+        SWD_IF_BPPROF(acc_cn += tc1 - tc0; acc_any += tc2 - tc1;
+            if (it > 0 && !any && !FULL && tid == 0) { s.scal[24] += (int)acc_cn; s.scal[25] += (int)acc_any; s.scal[26] += (int)acc_vn; s.scal[27] += (int)acc_bar; })
         if (it > 0 && !any) {
             if constexpr (kHardDefer) { hard_flush(); __syncthreads(); } // (callers read other threads' decisions)
             iters_done = it;
@@ -1197,13 +1188,9 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
         vn_rows(vn_rows, std::integral_constant<int, 0>{});
         BPT(tc3);
         __syncthreads();
-#ifdef SWD_BPPROF
-        acc_vn += tc3 - tc2; acc_bar += clock64() - tc3;
-#endif
+        SWD_IF_BPPROF(acc_vn += tc3 - tc2; acc_bar += clock64() - tc3;)
     }
-#ifdef SWD_BPPROF
-    if (!FULL && tid == 0) { s.scal[24] += (int)acc_cn; s.scal[25] += (int)acc_any; s.scal[26] += (int)acc_vn; s.scal[27] += (int)acc_bar; }
-#endif
+    SWD_IF_BPPROF(if (!FULL && tid == 0) { s.scal[24] += (int)acc_cn; s.scal[25] += (int)acc_any; s.scal[26] += (int)acc_vn; s.scal[27] += (int)acc_bar; })
     hard_flush(); // (visible to the other threads behind block_any's barrier)
     bool unsat = force_unsat;
     for (int l = tid; l < m; l += NT)
@@ -1521,14 +1508,11 @@ __device__ __forceinline__ int osd0_block(const SwdGraphDev &g, Lds &s, const ui
     int *ctl = s.iaux + 8;
     uint64_t Pw = 0;                    // word w of the pivoted-row mask (replicated per column group), wave 0
     int npiv = 0, rowadds = 0, p = 0;
-#ifdef SWD_OSDPROF // diagnostic build: cycles of the pick (wave 0), the barrier waits and the row operation, per elimination
-    long long tp_ = 0, tb_ = 0, tu_ = 0, q0_, q1_, q2_, q3_;
-    int nsteps_ = 0;
-#endif
+    // diagnostic build: cycles of the pick (wave 0), the barrier waits and the row operation, per elimination
+    SWD_IF_OSDPROF(long long tp_ = 0, tb_ = 0, tu_ = 0, q0_, q1_, q2_, q3_;
+        int nsteps_ = 0;)
     for (;;) {
-#ifdef SWD_OSDPROF
-        q0_ = clock64();
-#endif
+        SWD_IF_OSDPROF(q0_ = clock64();)
         if (tid < 64) {
             int found = 0;
             while (!found && p < n && npiv < rank) { // T only changes at a pivot: runs of dependent columns need no barrier
@@ -1575,13 +1559,9 @@ __device__ __forceinline__ int osd0_block(const SwdGraphDev &g, Lds &s, const ui
             }
             if (lane == 0) ctl[0] = found | ((p < n && npiv < rank) ? 0 : 2);
         }
-#ifdef SWD_OSDPROF
-        q1_ = clock64();
-#endif
+        SWD_IF_OSDPROF(q1_ = clock64();)
         __syncthreads();
-#ifdef SWD_OSDPROF
-        q2_ = clock64();
-#endif
+        SWD_IF_OSDPROF(q2_ = clock64();)
         const int c0 = ctl[0];
         if (c0 & 1) { // T[:, j] ^= S for every column j of T with T[r][j] = 1
             const int r = ctl[1];
@@ -1594,12 +1574,10 @@ __device__ __forceinline__ int osd0_block(const SwdGraphDev &g, Lds &s, const ui
             }
         }
         __syncthreads();
-#ifdef SWD_OSDPROF
-        q3_ = clock64();
-        tp_ += q1_ - q0_; tb_ += q2_ - q1_; tu_ += q3_ - q2_; ++nsteps_;
-        if ((c0 & 2) && (tid == 0 || tid == 512) && (blockIdx.x & 63) == 0)
-            printf("osdprof thread %d: eliminations %d  pick %lld  barrier wait %lld  row operation + barrier %lld cycles\n", tid, nsteps_, tp_, tb_, tu_);
-#endif
+        SWD_IF_OSDPROF(q3_ = clock64();
+            tp_ += q1_ - q0_; tb_ += q2_ - q1_; tu_ += q3_ - q2_; ++nsteps_;
+            if ((c0 & 2) && (tid == 0 || tid == 512) && (blockIdx.x & 63) == 0)
+                printf("osdprof thread %d: eliminations %d  pick %lld  barrier wait %lld  row operation + barrier %lld cycles\n", tid, nsteps_, tp_, tb_, tu_);)
         if (c0 & 2) break;
     }
     if (tid < 64) {
@@ -1744,15 +1722,12 @@ __device__ __forceinline__ int osd0_cols(const SwdGraphDev &g, Lds &s, const uin
     uint64_t Pmine = 0;
     int racc = 0;
     int npiv = 0, p = 0;
-#ifdef SWD_OSDPROF // diagnostic build: cycles of the resolver (evaluation, hand-over waits, pivots), of a column wave (applying, waiting) and between the barriers
-    long long q_eval = 0, q_res = 0, q_app = 0, q_wait = 0, q_sync = 0, q_hand = 0, q0_;
-    int q_rounds = 0, q_batches = 0;
-#endif
+    // diagnostic build: cycles of the resolver (evaluation, hand-over waits, pivots), of a column wave (applying, waiting) and between the barriers
+    SWD_IF_OSDPROF(long long q_eval = 0, q_res = 0, q_app = 0, q_wait = 0, q_sync = 0, q_hand = 0, q0_;
+        int q_rounds = 0, q_batches = 0;)
     for (;;) {
         const int npiv0 = npiv, p0 = p;
-#ifdef SWD_OSDPROF
-        q0_ = clock64(); ++q_rounds;
-#endif
+        SWD_IF_OSDPROF(q0_ = clock64(); ++q_rounds;)
         if (wave == 0) {
             int used = 0, nbatch = 0; // operations published this round, batches begun
             bool fin = false;
@@ -1769,10 +1744,8 @@ __device__ __forceinline__ int osd0_cols(const SwdGraphDev &g, Lds &s, const uin
                     for (int x = 0; x < WMC; ++x) red[x] = (x < wm) ? hbuf[x * NBC + lane] : 0ull;
                 }
                 bool alive = p + lane < n;
-#ifdef SWD_OSDPROF
-                if (nbatch == 0) q_eval += clock64() - q0_; else q_hand += clock64() - q0_;
-                q0_ = clock64(); ++q_batches;
-#endif
+                SWD_IF_OSDPROF(if (nbatch == 0) q_eval += clock64() - q0_; else q_hand += clock64() - q0_;
+                    q0_ = clock64(); ++q_batches;)
                 uint64_t pb[WMC]; // the pivoted-row mask, every word in every lane (read back after each pivot, ahead of its use)
 #pragma unroll
                 for (int x = 0; x < WMC; ++x) pb[x] = Pl[x];
@@ -1826,9 +1799,7 @@ __device__ __forceinline__ int osd0_cols(const SwdGraphDev &g, Lds &s, const uin
                     ++npiv; ++used;
                 }
                 p += NBC; ++nbatch;
-#ifdef SWD_OSDPROF
-                q_res += clock64() - q0_; q0_ = clock64();
-#endif
+                SWD_IF_OSDPROF(q_res += clock64() - q0_; q0_ = clock64();)
                 fin = !(p < n && npiv < rank);
                 if (fin || nbatch > NHELP || used + NBC > RING) break;
             }
@@ -1846,9 +1817,7 @@ __device__ __forceinline__ int osd0_cols(const SwdGraphDev &g, Lds &s, const uin
             for (;;) {
                 const int closed = vctl[1]; // read before the count: a closed round's count is final
                 const int avail = vctl[0];
-#ifdef SWD_OSDPROF
-                q_wait += clock64() - q0_; q0_ = clock64();
-#endif
+                SWD_IF_OSDPROF(q_wait += clock64() - q0_; q0_ = clock64();)
                 while (done_ops < avail) {
                     SWD_LDS_AS const uint64_t *ent = ringS + done_ops * ES;
                     uint64_t S[WMC];
@@ -1862,9 +1831,7 @@ __device__ __forceinline__ int osd0_cols(const SwdGraphDev &g, Lds &s, const uin
                     }
                     ++done_ops;
                 }
-#ifdef SWD_OSDPROF
-                q_app += clock64() - q0_; q0_ = clock64();
-#endif
+                SWD_IF_OSDPROF(q_app += clock64() - q0_; q0_ = clock64();)
                 if (closed) break;
                 __builtin_amdgcn_s_sleep(1);
             }
@@ -1921,12 +1888,10 @@ __device__ __forceinline__ int osd0_cols(const SwdGraphDev &g, Lds &s, const uin
         }
         if (tid < wm) Sbuf[tid] = 0ull; // (used after the last round)
         __syncthreads();
-#ifdef SWD_OSDPROF
-        q_sync += clock64() - q0_;
-        if (fin && (tid == 0 || tid == 64 || tid == 13 * 64) && (blockIdx.x & 63) == 0)
-            printf("osdprof cols2 thread %d: rounds %d batches %d pivots %d | resolver: evaluation %lld hand-over %lld resolve %lld | column wave: apply %lld wait %lld | rest of the round %lld cycles\n",
-                   tid, q_rounds, q_batches, npiv, q_eval, q_hand, q_res, q_app, q_wait, q_sync);
-#endif
+        SWD_IF_OSDPROF(q_sync += clock64() - q0_;
+            if (fin && (tid == 0 || tid == 64 || tid == 13 * 64) && (blockIdx.x & 63) == 0)
+                printf("osdprof cols2 thread %d: rounds %d batches %d pivots %d | resolver: evaluation %lld hand-over %lld resolve %lld | column wave: apply %lld wait %lld | rest of the round %lld cycles\n",
+                       tid, q_rounds, q_batches, npiv, q_eval, q_hand, q_res, q_app, q_wait, q_sync);)
         if (fin) break;
     }
     // y = T * s (s in original row order)
@@ -1984,22 +1949,16 @@ __device__ __forceinline__ int osd0_colsw(const SwdGraphDev &g, Lds &s, const ui
     uint64_t Pmine = 0;
     int racc = 0;
     int npiv = 0, p = 0;
-#ifdef SWD_OSDPROF
-    long long q_eval = 0, q_res = 0, q_app = 0, q_wait = 0, q_sync = 0, q0_;
-    int q_batches = 0;
-#endif
+    SWD_IF_OSDPROF(long long q_eval = 0, q_res = 0, q_app = 0, q_wait = 0, q_sync = 0, q0_;
+        int q_batches = 0;)
     for (;;) {
         const int npiv0 = npiv;
         int p0 = p;
-#ifdef SWD_OSDPROF
-        q0_ = clock64(); ++q_batches;
-#endif
+        SWD_IF_OSDPROF(q0_ = clock64(); ++q_batches;)
         if (wave == 0) {
           for (;;) { // batches, until one finds a pivot (the others change nothing anybody else would have to see)
             p0 = p;
-#ifdef SWD_OSDPROF
-            q0_ = clock64();
-#endif
+            SWD_IF_OSDPROF(q0_ = clock64();)
             const int pc = p + lane;
             const bool cval = pc < n;
             int rows[DM];
@@ -2026,9 +1985,7 @@ __device__ __forceinline__ int osd0_colsw(const SwdGraphDev &g, Lds &s, const ui
             }
             bool alive = cval;
             int nb = 0, last_cs = NBC - 1; // pivots of this batch, its last pivot column
-#ifdef SWD_OSDPROF
-            q_eval += clock64() - q0_; q0_ = clock64();
-#endif
+            SWD_IF_OSDPROF(q_eval += clock64() - q0_; q0_ = clock64();)
             while (npiv < rank && nb < ring) {
                 uint32_t nz = 0; // (the pivoted-row mask is read where it is used: fifteen more registers do not fit the 128 of this kernel)
 #pragma unroll
@@ -2074,9 +2031,7 @@ __device__ __forceinline__ int osd0_colsw(const SwdGraphDev &g, Lds &s, const ui
                 ++npiv; ++nb;
             }
             p = (nb >= ring && npiv < rank) ? p0 + last_cs + 1 : p0 + NBC; // (ring full: the columns behind the last pivot are evaluated again)
-#ifdef SWD_OSDPROF
-            q_res += clock64() - q0_; q0_ = clock64();
-#endif
+            SWD_IF_OSDPROF(q_res += clock64() - q0_; q0_ = clock64();)
             if (nb > 0 || !(p < n && npiv < rank)) break;
           }
             int rsum = racc;
@@ -2093,9 +2048,7 @@ __device__ __forceinline__ int osd0_colsw(const SwdGraphDev &g, Lds &s, const ui
             for (;;) {
                 const int closed = vctl[1]; // read before the count: a closed batch's count is final
                 const int avail = vctl[0];
-#ifdef SWD_OSDPROF
-                q_wait += clock64() - q0_; q0_ = clock64();
-#endif
+                SWD_IF_OSDPROF(q_wait += clock64() - q0_; q0_ = clock64();)
                 while (done_ops < avail) {
                     SWD_LDS_AS const uint64_t *ent = ringS + done_ops * ES;
                     const int r = __builtin_amdgcn_readfirstlane((int)(uint32_t)ent[WMC]) & 0xFFFF;
@@ -2106,9 +2059,7 @@ __device__ __forceinline__ int osd0_colsw(const SwdGraphDev &g, Lds &s, const ui
                     }
                     ++done_ops;
                 }
-#ifdef SWD_OSDPROF
-                q_app += clock64() - q0_; q0_ = clock64();
-#endif
+                SWD_IF_OSDPROF(q_app += clock64() - q0_; q0_ = clock64();)
                 if (closed) break;
                 __builtin_amdgcn_s_sleep(1);
             }
@@ -2138,12 +2089,10 @@ __device__ __forceinline__ int osd0_colsw(const SwdGraphDev &g, Lds &s, const ui
         if (tid < wm) Sbuf[tid] = 0ull; // (used after the last batch)
         if (tid == 0) { ctl[0] = 0; ctl[1] = 0; } // nobody reads these two between the barriers
         __syncthreads();
-#ifdef SWD_OSDPROF
-        q_sync += clock64() - q0_;
-        if (fin && (tid == 0 || tid == 64) && (blockIdx.x & 63) == 0)
-            printf("osdprof colsw thread %d: batches %d pivots %d | resolver: evaluation %lld resolve %lld | column wave: apply %lld wait %lld | rest of the batch %lld cycles\n",
-                   tid, q_batches, npiv, q_eval, q_res, q_app, q_wait, q_sync);
-#endif
+        SWD_IF_OSDPROF(q_sync += clock64() - q0_;
+            if (fin && (tid == 0 || tid == 64) && (blockIdx.x & 63) == 0)
+                printf("osdprof colsw thread %d: batches %d pivots %d | resolver: evaluation %lld resolve %lld | column wave: apply %lld wait %lld | rest of the batch %lld cycles\n",
+                       tid, q_batches, npiv, q_eval, q_res, q_app, q_wait, q_sync);)
         if (fin) break;
     }
     // y = T * s (s in original row order)
@@ -2221,13 +2170,9 @@ __device__ __forceinline__ int osd0_wave_reg(const SwdGraphDev &g, Lds &s, const
         for (int x = 0; x < 4; ++x) t[q][x] = (x == q && q * 64 + lane < m) ? (1ull << lane) : 0ull;
     uint64_t Pw = 0;                    // word w of the pivoted-row mask (replicated per column group)
     int npiv = 0, rowadds = 0, p = 0;
-#ifdef SWD_BPPROF
-    long long acc_scan = 0, acc_upd = 0, acc_f1 = 0; int nscan = 0;
-#endif
+    SWD_IF_BPPROF(long long acc_scan = 0, acc_upd = 0, acc_f1 = 0; int nscan = 0;)
     while (p < n && npiv < rank) {
-#ifdef SWD_BPPROF
-        long long t0 = clock64(); ++nscan;
-#endif
+        SWD_IF_BPPROF(long long t0 = clock64(); ++nscan;)
         const int pc = p + c;
         const bool cval = wact && pc < n;
         int rows[DM];
@@ -2249,10 +2194,8 @@ __device__ __forceinline__ int osd0_wave_reg(const SwdGraphDev &g, Lds &s, const
         if (!cval) red = 0ull;
         uint64_t cand = red & ~Pw;
         bool found = false;
-#ifdef SWD_BPPROF
-        long long tA = clock64();
-        acc_scan += tA - t0;
-#endif
+        SWD_IF_BPPROF(long long tA = clock64();
+            acc_scan += tA - t0;)
         for (;;) {
             const unsigned long long bal = __ballot(cand != 0ull);
             if (bal == 0ull) break;
@@ -2294,13 +2237,9 @@ __device__ __forceinline__ int osd0_wave_reg(const SwdGraphDev &g, Lds &s, const
             wave_fence();
         }
         p += NB;
-#ifdef SWD_BPPROF
-        acc_upd += clock64() - tA;
-#endif
+        SWD_IF_BPPROF(acc_upd += clock64() - tA;)
     }
-#ifdef SWD_BPPROF
-    if (lane == 0) { s.scal[20] = nscan; s.scal[21] = (int)(acc_scan >> 4); s.scal[22] = (int)(acc_upd >> 4); s.scal[23] = (int)(acc_f1 >> 4); }
-#endif
+    SWD_IF_BPPROF(if (lane == 0) { s.scal[20] = nscan; s.scal[21] = (int)(acc_scan >> 4); s.scal[22] = (int)(acc_upd >> 4); s.scal[23] = (int)(acc_f1 >> 4); })
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) rowadds += __shfl_xor(rowadds, d, 64);
     // y = T * s  (s in original row order): XOR of the owned columns the syndrome selects, reduced over the wave
@@ -2383,20 +2322,14 @@ __device__ __forceinline__ int osd0_quad(const SwdGraphDev &g, Lds &s, const uin
     int npiv = 0, p = 0;
     if (tid < SWD_QUAD_RING) ring[tid].tagpos = 0ull;
     __syncthreads();
-#ifdef SWD_BPPROF
-    long long q_eval = 0, q_chain = 0, q_sync = 0, q0_ = clock64(); int q_steps = 0;
-#endif
+    SWD_IF_BPPROF(long long q_eval = 0, q_chain = 0, q_sync = 0, q0_ = clock64(); int q_steps = 0;)
     for (int gen = 1;; ++gen) {
-#ifdef SWD_BPPROF
-        if (gen > 1) q_sync += clock64() - q0_;
-#endif
+        SWD_IF_BPPROF(if (gen > 1) q_sync += clock64() - q0_;)
         if (wave == 0) {
             int used = 0;
             bool fin = false;
             for (;;) {
-#ifdef SWD_BPPROF
-                q0_ = clock64(); ++q_steps;
-#endif
+                SWD_IF_BPPROF(q0_ = clock64(); ++q_steps;)
                 const int pc = p + c;
                 const bool cval = wact && pc < n;
                 int rows[DM];
@@ -2431,9 +2364,7 @@ __device__ __forceinline__ int osd0_quad(const SwdGraphDev &g, Lds &s, const uin
                     }
                 }
                 uint64_t cand = red & U;
-#ifdef SWD_BPPROF
-                q_eval += clock64() - q0_; q0_ = clock64();
-#endif
+                SWD_IF_BPPROF(q_eval += clock64() - q0_; q0_ = clock64();)
                 for (;;) {
                     const unsigned long long bal = __ballot(cand != 0ull);
                     if (bal == 0ull) break;
@@ -2468,15 +2399,11 @@ __device__ __forceinline__ int osd0_quad(const SwdGraphDev &g, Lds &s, const uin
                     cand = later ? (red & U) : 0ull;
                 }
                 p += NB;
-#ifdef SWD_BPPROF
-                q_chain += clock64() - q0_;
-#endif
+                SWD_IF_BPPROF(q_chain += clock64() - q0_;)
                 fin = !(p < n && npiv < rank);
                 if (used >= (SWD_QUAD_LAZY > 0 ? SWD_QUAD_LAZY : 1) || fin) break;
             }
-#ifdef SWD_BPPROF
-            q0_ = clock64();
-#endif
+            SWD_IF_BPPROF(q0_ = clock64();)
             int rsum = 0;
             if (fin) {
                 rsum = racc;
@@ -2545,9 +2472,8 @@ __device__ __forceinline__ int osd0_quad(const SwdGraphDev &g, Lds &s, const uin
         __syncthreads();
         if (fin) break;
     }
-#ifdef SWD_BPPROF // steps, cycles / 16 of the evaluations (pending operations included), of the pivot loops, of the closes (CLOSE entry to the second barrier)
-    if (tid == 0) { q_sync += clock64() - q0_; s.scal[20] = q_steps; s.scal[21] = (int)(q_eval >> 4); s.scal[22] = (int)(q_chain >> 4); s.scal[23] = (int)(q_sync >> 4); }
-#endif
+    // steps, cycles / 16 of the evaluations (pending operations included), of the pivot loops, of the closes (CLOSE entry to the second barrier)
+    SWD_IF_BPPROF(if (tid == 0) { q_sync += clock64() - q0_; s.scal[20] = q_steps; s.scal[21] = (int)(q_eval >> 4); s.scal[22] = (int)(q_chain >> 4); s.scal[23] = (int)(q_sync >> 4); })
     // y = T * s (s in original row order)
     if (wave > 0) {
         const bool ona = jc < m && synd_b[jc < m ? jc : 0] != 0, onb = jc2 < m && synd_b[jc2 < m ? jc2 : 0] != 0;
@@ -2895,9 +2821,7 @@ struct WinResult {
     int exit_class, conv, total_it, pre_it, post_it, live_vn, live_cn, live_e, osd_rowadds;
     double pm;
     long long t[9]; // phase boundaries (wall_clock64 ticks): init, pre, sort, shorten, post, osd sort, elim, sweep
-#ifdef SWD_GDGPROF
-    long long gp[5]; // guessing decoders, diagnostic build: cache rebuilds, BP blocks, select_vn, branch starts, path metrics
-#endif
+    SWD_IF_GDGPROF(long long gp[5];) // guessing decoders, diagnostic build: cache rebuilds, BP blocks, select_vn, branch starts, path metrics
 };
 
 // scratch: where the scratch region of this workgroup starts -- the LDS block itself, or (BIG kernels) its region in HBM, in which
@@ -2977,9 +2901,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     // the tuned kernels use the packed caches and their overloads of the BP routines: byte offsets + parity bytes up to 256
     // threads, slot numbers + parity words in the 1024-thread kernels
     std::conditional_t<SWD_P16(NT), VnCacheP<VF, DM, 0, false>, VnCacheP<VF, DM, 3, false>> vc;
-#ifdef SWD_INITPROF
-    const long long ip0 = wall_clock64();
-#endif
+    SWD_IF_INITPROF(const long long ip0 = wall_clock64();)
     // large graphs: check-to-bit messages as one record per check in LDS (bp_run<..., REC>) when the layout's LDS block has room for them
     constexpr bool kTbl = BIG && SWD_BIG_TBL && !kSplitLoad; // the full graph's variable-node pass from the graph's tables (bp_run<..., TBL>)
     constexpr bool kRec = BIG && SWD_BIG_REC && !kTbl && !kSplitLoad;
@@ -2992,17 +2914,13 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
         if (kRec && rec_on) { if constexpr (kRec) vn_cache_load<NT, VF, DM, true, false, true>(g, s, n, vc); }
         else vn_cache_load<NT, VF, DM, true>(g, s, n, vc);
     }
-#ifdef SWD_INITPROF
-    asm volatile("" : "+v"(vc.edp[VF - 1][0]), "+v"(vc.llr[0]));
-    const long long ip1 = wall_clock64();
-#endif
+    SWD_IF_INITPROF(asm volatile("" : "+v"(vc.edp[VF - 1][0]), "+v"(vc.llr[0]));
+        const long long ip1 = wall_clock64();)
     // the check state and jptr written above are read below by OTHER threads (a check is served by the thread
     // whose ctid equals its lane number, which need not be the thread that initialised it; with the check cache taken from the image the
     // first reader is bp_run, behind the second barrier -- this one is kept as it was, its removal is a measurement of its own)
     __syncthreads();
-#ifdef SWD_INITPROF
-    const long long ip2 = wall_clock64();
-#endif
+    SWD_IF_INITPROF(const long long ip2 = wall_clock64();)
     // large graphs: the LDS region that will hold the shortened graph's messages / the OSD arrays is idle in this phase -- the TOP of the
     // message array (the far and zero slots included) lives there, one select per access (flat addresses reach both memories)
     constexpr bool kHyb = BIG;
@@ -3023,9 +2941,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     if constexpr (kTbl) bp_init_tbl<NT, VF, DM, kHyb>(g, s);
     else if constexpr (PROF::on) bp_init_depth<PROF, VF, DM>(s, vc);
     else bp_init<VF, DM, kHyb>(s, vc);
-#ifdef SWD_INITPROF
-    const long long ip3 = wall_clock64();
-#endif
+    SWD_IF_INITPROF(const long long ip3 = wall_clock64();)
     std::conditional_t<SWD_P16(NT), CnCacheP<KG>, CnCacheP<KG, 3>> cn;
     if constexpr (kSplitLoad) swd_cache_img_cn(img, cn);
     else if constexpr (SF) { // heavy checks are shared by 2 or 4 threads in the full-graph phase too (host-built map)
@@ -3043,9 +2959,8 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     R.live_vn = n; R.live_cn = m; R.live_e = g.nnz; R.osd_rowadds = 0;
     uint16_t *list0 = (uint16_t *)s.scratch;
     R.t[1] = wall_clock64();
-#ifdef SWD_INITPROF // diagnostic build: where the set-up of a window goes (reset loops | cache loads | barrier | bp_init | check caches)
-    if (tid == 0) { s.scal[20] = (int)(ip0 - R.t[0]); s.scal[21] = (int)(ip1 - ip0); s.scal[22] = (int)(ip2 - ip1); s.scal[23] = (int)(ip3 - ip2); s.scal[24] = (int)(R.t[1] - ip3); }
-#endif
+    // diagnostic build: where the set-up of a window goes (reset loops | cache loads | barrier | bp_init | check caches)
+    SWD_IF_INITPROF(if (tid == 0) { s.scal[20] = (int)(ip0 - R.t[0]); s.scal[21] = (int)(ip1 - ip0); s.scal[22] = (int)(ip2 - ip1); s.scal[23] = (int)(ip3 - ip2); s.scal[24] = (int)(R.t[1] - ip3); })
 
     double hs[VF]; // HACC: summed posterior history of this thread's variable nodes
 #pragma unroll
@@ -3060,13 +2975,9 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     R.t[2] = wall_clock64();
     if (R.conv) {
         R.exit_class = SWD_EXIT_PRE;
-#ifdef SWD_INITPROF
-        const long long pm0 = wall_clock64();
-#endif
+        SWD_IF_INITPROF(const long long pm0 = wall_clock64();)
         if (want_pm) R.pm = ordered_pm<NT>(g, s, list0);
-#ifdef SWD_INITPROF
-        if (tid == 0) s.scal[25] = (int)(wall_clock64() - pm0);
-#endif
+        SWD_IF_INITPROF(if (tid == 0) s.scal[25] = (int)(wall_clock64() - pm0);)
         R.total_it = R.pre_it;
         return;
     }
@@ -3131,9 +3042,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
         }
     }
     const bool any_contra = block_any<NT>(contra, s);
-#ifdef SWD_SHPROF
-    long long sh0 = wall_clock64();
-#endif
+    SWD_IF_SHPROF(long long sh0 = wall_clock64();)
     if (any_contra) {
         // "setting vn failed" (osd_window.pyx:179-181): the reference stops at the first decimation
         // that empties an unsatisfied check; only VNs up to that sorted position were zeroed.
@@ -3263,9 +3172,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
         if (tid == 0) { s.scal[2] = 0; s.scal[3] = 0; }
     }
     __syncthreads();
-#ifdef SWD_SHPROF
-    long long sh1 = wall_clock64();
-#endif
+    SWD_IF_SHPROF(long long sh1 = wall_clock64();)
     if (s.scal[1]) {
         R.exit_class = SWD_EXIT_FAIL_PEEL;
         R.total_it = R.pre_it;
@@ -3366,9 +3273,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
         }
     }
     __syncthreads();
-#ifdef SWD_SHPROF
-    long long sh2 = wall_clock64();
-#endif
+    SWD_IF_SHPROF(long long sh2 = wall_clock64();)
     R.live_vn = nlive; R.live_cn = s.scal[2]; R.live_e = s.scal[3];
     int clc, csub, cgrp;
     cn_assign<NT, KG>(g, s, dhist, cord, uselist, true, R.live_cn, clc, csub, cgrp);
@@ -3475,9 +3380,7 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
         }
     }
     if (!post_done) R.conv = run_post(vc, cn, hs, std::integral_constant<int, VF>{}, std::integral_constant<int, KG>{}, std::false_type{}, std::false_type{});
-#ifdef SWD_SHPROF
-    if (tid == 0) { s.scal[20] = (int)(sh0 - R.t[3]); s.scal[21] = (int)(sh1 - sh0); s.scal[22] = (int)(sh2 - sh1); s.scal[23] = (int)(R.t[4] - sh2); }
-#endif
+    SWD_IF_SHPROF(if (tid == 0) { s.scal[20] = (int)(sh0 - R.t[3]); s.scal[21] = (int)(sh1 - sh0); s.scal[22] = (int)(sh2 - sh1); s.scal[23] = (int)(R.t[4] - sh2); })
     if constexpr (BIG) {
         s.msg = (double *)s.scratch;
         if (L.osd_lds) s.aux = (char *)s.hard - L.off_hard + L.off_pmsg; // the arrays of the OSD phase go where the post-phase messages were
@@ -3487,13 +3390,9 @@ __device__ __forceinline__ void decode_window(const SwdGraphDev &g, const SwdLds
     R.total_it = R.pre_it + R.post_it;
     if (R.conv) {
         R.exit_class = SWD_EXIT_POST;
-#ifdef SWD_INITPROF
-        const long long pm0 = wall_clock64();
-#endif
+        SWD_IF_INITPROF(const long long pm0 = wall_clock64();)
         if (want_pm) R.pm = ordered_pm<NT>(g, s, list0);
-#ifdef SWD_INITPROF
-        if (tid == 0) s.scal[25] = (int)(wall_clock64() - pm0);
-#endif
+        SWD_IF_INITPROF(if (tid == 0) s.scal[25] = (int)(wall_clock64() - pm0);)
         return;
     }
     if (P.osd_order < 0) { R.exit_class = SWD_EXIT_NO_OSD; return; }
@@ -3678,10 +3577,9 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
     const uint32_t nunits = (uint32_t)a.B * (uint32_t)a.W;
     Lds s;
     swd_wave_roles<NT>(s, acc + 2);
-#ifdef SWD_RESIDENCY // diagnostics: how many workgroups of this launch are resident at the same time? (status words 4: now, 5: most, 6: with >= 1 unit)
-    if (tid == 0) { const uint32_t now = atomicAdd(&a.status[4], 1u) + 1u; atomicMax(&a.status[5], now); }
-    uint32_t res_units = 0;
-#endif
+    // diagnostics: how many workgroups of this launch are resident at the same time? (status words 4: now, 5: most, 6: with >= 1 unit)
+    SWD_IF_RESIDENCY(if (tid == 0) { const uint32_t now = atomicAdd(&a.status[4], 1u) + 1u; atomicMax(&a.status[5], now); }
+        uint32_t res_units = 0;)
     bool queued = false; // parallel form of the guessing decoders: work items instead of window-major tickets
     constexpr bool kQueue = KIND == 2 || KIND == 7; // (kind 7, the threaded ensemble: UNIT items only -- its units run from 50 us to several ms, and a
                                                     //  workgroup that draws a ticket whose predecessor is such a unit would idle for that long)
@@ -3694,9 +3592,7 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
     int wi, b, final_ctx = -1;
     [[maybe_unused]] bool ens_task = false;      // kind 7: this turn runs a tree thread of a parked ensemble, not a unit
     [[maybe_unused]] uint32_t ens_item = 0;
-#ifdef SWD_GDG_DEBUG
-    long long dbg_ta = 0, dbg_tb = 0, dbg_tc = 0;
-#endif
+    SWD_IF_GDG_DEBUG(long long dbg_ta = 0, dbg_tb = 0, dbg_tc = 0;)
     if (queued) {
         // Work items (swd_gdg_kernel.h) from one FIFO ring: windows of admitted shots (a window is queued when its
         // predecessor has committed), side branches and results of parked decimation trees.  No item waits for
@@ -3717,10 +3613,8 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
             __syncthreads();
             item = acc[2];
         }
-#ifdef SWD_GDG_DEBUG
-        asm volatile("" ::: "memory"); dbg_ta = wall_clock64(); asm volatile("" ::: "memory");
-        if (tid == 0) { uint32_t *dbg_status = a.gdgp.chk_status; GDG_COUNT(7, 1); GDG_COUNT(8, dbg_ta - t_unit0); if (dbg_ta - t_unit0 > 5000) { GDG_COUNT(6, 1); GDG_COUNT(15, dbg_ta - t_unit0); } }
-#endif
+        SWD_IF_GDG_DEBUG(asm volatile("" ::: "memory"); dbg_ta = wall_clock64(); asm volatile("" ::: "memory");
+            if (tid == 0) { uint32_t *dbg_status = a.gdgp.chk_status; GDG_COUNT(7, 1); GDG_COUNT(8, dbg_ta - t_unit0); if (dbg_ta - t_unit0 > 5000) { GDG_COUNT(6, 1); GDG_COUNT(15, dbg_ta - t_unit0); } })
         if (item == SWD_ITEM_EXIT) break;
         const uint32_t type = item >> 30;
         if (type == SWD_ITEM_SIDE) {
@@ -3810,26 +3704,19 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
     double *hist_b = a.hist + (int64_t)sidx * a.hist_stride;
     s.fpar = 0;
     __syncthreads();
-#ifdef SWD_TSPROF // diagnostic build: when the unit started (a parked tree's commit happens in another iteration of this loop)
-    if (a.prof && tid == 0 && final_ctx < 0 && !ens_task) a.prof[((int64_t)b * a.W + wi) * 8 + 4] = wall_clock64();
-#endif
-#ifdef SWD_GDG_DEBUG
-    asm volatile("" ::: "memory"); dbg_tb = wall_clock64(); asm volatile("" ::: "memory");
-    if (queued && tid == 0) { uint32_t *dbg_status = a.gdgp.chk_status; GDG_COUNT(13, dbg_tb - t_unit0); GDG_COUNT(14, 1); }
-#endif
+    // diagnostic build: when the unit started (a parked tree's commit happens in another iteration of this loop)
+    SWD_IF_TSPROF(if (a.prof && tid == 0 && final_ctx < 0 && !ens_task) a.prof[((int64_t)b * a.W + wi) * 8 + 4] = wall_clock64();)
+    SWD_IF_GDG_DEBUG(asm volatile("" ::: "memory"); dbg_tb = wall_clock64(); asm volatile("" ::: "memory");
+        if (queued && tid == 0) { uint32_t *dbg_status = a.gdgp.chk_status; GDG_COUNT(13, dbg_tb - t_unit0); GDG_COUNT(14, 1); })
     {
         const SwdWindowDev &w = a.wins[wi];
         const SwdGraphDev &g = w.g;
         const SwdLdsLayout &L = w.L;
         lds_bind(s, smem, L, BIG ? (char *)(a.big + (int64_t)blockIdx.x * a.big_stride) : smem);
         WinResult R;
-#ifdef SWD_SELPROF
-        if (tid < 8) s.scal[20 + tid] = 0;
-        __syncthreads();
-#endif
-#ifdef SWD_BPPROF
-        if (tid == 0) { s.scal[24] = s.scal[25] = s.scal[26] = s.scal[27] = 0; s.scal[20] = s.scal[21] = s.scal[22] = 0; }
-#endif
+        SWD_IF_SELPROF(if (tid < 8) s.scal[20 + tid] = 0;
+            __syncthreads();)
+        SWD_IF_BPPROF(if (tid == 0) { s.scal[24] = s.scal[25] = s.scal[26] = s.scal[27] = 0; s.scal[20] = s.scal[21] = s.scal[22] = 0; })
         if (acc[3]) { // the predecessor never arrived: nothing is decoded or committed for this unit
             for (int v = tid; v < g.n; v += NT) s.hard[v] = 0;
             R = WinResult{};
@@ -3853,15 +3740,13 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
             } else
             if (final_ctx >= 0) { // the result of a parked tree
                 const GdgCtx c = gdg_ctx(a.gdgp, final_ctx);
-#ifdef SWD_GDG_CHECKS
-                if (tid == 0) {
+                SWD_IF_GDG_CHECKS(if (tid == 0) {
                     uint32_t *chk_status = a.gdgp.chk_status;
                     GDG_CHECK(final_ctx < a.gdgp.nctx, 9);
                     GDG_CHECK(atomicExch(&c.hdr[1], 2u) == 1u, 10);   // exactly one FINAL per parked tree
                     GDG_CHECK(ag_ld(&c.hdr[22]) == 1u && ag_ld(&c.hdr[18]) == ag_ld(&c.hdr[19]), 11);
                     GDG_CHECK(wi < a.W && b < a.B, 12);
-                }
-#endif
+                })
                 redo = !gdg_finalize<NT>(g, a.P, s, c, R); // its snapshot area overflowed: the whole unit again, serially
                 if (tid == 0) {
                     while (ag_ld(&c.hdr[0]) != 0u) __builtin_amdgcn_s_sleep(2); // the scheduler run that queued this item has left
@@ -3870,14 +3755,10 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
                 __syncthreads();
             }
             if (!ens_task && (final_ctx < 0 || redo)) {
-#ifdef SWD_GDG_DEBUG
-                asm volatile("" ::: "memory"); dbg_tc = wall_clock64(); asm volatile("" ::: "memory");
-#endif
+                SWD_IF_GDG_DEBUG(asm volatile("" ::: "memory"); dbg_tc = wall_clock64(); asm volatile("" ::: "memory");)
                 s.fpar = 0;
                 decode_window_gdg<NT, VF, DM, KG, KIND == 7, VFP>(g, L, a.P, s, sdet + (w.row0 - dbase), hist_b, snap_b, R, (queued && !redo) ? &a : nullptr, acc, wi, b);
-#ifdef SWD_GDG_DEBUG
-                if (tid == 0 && queued) { uint32_t *dbg_status = a.gdgp.chk_status; GDG_COUNT(R.exit_class == -2 ? 9 : 10, 1); GDG_COUNT(R.exit_class == -2 ? 11 : 12, wall_clock64() - t_unit0); }
-#endif
+                SWD_IF_GDG_DEBUG(if (tid == 0 && queued) { uint32_t *dbg_status = a.gdgp.chk_status; GDG_COUNT(R.exit_class == -2 ? 9 : 10, 1); GDG_COUNT(R.exit_class == -2 ? 11 : 12, wall_clock64() - t_unit0); })
                 if (R.exit_class == -2) continue; // parked: a FINAL item brings the result
             }
             if constexpr (KIND == 7) {
@@ -3952,15 +3833,14 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
             }
         }
         __syncthreads();
-#ifdef SWD_GDG_DEBUG // diagnostic build: checksums of the unit's input syndrome and of its result vector (statistics words 5, 6)
-        if (tid == 0) {
+        // diagnostic build: checksums of the unit's input syndrome and of its result vector (statistics words 5, 6)
+        SWD_IF_GDG_DEBUG(if (tid == 0) {
             uint32_t hi = 2166136261u, ho = 2166136261u;
             for (int r = 0; r < g.m; ++r) hi = (hi ^ sdet[w.row0 - dbase + r]) * 16777619u;
             for (int v = 0; v < g.n; ++v) ho = (ho ^ s.hard[v]) * 16777619u;
             R.live_cn = (int)hi; R.live_e = (int)ho;
         }
-        __syncthreads();
-#endif
+        __syncthreads();)
         if (a.total) {
             uint8_t *tot_b = a.total + (int64_t)b * a.total_stride + w.col0;
             uint32_t *sdet_w = (uint32_t *)sdet;
@@ -3990,23 +3870,16 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
                 st[0] = R.exit_class | (R.conv ? SWD_STATUS_CONVERGE : 0);
                 st[1] = R.total_it; st[2] = R.pre_it; st[3] = R.post_it;
                 st[4] = R.live_vn; st[5] = R.live_cn; st[6] = R.live_e;
-#ifdef SWD_GDG_DEBUG // diagnostic build: word 7 counts how often the unit was committed (the caller zeroes the array)
-                atomicAdd(&st[7], 1);
-#else
-                st[7] = R.osd_rowadds;
-#endif
-#ifdef SWD_BPPROF
-                if (R.post_it > 0) st[7] = s.scal[28];
-#endif
+                SWD_IF_NOT_GDG_DEBUG(st[7] = R.osd_rowadds;)
+                SWD_IF_GDG_DEBUG(atomicAdd(&st[7], 1);) // word 7 counts how often the unit was committed (the caller zeroes the array)
+                SWD_IF_BPPROF(if (R.post_it > 0) st[7] = s.scal[28];)
             }
             if (a.min_pm) a.min_pm[(int64_t)b * a.W + wi] = R.pm;
             if (a.prof) {
                 int64_t *pr = a.prof + ((int64_t)b * a.W + wi) * 8;
                 const long long tend = wall_clock64();
                 long long prev = R.t[0];
-#ifdef SWD_TSPROF
-                const int64_t ts_start = pr[4];
-#endif
+                SWD_IF_TSPROF(const int64_t ts_start = pr[4];)
 #pragma unroll
                 for (int i = 1; i <= 7; ++i) {
                     const long long cur = R.t[i] ? R.t[i] : prev;
@@ -4014,34 +3887,19 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
                     prev = cur;
                 }
                 pr[7] = tend - prev;
-#ifdef SWD_GDG_DEBUG
-                pr[6] = R.t[0] - t_unit0; pr[2] = dbg_ta - t_unit0; pr[3] = dbg_tb - t_unit0; pr[4] = dbg_tc - t_unit0;
-#else
-                pr[0] += R.t[0] - t_unit0; // ticket, wait for the previous window, state load
-#endif
-#ifdef SWD_TSPROF
-                pr[5] = t_unit0; pr[6] = tend; pr[4] = ts_start; // absolute ticks: start of the iteration that committed, commit, start of the unit
-#endif
-#ifdef SWD_GDGPROF
-                pr[0] = R.t[2] - R.t[0]; pr[1] = (R.t[3] ? R.t[3] : R.t[2]) - R.t[2];
-                pr[2] = R.gp[0]; pr[3] = R.gp[1]; pr[4] = R.gp[2]; pr[5] = R.gp[3]; pr[6] = R.gp[4]; pr[7] = tend - R.t[0];
-#endif
-#ifdef SWD_BPPROF
-                pr[0] = s.scal[24]; pr[5] = s.scal[25]; pr[6] = s.scal[26]; pr[7] = s.scal[27];
-                pr[1] = s.scal[20]; pr[2] = s.scal[21]; pr[3] = s.scal[22]; pr[4] = s.scal[23];
-#endif
-#ifdef SWD_INITPROF
-                pr[0] = R.t[0] - t_unit0; pr[1] = s.scal[20]; pr[2] = s.scal[21]; pr[3] = s.scal[22]; pr[4] = s.scal[23]; pr[5] = s.scal[24];
-                pr[6] = tend - R.t[1]; pr[7] = (R.exit_class == SWD_EXIT_PRE || R.exit_class == SWD_EXIT_POST) ? s.scal[25] : 0; // ordered_pm of the BP exits
-#endif
-#ifdef SWD_SELPROF
-                for (int k = 0; k < 8; ++k) { pr[k] = s.scal[20 + k]; s.scal[20 + k] = 0; }
-#endif
-#ifdef SWD_SHPROF
-                pr[5] = R.t[3] ? R.t[3] - R.t[2] : 0; // (the column select, which the four words below overwrite)
-                pr[1] = s.scal[20]; pr[2] = s.scal[21]; pr[3] = s.scal[22]; pr[4] = s.scal[23];
-                if (tid == 0) { s.scal[20] = s.scal[21] = s.scal[22] = s.scal[23] = 0; }
-#endif
+                SWD_IF_NOT_GDG_DEBUG(pr[0] += R.t[0] - t_unit0;) // ticket, wait for the previous window, state load
+                SWD_IF_GDG_DEBUG(pr[6] = R.t[0] - t_unit0; pr[2] = dbg_ta - t_unit0; pr[3] = dbg_tb - t_unit0; pr[4] = dbg_tc - t_unit0;)
+                SWD_IF_TSPROF(pr[5] = t_unit0; pr[6] = tend; pr[4] = ts_start;) // absolute ticks: start of the iteration that committed, commit, start of the unit
+                SWD_IF_GDGPROF(pr[0] = R.t[2] - R.t[0]; pr[1] = (R.t[3] ? R.t[3] : R.t[2]) - R.t[2];
+                    pr[2] = R.gp[0]; pr[3] = R.gp[1]; pr[4] = R.gp[2]; pr[5] = R.gp[3]; pr[6] = R.gp[4]; pr[7] = tend - R.t[0];)
+                SWD_IF_BPPROF(pr[0] = s.scal[24]; pr[5] = s.scal[25]; pr[6] = s.scal[26]; pr[7] = s.scal[27];
+                    pr[1] = s.scal[20]; pr[2] = s.scal[21]; pr[3] = s.scal[22]; pr[4] = s.scal[23];)
+                SWD_IF_INITPROF(pr[0] = R.t[0] - t_unit0; pr[1] = s.scal[20]; pr[2] = s.scal[21]; pr[3] = s.scal[22]; pr[4] = s.scal[23]; pr[5] = s.scal[24];
+                    pr[6] = tend - R.t[1]; pr[7] = (R.exit_class == SWD_EXIT_PRE || R.exit_class == SWD_EXIT_POST) ? s.scal[25] : 0;) // ordered_pm of the BP exits
+                SWD_IF_SELPROF(for (int k = 0; k < 8; ++k) { pr[k] = s.scal[20 + k]; s.scal[20 + k] = 0; })
+                SWD_IF_SHPROF(pr[5] = R.t[3] ? R.t[3] - R.t[2] : 0; // (the column select, which the four words below overwrite)
+                    pr[1] = s.scal[20]; pr[2] = s.scal[21]; pr[3] = s.scal[22]; pr[4] = s.scal[23];
+                    if (tid == 0) { s.scal[20] = s.scal[21] = s.scal[22] = s.scal[23] = 0; })
             }
         }
         __syncthreads();
@@ -4094,13 +3952,9 @@ __global__ void __launch_bounds__(NT, (NT >= 1024 ? 4 : ((SWD_OSDW_TUNED && NT =
         const bool any = block_any<NT>(nz, s);
         if (tid == 0) { a.shot_result[2 * b] = (int32_t)acc[0]; a.shot_result[2 * b + 1] = any ? 1 : 0; }
     }
-#ifdef SWD_RESIDENCY
-    ++res_units;
-#endif
+    SWD_IF_RESIDENCY(++res_units;)
     } // next unit
-#ifdef SWD_RESIDENCY
-    if (tid == 0) { atomicSub(&a.status[4], 1u); if (res_units) atomicAdd(&a.status[6], 1u); atomicMax(&a.status[7], res_units); }
-#endif
+    SWD_IF_RESIDENCY(if (tid == 0) { atomicSub(&a.status[4], 1u); if (res_units) atomicAdd(&a.status[6], 1u); atomicMax(&a.status[7], res_units); })
 }
 
 } // namespace swd
