@@ -864,6 +864,11 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
     const int farslot = swd_slot_far_of<SH>(g, s), zeroslot = swd_slot_zero_of<NT, SH>(g, s);
     constexpr int K4 = KG * 4;
     constexpr int NR = (K4 + 31) / 32;       // sign shift registers
+#ifdef SWD_NO_SCALAR_WMAX
+    constexpr bool kChain = false;
+#else
+    constexpr bool kChain = SH == 0;         // byte-offset caches: the tuned osd_window kernels of up to 256 threads (check pass below)
+#endif
     iters_done = 0;
     if (max_iter <= 0) return 0;
     // VNs this wave walks (wave-uniform): entries vtid + i*NT < vcnt for some lane
@@ -948,9 +953,12 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
             uint32_t neg[NR];
 #pragma unroll
             for (int r = 0; r < NR; ++r) neg[r] = 0;
-#pragma unroll
-            for (int gq = 0; gq < KG; ++gq) {
-                if (gq * 4 < wmax) { // wave-uniform
+            // kChain (round 14, tuned kernels of up to 256 threads): the walk bound is made opaque once per pass, so the group guards are
+            // scalar compares inside the loop (s_cmp + s_cbranch_scc) and not loop-invariant lane masks that live in spilled SGPR
+            // pairs; the groups form a chain that is left behind the wave's last live group
+            [[maybe_unused]] int wq = wmax;
+            if constexpr (kChain) asm volatile("" : "+s"(wq));
+            auto rd_group = [&](const int gq) {
                     double xs[4];
                     uint32_t ad[4];
                     cn.group(gq, ad);
@@ -968,10 +976,34 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
                     };
                     one(std::integral_constant<int, 0>{}); one(std::integral_constant<int, 1>{});
                     one(std::integral_constant<int, 2>{}); one(std::integral_constant<int, 3>{});
+            };
+            if constexpr (kChain) {
+                auto rd_chain = [&](auto self, auto gq_tag) -> void {
+                    constexpr int gq = decltype(gq_tag)::value;
+                    if constexpr (gq < KG) {
+                        if (gq * 4 < wq) { rd_group(gq); self(self, std::integral_constant<int, gq + 1>{}); } // wave-uniform
+                    }
+                };
+                rd_chain(rd_chain, std::integral_constant<int, 0>{});
+                // keep position k at bit (31 - k % 32): one shift per register by its positions behind the last group walked (a register
+                // without a walked position holds 0 whatever the shift)
+                const int walked = min(K4, (wq + 3) & ~3);
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    constexpr int cap0 = K4 - 32 * (NR - 1);
+                    const int cap = (r == NR - 1) ? cap0 : 32;
+                    neg[r] <<= (cap - min(max(walked - 32 * r, 0), cap)) & 31;
+                }
+            } else {
+#pragma unroll
+            for (int gq = 0; gq < KG; ++gq) {
+                if (gq * 4 < wmax) { // wave-uniform
+                    rd_group(gq);
                 } else {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) neg[(gq * 4 + u) >> 5] <<= 1; // keep position k at bit (31 - k % 32) ...
                 }
+            }
             }
             // ... after this alignment of a partly filled last register
             if (K4 & 31) neg[NR - 1] <<= (32 - (K4 & 31));
@@ -1021,9 +1053,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
                 }
                 swd_msg_st<HYB>(s, (uint32_t)farslot << 3, 64.0); // (nothing overwrote it; kept for symmetry with the message form)
             } else {
-#pragma unroll
-            for (int gq = 0; gq < KG; ++gq) {
-                if (gq * 4 < wmax) {
+            auto wr_group = [&](const int gq) {
                     uint32_t ad[4];
                     cn.group(gq, ad);
                     auto put = [&](auto u_tag) {
@@ -1035,7 +1065,20 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
                     };
                     put(std::integral_constant<int, 0>{}); put(std::integral_constant<int, 1>{});
                     put(std::integral_constant<int, 2>{}); put(std::integral_constant<int, 3>{});
-                }
+            };
+            if constexpr (kChain) {
+                auto wr_chain = [&](auto self, auto gq_tag) -> void {
+                    constexpr int gq = decltype(gq_tag)::value;
+                    if constexpr (gq < KG) {
+                        if (gq * 4 < wq) { wr_group(gq); self(self, std::integral_constant<int, gq + 1>{}); }
+                    }
+                };
+                wr_chain(wr_chain, std::integral_constant<int, 0>{});
+            } else {
+#pragma unroll
+            for (int gq = 0; gq < KG; ++gq) {
+                if (gq * 4 < wmax) wr_group(gq);
+            }
             }
             {
                 const uint32_t sb = ((0u - argneg) ^ flip) & 0x80000000u;
