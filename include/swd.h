@@ -89,7 +89,27 @@ typedef struct swd_osdw_params {
 
 typedef struct swd_osdw swd_osdw;
 
+/* Why the calling thread's most recent failure happened.  Every failing entry point leaves a message (swd_last_error) and, beside it,
+ * one of these classes (swd_last_error_class); both belong to the thread and stand until its next failure -- a call that succeeds
+ * leaves them alone.  Code that reacts to a failure reads the class, never the text.
+ *   SWD_ERR_FAILED    the default: misuse (a null handle, calls out of order), state, anything unclassified
+ *   SWD_ERR_VALUE     the caller's arguments are wrong in a way no form of the library would accept (an OSD order beyond the code's
+ *                     range, an unknown OSD method, probabilities that are none); the Python surface raises ValueError, as the
+ *                     reference does
+ *   SWD_ERR_CAPACITY  the input is valid but beyond a bound of the form that was asked: this build's graph tables, the kernel
+ *                     variants, a workgroup's LDS, a general form's own limit.  The only class a fallback follows:
+ *                       - swd_osdw_create / swd_gdg_create build the general form when the tuned set-up is refused with this class
+ *                         (or SWD_FORCE_HUGE is set); if the general form refuses too, its message and class stand;
+ *                       - swd_window_forms reports general = 1 for it and returns -1 for every other class;
+ *                       - swd_bp4_create_ex appends the general_form hint to a graph refusal of this class;
+ *                       - the Python SlidingWindowDecoder runs its window loop over single-window decoders when
+ *                         swd_pipeline_create / swd_pipeline_create_gdg refuse a plan with it.
+ *                     A malformed matrix or a failed device call never reaches another form.
+ *   SWD_ERR_DEVICE    a HIP call or a device / pinned allocation failed, or no usable device is there */
+enum swd_error_class { SWD_ERR_FAILED = 0, SWD_ERR_VALUE = 1, SWD_ERR_CAPACITY = 2, SWD_ERR_DEVICE = 3 };
+
 const char *swd_last_error(void);
+int swd_last_error_class(void); /* an enum swd_error_class */
 int swd_abi_version(void);
 int swd_device_count(void);
 
@@ -747,7 +767,9 @@ int swd_graph_cache_image(const swd_graph_desc *g, int32_t pads, int32_t nt, int
 #define SWD_FORM_WINDOW_WORDS 16
 /* host only (needs no device): the forms a handle built now from these windows would take.  Exactly one of p (osd_window) and gp
  * (guessing decoders) is given; num_det = rows of the global check matrix of a pipeline, <= 0 for a single-window handle (its
- * `reserved`, row0, col0 and commit are then 0).  A plan no window kernel takes is reported (plan[10]), not refused. */
+ * `reserved`, row0, col0 and commit are then 0).  A plan no window kernel takes (a refusal of class
+ * SWD_ERR_CAPACITY) is reported (plan[10]), not refused; input that no form takes -- a malformed matrix, an OSD order out of range --
+ * returns -1 with its message. */
 int swd_window_forms(int32_t num_windows, const swd_window_desc *wins, int32_t num_det, const swd_osdw_params *p,
                      const swd_gdg_params *gp, int32_t *plan, int32_t *window);
 /* the handle's forms and its most recent launch */

@@ -5,6 +5,7 @@ anywhere; the decoder classes need libswd_hip.so and a gfx950 GPU and raise othe
 """
 from .decoders import (CodeCapacityExperiment, CodeCapacityResult, DemSampler, MeasurementFrontEnd, MeasurementSession, RollingMeasurementSession, MemoryExperiment, MemoryResult, PauliSampler, RollingDemSampler, RollingMemoryExperiment, RollingMemoryResult, RollingSession, SlidingWindowDecoder, SlidingWindowSession, SlidingWindowStream, bp4_osd, bp_history_decoder, bpgd_decoder,  # noqa: F401
                        bpgdg_decoder, group_account_device, osd_window, window_forms)
+from ._lib import CapacityError  # noqa: F401
 from .codes import CSSCode, create_surface_codes, hypergraph_product, rep_code  # noqa: F401
 from .phenomenological import css_phenomenological_dem, phenomenological_dem  # noqa: F401
 from .measurements import MeasurementMap, measurement_map, phenomenological_measurement_map  # noqa: F401
@@ -20,4 +21,4 @@ __all__ = ["osd_window", "bpgdg_decoder", "bpgd_decoder", "bp_history_decoder", 
            "CodeCapacityExperiment", "CodeCapacityResult", "MemoryExperiment", "MemoryResult", "RollingDemSampler", "RollingMemoryExperiment",
            "RollingMemoryResult", "group_account_device", "window_forms", "CSSCode", "rep_code", "hypergraph_product", "create_surface_codes",
            "phenomenological_dem", "css_phenomenological_dem", "MeasurementFrontEnd", "MeasurementSession", "RollingMeasurementSession",
-           "MeasurementMap", "measurement_map", "phenomenological_measurement_map"]
+           "MeasurementMap", "measurement_map", "phenomenological_measurement_map", "CapacityError"]

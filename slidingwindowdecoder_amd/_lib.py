@@ -47,6 +47,7 @@ class Bp4Params(C.Structure):
 _vp, _i32, _i64, _dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = [
     ("swd_last_error", C.c_char_p, []),
+    ("swd_last_error_class", C.c_int, []),
     ("swd_abi_version", C.c_int, []),
     ("swd_device_count", C.c_int, []),
     ("swd_osdw_create", _vp, [C.POINTER(GraphDesc), C.POINTER(OsdwParams), C.c_int]),
@@ -203,3 +204,27 @@ def lib():
 
 def last_error() -> str:
     return (lib().swd_last_error() or b"").decode()
+
+
+ERR_FAILED, ERR_VALUE, ERR_CAPACITY, ERR_DEVICE = range(4)  # include/swd.h: enum swd_error_class
+
+
+def last_error_class() -> int:
+    return lib().swd_last_error_class()
+
+
+class CapacityError(ValueError, RuntimeError):
+    """The input is valid but beyond a bound of the form that was asked (include/swd.h, SWD_ERR_CAPACITY): this build's graph
+    tables, the kernel variants, a workgroup's LDS, a general form's own limit.  Both bases on purpose: such refusals used to
+    arrive as ValueError from one constructor and as RuntimeError from another."""
+
+
+def error(name, prefix_value=False):
+    """The exception for the failure the calling thread's last library call reported -- the one place that turns the library's
+    message and class into a Python exception.  ``name``: the entry point that failed.  SWD_ERR_VALUE: ValueError with the
+    bare message (``prefix_value``: with the ``name failed:`` prefix too); SWD_ERR_CAPACITY: CapacityError; anything else:
+    RuntimeError."""
+    msg, cls = last_error(), last_error_class()
+    if cls == ERR_VALUE and not prefix_value:
+        return ValueError(msg)
+    return {ERR_VALUE: ValueError, ERR_CAPACITY: CapacityError}.get(cls, RuntimeError)(f"{name} failed: {msg}")

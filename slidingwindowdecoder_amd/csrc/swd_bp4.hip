@@ -10,7 +10,6 @@
 
 namespace swd {
 int make_layout_for_osd(const Graph &g, int nt, SwdLdsLayout &L); // swd_osdw.hip
-const char *last_error();                                          // swd_graph.hip
 // what the refusals of a graph beyond the tuned kernels end with
 #define SWD_BP4_GENERAL_HINT " (bp4_osd(..., general_form=True) takes such a graph: BP only, osd_order=-1 or camel_decode)"
 // what the refusals of an OSD the tuned elimination kernel cannot run end with
@@ -171,16 +170,16 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
                                       const double *pz, const swd_bp4_params *p, int device, int32_t flags) {
     if (!hx || !hz || !px || !py || !pz || !p) { set_error("null argument"); return nullptr; }
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: the MI355X decoder has no CPU fallback"); return nullptr; }
-    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) { set_error("device %d not usable", device); return nullptr; }
-    if (hx->n != hz->n) { set_error("Hx, Hz blocklength does not match!"); return nullptr; }
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error(SWD_ERR_DEVICE, "no HIP device available: the MI355X decoder has no CPU fallback"); return nullptr; }
+    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) { set_error(SWD_ERR_DEVICE, "device %d not usable", device); return nullptr; }
+    if (hx->n != hz->n) { set_error(SWD_ERR_VALUE, "Hx, Hz blocklength does not match!"); return nullptr; }
     Bp4 *d = new Bp4();
     d->device = device; d->p = *p; d->n = hx->n;
     const int n = hx->n;
     const int asked_order = d->p.osd_order;
     d->general_osd = (flags & SWD_BP4_GENERAL_OSD) != 0;
     if (d->p.osd_method == 0) d->p.osd_order = 0;
-    if (d->p.osd_method < 0 || d->p.osd_method > 2) { set_error("ERROR: OSD method '%d' invalid.", d->p.osd_method); delete d; return nullptr; }
+    if (d->p.osd_method < 0 || d->p.osd_method > 2) { set_error(SWD_ERR_VALUE, "ERROR: OSD method '%d' invalid.", d->p.osd_method); delete d; return nullptr; }
     // OSD path metrics use prior_llr_x = log((1-(px+py))/(px+py)), prior_llr_z = log((1-(pz+py))/(pz+py)) (bp4_osd.pyx:134-137)
     std::vector<double> qx(n), qz(n);
     for (int v = 0; v < n; ++v) { qx[v] = px[v] + py[v]; qz[v] = pz[v] + py[v]; }
@@ -200,7 +199,7 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
         // With SWD_BP4_GENERAL_OSD beside it the order is the reference's (osd_method 0 resets it to 0) and the queued decodes go
         // to the general elimination, which shares the graphs.
         if (!d->general_osd && asked_order >= 0) {
-            set_error("OSD in the general form is not supported: create the decoder with osd_order=-1 (decode then returns the BP "
+            set_error(SWD_ERR_VALUE, "OSD in the general form is not supported: create the decoder with osd_order=-1 (decode then returns the BP "
                       "decisions) or use camel_decode" SWD_BP4_GENERAL_OSD_HINT);
             delete d; return nullptr;
         }
@@ -227,7 +226,7 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
             std::vector<int> ws;
             for (int v : heavy) ws.push_back(w[v]);
             std::sort(ws.begin(), ws.end(), [](int a, int b) { return a > b; });
-            set_error("column weight %d exceeds this build's bound %d (accepted beside it: up to %d heavy columns of any weight up to m <= %d, "
+            set_error(SWD_ERR_CAPACITY, "column weight %d exceeds this build's bound %d (accepted beside it: up to %d heavy columns of any weight up to m <= %d, "
                       "with osd_order=-1 or camel_decode; this graph has %d columns above the bound)" SWD_BP4_GENERAL_HINT,
                       ws[SWD_MAX_HEAVY], SWD_DMAX, SWD_MAX_HEAVY, SWD_MAX_M, (int)heavy.size());
             delete d; return nullptr;
@@ -238,20 +237,21 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
         // (the elimination kernel's ELL column tables hold light columns only; with osd_method "osd_0" the reference resets the order to
         // 0, bp4_osd.pyx:74-76, which its camel_decode never looks at -- here the caller's -1 stands, and decode returns the BP
         // decisions of a shot that did not converge, as the reference does for the other methods with osd_order = -1)
-        set_error("OSD on a graph with heavy columns (%d of weight above %d, up to %d) is not supported: create the decoder with "
+        set_error(SWD_ERR_VALUE, "OSD on a graph with heavy columns (%d of weight above %d, up to %d) is not supported: create the decoder with "
                   "osd_order=-1 (decode then returns the BP decisions) or use camel_decode" SWD_BP4_GENERAL_OSD_HINT, d->heavy, SWD_DMAX, d->heavy_deg);
         delete d; return nullptr;
     }
     if (d->heavy && !d->general_osd) d->p.osd_order = -1;
     if (d->gx.build(&dx, d->heavy ? &heavy : nullptr) || d->gz.build(&dz, d->heavy ? &heavy : nullptr)) {
-        const std::string why = last_error(); // (more than 1024 checks, a row or a light column past the graph tables: sizes the general form takes)
-        if (why.find("exceeds this build's limit") != std::string::npos || why.find("has weight") != std::string::npos)
-            set_error("%s" SWD_BP4_GENERAL_HINT, why.c_str());
+        if (last_error_class() == SWD_ERR_CAPACITY) { // (more than 1024 checks, a row or a light column past the graph tables: sizes the general form takes)
+            const std::string why = last_error();
+            set_error(SWD_ERR_CAPACITY, "%s" SWD_BP4_GENERAL_HINT, why.c_str());
+        }
         delete d; return nullptr;
     }
     const int kmin = std::min(n - d->gx.rank, n - d->gz.rank);
     if (d->p.osd_order > kmin) { // bp4_osd.pyx:92-98
-        set_error("For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", kmin);
+        set_error(SWD_ERR_VALUE, "For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", kmin);
         delete d; return nullptr;
     }
     if (d->p.osd_order > 0 && d->gx.rank < d->gz.rank) {
@@ -262,7 +262,7 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
     }
     if (d->p.osd_method == 1 && d->p.osd_order > 15) { set_error("osd_e supports osd_order <= 15 on the device"); delete d; return nullptr; }
     const int D = std::max(d->gx.D, d->gz.D);
-    if (D > SWD_DMAX) { set_error("column weight %d exceeds this build's bound %d", D, SWD_DMAX); delete d; return nullptr; } // (not reached: such a column is heavy)
+    if (D > SWD_DMAX) { set_error(SWD_ERR_CAPACITY, "column weight %d exceeds this build's bound %d", D, SWD_DMAX); delete d; return nullptr; } // (not reached: such a column is heavy)
     d->dm = d->heavy ? SWD_DMAX : (D <= 4 ? 4 : (D <= 8 ? 8 : SWD_DMAX)); // SHYPS stabiliser matrices reach column weight 9
     d->nt_osd = n <= 3072 ? 256 : 1024;
     d->nt = n <= 1024 ? std::max(64, (n + 63) / 64 * 64) : 1024;
@@ -315,9 +315,9 @@ extern "C" swd_bp4 *swd_bp4_create_ex(const swd_graph_desc *hx, const swd_graph_
         L.off_hve = o; o += ((int)d->gx.hv_edge.size() + (int)d->gz.hv_edge.size()) * 4;
     }
     L.total = al(o, 16);
-    if (L.total > 160 * 1024) { set_error("code needs %d bytes of LDS per shot (> 163840)" SWD_BP4_GENERAL_HINT, L.total); delete d; return nullptr; }
+    if (L.total > 160 * 1024) { set_error(SWD_ERR_CAPACITY, "code needs %d bytes of LDS per shot (> 163840)" SWD_BP4_GENERAL_HINT, L.total); delete d; return nullptr; }
     if (d->llr.reserve(llr.size() * 8)) { delete d; return nullptr; }
-    if (hipMemcpy(d->llr.p, llr.data(), llr.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy failed"); delete d; return nullptr; }
+    if (hipMemcpy(d->llr.p, llr.data(), llr.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { set_error(SWD_ERR_DEVICE, "hipMemcpy failed"); delete d; return nullptr; }
     d->d_llr_x = d->llr.as<double>(); d->d_llr_y = d->d_llr_x + n; d->d_llr_z = d->d_llr_y + n;
     return (swd_bp4 *)d;
 }

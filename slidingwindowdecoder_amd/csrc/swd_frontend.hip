@@ -250,8 +250,8 @@ extern "C" swd_frontend *swd_frontend_create(const swd_graph_desc *head, const s
         fe_ingest(tail, "tail", h, mpr + mfin, 0, rowptr, off) || (obs_tail && fe_ingest(obs_tail, "observable", nobs, mpr + mfin, 0, rowptr, off)))
         return nullptr;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: the MI355X decoder has no CPU fallback"); return nullptr; }
-    if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return nullptr; }
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error(SWD_ERR_DEVICE, "no HIP device available: the MI355X decoder has no CPU fallback"); return nullptr; }
+    if (device < 0 || device >= ndev) { set_error(SWD_ERR_DEVICE, "device %d out of range (%d devices)", device, ndev); return nullptr; }
     FrontEnd *f = new FrontEnd();
     f->device = device; f->max_shots = max_shots; f->mpr = mpr; f->mfin = mfin; f->h = h; f->nobs = nobs;
     f->state_stride = ((int64_t)2 * mpr + 15) & ~(int64_t)15;
@@ -263,7 +263,7 @@ extern "C" swd_frontend *swd_frontend_create(const swd_graph_desc *head, const s
         hipMemcpy(f->dev.p, rowptr.data(), rowptr.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         (!off.empty() && hipMemcpy((char *)f->dev.p + f->o_off, off.data(), off.size() * 2, hipMemcpyHostToDevice) != hipSuccess) ||
         hipStreamCreateWithFlags(&f->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&f->ev, hipEventDisableTiming) != hipSuccess) {
-        set_error("front end: device allocation failed on device %d", device);
+        set_error(SWD_ERR_DEVICE, "front end: device allocation failed on device %d", device);
         delete f;
         return nullptr;
     }

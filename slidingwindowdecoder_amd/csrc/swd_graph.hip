@@ -12,17 +12,31 @@
 namespace swd {
 
 static thread_local std::string g_err;
+static thread_local swd_error_class g_err_class = SWD_ERR_FAILED;
+
+static void set_error_v(swd_error_class cls, const char *fmt, va_list ap) {
+    char buf[1024];
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    g_err = buf;
+    g_err_class = cls;
+}
 
 void set_error(const char *fmt, ...) {
-    char buf[1024];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    set_error_v(SWD_ERR_FAILED, fmt, ap);
     va_end(ap);
-    g_err = buf;
+}
+
+void set_error(swd_error_class cls, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    set_error_v(cls, fmt, ap);
+    va_end(ap);
 }
 
 const char *last_error() { return g_err.c_str(); }
+swd_error_class last_error_class() { return g_err_class; }
 
 int gf2_rank(int m, int n, const std::vector<int32_t> &row_ptr, const std::vector<int32_t> &col_idx) {
     const int W = (n + 63) / 64;
@@ -318,9 +332,9 @@ int Graph::build(const swd_graph_desc *g, const std::vector<int32_t> *heavy) {
     m = g->m; n = g->n; E = g->nnz;
     if (m <= 0 || n <= 0 || E <= 0) { set_error("empty check matrix (m=%d n=%d nnz=%d)", m, n, E); return -1; }
     if (g->row_ptr[0] != 0 || g->row_ptr[m] != E) { set_error("row_ptr does not span nnz"); return -1; }
-    if (m > SWD_MAX_M) { set_error("m=%d exceeds this build's limit of %d checks", m, SWD_MAX_M); return -1; }
-    if (n > 65534) { set_error("n=%d exceeds this build's limit of 65534 columns", n); return -1; }
-    if (E > SWD_MAX_E) { set_error("nnz=%d exceeds this build's limit of %d edges", E, SWD_MAX_E); return -1; }
+    if (m > SWD_MAX_M) { set_error(SWD_ERR_CAPACITY, "m=%d exceeds this build's limit of %d checks", m, SWD_MAX_M); return -1; }
+    if (n > 65534) { set_error(SWD_ERR_CAPACITY, "n=%d exceeds this build's limit of 65534 columns", n); return -1; }
+    if (E > SWD_MAX_E) { set_error(SWD_ERR_CAPACITY, "nnz=%d exceeds this build's limit of %d edges", E, SWD_MAX_E); return -1; }
     row_ptr.assign(g->row_ptr, g->row_ptr + m + 1);
     col_idx.assign(g->col_idx, g->col_idx + E);
     if (csr_check_rows(m, n, row_ptr, col_idx)) return -1;
@@ -331,7 +345,7 @@ int Graph::build(const swd_graph_desc *g, const std::vector<int32_t> *heavy) {
     std::vector<int> cdeg(n, 0);
     for (int r = 0; r < m; ++r) {
         int d = row_ptr[r + 1] - row_ptr[r];
-        if (d > SWD_MAX_ROW_DEG) { set_error("row %d has weight %d > %d", r, d, SWD_MAX_ROW_DEG); return -1; }
+        if (d > SWD_MAX_ROW_DEG) { set_error(SWD_ERR_CAPACITY, "row %d has weight %d > %d", r, d, SWD_MAX_ROW_DEG); return -1; }
         if (d == 0) { set_error("row %d is empty: every check needs degree > 0 (osd_window.pyx:117)", r); return -1; }
         K = std::max(K, d);
         for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) cdeg[col_idx[e]]++;
@@ -339,7 +353,7 @@ int Graph::build(const swd_graph_desc *g, const std::vector<int32_t> *heavy) {
     hv_id.clear(); hv_deg.clear(); hv_ptr.clear(); hv_edge.clear();
     std::vector<int> ldeg(cdeg); // weights the ELL tables see: 0 for a column of the side list
     if (heavy && !heavy->empty()) {
-        if (heavy->size() > SWD_MAX_HEAVY) { set_error("%d heavy columns exceed this build's bound %d", (int)heavy->size(), SWD_MAX_HEAVY); return -1; }
+        if (heavy->size() > SWD_MAX_HEAVY) { set_error(SWD_ERR_CAPACITY, "%d heavy columns exceed this build's bound %d", (int)heavy->size(), SWD_MAX_HEAVY); return -1; }
         hv_ptr.push_back(0);
         for (size_t h = 0; h < heavy->size(); ++h) {
             const int v = (*heavy)[h];
@@ -349,7 +363,7 @@ int Graph::build(const swd_graph_desc *g, const std::vector<int32_t> *heavy) {
         }
     }
     for (int v = 0; v < n; ++v) {
-        if (ldeg[v] > SWD_MAX_COL_DEG) { set_error("column %d has weight %d > %d", v, ldeg[v], SWD_MAX_COL_DEG); return -1; }
+        if (ldeg[v] > SWD_MAX_COL_DEG) { set_error(SWD_ERR_CAPACITY, "column %d has weight %d > %d", v, ldeg[v], SWD_MAX_COL_DEG); return -1; }
         D = std::max(D, ldeg[v]);
         col_deg[v] = (uint8_t)ldeg[v];
     }
@@ -557,6 +571,7 @@ extern "C" int swd_graph_cache_image(const swd_graph_desc *g, int32_t pads, int3
 }
 
 extern "C" const char *swd_last_error(void) { return swd::last_error(); }
+extern "C" int swd_last_error_class(void) { return swd::last_error_class(); }
 extern "C" int swd_abi_version(void) { return SWD_ABI_VERSION; }
 extern "C" int swd_device_count(void) {
     int c = 0;

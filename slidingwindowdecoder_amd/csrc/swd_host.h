@@ -16,13 +16,19 @@
 
 namespace swd {
 
+// The calling thread's failure: a message and, beside it, its class (include/swd.h, swd_error_class).  Without a class: SWD_ERR_FAILED.
+// What reacts to a failure -- a create that falls back to a general form, the Python surface choosing an exception -- reads
+// last_error_class(), never the text.
 void set_error(const char *fmt, ...);
+void set_error(swd_error_class cls, const char *fmt, ...);
+const char *last_error();
+swd_error_class last_error_class();
 
 #define SWD_HIP(expr)                                                                         \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \
         if (_e != hipSuccess) {                                                               \
-            swd::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__,   \
+            swd::set_error(SWD_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
                            __LINE__);                                                         \
             return -1;                                                                        \
         }                                                                                     \
@@ -50,7 +56,7 @@ struct DevBuf {
         size_t got = want;
         if (e != hipSuccess && want > bytes) { (void)hipGetLastError(); e = hipMalloc(&q, bytes); got = bytes; }
         if (e != hipSuccess) {
-            swd::set_error("hipMalloc(%zu bytes) failed: %s (%s:%d)", bytes, hipGetErrorString(e), __FILE__, __LINE__);
+            swd::set_error(SWD_ERR_DEVICE, "hipMalloc(%zu bytes) failed: %s (%s:%d)", bytes, hipGetErrorString(e), __FILE__, __LINE__);
             return -1;
         }
         if (p) retired.push_back(p);

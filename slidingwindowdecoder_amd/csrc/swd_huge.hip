@@ -393,8 +393,8 @@ struct Huge : HugeHost {
 HugeIface *huge_create(const swd_graph_desc *g, const swd_osdw_params *p, int device) {
     if (HugeHost::check_desc(g)) return nullptr;
     const int m = g->m, n = g->n, E = g->nnz;
-    if (m > 4096) { set_error("m=%d exceeds the general form's limit of 4096 checks (64 words per column of the elimination's transform matrix)", m); return nullptr; }
-    if ((long long)n > (1 << 22)) { set_error("n=%d exceeds the general form's limit of 4194304 columns", n); return nullptr; }
+    if (m > 4096) { set_error(SWD_ERR_CAPACITY, "m=%d exceeds the general form's limit of 4096 checks (64 words per column of the elimination's transform matrix)", m); return nullptr; }
+    if ((long long)n > (1 << 22)) { set_error(SWD_ERR_CAPACITY, "n=%d exceeds the general form's limit of 4194304 columns", n); return nullptr; }
     std::unique_ptr<Huge> h(new Huge());
     SwdHugeArgs &a = h->tmpl;
     CsrHost c;
@@ -403,7 +403,7 @@ HugeIface *huge_create(const swd_graph_desc *g, const swd_osdw_params *p, int de
     h->new_n = (p->new_n <= 0) ? std::min(n, 2 * m) : std::min(p->new_n, n); // osd_window.pyx:60-63
     const int order = p->osd_method == 0 ? 0 : p->osd_order;
     if (order > h->new_n - h->rank) {
-        set_error("For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", h->new_n - h->rank);
+        set_error(SWD_ERR_VALUE, "For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", h->new_n - h->rank);
         return nullptr;
     }
     if (p->osd_method == 1 && order > 15) { set_error("osd_e supports osd_order <= 15 on the device"); return nullptr; }

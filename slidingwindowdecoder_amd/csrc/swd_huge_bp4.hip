@@ -335,25 +335,25 @@ struct HugeBp4 : HugeBp4Iface {
 HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz, const double *llr, int device, bool bp,
                               const swd_bp4_params *osd) {
     if (HugeHost::check_desc(hx) || HugeHost::check_desc(hz)) return nullptr;
-    if (hx->n != hz->n) { set_error("Hx, Hz blocklength does not match!"); return nullptr; }
+    if (hx->n != hz->n) { set_error(SWD_ERR_VALUE, "Hx, Hz blocklength does not match!"); return nullptr; }
     const int n = hx->n;
     // the bounds of the form: int32 ids with room for the strided loops' increments, and one scratch allocation per launch slot
-    if ((long long)n > (1 << 20)) { set_error("n=%d exceeds bp4_osd's general form limit of 1048576 qubits", n); return nullptr; }
+    if ((long long)n > (1 << 20)) { set_error(SWD_ERR_CAPACITY, "n=%d exceeds bp4_osd's general form limit of 1048576 qubits", n); return nullptr; }
     for (const swd_graph_desc *g : {hx, hz})
-        if ((long long)g->m > (1 << 20)) { set_error("m=%d exceeds bp4_osd's general form limit of 1048576 checks per matrix", g->m); return nullptr; }
+        if ((long long)g->m > (1 << 20)) { set_error(SWD_ERR_CAPACITY, "m=%d exceeds bp4_osd's general form limit of 1048576 checks per matrix", g->m); return nullptr; }
     if ((long long)hx->nnz + hz->nnz > (1ll << 26)) {
-        set_error("%lld edges exceed bp4_osd's general form limit of 67108864 edges in Hx and Hz together", (long long)hx->nnz + hz->nnz);
+        set_error(SWD_ERR_CAPACITY, "%lld edges exceed bp4_osd's general form limit of 67108864 edges in Hx and Hz together", (long long)hx->nnz + hz->nnz);
         return nullptr;
     }
     if (osd)
         for (const swd_graph_desc *g : {hx, hz})
             if (g->m > 4096) {
-                set_error("m=%d exceeds the general OSD's limit of 4096 checks per matrix (64 words per column of the elimination's transform matrix)", g->m);
+                set_error(SWD_ERR_CAPACITY, "m=%d exceeds the general OSD's limit of 4096 checks per matrix (64 words per column of the elimination's transform matrix)", g->m);
                 return nullptr;
             }
     std::unique_ptr<HugeBp4> h(new HugeBp4());
     h->device = device; h->mx = hx->m; h->mz = hz->m; h->n = n; h->has_bp = bp; h->has_osd = osd != nullptr;
-    if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return nullptr; }
+    if (hipSetDevice(device) != hipSuccess) { set_error(SWD_ERR_DEVICE, "hipSetDevice(%d) failed", device); return nullptr; }
     CsrHost c[2];
     std::vector<int32_t> node[2];
     const swd_graph_desc *gs[2] = {hx, hz};
@@ -374,7 +374,7 @@ HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz
     }
     if (osd) {
         const int kmin = std::min(n - h->rank_x, n - h->rank_z);
-        if (osd->osd_order > kmin) { set_error("For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", kmin); return nullptr; }
+        if (osd->osd_order > kmin) { set_error(SWD_ERR_VALUE, "For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", kmin); return nullptr; }
         if (osd->osd_order > 0 && h->rank_x < h->rank_z) {
             set_error("higher-order OSD with rank(Hx) < rank(Hz) is undefined in the reference (kz = n - rank_x: it reads past its column array) and not supported");
             return nullptr;
@@ -398,7 +398,7 @@ HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz
     if (h->graph.reserve(off.back())) return nullptr;
     char *d = (char *)h->graph.p;
     for (size_t i = 0; i < seg.size(); ++i)
-        if (hipMemcpy(d + off[i], seg[i].src, seg[i].bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy of the graph failed"); return nullptr; }
+        if (hipMemcpy(d + off[i], seg[i].src, seg[i].bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error(SWD_ERR_DEVICE, "hipMemcpy of the graph failed"); return nullptr; }
     SwdHugeBp4Args &a = h->tmpl;
     auto ip = [&](int i) { return (const int32_t *)(d + off[i]); };
     a.gx = HugeGraphDev{hx->m, n, ip(0), ip(1), ip(2), ip(3), ip(4), (const double *)(d + off[15])}; a.r2cx = ip(5); a.nodex = ip(6);
@@ -442,7 +442,7 @@ HugeBp4Iface *huge_bp4_create(const swd_graph_desc *hx, const swd_graph_desc *hz
         o.o_lc = tk((size_t)std::max(mm, n) * 4); o.o_best = tk(64); o.o_bak = tk((size_t)n); o.o_hard = tk((size_t)n);
         o.stride = st;
         if (st > HugeBp4::kSlotBytes) {
-            set_error("the elimination needs %lld bytes per workgroup, which exceeds the general OSD's limit of %lld bytes (8 GiB) per launch slot",
+            set_error(SWD_ERR_CAPACITY, "the elimination needs %lld bytes per workgroup, which exceeds the general OSD's limit of %lld bytes (8 GiB) per launch slot",
                       (long long)st, (long long)HugeBp4::kSlotBytes);
             return nullptr;
         }

@@ -432,7 +432,7 @@ struct HugeHost : HugeIface {
         if (csr_check_rows(m, n, c.row_ptr, c.col_idx)) return -1;
         csr_transpose(m, n, g->channel_probs, r2c != nullptr, c);
         npad = 2; while (npad < n) npad <<= 1;
-        if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return -1; }
+        if (hipSetDevice(device) != hipSuccess) { set_error(SWD_ERR_DEVICE, "hipSetDevice(%d) failed", device); return -1; }
         const struct { const void *src; size_t bytes; } seg[7] = {
             {c.row_ptr.data(), (size_t)(m + 1) * 4}, {c.col_idx.data(), E * 4}, {c.col_ptr.data(), (size_t)(n + 1) * 4}, {c.row_idx.data(), E * 4},
             {c.c2r.data(), E * 4}, {c.llr.data(), (size_t)n * 8}, {c.r2c.data(), r2c ? E * 4 : 0}};
@@ -441,7 +441,7 @@ struct HugeHost : HugeIface {
         if (graph.reserve(off[7])) return -1;
         char *d = (char *)graph.p;
         for (int i = 0; i < 7; ++i)
-            if (seg[i].bytes && hipMemcpy(d + off[i], seg[i].src, seg[i].bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy of the graph failed"); return -1; }
+            if (seg[i].bytes && hipMemcpy(d + off[i], seg[i].src, seg[i].bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error(SWD_ERR_DEVICE, "hipMemcpy of the graph failed"); return -1; }
         *gd = HugeGraphDev{m, n, (const int32_t *)(d + off[0]), (const int32_t *)(d + off[1]), (const int32_t *)(d + off[2]),
                            (const int32_t *)(d + off[3]), (const int32_t *)(d + off[4]), (const double *)(d + off[5])};
         if (r2c) *r2c = (const int32_t *)(d + off[6]);

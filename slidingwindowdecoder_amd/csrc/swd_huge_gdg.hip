@@ -679,10 +679,10 @@ struct HugeGdg : HugeHost {
 HugeIface *huge_gdg_create(const swd_graph_desc *g, const swd_gdg_params *p, int device) {
     if (HugeHost::check_desc(g)) return nullptr;
     const int m = g->m, n = g->n, E = g->nnz;
-    if (m > 4096) { set_error("m=%d exceeds the guessing decoders' general form limit of 4096 checks", m); return nullptr; }
-    if ((long long)n > (1 << 22)) { set_error("n=%d exceeds the guessing decoders' general form limit of 4194304 columns", n); return nullptr; }
+    if (m > 4096) { set_error(SWD_ERR_CAPACITY, "m=%d exceeds the guessing decoders' general form limit of 4096 checks", m); return nullptr; }
+    if ((long long)n > (1 << 22)) { set_error(SWD_ERR_CAPACITY, "n=%d exceeds the guessing decoders' general form limit of 4194304 columns", n); return nullptr; }
     if (p->multi_thread == 2) {
-        set_error("hypotheses= / multi_thread=2 needs a kernel variant, and none takes this graph (m=%d, n=%d) with these parameters: the "
+        set_error(SWD_ERR_CAPACITY, "hypotheses= / multi_thread=2 needs a kernel variant, and none takes this graph (m=%d, n=%d) with these parameters: the "
                   "general form runs the reference's modes only", m, n);
         return nullptr;
     }
@@ -692,7 +692,7 @@ HugeIface *huge_gdg_create(const swd_graph_desc *g, const swd_gdg_params *p, int
     const int NS = std::max(S - D, 0);
     const bool ens = p->mode == 0 && p->multi_thread == 1;
     const int nslots = p->mode == 0 ? (ens ? NS + 2 : max_guess) : 1;
-    if (nslots > 4096) { set_error("%d snapshots per shot exceed the guessing decoders' general form limit of 4096", nslots); return nullptr; }
+    if (nslots > 4096) { set_error(SWD_ERR_CAPACITY, "%d snapshots per shot exceed the guessing decoders' general form limit of 4096", nslots); return nullptr; }
     std::unique_ptr<HugeGdg> h(new HugeGdg());
     SwdHugeGdgArgs &a = h->tmpl;
     CsrHost c;
@@ -700,7 +700,7 @@ HugeIface *huge_gdg_create(const swd_graph_desc *g, const swd_gdg_params *p, int
     // the reference keeps check degrees in char (bpgd.hpp:23, bpgd.cpp:204-223): from 128 on they wrap, no answer is pinned
     for (int r = 0; r < m && p->mode != 2; ++r)
         if (c.row_ptr[r + 1] - c.row_ptr[r] >= 128) {
-            set_error("check %d has weight %d: the guessing decoders' general form takes check weights below 128 (the reference's "
+            set_error(SWD_ERR_CAPACITY, "check %d has weight %d: the guessing decoders' general form takes check weights below 128 (the reference's "
                       "char check degrees wrap there)", r, c.row_ptr[r + 1] - c.row_ptr[r]);
             return nullptr;
         }

@@ -299,17 +299,17 @@ int launch(Plan *d, const SwdPipeArgs &a0, hipStream_t st) {
 static int check_device(int device) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device available: the MI355X decoder has no CPU fallback");
+        set_error(SWD_ERR_DEVICE, "no HIP device available: the MI355X decoder has no CPU fallback");
         return -1;
     }
-    if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return -1; }
-    if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return -1; }
+    if (device < 0 || device >= ndev) { set_error(SWD_ERR_DEVICE, "device %d out of range (%d devices)", device, ndev); return -1; }
+    if (hipSetDevice(device) != hipSuccess) { set_error(SWD_ERR_DEVICE, "hipSetDevice(%d) failed", device); return -1; }
     return 0;
 }
 
 static int check_params(swd_osdw_params &p) {
     if (p.osd_method == 0) p.osd_order = 0; // osd_window.pyx:69-71
-    if (p.osd_method < 0 || p.osd_method > 2) { set_error("ERROR: OSD method '%d' invalid.", p.osd_method); return -1; }
+    if (p.osd_method < 0 || p.osd_method > 2) { set_error(SWD_ERR_VALUE, "ERROR: OSD method '%d' invalid.", p.osd_method); return -1; }
     return 0;
 }
 
@@ -348,9 +348,11 @@ extern "C" swd_osdw *swd_osdw_create(const swd_graph_desc *g, const swd_osdw_par
     d->p = *p;
     std::map<std::string, std::shared_ptr<Graph>> cache;
     if (check_params(d->p)) { delete d; return nullptr; }
-    if (env::on(env::FORCE_HUGE) /* tests: the general form on graphs a variant would take */ || d->add_window(g, 0, 0, 0, cache) || d->finalize(nullptr)) {
+    const bool forced = env::on(env::FORCE_HUGE); // tests: the general form on graphs a variant would take
+    if (forced || d->add_window(g, 0, 0, 0, cache) || d->finalize(nullptr)) {
         // no kernel variant takes this graph (more than 1024 checks, 9216 columns, 65 535 edges, row weight 64 or column weight 10):
         // the general form, every array in HBM (swd_huge.hip) -- the reference's mod2sparse has no size limit
+        if (!forced && last_error_class() != SWD_ERR_CAPACITY) { delete d; return nullptr; } // any other refusal stands: bad input, a failed device call
         d->wins.clear();
         d->huge.reset(huge_create(g, &d->p, device));
         if (!d->huge) { delete d; return nullptr; }
@@ -697,7 +699,7 @@ static int stream_lane_init(StreamLane &l, bool high_priority) {
 static HostStream *stream_new(Plan *d, int max_shots, int flags) {
     if (d->wins.empty() || d->num_col <= 0) { set_error("streaming needs a sliding-window pipeline"); return nullptr; }
     if (max_shots <= 0) { set_error("max_shots must be positive"); return nullptr; }
-    if (hipSetDevice(d->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", d->device); return nullptr; }
+    if (hipSetDevice(d->device) != hipSuccess) { set_error(SWD_ERR_DEVICE, "hipSetDevice(%d) failed", d->device); return nullptr; }
     HostStream *hs = new HostStream();
     hs->plan = d; hs->max_shots = max_shots; hs->flags = flags; hs->device = d->device;
     for (int i = 0; i < 2; ++i)
@@ -963,10 +965,10 @@ extern "C" int swd_pipeline_get_profile(swd_pipeline *h, int32_t B, int64_t *out
 // guessing decoders (bpgdg_decoder / bpgd_decoder / bp_history_decoder)
 // ------------------------------------------------------------------------------------------
 static int check_gdg_params(const swd_gdg_params &gp) {
-    if (gp.mode < 0 || gp.mode > 2) { set_error("gdg mode %d invalid (0 bpgdg, 1 bpgd, 2 bp_history)", gp.mode); return -1; }
-    if (gp.multi_thread < 0 || gp.multi_thread > 2) { set_error("invalid guessing-decoder parameters: multi_thread"); return -1; }
+    if (gp.mode < 0 || gp.mode > 2) { set_error(SWD_ERR_VALUE, "gdg mode %d invalid (0 bpgdg, 1 bpgd, 2 bp_history)", gp.mode); return -1; }
+    if (gp.multi_thread < 0 || gp.multi_thread > 2) { set_error(SWD_ERR_VALUE, "invalid guessing-decoder parameters: multi_thread"); return -1; }
     if (gp.max_iter_per_step < 0 || gp.max_step < 0 || gp.max_tree_depth < 0 || gp.max_tree_depth > 6) {
-        set_error("invalid guessing-decoder parameters"); return -1;
+        set_error(SWD_ERR_VALUE, "invalid guessing-decoder parameters"); return -1;
     }
     return 0;
 }
@@ -980,8 +982,10 @@ extern "C" swd_gdg *swd_gdg_create(const swd_graph_desc *g, const swd_gdg_params
     d->kind = gp->mode + 1;
     d->p.pre_max_iter = gp->max_iter; d->p.osd_order = -1; d->p.ms_scaling_factor = gp->ms_scaling_factor;
     std::map<std::string, std::shared_ptr<Graph>> cache;
-    if (env::on(env::FORCE_HUGE) /* tests: the general form on graphs a variant would take */ || d->add_window(g, 0, 0, 0, cache) || d->finalize(nullptr)) {
+    const bool forced = env::on(env::FORCE_HUGE); // tests: the general form on graphs a variant would take
+    if (forced || d->add_window(g, 0, 0, 0, cache) || d->finalize(nullptr)) {
         // no kernel variant takes this graph: the guessing decoders' general form, every array in HBM (swd_huge_gdg.hip)
+        if (!forced && last_error_class() != SWD_ERR_CAPACITY) { delete d; return nullptr; } // any other refusal stands: bad input, a failed device call
         d->wins.clear();
         d->huge.reset(huge_gdg_create(g, gp, device));
         if (!d->huge) { delete d; return nullptr; }
@@ -1078,6 +1082,7 @@ extern "C" int swd_window_forms(int32_t num_windows, const swd_window_desc *wins
     swd_graph_desc chk{};
     chk.m = num_det; // (select_forms reads the global matrix's dimensions only)
     if (!general) general = d.select_forms(num_det > 0 ? &chk : nullptr) != 0;
+    if (general && last_error_class() != SWD_ERR_CAPACITY) return -1; // input no form takes: the refusal stands
     if (general) d.variant = nullptr; // no window kernel takes the plan: a handle would go to the general form (single windows) or fail
     if (plan) plan_record(&d, plan);
     if (window)

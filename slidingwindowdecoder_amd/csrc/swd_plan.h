@@ -293,7 +293,7 @@ struct Plan {
         else {
             w.g = std::make_shared<Graph>();
             if (w.g->build(gd)) return -1;
-            if (w.g->D > SWD_DMAX) { set_error("column weight %d exceeds this build's bound %d", w.g->D, SWD_DMAX); return -1; }
+            if (w.g->D > SWD_DMAX) { set_error(SWD_ERR_CAPACITY, "column weight %d exceeds this build's bound %d", w.g->D, SWD_DMAX); return -1; }
             // (finalize uploads it: the kernel variant decides how many pad cells its layout may take)
             cache[key] = w.g;
         }
@@ -301,11 +301,11 @@ struct Plan {
         const int req_new_n = (kind == 0) ? p.new_n : gp.new_n;
         w.new_n = (req_new_n <= 0) ? std::min(n, 2 * m) : std::min(req_new_n, n); // osd_window.pyx:60-63
         if (kind == 0 && p.osd_order > w.new_n - w.g->rank) {                              // osd_window.pyx:88-92
-            set_error("For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", w.new_n - w.g->rank);
+            set_error(SWD_ERR_VALUE, "For this code, the OSD order should be set in the range 0<=osd_oder<=%d.", w.new_n - w.g->rank);
             return -1;
         }
         if (commit < 0 || commit > n || row0 < 0 || col0 < 0) { // osd.py:140,170-173: e_hat[:commit] is a slice of the window's estimate
-            set_error("invalid window placement: row0 %d col0 %d commit %d for a window with %d columns", row0, col0, commit, n);
+            set_error(SWD_ERR_VALUE, "invalid window placement: row0 %d col0 %d commit %d for a window with %d columns", row0, col0, commit, n);
             return -1;
         }
         w.row0 = row0; w.col0 = col0; w.commit = commit;
@@ -368,11 +368,11 @@ struct Plan {
         if (kind != 0) {
             max_guess = ((1 << gp.max_tree_depth) - 1) * 2 + gp.max_side_depth - gp.max_tree_depth; // bp_guessing_decoder.pyx:181
             if (max_guess < 0) max_guess = 0;
-            if (max_guess > SWD_GDG_MAXGUESS) { set_error("max_guess=%d exceeds the device limit of %d snapshots", max_guess, SWD_GDG_MAXGUESS); return -1; }
+            if (max_guess > SWD_GDG_MAXGUESS) { set_error(SWD_ERR_CAPACITY, "max_guess=%d exceeds the device limit of %d snapshots", max_guess, SWD_GDG_MAXGUESS); return -1; }
             // parallel form of the tree search (swd_gdg_kernel.h): needs its record formats to hold the parameters
             // (and its work items to hold the unit: item_unit packs the window in 8 bits and the shot in 22, swd_gdg_kernel.h)
             if (gp.multi_thread == 1 && (gp.max_side_depth - gp.max_tree_depth > SWD_GDG_MAXGUESS - 2 || gp.max_tree_depth > 6)) {
-                set_error("multi_thread: at most %d side threads and tree depth 6 on the device", SWD_GDG_MAXGUESS - 2); return -1;
+                set_error(SWD_ERR_CAPACITY, "multi_thread: at most %d side threads and tree depth 6 on the device", SWD_GDG_MAXGUESS - 2); return -1;
             }
             // (... and a tree of at most SWD_GDG_SLOTS snapshots: deeper trees take the serial walk)
             gdg_parallel = kind == 1 && gp.multi_thread != 1 && max_guess <= SWD_GDG_SLOTS && gp.max_side_branch_step <= SWD_GDG_MAXSTEP && gp.max_step < 200 && gp.max_side_depth < 200 &&
@@ -399,14 +399,14 @@ struct Plan {
             variant = big ? select_big_variant(mtop, nmax, dm, ktop, kind) : select_variant(wins, mtop, nmax, dm, ktop, kind);
             if (variant && big && kind == 1 && gp.multi_thread == 1 && !variant->launch_ens) variant = nullptr;
             if (!variant) {
-                set_error("no kernel variant for m=%d n=%d column weight %d row weight %d%s", mtop, nmax, dm, ktop,
+                set_error(SWD_ERR_CAPACITY, "no kernel variant for m=%d n=%d column weight %d row weight %d%s", mtop, nmax, dm, ktop,
                           big ? " (large-graph kernels: up to 1024 checks, 9216 columns, column weight 10, row weight 64)" : "");
                 continue;
             }
             if (big && kind != 0) {
                 bool d2 = true;
                 for (auto &w : wins) d2 = d2 && w.new_n <= 2 * variant->nt;
-                if (!d2) { set_error("guessing decoders on large graphs keep at most %d columns (new_n <= 2 x threads)", 2 * variant->nt); variant = nullptr; continue; }
+                if (!d2) { set_error(SWD_ERR_CAPACITY, "guessing decoders on large graphs keep at most %d columns (new_n <= 2 x threads)", 2 * variant->nt); variant = nullptr; continue; }
                 gdg_parallel = false; // (no work items: the serial tree walk)
                 size_snapshots();     // ... whose snapshot area holds max_guess records per workgroup, not the parallel form's slots
             }
@@ -429,7 +429,7 @@ struct Plan {
             }
             lds_total = off_det + align_up(dmax, 16);
             if (lds_total > 160 * 1024) {
-                set_error("window graph needs %d bytes of LDS per shot (> 163840)%s", lds_total, big ? " even with its messages in HBM" : "");
+                set_error(SWD_ERR_CAPACITY, "window graph needs %d bytes of LDS per shot (> 163840)%s", lds_total, big ? " even with its messages in HBM" : "");
                 variant = nullptr;
                 continue;
             }
@@ -520,7 +520,7 @@ struct Plan {
             for (auto &w : wins)
                 if (w.col0 + w.commit > num_col) { set_error("commit range exceeds the global column count"); return -1; }
             for (auto &w : wins)
-                if (w.row0 + w.g->m > chk->m) { set_error("invalid window placement: rows %d..%d exceed the %d detectors", w.row0, w.row0 + w.g->m, chk->m); return -1; }
+                if (w.row0 + w.g->m > chk->m) { set_error(SWD_ERR_VALUE, "invalid window placement: rows %d..%d exceed the %d detectors", w.row0, w.row0 + w.g->m, chk->m); return -1; }
         }
         return 0;
     }

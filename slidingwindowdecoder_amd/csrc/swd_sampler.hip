@@ -74,8 +74,8 @@ extern "C" swd_sampler *swd_sampler_create(const swd_graph_desc *chk, const swd_
     if (obs && (obs->m > 32 || obs->n != chk->n)) { set_error("observable matrix must be (<= 32) x %d", chk->n); return nullptr; }
     {
         int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: the MI355X decoder has no CPU fallback"); return nullptr; }
-        if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return nullptr; }
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error(SWD_ERR_DEVICE, "no HIP device available: the MI355X decoder has no CPU fallback"); return nullptr; }
+        if (device < 0 || device >= ndev) { set_error(SWD_ERR_DEVICE, "device %d out of range (%d devices)", device, ndev); return nullptr; }
     }
     Sampler *s = new Sampler();
     s->device = device; s->num_det = chk->m; s->num_col = chk->n; s->num_obs = obs ? obs->m : 0;
@@ -112,7 +112,7 @@ extern "C" swd_sampler *swd_sampler_create(const swd_graph_desc *chk, const swd_
     memcpy(&h[o_rows], rows.data(), rows.size() * 2); memcpy(&h[o_obs], omask.data(), n * 4);
     if (hipSetDevice(device) != hipSuccess || s->buf.reserve(total) ||
         hipMemcpy(s->buf.p, h.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("sampler: device allocation failed on device %d", device);
+        set_error(SWD_ERR_DEVICE, "sampler: device allocation failed on device %d", device);
         delete s;
         return nullptr;
     }
@@ -185,7 +185,7 @@ struct LdsRows {
         for (int r = r0; r < r1; ++r) {
             if (g->row_ptr[r] > g->row_ptr[r + 1] || g->row_ptr[r] < 0) { set_error("%s: row_ptr is not monotone", what); return -1; }
             for (int e = g->row_ptr[r]; e < g->row_ptr[r + 1]; ++e) {
-                if (g->col_idx[e] < 0 || g->col_idx[e] >= n) { set_error("%s: column out of range", what); return -1; }
+                if (g->col_idx[e] < 0 || g->col_idx[e] >= n) { set_error(SWD_ERR_VALUE, "%s: column out of range", what); return -1; }
                 idx.push_back((uint16_t)(base + g->col_idx[e]));
             }
             ptr.push_back((uint32_t)idx.size());
@@ -196,8 +196,8 @@ struct LdsRows {
 
 int capacity_device_ok(int device) {
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: the MI355X decoder has no CPU fallback"); return -1; }
-    if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return -1; }
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error(SWD_ERR_DEVICE, "no HIP device available: the MI355X decoder has no CPU fallback"); return -1; }
+    if (device < 0 || device >= ndev) { set_error(SWD_ERR_DEVICE, "device %d out of range (%d devices)", device, ndev); return -1; }
     return 0;
 }
 
@@ -310,7 +310,7 @@ extern "C" swd_pauli_sampler *swd_pauli_sampler_create(const swd_graph_desc *hx,
     if (hx->n != hz->n) { set_error("Hx, Hz blocklength does not match!"); return nullptr; }
     const int n = hx->n, n4 = (n + 3) & ~3;
     if (n > kCapacityMaxN || (int64_t)hx->m + hz->m > 65535) {
-        set_error("Pauli sampler: %d qubits, %d + %d checks out of range (%d qubits, 65535 checks)", n, hx->m, hz->m, kCapacityMaxN);
+        set_error(SWD_ERR_VALUE, "Pauli sampler: %d qubits, %d + %d checks out of range (%d qubits, 65535 checks)", n, hx->m, hz->m, kCapacityMaxN);
         return nullptr;
     }
     if (capacity_device_ok(device)) return nullptr;
@@ -319,10 +319,10 @@ extern "C" swd_pauli_sampler *swd_pauli_sampler_create(const swd_graph_desc *hx,
     for (int q = 0; q < n; ++q) {
         const double x = px[q], y = py[q], z = pz[q], xy = x + y, xyz = xy + z;
         if (!(x >= 0.0 && x <= 1.0) || !(y >= 0.0 && y <= 1.0) || !(z >= 0.0 && z <= 1.0)) {
-            set_error("qubit %d: (%g, %g, %g) are not probabilities", q, x, y, z);
+            set_error(SWD_ERR_VALUE, "qubit %d: (%g, %g, %g) are not probabilities", q, x, y, z);
             return nullptr;
         }
-        if (!(xyz <= 1.0)) { set_error("qubit %d: px + py + pz = %.17g exceeds 1", q, xyz); return nullptr; }
+        if (!(xyz <= 1.0)) { set_error(SWD_ERR_VALUE, "qubit %d: px + py + pz = %.17g exceeds 1", q, xyz); return nullptr; }
         thr[q] = threshold(x); thr[n4 + q] = threshold(xy); thr[2 * (size_t)n4 + q] = threshold(xyz);
     }
     LdsRows rows; // sx = Hx err_z reads the Z string at byte n4, sz = Hz err_x the X string at byte 0
@@ -335,7 +335,7 @@ extern "C" swd_pauli_sampler *swd_pauli_sampler_create(const swd_graph_desc *hx,
     memcpy(&h[o_thr], thr.data(), thr.size() * 4); memcpy(&h[o_ptr], rows.ptr.data(), rows.ptr.size() * 4);
     if (!rows.idx.empty()) memcpy(&h[o_idx], rows.idx.data(), rows.idx.size() * 2);
     if (hipSetDevice(device) != hipSuccess || s->buf.reserve(total) || hipMemcpy(s->buf.p, h.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("Pauli sampler: device allocation failed on device %d", device);
+        set_error(SWD_ERR_DEVICE, "Pauli sampler: device allocation failed on device %d", device);
         delete s;
         return nullptr;
     }
@@ -421,7 +421,7 @@ extern "C" swd_css_account *swd_css_account_create(const swd_graph_desc *cx, int
     memcpy(&h[0], lr.ptr.data(), lr.ptr.size() * 4);
     if (!lr.idx.empty()) memcpy(&h[o_idx], lr.idx.data(), lr.idx.size() * 2);
     if (hipSetDevice(device) != hipSuccess || a->buf.reserve(total) || hipMemcpy(a->buf.p, h.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("CSS accounting: device allocation failed on device %d", device);
+        set_error(SWD_ERR_DEVICE, "CSS accounting: device allocation failed on device %d", device);
         delete a;
         return nullptr;
     }
@@ -748,13 +748,13 @@ extern "C" swd_rolling_sampler *swd_rolling_sampler_create(const swd_graph_desc 
                                                            int32_t j1, const int64_t *anchor_cols, int32_t num_blocks, int device) {
     if (!chk || !chk->row_ptr || !chk->col_idx || !chk->channel_probs || !anchor_cols) { set_error("null argument"); return nullptr; }
     const int h = n_half, n = chk->n, nb = num_blocks;
-    if (h <= 0 || h > 65535 / 2) { set_error("rolling sampler: n_half = %d out of range (1 .. 32767: a column's rows are 16-bit offsets within two blocks)", h); return nullptr; }
-    if (nb <= 0 || n <= 0 || (int64_t)chk->m != (int64_t)nb * h) { set_error("rolling sampler: %d detector rows are not %d blocks of %d", chk->m, nb, h); return nullptr; }
-    if (obs && (!obs->row_ptr || !obs->col_idx || obs->m > 32 || obs->n != n)) { set_error("observable matrix must be (<= 32) x %d: at most 32 observables", n); return nullptr; }
-    if (j0 < 0 || j1 <= j0 || j1 > nb - 1) { set_error("rolling sampler: body blocks %d .. %d are not within the %d blocks (a tail block must follow)", j0, j1 - 1, nb); return nullptr; }
-    if (anchor_cols[0] != 0 || anchor_cols[nb] != n) { set_error("rolling sampler: anchor columns must run from 0 to %d", n); return nullptr; }
+    if (h <= 0 || h > 65535 / 2) { set_error(SWD_ERR_VALUE, "rolling sampler: n_half = %d out of range (1 .. 32767: a column's rows are 16-bit offsets within two blocks)", h); return nullptr; }
+    if (nb <= 0 || n <= 0 || (int64_t)chk->m != (int64_t)nb * h) { set_error(SWD_ERR_VALUE, "rolling sampler: %d detector rows are not %d blocks of %d", chk->m, nb, h); return nullptr; }
+    if (obs && (!obs->row_ptr || !obs->col_idx || obs->m > 32 || obs->n != n)) { set_error(SWD_ERR_VALUE, "observable matrix must be (<= 32) x %d: at most 32 observables", n); return nullptr; }
+    if (j0 < 0 || j1 <= j0 || j1 > nb - 1) { set_error(SWD_ERR_VALUE, "rolling sampler: body blocks %d .. %d are not within the %d blocks (a tail block must follow)", j0, j1 - 1, nb); return nullptr; }
+    if (anchor_cols[0] != 0 || anchor_cols[nb] != n) { set_error(SWD_ERR_VALUE, "rolling sampler: anchor columns must run from 0 to %d", n); return nullptr; }
     for (int b = 0; b < nb; ++b)
-        if (anchor_cols[b + 1] <= anchor_cols[b]) { set_error("rolling sampler: anchor columns must increase (block %d)", b); return nullptr; }
+        if (anchor_cols[b + 1] <= anchor_cols[b]) { set_error(SWD_ERR_VALUE, "rolling sampler: anchor columns must increase (block %d)", b); return nullptr; }
     if (capacity_device_ok(device)) return nullptr;
     const int E = chk->row_ptr[chk->m];
     std::vector<uint32_t> thr(n), colptr(n + 1, 0), omask(n, 0);
@@ -779,7 +779,7 @@ extern "C" swd_rolling_sampler *swd_rolling_sampler_create(const swd_graph_desc 
             for (int e = chk->row_ptr[r]; e < chk->row_ptr[r + 1]; ++e) {
                 const int c = chk->col_idx[e], b = block_of[c];
                 if (r < b * h || r >= (b + 2) * h) { // (r < chk->m = nb h holds: the last block keeps to its own rows)
-                    set_error("rolling sampler: column %d of round block %d touches row %d, outside the rows [%d, %d) of blocks %d and %d", c, b, r,
+                    set_error(SWD_ERR_VALUE, "rolling sampler: column %d of round block %d touches row %d, outside the rows [%d, %d) of blocks %d and %d", c, b, r,
                               b * h, (b + 2) * h, b, b + 1);
                     return nullptr;
                 }
@@ -789,7 +789,7 @@ extern "C" swd_rolling_sampler *swd_rolling_sampler_create(const swd_graph_desc 
     if (obs)
         for (int k = 0; k < obs->m; ++k)
             for (int e = obs->row_ptr[k]; e < obs->row_ptr[k + 1]; ++e) {
-                if (obs->col_idx[e] < 0 || obs->col_idx[e] >= n) { set_error("observable matrix: column out of range"); return nullptr; }
+                if (obs->col_idx[e] < 0 || obs->col_idx[e] >= n) { set_error(SWD_ERR_VALUE, "observable matrix: column out of range"); return nullptr; }
                 omask[obs->col_idx[e]] ^= 1u << k;
             }
     // the body blocks: translates of block j0 -- the rows are relative already
@@ -797,7 +797,7 @@ extern "C" swd_rolling_sampler *swd_rolling_sampler_create(const swd_graph_desc 
     for (int j = j0 + 1; j < j1; ++j) {
         const int64_t aj = anchor_cols[j];
         if (anchor_cols[j + 1] - aj != cs) {
-            set_error("rolling sampler: the body blocks are not translates: block %d has %lld columns, block %d has %lld", j, (long long)(anchor_cols[j + 1] - aj), j0, (long long)cs);
+            set_error(SWD_ERR_VALUE, "rolling sampler: the body blocks are not translates: block %d has %lld columns, block %d has %lld", j, (long long)(anchor_cols[j + 1] - aj), j0, (long long)cs);
             return nullptr;
         }
         for (int64_t i = 0; i < cs; ++i) {
@@ -806,7 +806,7 @@ extern "C" swd_rolling_sampler *swd_rolling_sampler_create(const swd_graph_desc 
             for (uint32_t e = 0; !what && e < da; ++e)
                 if (rows[colptr[a0 + i] + e] != rows[colptr[aj + i] + e]) what = "rows";
             if (what) {
-                set_error("rolling sampler: the body blocks are not translates: column %lld of block %d differs from that of block %d in its %s", (long long)i, j, j0, what);
+                set_error(SWD_ERR_VALUE, "rolling sampler: the body blocks are not translates: column %lld of block %d differs from that of block %d in its %s", (long long)i, j, j0, what);
                 return nullptr;
             }
         }
@@ -821,7 +821,7 @@ extern "C" swd_rolling_sampler *swd_rolling_sampler_create(const swd_graph_desc 
     memcpy(&hb[o_thr], thr.data(), (size_t)n * 4); memcpy(&hb[o_cp], colptr.data(), ((size_t)n + 1) * 4);
     memcpy(&hb[o_rows], rows.data(), rows.size() * 2); memcpy(&hb[o_obs], omask.data(), (size_t)n * 4);
     if (hipSetDevice(device) != hipSuccess || s->buf.reserve(total) || hipMemcpy(s->buf.p, hb.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("rolling sampler: device allocation failed on device %d", device);
+        set_error(SWD_ERR_DEVICE, "rolling sampler: device allocation failed on device %d", device);
         delete s;
         return nullptr;
     }

@@ -269,7 +269,7 @@ extern "C" swd_session *swd_pipeline_session_create(swd_pipeline *h, int32_t max
     if (!d) { set_error("null pipeline"); return nullptr; }
     if (d->wins.empty() || d->num_col <= 0) { set_error("a session needs a sliding-window pipeline"); return nullptr; }
     if (max_shots <= 0) { set_error("max_shots must be positive"); return nullptr; }
-    if (hipSetDevice(d->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", d->device); return nullptr; }
+    if (hipSetDevice(d->device) != hipSuccess) { set_error(SWD_ERR_DEVICE, "hipSetDevice(%d) failed", d->device); return nullptr; }
     Session *s = new Session();
     s->plan = d; s->device = d->device; s->max_shots = max_shots;
     s->W = (int)d->wins.size(); s->num_det = d->num_det; s->num_col = d->num_col;
@@ -289,7 +289,7 @@ extern "C" swd_session *swd_pipeline_session_create(swd_pipeline *h, int32_t max
     s->o_in = s->o_fin + s->fin_bytes;
     if (s->dev.reserve(s->o_in + al(B * s->num_det)) || hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) {
-        if (s->dev.p) set_error("session: stream / event creation failed");
+        if (s->dev.p) set_error(SWD_ERR_DEVICE, "session: stream / event creation failed");
         delete s;
         return nullptr;
     }
@@ -569,7 +569,7 @@ extern "C" swd_rolling *swd_pipeline_rolling_create(swd_pipeline *h, int32_t max
     if (max_shots <= 0) { set_error("max_shots must be positive"); return nullptr; }
     const int n = (int)d->wins.size();
     if (n < 3) { set_error("rolling template: %d windows, a first, a body and a last window are needed", n); return nullptr; }
-    if (hipSetDevice(d->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", d->device); return nullptr; }
+    if (hipSetDevice(d->device) != hipSuccess) { set_error(SWD_ERR_DEVICE, "hipSetDevice(%d) failed", d->device); return nullptr; }
     const WindowHost &w0 = d->wins[0], &w1 = d->wins[1], &wl = d->wins[n - 1];
     const int rs = d->wins[2].row0 - w1.row0, cs = d->wins[2].col0 - w1.col0;
     if (rs <= 0 || cs <= 0 || w0.row0 != 0 || w0.col0 != 0 || w1.row0 != rs || w1.g->m != w0.g->m || w1.commit != cs || w0.commit != w1.col0 ||
@@ -628,7 +628,7 @@ extern "C" swd_rolling *swd_pipeline_rolling_create(swd_pipeline *h, int32_t max
     if (r->dev.reserve(r->dev_bytes) || r->wins3.reserve(3 * sizeof(SwdWindowDev)) ||
         hipMemcpy(r->wins3.p, hw.data(), 3 * sizeof(SwdWindowDev), hipMemcpyHostToDevice) != hipSuccess ||
         hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&r->ev, hipEventDisableTiming) != hipSuccess) {
-        if (r->dev.p) set_error("rolling session: descriptor copy / stream / event creation failed");
+        if (r->dev.p) set_error(SWD_ERR_DEVICE, "rolling session: descriptor copy / stream / event creation failed");
         delete r;
         return nullptr;
     }

@@ -111,10 +111,7 @@ class osd_window(_Handle):
                             int(new_n) if new_n else 0, method, order)
         self._h = L.swd_osdw_create(C.byref(self._csr.desc), C.byref(p), self.device)
         if not self._h:
-            msg = _lib.last_error()
-            if "OSD order" in msg or "invalid" in msg:
-                raise ValueError(msg)
-            raise RuntimeError(f"swd_osdw_create failed: {msg}")
+            raise _lib.error("swd_osdw_create")
         i = [C.c_int32() for _ in range(4)]
         L.swd_osdw_info(self._h, *[C.byref(x) for x in i])
         self.new_n, self.rank = i[2].value, i[3].value
@@ -147,7 +144,7 @@ class osd_window(_Handle):
         rc = _lib.lib().swd_osdw_decode_batch(self._h, 1, s.ctypes.data, out.ctypes.data, st.ctypes.data,
                                               pm.ctypes.data, self._hist.ctypes.data, 1, osd0.ctypes.data, bpd.ctypes.data)
         if rc:
-            raise RuntimeError(f"swd_osdw_decode_batch failed: {_lib.last_error()}")
+            raise _lib.error("swd_osdw_decode_batch")
         self._last = dict(status=int(st[0]), iters=int(st[1]), min_pm=float(pm[0]))
         res = out.astype(np.int64)
         if (int(st[0]) & 0xFF) == EXIT_OSD:
@@ -176,7 +173,7 @@ class osd_window(_Handle):
                                               pm.ctypes.data, hist.ctypes.data if hist is not None else None, 0,
                                               osd0.ctypes.data if osd0 is not None else None, None)
         if rc:
-            raise RuntimeError(f"swd_osdw_decode_batch failed: {_lib.last_error()}")
+            raise _lib.error("swd_osdw_decode_batch")
         self.last_stats = st
         self.last_status, self.last_iterations, self.last_min_pm = st[:, 0].copy(), st[:, 1].copy(), pm
         self.last_history, self.last_osd0 = hist, osd0
@@ -197,7 +194,7 @@ class osd_window(_Handle):
                                                   out.stride(0), stats.data_ptr(), min_pm.data_ptr(), None, 0, None, None,
                                                   st.cuda_stream)
         if rc:
-            raise RuntimeError(f"swd_osdw_decode_batch_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_osdw_decode_batch_dev")
         return out, stats, min_pm
 
     def set_timing(self, on=True):
@@ -305,7 +302,7 @@ def _last_form(name, handle, nwin):
     plan = np.zeros(_lib.FORM_PLAN_WORDS, np.int32)
     wins = np.full((max(nwin, 1), _lib.FORM_WINDOW_WORDS), -1, np.int32)
     if getattr(_lib.lib(), name)(handle, plan.ctypes.data, wins.ctypes.data):
-        raise RuntimeError(f"{name} failed: {_lib.last_error()}")
+        raise _lib.error(name)
     return _form_dict(plan, wins[:nwin])
 
 
@@ -314,7 +311,8 @@ def window_forms(windows, decoder="osd_window", num_det=0, **kwargs):
     launch (``kind``, ``stream_serial`` and ``depth_launch`` are -1).  ``windows``: a ``windows.WindowPlan`` (a
     ``SlidingWindowDecoder``), or a list of ``(matrix, channel_probs)`` / ``(matrix, channel_probs, row0, col0, commit)`` with
     ``num_det`` rows in the global check matrix (0: one window, as ``osd_window`` / ``bpgdg_decoder`` / ``bpgd_decoder`` take it).
-    ``decoder`` and the keyword arguments are those of the decoder.  A plan no window kernel takes reports ``general=1``."""
+    ``decoder`` and the keyword arguments are those of the decoder.  A plan no window kernel takes reports ``general=1``; input no form
+    takes (a matrix with an empty row, an OSD order out of range) raises ValueError."""
     if hasattr(windows, "windows"):
         num_det = windows.chk.shape[0]
         windows = [(w.mat, w.prior, w.row0, w.col0, w.commit) for w in windows.windows]
@@ -393,7 +391,7 @@ class bp_history_decoder(_Handle):
         p = _gdg_params(kwargs, self._mode)
         self._h = L.swd_gdg_create(C.byref(self._csr.desc), C.byref(p), self.device)
         if not self._h:
-            raise RuntimeError(f"swd_gdg_create failed: {_lib.last_error()}")
+            raise _lib.error("swd_gdg_create")
         self._hist = np.zeros((4, self.n), dtype=np.float64)
         self._last = dict(status=0, iters=0, min_pm=0.0)
 
@@ -405,7 +403,7 @@ class bp_history_decoder(_Handle):
         rc = _lib.lib().swd_gdg_decode_batch(self._h, 1, s.ctypes.data, out.ctypes.data, st.ctypes.data,
                                              pm.ctypes.data, None, 0)
         if rc:
-            raise RuntimeError(f"swd_gdg_decode_batch failed: {_lib.last_error()}")
+            raise _lib.error("swd_gdg_decode_batch")
         self._last = dict(status=int(st[0]), iters=int(st[1]), min_pm=float(pm[0]))
         return out.astype(np.int64)
 
@@ -421,7 +419,7 @@ class bp_history_decoder(_Handle):
         rc = _lib.lib().swd_gdg_decode_batch(self._h, B, s.ctypes.data, out.ctypes.data, st.ctypes.data,
                                              pm.ctypes.data, None, 0)
         if rc:
-            raise RuntimeError(f"swd_gdg_decode_batch failed: {_lib.last_error()}")
+            raise _lib.error("swd_gdg_decode_batch")
         self.last_stats, self.last_min_pm = st, pm
         self.last_status = st[:, 0].copy()
         return out
@@ -468,7 +466,7 @@ class bpgdg_decoder(bp_history_decoder):
         hist = np.zeros((4, self.n), np.float64)
         rc = _lib.lib().swd_gdg_decode_batch(self._h, 1, s.ctypes.data, out.ctypes.data, st.ctypes.data, pm.ctypes.data, hist.ctypes.data, 0)
         if rc:
-            raise RuntimeError(f"swd_gdg_decode_batch failed: {_lib.last_error()}")
+            raise _lib.error("swd_gdg_decode_batch")
         self._last = dict(status=int(st[0]), iters=int(st[1]), min_pm=float(pm[0]))
         exit_class = int(st[0]) & 0xFF
         if exit_class == EXIT_PRE:  # the pre-processing BP converged: the ensemble object is not touched
@@ -547,11 +545,7 @@ class bp4_osd(_Handle):
                                       self._py.ctypes.data, self._pz.ctypes.data, C.byref(p), self.device,
                                       (1 if kwargs.get("general_form", False) else 0) | (2 if kwargs.get("general_osd", False) else 0))
         if not self._h:
-            msg = _lib.last_error()
-            if "OSD order" in msg or "invalid" in msg or "blocklength" in msg or "heavy columns" in msg or "column weight" in msg \
-                    or "the general form" in msg or "general form limit" in msg or "general OSD" in msg:
-                raise ValueError(msg)
-            raise RuntimeError(f"swd_bp4_create failed: {msg}")
+            raise _lib.error("swd_bp4_create")
         i = [C.c_int32() for _ in range(5)]
         L.swd_bp4_info(self._h, *[C.byref(x) for x in i])
         self.rank_x, self.rank_z = i[3].value, i[4].value
@@ -579,7 +573,7 @@ class bp4_osd(_Handle):
                                              lpr.ctypes.data if details else None, osd0.ctypes.data if details else None,
                                              bpd.ctypes.data if details else None)
         if rc:
-            raise RuntimeError(f"swd_bp4_decode_batch failed: {_lib.last_error()}")
+            raise _lib.error("swd_bp4_decode_batch")
         self.last_stats, self.last_status, self.last_iterations = st, st[:, 0].copy(), st[:, 1].copy()
         self.last_llr, self.last_osd0, self.last_bp_decoding = lpr, osd0, bpd
         return out
@@ -599,7 +593,7 @@ class bp4_osd(_Handle):
         rc = _lib.lib().swd_bp4_decode_batch_dev(self._h, B, synd_x.data_ptr(), synd_z.data_ptr(), out.data_ptr(), stats.data_ptr(),
                                                  llr.data_ptr() if llr is not None else None, None, None, st.cuda_stream)
         if rc:
-            raise RuntimeError(f"swd_bp4_decode_batch_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_bp4_decode_batch_dev")
         return out, stats
 
     @property
@@ -620,7 +614,7 @@ class bp4_osd(_Handle):
         no column is special."""
         c, d = C.c_int32(), C.c_int32()
         if _lib.lib().swd_bp4_heavy_info(self._h, C.byref(c), C.byref(d)):
-            raise RuntimeError(f"swd_bp4_heavy_info failed: {_lib.last_error()}")
+            raise _lib.error("swd_bp4_heavy_info")
         return c.value, d.value
 
     @property
@@ -663,7 +657,7 @@ class bp4_osd(_Handle):
         rc = _lib.lib().swd_bp4_camel_decode_batch(self._h, B, sx.ctypes.data, sz.ctypes.data, out.ctypes.data, st.ctypes.data,
                                                    pm.ctypes.data)
         if rc:
-            raise RuntimeError(f"swd_bp4_camel_decode_batch failed: {_lib.last_error()}")
+            raise _lib.error("swd_bp4_camel_decode_batch")
         self.last_stats, self.last_status, self.last_iterations, self.last_min_pm = st, st[:, 0].copy(), st[:, 1].copy(), pm
         return out
 
@@ -778,10 +772,7 @@ class SlidingWindowDecoder(_Handle):
         self._h = create(self.W, C.cast(descs, C.c_void_p), C.byref(chk.desc), C.byref(p), self.device)
         self._loop = None
         if not self._h:
-            msg = _lib.last_error()
-            if "OSD order" in msg or "invalid" in msg:
-                raise ValueError(msg)
-            if "no kernel variant" in msg or "exceeds" in msg or "needs" in msg:
+            if _lib.last_error_class() == _lib.ERR_CAPACITY:
                 # windows beyond every kernel variant (e.g. the un-windowed [[288,12,18]] model, 2736 x 26 208): the window loop of
                 # /root/reference/osd.py:130-179 as the reference runs it -- one device decoder per window (the general forms,
                 # csrc/swd_huge.hip and csrc/swd_huge_gdg.hip), the residual syndrome det ^ chk @ total_e_hat between windows
@@ -795,7 +786,7 @@ class SlidingWindowDecoder(_Handle):
                 self.num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
                 self._obs_t = sp.csr_matrix(plan.obs.T.astype(np.int32)) if self.num_obs else None
                 return
-            raise RuntimeError(f"swd_pipeline_create failed: {msg}")
+            raise _lib.error("swd_pipeline_create")
         i = [C.c_int32() for _ in range(5)]
         L.swd_pipeline_info(self._h, *[C.byref(x) for x in i])
         self.lds_bytes, self.threads = i[3].value, i[4].value
@@ -807,7 +798,7 @@ class SlidingWindowDecoder(_Handle):
             rp, ci = np.ascontiguousarray(a.indptr, np.int32), np.ascontiguousarray(a.indices, np.int32)
             od = _lib.GraphDesc(a.shape[0], a.shape[1], int(rp[-1]), rp.ctypes.data, ci.ctypes.data, None)
             if L.swd_pipeline_set_observables(self._h, C.byref(od)):
-                raise RuntimeError(f"swd_pipeline_set_observables failed: {_lib.last_error()}")
+                raise _lib.error("swd_pipeline_set_observables")
 
     @property
     def last_form(self):
@@ -840,7 +831,7 @@ class SlidingWindowDecoder(_Handle):
         fn = _lib.lib().swd_pipeline_decode_packed if packed else _lib.lib().swd_pipeline_decode
         rc = fn(self._h, B, d.ctypes.data, total.ctypes.data, st.ctypes.data, pm.ctypes.data, shot.ctypes.data)
         if rc:
-            raise RuntimeError(f"swd_pipeline_decode failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_decode")
         self.last_stats, self.last_min_pm = st, pm
         self.last_obs_flips, self.last_flagged = shot[:, 0].astype(np.uint32), shot[:, 1].astype(bool)
         return total
@@ -957,7 +948,7 @@ class SlidingWindowDecoder(_Handle):
                                                 shot_result.data_ptr() if shot_result is not None else None,
                                                 st.cuda_stream)
         if rc:
-            raise RuntimeError(f"swd_pipeline_decode_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_decode_dev")
         return total, stats, min_pm
 
     def check_status(self):
@@ -968,7 +959,7 @@ class SlidingWindowDecoder(_Handle):
             return
         flags = C.c_uint32(0)
         if _lib.lib().swd_pipeline_status(self._h, C.byref(flags)):
-            raise RuntimeError(f"swd_pipeline_status failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_status")
         if flags.value:
             raise RuntimeError(f"sliding-window pipeline recorded a scheduling fault (flags 0x{flags.value:x})")
 
@@ -1003,7 +994,7 @@ class SlidingWindowStream(_Handle):
         flags = (_lib.STREAM_PACKED if packed else 0) | (0 if want_stats else _lib.STREAM_NO_STATS)
         self._h = _lib.lib().swd_pipeline_stream_create(dec._h, self.max_shots, flags)
         if not self._h:
-            raise RuntimeError(f"swd_pipeline_stream_create failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_stream_create")
         self._sizes = []
 
     close = _Handle._release
@@ -1015,7 +1006,7 @@ class SlidingWindowStream(_Handle):
     def push(self, det_data):
         d = self.dec._check_det(det_data)
         if _lib.lib().swd_pipeline_stream_push(self._h, d.shape[0], d.ctypes.data):
-            raise RuntimeError(f"swd_pipeline_stream_push failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_stream_push")
         self._sizes.append(d.shape[0])  # (the library has copied the detector bytes into its page-locked block)
 
     def pop(self):
@@ -1030,7 +1021,7 @@ class SlidingWindowStream(_Handle):
         rc = _lib.lib().swd_pipeline_stream_pop(self._h, total.ctypes.data, st.ctypes.data if st is not None else None,
                                                 pm.ctypes.data if pm is not None else None, shot.ctypes.data)
         if rc != B:
-            raise RuntimeError(f"swd_pipeline_stream_pop failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_stream_pop")
         return total, st, pm, shot[:, 0].astype(np.uint32), shot[:, 1].astype(bool)
 
     def push_device(self, det, total, stats=None, min_pm=None, shot_result=None, after=None):
@@ -1051,18 +1042,18 @@ class SlidingWindowStream(_Handle):
                                                      min_pm.data_ptr() if min_pm is not None else None,
                                                      shot_result.data_ptr() if shot_result is not None else None, aft)
         if rc:
-            raise RuntimeError(f"swd_pipeline_stream_push_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_stream_push_dev")
 
     def wait(self, stream=None):
         """stream=None: the host waits for both lanes; a torch stream: that stream waits (device-side)."""
         if _lib.lib().swd_pipeline_stream_wait(self._h, stream.cuda_stream if stream is not None else None):
-            raise RuntimeError(f"swd_pipeline_stream_wait failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_stream_wait")
 
     def wait_last(self, stream):
         """the torch stream ``stream`` waits (device-side) for the lane of the most recent push alone: the batch on the other lane
         stays in flight.  RuntimeError if nothing has been pushed."""
         if _lib.lib().swd_pipeline_stream_wait_last(self._h, stream.cuda_stream or None):
-            raise RuntimeError(f"swd_pipeline_stream_wait_last failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_stream_wait_last")
 
 
 class _SessionBase(_Handle):
@@ -1073,7 +1064,7 @@ class _SessionBase(_Handle):
     def begin(self, B):
         """Zero state for a batch of ``B <= max_shots`` shots; also restarts a session that has been used."""
         if getattr(_lib.lib(), self._C + "_begin")(self._h, int(B)):
-            raise RuntimeError(f"{self._C}_begin failed: {_lib.last_error()}")
+            raise _lib.error(f"{self._C}_begin")
         self.B = int(B)
 
     def _host_rows(self, rows, name="det_rows"):
@@ -1106,12 +1097,12 @@ class SlidingWindowSession(_SessionBase):
         self.dec, self.max_shots, self.B = dec, int(max_shots), 0
         self._h = _lib.lib().swd_pipeline_session_create(dec._h, self.max_shots)
         if not self._h:
-            raise RuntimeError(f"swd_pipeline_session_create failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_session_create")
 
     def _progress(self):
         rows, done = C.c_int32(), C.c_int32()
         if _lib.lib().swd_pipeline_session_buffers(self._h, None, None, C.byref(rows), C.byref(done)):
-            raise RuntimeError(f"swd_pipeline_session_buffers failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_session_buffers")
         return rows.value, done.value
 
     @property
@@ -1134,7 +1125,7 @@ class SlidingWindowSession(_SessionBase):
         faults = np.empty((B, int(w.commit)), np.uint8)
         st, pm = np.empty((B, _lib.STAT_WORDS), np.int32), np.empty(B, np.float64)
         if _lib.lib().swd_pipeline_session_window(self._h, int(t), faults.ctypes.data, st.ctypes.data, pm.ctypes.data):
-            raise RuntimeError(f"swd_pipeline_session_window failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_session_window")
         return int(t), int(w.col0), faults, st, pm
 
     def push(self, det_rows):
@@ -1143,7 +1134,7 @@ class SlidingWindowSession(_SessionBase):
         d = self._host_rows(det_rows)
         first, count = C.c_int32(), C.c_int32()
         if _lib.lib().swd_pipeline_session_push(self._h, d.shape[1], d.ctypes.data, C.byref(first), C.byref(count)):
-            raise RuntimeError(f"swd_pipeline_session_push failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_session_push")
         return [self.window(t) for t in range(first.value, first.value + count.value)]
 
     def push_device(self, det_rows, stream=None):
@@ -1156,7 +1147,7 @@ class SlidingWindowSession(_SessionBase):
         k = det_rows.shape[1]
         if _lib.lib().swd_pipeline_session_push_dev(self._h, k, det_rows.data_ptr() if k else None, det_rows.stride(0) if k else 0,
                                                     C.byref(first), C.byref(count), st.cuda_stream):
-            raise RuntimeError(f"swd_pipeline_session_push_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_session_push_dev")
         return first.value, count.value
 
     def finish(self):
@@ -1167,7 +1158,7 @@ class SlidingWindowSession(_SessionBase):
         st, pm = np.empty((B, dec.W, _lib.STAT_WORDS), np.int32), np.empty((B, dec.W), np.float64)
         shot = np.empty((B, 2), np.int32)
         if _lib.lib().swd_pipeline_session_finish(self._h, total.ctypes.data, st.ctypes.data, pm.ctypes.data, shot.ctypes.data):
-            raise RuntimeError(f"swd_pipeline_session_finish failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_session_finish")
         return total, st, pm, shot[:, 0].astype(np.uint32), shot[:, 1].astype(bool)
 
     def total_device(self):
@@ -1176,7 +1167,7 @@ class SlidingWindowSession(_SessionBase):
         import torch
         ptr, stride = C.c_void_p(), C.c_int64()
         if _lib.lib().swd_pipeline_session_buffers(self._h, C.byref(ptr), C.byref(stride), None, None):
-            raise RuntimeError(f"swd_pipeline_session_buffers failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_session_buffers")
 
         class _View:
             pass
@@ -1210,10 +1201,10 @@ class RollingSession(_SessionBase):
         self.dec, self.max_shots, self.B = dec, int(max_shots), 0
         self._h = _lib.lib().swd_pipeline_rolling_create(dec._h, self.max_shots)
         if not self._h:
-            raise RuntimeError(f"swd_pipeline_rolling_create failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_rolling_create")
         info = (C.c_int32 * 8)()
         if _lib.lib().swd_pipeline_rolling_state(self._h, None, None, None, info, None):
-            raise RuntimeError(f"swd_pipeline_rolling_state failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_rolling_state")
         T = self.template
         self._need, self._cmax = int(info[1]), int(info[7])
         want = [T.frame_rows, T.head.row1, T.row_stride, T.tail.row1 - T.tail.row0, T.head.commit, T.body.commit, T.tail.commit,
@@ -1224,7 +1215,7 @@ class RollingSession(_SessionBase):
     def _state(self):
         rows, done, fill, nbytes = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
         if _lib.lib().swd_pipeline_rolling_state(self._h, C.byref(rows), C.byref(done), C.byref(fill), None, C.byref(nbytes)):
-            raise RuntimeError(f"swd_pipeline_rolling_state failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_rolling_state")
         return rows.value, done.value, fill.value, nbytes.value
 
     @property
@@ -1267,7 +1258,7 @@ class RollingSession(_SessionBase):
         first, count = C.c_int64(), C.c_int32()
         if _lib.lib().swd_pipeline_rolling_push(self._h, d.shape[1], d.ctypes.data, n, faults.ctypes.data, st.ctypes.data, pm.ctypes.data,
                                                 C.byref(first), C.byref(count)):
-            raise RuntimeError(f"swd_pipeline_rolling_push failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_rolling_push")
         return [(first.value + k, faults[k, :, :self._commit(first.value + k)], st[k], pm[k]) for k in range(count.value)]
 
     def push_device(self, det_rows, faults_out=None, stream=None):
@@ -1293,7 +1284,7 @@ class RollingSession(_SessionBase):
         if _lib.lib().swd_pipeline_rolling_push_dev(self._h, k, det_rows.data_ptr() if k else None, det_rows.stride(0) if k else 0, n,
                                                     faults_out.data_ptr() if n else None, stats.data_ptr() if n else None,
                                                     pm.data_ptr() if n else None, C.byref(first), C.byref(count), st.cuda_stream):
-            raise RuntimeError(f"swd_pipeline_rolling_push_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_rolling_push_dev")
         return [(first.value + j, faults_out[j, :, :self._commit(first.value + j)], stats[j], pm[j]) for j in range(count.value)]
 
     def _check_finish(self, k):
@@ -1319,7 +1310,7 @@ class RollingSession(_SessionBase):
         st, pm, shot = np.empty((B, _lib.STAT_WORDS), np.int32), np.empty(B, np.float64), np.empty((B, 2), np.int32)
         if _lib.lib().swd_pipeline_rolling_finish(self._h, d.shape[1], d.ctypes.data, faults.ctypes.data, st.ctypes.data, pm.ctypes.data,
                                                   shot.ctypes.data):
-            raise RuntimeError(f"swd_pipeline_rolling_finish failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_rolling_finish")
         return t, faults, st, pm, shot[:, 0].astype(np.uint32), shot[:, 1].astype(bool)
 
     def finish_device(self, final_rows, stream=None):
@@ -1337,7 +1328,7 @@ class RollingSession(_SessionBase):
             shot = torch.empty((B, 2), dtype=torch.int32, device=dev)
         if _lib.lib().swd_pipeline_rolling_finish_dev(self._h, final_rows.shape[1], final_rows.data_ptr(), final_rows.stride(0),
                                                       faults.data_ptr(), stats.data_ptr(), pm.data_ptr(), shot.data_ptr(), st.cuda_stream):
-            raise RuntimeError(f"swd_pipeline_rolling_finish_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_pipeline_rolling_finish_dev")
         return t, faults, stats, pm, shot[:, 0], shot[:, 1]
 
 
@@ -1378,17 +1369,17 @@ class MeasurementFrontEnd(_Handle):
         self._h = _lib.lib().swd_frontend_create(C.byref(d[0]), C.byref(d[1]), C.byref(d[2]), C.byref(d[3]) if self.num_obs else None,
                                                  blk.meas_per_round, blk.meas_final, blk.n_half, self.max_shots, self.device)
         if not self._h:
-            raise RuntimeError(f"swd_frontend_create failed: {_lib.last_error()}")
+            raise _lib.error("swd_frontend_create")
 
     def begin(self, B):
         if _lib.lib().swd_frontend_begin(self._h, int(B)):
-            raise RuntimeError(f"swd_frontend_begin failed: {_lib.last_error()}")
+            raise _lib.error("swd_frontend_begin")
         self.B = int(B)
 
     def _state(self):
         bits, rounds, info, nbytes = C.c_int64(), C.c_int64(), (C.c_int32 * 8)(), C.c_int64()
         if _lib.lib().swd_frontend_state(self._h, C.byref(bits), C.byref(rounds), info, C.byref(nbytes)):
-            raise RuntimeError(f"swd_frontend_state failed: {_lib.last_error()}")
+            raise _lib.error("swd_frontend_state")
         return bits.value, rounds.value, int(info[4]), bool(info[5]), nbytes.value
 
     @property
@@ -1445,7 +1436,7 @@ class MeasurementFrontEnd(_Handle):
         rows = np.empty((self.B, self.rows_for(nbits) if self.B else 0), np.uint8)
         n = C.c_int32()
         if _lib.lib().swd_frontend_push(self._h, nbits, d.ctypes.data, _is_packed(packed), rows.ctypes.data, C.byref(n)):
-            raise RuntimeError(f"swd_frontend_push failed: {_lib.last_error()}")
+            raise _lib.error("swd_frontend_push")
         assert n.value == rows.shape[1]
         return rows
 
@@ -1456,7 +1447,7 @@ class MeasurementFrontEnd(_Handle):
         rows = np.empty((self.B, self.rows_for(nbits, final=True) if self.B else 0), np.uint8)
         raw, n = np.zeros(self.B, np.uint32), C.c_int32()
         if _lib.lib().swd_frontend_finish(self._h, nbits, d.ctypes.data, _is_packed(packed), rows.ctypes.data, C.byref(n), raw.ctypes.data):
-            raise RuntimeError(f"swd_frontend_finish failed: {_lib.last_error()}")
+            raise _lib.error("swd_frontend_finish")
         return rows, raw
 
     def push_device(self, meas, packed=False, out=None, stream=None):
@@ -1475,7 +1466,7 @@ class MeasurementFrontEnd(_Handle):
         n = C.c_int32()
         if _lib.lib().swd_frontend_push_dev(self._h, nbits, meas.data_ptr() if nbits else None, meas.stride(0) if nbits else 0, _is_packed(packed),
                                             out.data_ptr() if rows else None, out.stride(0) if rows else 0, C.byref(n), st.cuda_stream):
-            raise RuntimeError(f"swd_frontend_push_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_frontend_push_dev")
         return out[:, :rows] if out.shape[1] != rows else out
 
     def finish_device(self, final_meas, packed=False, stream=None):
@@ -1490,7 +1481,7 @@ class MeasurementFrontEnd(_Handle):
         n = C.c_int32()
         if _lib.lib().swd_frontend_finish_dev(self._h, nbits, final_meas.data_ptr(), final_meas.stride(0), _is_packed(packed), out.data_ptr(),
                                               out.stride(0), C.byref(n), raw.data_ptr(), st.cuda_stream):
-            raise RuntimeError(f"swd_frontend_finish_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_frontend_finish_dev")
         return out, raw
 
 
@@ -1663,7 +1654,7 @@ class DemSampler(_Handle):
         self.device = int(device)
         self._h = L.swd_sampler_create(C.byref(self._chk.desc), C.byref(od) if od is not None else None, self.device)
         if not self._h:
-            raise RuntimeError(f"swd_sampler_create failed: {_lib.last_error()}")
+            raise _lib.error("swd_sampler_create")
 
     def sample(self, shots, seed=20240318, first_shot=0, return_faults=False):
         """-> det uint8 [shots, num_det], obs uint8 [shots, num_obs] (, faults uint8 [shots, num_col])."""
@@ -1672,7 +1663,7 @@ class DemSampler(_Handle):
         faults = np.zeros((shots, self.num_col), np.uint8) if return_faults else None
         if _lib.lib().swd_sampler_sample(self._h, shots, int(seed), int(first_shot), det.ctypes.data, flips.ctypes.data,
                                          faults.ctypes.data if return_faults else None):
-            raise RuntimeError(f"swd_sampler_sample failed: {_lib.last_error()}")
+            raise _lib.error("swd_sampler_sample")
         obs = ((flips[:, None] >> np.arange(self.num_obs, dtype=np.uint32)) & 1).astype(np.uint8)
         return (det, obs, faults) if return_faults else (det, obs)
 
@@ -1690,7 +1681,7 @@ class DemSampler(_Handle):
         if _lib.lib().swd_sampler_sample_dev(self._h, shots, int(seed), int(first_shot), det.data_ptr(), 0,
                                              flips.data_ptr() if flips is not None else None,
                                              faults.data_ptr() if faults is not None else None, 0, st.cuda_stream):
-            raise RuntimeError(f"swd_sampler_sample_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_sampler_sample_dev")
         return det[:shots], flips[:shots] if flips is not None else None
 
 
@@ -1721,10 +1712,7 @@ class PauliSampler(_Handle):
         self._h = L.swd_pauli_sampler_create(C.byref(self._cx.desc), C.byref(self._cz.desc), px.ctypes.data, py.ctypes.data,
                                              pz.ctypes.data, self.device)
         if not self._h:
-            msg = _lib.last_error()
-            if "probabilit" in msg or "exceeds 1" in msg or "out of range" in msg:
-                raise ValueError(msg)
-            raise RuntimeError(f"swd_pauli_sampler_create failed: {msg}")
+            raise _lib.error("swd_pauli_sampler_create")
 
     def sample(self, shots, seed=20240318, first_shot=0):
         """-> err uint8 [shots, 2, n] (row 0 the X string, row 1 the Z string), sx uint8 [shots, mx] = Hx err_z,
@@ -1733,7 +1721,7 @@ class PauliSampler(_Handle):
         sx, sz = np.zeros((shots, self.mx), np.uint8), np.zeros((shots, self.mz), np.uint8)
         if _lib.lib().swd_pauli_sampler_sample(self._h, shots, int(seed), int(first_shot), err.ctypes.data, sx.ctypes.data,
                                                sz.ctypes.data):
-            raise RuntimeError(f"swd_pauli_sampler_sample failed: {_lib.last_error()}")
+            raise _lib.error("swd_pauli_sampler_sample")
         return err, sx, sz
 
     def sample_device(self, shots, seed=20240318, first_shot=0, out=None, stream=None):
@@ -1749,7 +1737,7 @@ class PauliSampler(_Handle):
         st = torch.cuda.current_stream(dev) if stream is None else stream
         if _lib.lib().swd_pauli_sampler_sample_dev(self._h, shots, int(seed), int(first_shot), err.data_ptr(), 0, sx.data_ptr(), 0,
                                                    sz.data_ptr(), 0, st.cuda_stream):
-            raise RuntimeError(f"swd_pauli_sampler_sample_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_pauli_sampler_sample_dev")
         return err[:shots], sx[:shots], sz[:shots]
 
 
@@ -1773,7 +1761,7 @@ class _CssAccount(_Handle):
         self._h = _lib.lib().swd_css_account_create(C.byref(descs[0]) if descs[0] is not None else None, int(stab_x),
                                                     C.byref(descs[1]) if descs[1] is not None else None, int(stab_z), int(device))
         if not self._h:
-            raise RuntimeError(f"swd_css_account_create failed: {_lib.last_error()}")
+            raise _lib.error("swd_css_account_create")
 
     def account(self, B, est, err, stats, result, counters, stream):
         """torch tensors (rows may be strided); ``stats`` / ``result`` / ``counters`` may be None."""
@@ -1781,7 +1769,7 @@ class _CssAccount(_Handle):
                                           stats.data_ptr() if stats is not None else None, STATUS_CONVERGE,
                                           result.data_ptr() if result is not None else None,
                                           counters.data_ptr() if counters is not None else None, stream.cuda_stream):
-            raise RuntimeError(f"swd_css_account_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_css_account_dev")
 
 
 class _ErrorRate:
@@ -1955,7 +1943,7 @@ class CodeCapacityExperiment(_LaneExperiment):
                     rc = L.swd_gdg_decode_batch_dev(d._h, B, ln["sx"].data_ptr(), 0, ln["est"].data_ptr(), 0, ln["stats"].data_ptr(),
                                                     ln["min_pm"].data_ptr(), s)
             if rc:
-                raise RuntimeError(f"{self.decoder_name} device decode failed: {_lib.last_error()}")
+                raise _lib.error(f"{self.decoder_name} device decode")
             self._acct.account(B, ln["est"], ln["err"], ln["stats"], ln["result"], counters, st)
             if osd0:
                 self._acct.account(B, ln["osd0"], ln["err"], None, ln["result0"], counters0, st)
@@ -2033,7 +2021,7 @@ def shot_account_device(shot_result, true_flips, stats=None, first_shot=0, resul
     if _lib.lib().swd_shot_account_dev(dev.index, B, W, ptr(shot_result), ptr(true_flips), ptr(stats), int(first_shot), ptr(result),
                                        ptr(counters), ptr(window_counters), ptr(failed), failed.numel() - 1 if failed is not None else 0,
                                        st.cuda_stream or None):
-        raise RuntimeError(f"swd_shot_account_dev failed: {_lib.last_error()}")
+        raise _lib.error("swd_shot_account_dev")
 
 
 def _observable_groups(groups, num_obs):
@@ -2082,7 +2070,7 @@ def group_account_device(shot_result, true_flips, masks, counters, stream=None):
     st = torch.cuda.current_stream(dev) if stream is None else stream
     if _lib.lib().swd_group_account_dev(dev.index, B, shot_result.data_ptr(), true_flips.data_ptr(), len(m), m.ctypes.data, counters.data_ptr(),
                                         st.cuda_stream or None):
-        raise RuntimeError(f"swd_group_account_dev failed: {_lib.last_error()}")
+        raise _lib.error("swd_group_account_dev")
 
 
 class MemoryResult(_ErrorRate):
@@ -2369,9 +2357,7 @@ class RollingDemSampler(_Handle):
         self._h = L.swd_rolling_sampler_create(C.byref(self._chk.desc), C.byref(od) if od is not None else None, int(n_half), int(j0), int(j1),
                                                cols.ctypes.data, len(cols) - 1, self.device)
         if not self._h:
-            msg = _lib.last_error()
-            raise (ValueError if msg.startswith("rolling sampler:") or "observable" in msg else RuntimeError)(
-                f"swd_rolling_sampler_create failed: {msg}")
+            raise _lib.error("swd_rolling_sampler_create", prefix_value=True)
         info = (C.c_int32 * 8)()
         L.swd_rolling_sampler_info(self._h, info, -1, 0, 0, None, None)
         self.n_half, self.num_obs, self.R0, self.min_rounds = int(info[0]), int(info[2]), int(info[3]), int(info[6])
@@ -2413,7 +2399,7 @@ class RollingDemSampler(_Handle):
                                                    out.stride(0) if shots > 1 else 0, flips.data_ptr() if flips is not None else None,
                                                    faults.data_ptr() if faults is not None else None,
                                                    faults.stride(0) if faults is not None and shots > 1 else 0, st.cuda_stream or None):
-            raise RuntimeError(f"swd_rolling_sampler_rows_dev failed: {_lib.last_error()}")
+            raise _lib.error("swd_rolling_sampler_rows_dev")
         return out
 
     def sample(self, shots, rounds, seed=20240318, first_shot=0, return_faults=False):
@@ -2426,7 +2412,7 @@ class RollingDemSampler(_Handle):
         faults = np.zeros((shots, ncols), np.uint8) if return_faults else None
         if _lib.lib().swd_rolling_sampler_rows(self._h, shots, int(seed), int(first_shot), int(rounds), 0, int(rounds) + 1, det.ctypes.data,
                                                flips.ctypes.data, faults.ctypes.data if return_faults else None):
-            raise RuntimeError(f"swd_rolling_sampler_rows failed: {_lib.last_error()}")
+            raise _lib.error("swd_rolling_sampler_rows")
         obs = ((flips[:, None] >> np.arange(self.num_obs, dtype=np.uint32)) & 1).astype(np.uint8)
         return (det, obs, faults) if return_faults else (det, obs)
 
@@ -2582,7 +2568,7 @@ class RollingMemoryExperiment(_MemoryLaneExperiment):
             stats = ln["stats"] if stats_all is None else stats_all[k]
             if L.swd_rolling_sampler_rows_dev(self.sampler._h, B, int(seed), int(first_shot), rounds, b0, n, rows.data_ptr(), rows.stride(0),
                                               flips.data_ptr(), None, 0, sp_):
-                raise RuntimeError(f"swd_rolling_sampler_rows_dev failed: {_lib.last_error()}")
+                raise _lib.error("swd_rolling_sampler_rows_dev")
             sptr = stats.data_ptr() if window_stats else None
             if not last:
                 if L.swd_pipeline_rolling_push_dev(ses._h, n * h, rows.data_ptr(), rows.stride(0), 1, None, sptr, None, C.byref(first),
@@ -2591,16 +2577,16 @@ class RollingMemoryExperiment(_MemoryLaneExperiment):
                 if window_stats and window_counters is not None:  # the counts of this window alone, into the row of its kind
                     if L.swd_shot_account_dev(self.device, B, 1, shot.data_ptr(), flips.data_ptr(), sptr, 0, None, None,
                                               window_counters[min(k, 1)].data_ptr(), None, 0, sp_):
-                        raise RuntimeError(f"swd_shot_account_dev failed: {_lib.last_error()}")
+                        raise _lib.error("swd_shot_account_dev")
                 continue
             if L.swd_pipeline_rolling_finish_dev(ses._h, n * h, rows.data_ptr(), rows.stride(0), None, sptr, None, shot.data_ptr(), sp_):
-                raise RuntimeError(f"swd_pipeline_rolling_finish_dev failed: {_lib.last_error()}")
+                raise _lib.error("swd_pipeline_rolling_finish_dev")
             wins = window_stats and window_counters is not None
             if L.swd_shot_account_dev(self.device, B, 1 if wins else 0, shot.data_ptr(), flips.data_ptr(), sptr if wins else None, int(first_shot),
                                       ln["result"].data_ptr(), counters.data_ptr() if counters is not None else None,
                                       window_counters[2].data_ptr() if wins else None, failed.data_ptr() if failed is not None else None,
                                       failed.numel() - 1 if failed is not None else 0, sp_):
-                raise RuntimeError(f"swd_shot_account_dev failed: {_lib.last_error()}")
+                raise _lib.error("swd_shot_account_dev")
             if groups is not None:
                 group_account_device(shot[:B], flips[:B], groups[0], groups[1], stream=ln["stream"])
 

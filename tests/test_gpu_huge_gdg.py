@@ -257,6 +257,49 @@ def test_window_loop_with_the_guessing_decoder_beyond_every_pipeline_kernel():
         next(dec.decode_stream([det]))
 
 
+def test_window_loop_for_a_plan_beyond_the_large_graph_column_bound():
+    """Two 600 x 2100 windows that keep new_n = 2049 columns: too much LDS for the resident kernels, and the large-graph kernels
+    of the guessing decoders keep at most 2048 -- a size refusal (SWD_ERR_CAPACITY) like every other, so the plan takes the window
+    loop over general-form decoders and equals the same loop over the oracle"""
+    from oracle import oracle as O
+    from slidingwindowdecoder_amd import SlidingWindowDecoder, _lib, window_forms
+    from slidingwindowdecoder_amd.windows import Window, WindowPlan
+    rng = np.random.default_rng(11)
+    m, n = 600, 2100
+    mats = [_rand_h(rng, m, n, 3, ragged=False) for _ in range(2)]
+    assert all(np.diff(H.indptr).min() > 0 for H in mats)
+    pri = np.full(n, 0.01)  # (the three shots leave by the pre-processing BP, by the tree search, and without converging)
+    chk = sp.block_diag(mats, format="csr").astype(np.uint8)
+    wins = [Window(k * m, (k + 1) * m, k * n, n, n, mats[k], pri, k == 1) for k in range(2)]
+    plan = WindowPlan(chk, sp.csr_matrix((0, 2 * n), dtype=np.uint8), np.tile(pri, 2), np.arange(2 * n), [], wins, None, 0)
+    kw = dict(max_iter=8, max_iter_per_step=6, max_step=4, max_tree_depth=2, max_side_depth=4, max_tree_branch_step=4,
+              max_side_branch_step=4, gdg_factor=1.0, ms_scaling_factor=1.0, new_n=2049)
+    assert window_forms(plan, decoder="bpgdg_decoder", **kw)["general"] == 1
+    assert "keep at most 2048 columns" in _lib.last_error() and _lib.last_error_class() == _lib.ERR_CAPACITY
+    assert window_forms(plan, decoder="bpgdg_decoder", **dict(kw, new_n=2048))["big"] == 1  # one column fewer: the large-graph kernel
+    dec = SlidingWindowDecoder(plan, decoder="bpgdg_decoder", **kw)
+    assert dec._loop is not None and len(dec._loop) == 2 and dec.last_form is None
+    e = (rng.random((3, 2 * n)) < 0.01).astype(np.int64)
+    det = ((chk.astype(np.int64) @ e.T).T % 2).astype(np.uint8)
+    total = dec.decode(det)
+    chk_t = sp.csr_matrix(chk.T.astype(np.int32))
+    want = np.zeros_like(total)
+    cur = det.copy()
+    for wi, w in enumerate(plan.windows):
+        o, prev_it = O.bpgdg_decoder(w.mat, channel_probs=w.prior, **kw), 0
+        for k in range(len(det)):
+            o.clear_history()
+            out = o.decode(cur[k, w.row0:w.row1])
+            want[k, w.col0:w.col0 + w.commit] = out[:w.commit]
+            assert bool(dec.last_stats[k, wi, 0] & 0x100) == bool(o.converge), f"window {wi} shot {k}"
+            if (int(dec.last_stats[k, wi, 0]) & 0xFF) != 1:  # (gdg() sets the oracle's count to 0 once BPGD::reset succeeded: _vs_oracle)
+                assert dec.last_stats[k, wi, 2] == o._res.bp_iteration - prev_it, f"window {wi} shot {k}"
+            prev_it = o._res.bp_iteration
+        cur =((det + (sp.csr_matrix(want) @ chk_t).toarray()) % 2).astype(np.uint8)
+    assert np.array_equal(total, want)
+    assert np.array_equal(dec.last_flagged, cur.any(axis=1))
+
+
 def test_device_pointers_on_a_side_stream_equal_the_host_call():
     import torch
     from slidingwindowdecoder_amd import _lib

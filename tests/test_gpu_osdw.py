@@ -211,6 +211,28 @@ def test_constructor_and_decode_errors():
     assert out.dtype == np.int64 and not out.any()
 
 
+def test_refusals_that_are_no_size_matter_never_reach_the_general_form():
+    """an OSD order beyond the code's range and a matrix with an empty row are refused by the tuned set-up with its own message and
+    class; swd_osdw_create returns no handle instead of trying the general form (which has no empty-row check of its own)"""
+    import ctypes as C
+    from slidingwindowdecoder_amd import _lib, osd_window
+    from slidingwindowdecoder_amd.decoders import _Csr
+    f = fx.load("bb72_capacity.npz")
+    H36, priors = fx.graph(f, "c1_")
+    assert H36.shape[0] == 36
+    with pytest.raises(ValueError, match=r"^For this code, the OSD order should be set in the range 0<=osd_oder<=\d+\.$"):
+        osd_window(H36, channel_probs=priors, osd_method="osd_cs", osd_order=43)
+    assert _lib.last_error_class() == _lib.ERR_VALUE
+    H = np.array([[1, 1, 0, 1, 0, 0], [0, 0, 0, 0, 0, 0], [0, 1, 1, 0, 1, 1]], np.uint8)
+    with pytest.raises(RuntimeError, match=r"swd_osdw_create failed: row 1 is empty: every check needs degree > 0"):
+        osd_window(H, channel_probs=np.full(6, 0.1))
+    assert _lib.last_error_class() == _lib.ERR_FAILED
+    csr = _Csr(H, np.full(6, 0.1))
+    p = _lib.OsdwParams(8, 100, 1.0, 0, 0, 0)
+    assert not _lib.lib().swd_osdw_create(C.byref(csr.desc), C.byref(p), 0)
+    assert "is empty" in _lib.last_error() and "general form" not in _lib.last_error()
+
+
 def test_fuzz_medium_codes_vs_oracle():
     """Randomised matrices with 65..120 checks (the 256-thread kernel variants: a check is served by a thread of
     another wave than the one that initialised it) -- tests/fuzz_vs_oracle.py with a fixed seed."""

@@ -118,6 +118,26 @@ def test_window_placement_is_validated():
         SlidingWindowDecoder(plan, **fx.params(f, "osd0_params"))
 
 
+def test_a_commit_range_beyond_the_global_columns_is_refused_not_looped():
+    """Two windows whose second commit runs one column past the global matrix: an input error (not SWD_ERR_CAPACITY), so the
+    create's refusal is raised and no window loop is built -- its text holds "exceeds", on which the loop used to be chosen"""
+    from slidingwindowdecoder_amd import SlidingWindowDecoder, _lib
+    from slidingwindowdecoder_amd.windows import Window, WindowPlan
+    mat, pri = fx.graph(fx.load("bb72_capacity.npz"), "c1_")
+    m, n = mat.shape
+    chk = sp.block_diag([mat, mat], format="csr").astype(np.uint8)
+    wins = [Window(0, m, 0, n, n, mat, pri, False), Window(m, 2 * m, n + 1, n, n, mat, pri, True)]
+    plan = WindowPlan(chk, sp.csr_matrix((0, 2 * n), dtype=np.uint8), np.tile(pri, 2), np.arange(2 * n), [], wins, None, 0)
+    dec = SlidingWindowDecoder.__new__(SlidingWindowDecoder)
+    with pytest.raises((RuntimeError, ValueError), match="commit range exceeds the global column count"):
+        dec.__init__(plan, pre_max_iter=8, post_max_iter=20, osd_method="osd_0")
+    assert dec._loop is None and not dec._h
+    assert _lib.last_error_class() not in (_lib.ERR_CAPACITY, _lib.ERR_DEVICE)
+    wins[1] = Window(m, 2 * m, n, n, n, mat, pri, True)  # placed right, the plan is taken by the one-launch pipeline
+    ok = SlidingWindowDecoder(plan, pre_max_iter=8, post_max_iter=20, osd_method="osd_0")
+    assert ok._loop is None and ok._h
+
+
 @pytest.mark.parametrize("method,W,F,noisy", [(0, 3, 1, None), (2, 3, 1, None), (2, 4, 2, None), (1, 3, 1, 0.05), (2, 3, 2, 0.02)])
 def test_plan_windows_methods_vs_oracle_host_loop(method, W, F, noisy):
     """Window extraction variants of osd.py:79-121: method 0 (plain sub-matrices), method 2 (identity block behind ALL faults
