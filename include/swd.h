@@ -461,6 +461,41 @@ int swd_pipeline_stream_wait(swd_stream *s, void *stream);
  * batch k + 1 on the other lane stays in flight.  Fails if nothing has been pushed on this stream object. */
 int swd_pipeline_stream_wait_last(swd_stream *s, void *stream);
 
+/* ---- device window loop: plans beyond the one-launch pipeline kernels ---------------------------
+ * The same window loop (/root/reference/osd.py:130-179) for plans whose windows swd_pipeline_create refuses with SWD_ERR_CAPACITY --
+ * more than 1024 checks, 9216 columns, row weight 64 or column weight 10 in a window: [[756,16,<=34]] at (W, F) = (3, 1),
+ * [[288,12,18]] at W = 8 -- and, on request, for any other plan.  Opt-in (csrc/swd_loop.hip); additive, SWD_ABI_VERSION stays 4.
+ * The handle owns ONE single-window decoder per DISTINCT window, built through swd_osdw_create (decoder = 0, params = swd_osdw_params*)
+ * or swd_gdg_create (decoder = 1, params = swd_gdg_params*): each takes a tuned kernel, a large-graph kernel or the general form by
+ * itself, and SWD_FORCE_HUGE keeps its meaning.  Two windows are the same when matrix and priors agree (new_n is one parameter of the
+ * loop): the BB plans have 4 windows and 3 distinct ones, which matters because every general-form handle holds CUs x slice of scratch.
+ * It keeps the CSC of chk with int32 rows, the observable masks (obs nullable, <= 32 rows), and buffers that grow with B: the residual
+ * syndrome [B][num_det rounded up to 4], the estimate [B][largest window n], one window's statistics and path metrics.
+ *   create     NULL with a message and class.  A refusal of a window's own create stands with its class, "window <t>: " in front.
+ *              SWD_ERR_CAPACITY of the loop itself: the committed columns of a window reach a span of more than 65 536 rows of chk
+ *              (one commit stages the span in LDS; on the BB plans the span lies inside the window).
+ *   info       all nullable; device_bytes = the handle's own arrays as they are now (the window decoders' graphs and scratch not counted)
+ *   decode_dev arguments and results exactly those of swd_pipeline_decode_dev: det is not modified, total is zeroed first, stats
+ *              [B][W][SWD_STAT_WORDS] (every word of the window decode), min_pm [B][W] and shot_result [B][2] nullable.  Everything is
+ *              queued on `stream`: begin (resid = det), then per window its *_decode_batch_dev on resid + row0 with the residual's
+ *              stride and one commit launch (loop_commit_kernel: committed faults into total, their columns of chk into the residual
+ *              rows they reach, their observable masks into the accumulator, the window's record to [shot][window]; the last window's
+ *              launch also reduces "residual != 0" into shot_result).  No host synchronisation of its own -- a general-form window
+ *              decoder still synchronises with its previous stream when the stream changes.  Decodes of one handle on different
+ *              streams are ordered by an event (the buffers are shared), so results do not depend on how streams alternate.
+ *   decode     the same with host pointers (det [B*num_det], total [B*num_col], ...); synchronous.
+ * Not served: stream objects, sessions of every kind, rolling experiments -- they need the one-launch pipeline. */
+typedef struct swd_window_loop swd_window_loop;
+swd_window_loop *swd_window_loop_create(int32_t num_windows, const swd_window_desc *wins, const swd_graph_desc *chk,
+                                        const swd_graph_desc *obs, int32_t decoder, const void *params, int device);
+void swd_window_loop_destroy(swd_window_loop *l);
+int swd_window_loop_info(const swd_window_loop *l, int32_t *num_windows, int32_t *num_det, int32_t *num_col,
+                         int32_t *distinct_decoders, int64_t *device_bytes);
+int swd_window_loop_decode_dev(swd_window_loop *l, int32_t B, const uint8_t *det, int64_t det_stride, uint8_t *total,
+                               int64_t total_stride, int32_t *stats, double *min_pm, int32_t *shot_result, void *stream);
+int swd_window_loop_decode(swd_window_loop *l, int32_t B, const uint8_t *det, uint8_t *total, int32_t *stats,
+                           double *min_pm, int32_t *shot_result);
+
 /* ---- memory experiments: per-shot accounting of a window-loop batch ------------------------------
  * The last lines of the reference's sliding_window_decoder (/root/reference/osd.py:181-191) on the device, so that sample -> window
  * loop -> count needs no per-shot array on the host.

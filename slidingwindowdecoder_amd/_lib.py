@@ -89,6 +89,11 @@ SYMBOLS = [
     ("swd_pipeline_stream_push_dev", C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     ("swd_pipeline_stream_wait", C.c_int, [_vp, _vp]),
     ("swd_pipeline_stream_wait_last", C.c_int, [_vp, _vp]),
+    ("swd_window_loop_create", _vp, [_i32, _vp, C.POINTER(GraphDesc), C.POINTER(GraphDesc), _i32, _vp, C.c_int]),
+    ("swd_window_loop_destroy", None, [_vp]),
+    ("swd_window_loop_info", C.c_int, [_vp] + [C.POINTER(_i32)] * 4 + [C.POINTER(_i64)]),
+    ("swd_window_loop_decode_dev", C.c_int, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    ("swd_window_loop_decode", C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     ("swd_pipeline_session_create", _vp, [_vp, _i32]),
     ("swd_pipeline_session_destroy", None, [_vp]),
     ("swd_pipeline_session_begin", C.c_int, [_vp, _i32]),

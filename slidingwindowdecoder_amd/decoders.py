@@ -739,10 +739,24 @@ class SlidingWindowDecoder(_Handle):
     committing ``commit`` columns per window and folding them back into the residual syndrome.
 
     ``plan`` is a ``windows.WindowPlan``; decoder kwargs are those of ``osd_window`` and apply to
-    every window like in osd.py:152-161."""
+    every window like in osd.py:152-161.
+
+    ``window_loop`` says who runs the loop over the windows (read back as the attribute ``window_loop``: "pipeline", "host" or
+    "device"; ``distinct_windows`` is the number of different window graphs of the plan):
+      None      the one-launch pipeline; if the plan is beyond its kernels (the library refuses it with SWD_ERR_CAPACITY), the
+                host loop -- one batched device decode per window through host memory, commit and residual syndrome on the host,
+                ``decode()`` only;
+      "host"    that host loop on any plan (it records every statistics word of a window decode; the fall-back of ``None``
+                keeps to words 0 and 1 for ``osd_window``, as it always did);
+      "device"  the device window loop on any plan (C ABI: swd_window_loop_*, csrc/swd_loop.hip): one single-window decoder per
+                distinct window, residual syndrome, commit and accounting on the device, nothing synchronised on the host.  It
+                serves ``decode``, ``decode_device`` and ``MemoryExperiment``; stream objects, sessions and rolling experiments
+                need the one-launch pipeline."""
     _destroy = "swd_pipeline_destroy"
 
-    def __init__(self, plan, device=0, decoder="osd_window", **kwargs):
+    def __init__(self, plan, device=0, decoder="osd_window", window_loop=None, **kwargs):
+        if window_loop not in (None, "host", "device"):
+            raise ValueError(f"window_loop must be None, 'host' or 'device', not {window_loop!r}")
         L = _lib.lib()
         self.plan = plan
         self.W = len(plan.windows)
@@ -768,11 +782,27 @@ class SlidingWindowDecoder(_Handle):
         self._keep.append(chk)
         self.device = int(device)
         self._pool = _HostPool()
-        create = L.swd_pipeline_create if decoder == "osd_window" else L.swd_pipeline_create_gdg
-        self._h = create(self.W, C.cast(descs, C.c_void_p), C.byref(chk.desc), C.byref(p), self.device)
         self._loop = None
+        self.num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
+        self.window_loop = "pipeline"
+        if window_loop == "device":
+            od = self._obs_desc() if 0 < self.num_obs <= 32 else None
+            self._h = L.swd_window_loop_create(self.W, C.cast(descs, C.c_void_p), C.byref(chk.desc), C.byref(od) if od is not None else None,
+                                               0 if decoder == "osd_window" else 1, C.cast(C.pointer(p), C.c_void_p), self.device)
+            if not self._h:
+                raise _lib.error("swd_window_loop_create")
+            self._destroy, self.window_loop = "swd_window_loop_destroy", "device"
+            k = C.c_int32()
+            L.swd_window_loop_info(self._h, None, None, None, C.byref(k), None)
+            self.distinct_windows = k.value
+            self.lds_bytes, self.threads, self.node_pass = 0, 1024, "uniform"
+            return
+        from .windows import distinct_windows
+        self.distinct_windows = len(set(distinct_windows(plan)))
+        create = L.swd_pipeline_create if decoder == "osd_window" else L.swd_pipeline_create_gdg
+        self._h = create(self.W, C.cast(descs, C.c_void_p), C.byref(chk.desc), C.byref(p), self.device) if window_loop is None else None
         if not self._h:
-            if _lib.last_error_class() == _lib.ERR_CAPACITY:
+            if window_loop == "host" or _lib.last_error_class() == _lib.ERR_CAPACITY:
                 # windows beyond every kernel variant (e.g. the un-windowed [[288,12,18]] model, 2736 x 26 208): the window loop of
                 # /root/reference/osd.py:130-179 as the reference runs it -- one device decoder per window (the general forms,
                 # csrc/swd_huge.hip and csrc/swd_huge_gdg.hip), the residual syndrome det ^ chk @ total_e_hat between windows
@@ -783,7 +813,7 @@ class SlidingWindowDecoder(_Handle):
                                   **{k: v for k, v in kwargs.items() if k != "device"}) for w in plan.windows]
                 self._chk_t = sp.csr_matrix(plan.chk.T.astype(np.int32))
                 self.lds_bytes, self.threads, self.node_pass = 0, 1024, "uniform"
-                self.num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
+                self.window_loop, self._all_stats = "host", window_loop == "host"
                 self._obs_t = sp.csr_matrix(plan.obs.T.astype(np.int32)) if self.num_obs else None
                 return
             raise _lib.error("swd_pipeline_create")
@@ -791,20 +821,22 @@ class SlidingWindowDecoder(_Handle):
         L.swd_pipeline_info(self._h, *[C.byref(x) for x in i])
         self.lds_bytes, self.threads = i[3].value, i[4].value
         self.node_pass = "depth" if _node_depth(L, "swd_pipeline_node_depth", self._h) else "uniform"  # (as osd_window.node_pass)
-        self.num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
         if 0 < self.num_obs <= 32:
-            a = sp.csr_matrix(plan.obs)
-            a.sort_indices()
-            rp, ci = np.ascontiguousarray(a.indptr, np.int32), np.ascontiguousarray(a.indices, np.int32)
-            od = _lib.GraphDesc(a.shape[0], a.shape[1], int(rp[-1]), rp.ctypes.data, ci.ctypes.data, None)
-            if L.swd_pipeline_set_observables(self._h, C.byref(od)):
+            if L.swd_pipeline_set_observables(self._h, C.byref(self._obs_desc())):
                 raise _lib.error("swd_pipeline_set_observables")
+
+    def _obs_desc(self):
+        a = sp.csr_matrix(self.plan.obs)
+        a.sort_indices()
+        rp, ci = np.ascontiguousarray(a.indptr, np.int32), np.ascontiguousarray(a.indices, np.int32)
+        self._keep += [rp, ci]
+        return _lib.GraphDesc(a.shape[0], a.shape[1], int(rp[-1]), rp.ctypes.data, ci.ctypes.data, None)
 
     @property
     def last_form(self):
-        """As ``osd_window.last_form``, one entry of ``windows`` per window (include/swd.h, swd_pipeline_last_form); None when the
-        window loop runs on the host over general-form decoders."""
-        return _last_form("swd_pipeline_last_form", self._h, self.W) if self._h else None
+        """As ``osd_window.last_form``, one entry of ``windows`` per window (include/swd.h, swd_pipeline_last_form); None when a
+        window loop runs over single-window decoders, on the host or on the device."""
+        return _last_form("swd_pipeline_last_form", self._h, self.W) if self.window_loop == "pipeline" else None
 
     def _check_det(self, det_data):
         d = np.asarray(det_data)
@@ -824,17 +856,18 @@ class SlidingWindowDecoder(_Handle):
         if self._loop is not None:
             return self._decode_window_loop(d, packed)
         pool = self._pool
-        total = pool.take((B, (self.num_col + 7) // 8 if packed else self.num_col), np.uint8)
+        device_loop = self.window_loop == "device"  # (it returns bytes; they are packed here)
+        total = pool.take((B, (self.num_col + 7) // 8 if packed and not device_loop else self.num_col), np.uint8)
         st = pool.take((B, self.W, _lib.STAT_WORDS), np.int32)
         pm = pool.take((B, self.W), np.float64)
-        shot = np.empty((B, 2), np.int32)
-        fn = _lib.lib().swd_pipeline_decode_packed if packed else _lib.lib().swd_pipeline_decode
-        rc = fn(self._h, B, d.ctypes.data, total.ctypes.data, st.ctypes.data, pm.ctypes.data, shot.ctypes.data)
+        shot = np.zeros((B, 2), np.int32)
+        name = "swd_window_loop_decode" if device_loop else "swd_pipeline_decode_packed" if packed else "swd_pipeline_decode"
+        rc = getattr(_lib.lib(), name)(self._h, B, d.ctypes.data, total.ctypes.data, st.ctypes.data, pm.ctypes.data, shot.ctypes.data)
         if rc:
-            raise _lib.error("swd_pipeline_decode")
+            raise _lib.error(name)
         self.last_stats, self.last_min_pm = st, pm
         self.last_obs_flips, self.last_flagged = shot[:, 0].astype(np.uint32), shot[:, 1].astype(bool)
-        return total
+        return np.packbits(total, axis=1, bitorder="little") if packed and device_loop else total
 
     def _decode_window_loop(self, d, packed):
         """the window loop for plans no pipeline kernel takes: per window one batched device decode, commit, residual"""
@@ -846,7 +879,7 @@ class SlidingWindowDecoder(_Handle):
         for wi, (w, dec) in enumerate(zip(self.plan.windows, self._loop)):
             out = dec.decode_batch(np.ascontiguousarray(cur[:, w.row0:w.row1])) if B else np.zeros((0, w.mat.shape[1]), np.uint8)
             total[:, w.col0:w.col0 + w.commit] = out[:, :w.commit]
-            if B and self.decoder == "osd_window":
+            if B and self.decoder == "osd_window" and not self._all_stats:
                 st[:, wi, 0], st[:, wi, 1], pm[:, wi] = dec.last_status, dec.last_iterations, dec.last_min_pm
             elif B:  # the guessing decoders: every statistics word of the window decode (include/swd.h)
                 st[:, wi], pm[:, wi] = dec.last_stats, dec.last_min_pm
@@ -860,10 +893,19 @@ class SlidingWindowDecoder(_Handle):
         self.last_obs_flips = flips
         return np.packbits(total, axis=1, bitorder="little") if packed else total
 
-    def _no_loop(self, what):
+    def _no_loop(self, what, device_ok=False):
+        if self.window_loop == "device" and not device_ok:
+            raise RuntimeError(f"{what} needs the one-launch pipeline; this decoder runs the device window loop of {self.decoder} decodes "
+                               f"(window_loop=\"device\"), which serves decode(), decode_device() and MemoryExperiment")
         if self._loop is not None:
             raise RuntimeError(f"{what} needs the one-launch pipeline; this plan's windows are beyond every kernel variant and run as a "
-                               f"window loop of {self.decoder} decodes (use decode())")
+                               f"window loop of {self.decoder} decodes (use decode(); window_loop=\"device\" runs that loop on the "
+                               f"device and also serves decode_device() and MemoryExperiment)")
+
+    def _no_device_loop(self, what):
+        """the pipeline's own diagnostics: the device window loop's handle is no pipeline"""
+        if self.window_loop == "device":
+            self._no_loop(what)
 
     def stream(self, max_shots, packed=False, want_stats=True):
         """Streaming form for consecutive batches (``SlidingWindowStream``): two batches in flight on two lanes of this
@@ -928,7 +970,7 @@ class SlidingWindowDecoder(_Handle):
         buffer is allocated and returned, as it always was.  ``want_min_pm=False`` (and no ``min_pm`` tensor) gives the
         launch no destination: None is returned in its place, and the windows that leave through BP do not compute one."""
         import torch
-        self._no_loop("decode_device()")
+        self._no_loop("decode_device()", device_ok=True)
         if det.dtype != torch.uint8 or det.dim() != 2 or det.shape[1] != self.num_det or det.stride(1) != 1:
             raise ValueError(f"det must be a uint8 tensor [B, {self.num_det}] with unit column stride")
         if not det.is_cuda or det.device.index != self.device:
@@ -936,26 +978,30 @@ class SlidingWindowDecoder(_Handle):
         if shot_result is not None and self.num_obs > 32:
             raise ValueError("shot_result carries at most 32 observables; decode the observables on the host for more")
         B, dev = det.shape[0], det.device
+        for name, t in (("total", total), ("stats", stats), ("min_pm", min_pm), ("shot_result", shot_result)):
+            if t is not None and t.device != dev:
+                raise ValueError(f"{name} lives on {t.device}, the pipeline on cuda:{self.device}")
         total = torch.empty((B, self.num_col), dtype=torch.uint8, device=dev) if total is None else total
         if want_stats:
             stats = torch.empty((B, self.W, _lib.STAT_WORDS), dtype=torch.int32, device=dev) if stats is None else stats
             if want_min_pm:
                 min_pm = torch.empty((B, self.W), dtype=torch.float64, device=dev) if min_pm is None else min_pm
         st = torch.cuda.current_stream(dev) if stream is None else stream
-        rc = _lib.lib().swd_pipeline_decode_dev(self._h, B, det.data_ptr(), det.stride(0), total.data_ptr(),
-                                                total.stride(0), stats.data_ptr() if stats is not None else None,
-                                                min_pm.data_ptr() if min_pm is not None else None,
-                                                shot_result.data_ptr() if shot_result is not None else None,
-                                                st.cuda_stream)
+        name = "swd_window_loop_decode_dev" if self.window_loop == "device" else "swd_pipeline_decode_dev"
+        rc = getattr(_lib.lib(), name)(self._h, B, det.data_ptr(), det.stride(0), total.data_ptr(),
+                                       total.stride(0), stats.data_ptr() if stats is not None else None,
+                                       min_pm.data_ptr() if min_pm is not None else None,
+                                       shot_result.data_ptr() if shot_result is not None else None,
+                                       st.cuda_stream)
         if rc:
-            raise _lib.error("swd_pipeline_decode_dev")
+            raise _lib.error(name)
         return total, stats, min_pm
 
     def check_status(self):
         """Synchronises the device and raises if any launch of this pipeline since the last check recorded a
         scheduling fault (a window whose predecessor never finished: exit class 6 in ``stats``).  The host-buffer
         ``decode`` checks by itself; callers of the asynchronous ``decode_device`` call this after their launches."""
-        if self._loop is not None:
+        if self.window_loop != "pipeline":  # (the single-window decoders of a window loop have no predecessor to wait for)
             return
         flags = C.c_uint32(0)
         if _lib.lib().swd_pipeline_status(self._h, C.byref(flags)):
@@ -964,19 +1010,23 @@ class SlidingWindowDecoder(_Handle):
             raise RuntimeError(f"sliding-window pipeline recorded a scheduling fault (flags 0x{flags.value:x})")
 
     def set_profiling(self, on=True):
+        self._no_device_loop("set_profiling()")
         _lib.lib().swd_pipeline_set_profiling(self._h, 1 if on else 0)
 
     def get_profile(self, B):
         """[B, W, 8] int64 ticks (100 MHz) per phase of the last launch (diagnostics)."""
+        self._no_device_loop("get_profile()")
         out = np.zeros((B, self.W, 8), np.int64)
         if _lib.lib().swd_pipeline_get_profile(self._h, B, out.ctypes.data):
             raise RuntimeError(_lib.last_error())
         return out
 
     def set_timing(self, on=True):
+        self._no_device_loop("set_timing()")
         _lib.lib().swd_pipeline_set_timing(self._h, 1 if on else 0)
 
     def get_timing(self):
+        self._no_device_loop("get_timing()")
         ms, k = C.c_double(), C.c_int64()
         _lib.lib().swd_pipeline_get_timing(self._h, C.byref(ms), C.byref(k))
         return ms.value, k.value
@@ -992,6 +1042,7 @@ class SlidingWindowStream(_Handle):
         self.dec, self.packed, self.want_stats = dec, bool(packed), bool(want_stats)
         self.max_shots = int(max_shots)
         flags = (_lib.STREAM_PACKED if packed else 0) | (0 if want_stats else _lib.STREAM_NO_STATS)
+        dec._no_device_loop("SlidingWindowStream")
         self._h = _lib.lib().swd_pipeline_stream_create(dec._h, self.max_shots, flags)
         if not self._h:
             raise _lib.error("swd_pipeline_stream_create")
@@ -1095,6 +1146,7 @@ class SlidingWindowSession(_SessionBase):
 
     def __init__(self, dec, max_shots):
         self.dec, self.max_shots, self.B = dec, int(max_shots), 0
+        dec._no_device_loop("SlidingWindowSession")
         self._h = _lib.lib().swd_pipeline_session_create(dec._h, self.max_shots)
         if not self._h:
             raise _lib.error("swd_pipeline_session_create")
@@ -1199,6 +1251,7 @@ class RollingSession(_SessionBase):
         from .windows import rolling_template
         self.template = rolling_template(dec.plan)  # ValueError names what is not periodic
         self.dec, self.max_shots, self.B = dec, int(max_shots), 0
+        dec._no_device_loop("RollingSession")
         self._h = _lib.lib().swd_pipeline_rolling_create(dec._h, self.max_shots)
         if not self._h:
             raise _lib.error("swd_pipeline_rolling_create")
@@ -2143,6 +2196,7 @@ class _MemoryLaneExperiment(_LaneExperiment):
     observables, the device counters of a run and the result they make, and the frame of ``run_batch``."""
 
     observable_groups = None  # what ``run`` counts per group when it is not told (``phenomenological(basis="both")`` sets it)
+    _device_loop = False      # whether the experiment runs on ``SlidingWindowDecoder(window_loop="device")``
 
     def __init__(self, plan, decoder, device, decoder_kwargs):
         num_obs = int(plan.obs.shape[0]) if plan.obs is not None else 0
@@ -2151,8 +2205,11 @@ class _MemoryLaneExperiment(_LaneExperiment):
         if num_obs > 32:
             raise ValueError(f"a memory experiment carries at most 32 observables per shot, plan.obs has {num_obs}")
         self.plan, self.device = plan, int(device)
+        if decoder_kwargs.get("window_loop") == "device" and not self._device_loop:  # (before the window decoders are built)
+            raise RuntimeError(f"{type(self).__name__} needs the one-launch pipeline: window_loop=\"device\" serves decode(), "
+                               f"decode_device() and MemoryExperiment")
         self.decoder = SlidingWindowDecoder(plan, device=self.device, decoder=decoder, **decoder_kwargs)
-        self.decoder._no_loop(type(self).__name__)
+        self.decoder._no_loop(type(self).__name__, device_ok=self._device_loop)
         self._lanes = []
 
     def _groups(self, observable_groups):
@@ -2209,7 +2266,12 @@ class MemoryExperiment(_MemoryLaneExperiment):
     the predicted observable flips with the true ones and reduce the per-window records -- only counters come back to the host.
 
     ``plan``: a ``windows.WindowPlan`` with 1..32 observables that the one-launch pipeline takes; ``decoder`` and the keyword
-    arguments are those of ``SlidingWindowDecoder``."""
+    arguments are those of ``SlidingWindowDecoder``.  With ``window_loop="device"`` any plan the single-window decoders take,
+    the ones beyond the pipeline kernels included: the lanes of ``run`` are then torch streams that call ``decode_device`` of
+    the one window-loop handle, whose decodes are ordered on the device (general-form windows also join their previous
+    stream on the host when the stream changes), so two lanes overlap sampling and accounting with the loop, not two loops."""
+
+    _device_loop = True
 
     def __init__(self, plan, decoder="osd_window", device=0, **decoder_kwargs):
         super().__init__(plan, decoder, device, decoder_kwargs)
@@ -2293,13 +2355,14 @@ class MemoryExperiment(_MemoryLaneExperiment):
             raise ValueError("shots >= 0, batch > 0, lanes 1 or 2 (a stream object has two), keep_failures >= 0")
         gnames, groups = self._groups(observable_groups)
         cap = max(1, min(batch, shots))
-        if lanes == 2 and (self._stream is None or self._stream.max_shots < cap):
+        streamed = lanes == 2 and self.decoder.window_loop == "pipeline"  # (the device window loop has no stream object: two torch streams)
+        if streamed and (self._stream is None or self._stream.max_shots < cap):
             self._sync_lanes()
             self.close()
             self._stream = self.decoder.stream(cap, want_stats=window_stats)
         counters, wc, failed = self._counters(self.W if window_stats else 0, keep)
         self._run(shots, batch, lanes, first_shot, max_errors,
-                  lambda k, B, s: self._enqueue(self._lane(k, cap, window_stats), B, seed, s, lanes == 2, window_stats, counters, wc, failed, groups),
+                  lambda k, B, s: self._enqueue(self._lane(k, cap, window_stats), B, seed, s, streamed, window_stats, counters, wc, failed, groups),
                   lambda: int(counters[1].item()))
         args, kw = self._result(counters, wc, failed, keep, gnames, groups)
         return MemoryResult(*args, **kw)

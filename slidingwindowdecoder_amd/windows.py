@@ -269,6 +269,34 @@ def memory_experiment_host(plan: WindowPlan, det_data, obs_data, decoder_factory
                 window_bp_iterations=its if have else None)
 
 
+def distinct_windows(plan: WindowPlan) -> list:
+    """For every window the index of the FIRST window with the same matrix and the same priors (bit for bit): the decoders a window
+    loop needs to build (``SlidingWindowDecoder(window_loop="device")`` builds one per distinct window; a BB plan of 4 windows has 3).
+    ``len(set(distinct_windows(plan)))`` is their number."""
+    seen, first = {}, []
+    for t, w in enumerate(plan.windows):
+        a = sp.csr_matrix(w.mat, copy=True)
+        a.eliminate_zeros()
+        a.sort_indices()
+        key = (a.shape, a.indptr.astype(np.int64).tobytes(), a.indices.astype(np.int64).tobytes(),
+               np.ascontiguousarray(w.prior, np.float64).tobytes())
+        first.append(seen.setdefault(key, t))
+    return first
+
+
+def commit_row_spans(plan: WindowPlan) -> list:
+    """Per window ``(lo, hi)``: the detector rows ``[lo, hi)`` of ``plan.chk`` that its committed columns ``[col0, col0 + commit)``
+    reach -- what a commit has to fold into the residual syndrome (osd.py:170-178); ``(0, 0)`` when they reach none.  On the BB plans
+    the span lies inside the window's own rows."""
+    c = sp.csc_matrix(plan.chk)
+    c.eliminate_zeros()
+    spans = []
+    for w in plan.windows:
+        rows = c.indices[c.indptr[w.col0]:c.indptr[w.col0 + w.commit]]
+        spans.append((int(rows.min()), int(rows.max()) + 1) if rows.size else (0, 0))
+    return spans
+
+
 @dataclass
 class RollingTemplate:
     """What a rolling session keeps of a template ``WindowPlan`` of R0 rounds (``rolling_template``): the head, body and tail
