@@ -757,6 +757,7 @@ __device__ __forceinline__ double quad_xor(double v) {
 __device__ __forceinline__ double vmin64(double a, double b) { double d; asm("v_min_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ double vmax64(double a, double b) { double d; asm("v_max_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ double vminabs64(double x, double c) { double d; asm("v_min_f64 %0, |%1|, %2" : "=v"(d) : "v"(x), "v"(c)); return d; }
+__device__ __forceinline__ double vmaxabs64(double x, double c) { double d; asm("v_max_f64 %0, |%1|, %2" : "=v"(d) : "v"(x), "v"(c)); return d; }
 // w = 2*w + (x <= 0): shift register of "is negative" bits (osd_window.pyx:404-409 counts <= 0 as negative)
 __device__ __forceinline__ void neg_shift_in(uint32_t &w, double x) {
     asm("v_cmp_ge_f64 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(w) : "v"(x) : "vcc");
@@ -958,6 +959,12 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
             // pairs; the groups form a chain that is left behind the wave's last live group
             [[maybe_unused]] int wq = wmax;
             if constexpr (kChain) asm volatile("" : "+s"(wq));
+            // kClipOnce (round 15, the same kernels): clipping is monotone, so it commutes with the order statistics -- min(50, k-th smallest
+            // |x|) = k-th smallest min(|x|, 50).  The walk runs on |x| itself (a source modifier of the compare, the max and the min) and the
+            // two minima are clipped once, behind the quad merges.  The position kept as first minimum may differ from the per-position
+            // clip's only where the clipped minima tie at 50; then p1 == p2 and every position gets its own sign, so every stored message
+            // is the same bit pattern.  The far slot's 64.0 is >= 50 either way.
+            constexpr bool kClipOnce = kChain && !REC && !HYB && !TBL;
             auto rd_group = [&](const int gq) {
                     double xs[4];
                     uint32_t ad[4];
@@ -967,11 +974,17 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
                     auto one = [&](auto u_tag) {
                         constexpr int u = decltype(u_tag)::value;
                         const int k = gq * 4 + u;
+                        if constexpr (kClipOnce) {
+                            argslot = (__builtin_fabs(xs[u]) < min1) ? ad[u] : argslot;
+                            min2 = vmin64(min2, vmaxabs64(xs[u], min1));
+                            min1 = vminabs64(xs[u], min1);
+                        } else {
                         const double ax = vminabs64(xs[u], 50.0);
                         if constexpr (REC) argk = (ax < min1) ? (uint32_t)k : argk;
                         argslot = (ax < min1) ? ad[u] : argslot; // (as sign-of-difference mask + v_bfi instead of v_cmp + v_cndmask: 10.1 against 10.0 ms, round 4)
                         min2 = vmin64(min2, vmax64(min1, ax));
                         min1 = vmin64(min1, ax);
+                        }
                         neg_shift_in(neg[k >> 5], xs[u]);
                     };
                     one(std::integral_constant<int, 0>{}); one(std::integral_constant<int, 1>{});
@@ -1039,6 +1052,7 @@ __device__ __forceinline__ int bp_run(const SwdGraphDev &g, const SwdDecodeParam
             const uint32_t flip = (npar & 1) ? 0xFFFFFFFFu : 0u;
             // the first position holding the minimum gets the second minimum (ties: both equal); its own sign: argneg
             if constexpr (!REC) argneg = (swd_msg_ld<HYB>(s, argslot) <= 0) ? 1u : 0u; // (re-read before the slots are overwritten)
+            if constexpr (kClipOnce) { min1 = vmin64(min1, 50.0); min2 = vmin64(min2, 50.0); } // the one clip of the check
             if (cn.live == 1) min1 = min2 = 1e308; // minimum over no other edge (the far slot may have come first)
             const double p1 = min1 * alpha, p2 = min2 * alpha;
             const uint32_t p1lo = (uint32_t)__double_as_longlong(p1), p1hi = (uint32_t)(__double_as_longlong(p1) >> 32);
