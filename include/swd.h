@@ -571,6 +571,55 @@ int swd_rolling_sampler_rows_dev(swd_rolling_sampler *s, int32_t B, uint64_t see
 int swd_rolling_sampler_rows(swd_rolling_sampler *s, int32_t B, uint64_t seed, uint64_t first_shot, int32_t rounds, int32_t block0,
                              int32_t nblocks, uint8_t *det_rows, uint32_t *obs_flips, uint8_t *faults);
 
+/* ---- circuit sampler: Pauli-frame simulation of a memory circuit's op list ----------------------------------------
+ * The forward execution of the gate / noise / measurement lists that circuit.dem_from_ops analyses backwards (the reference leaves
+ * this to Stim): per shot the raw MEASUREMENT RECORD of the noisy circuit -- what swd_frontend_* and the measurement sessions
+ * take -- and, as parities of it, detectors and true observable flips in the form swd_sampler_sample_dev writes them.  Additive;
+ * SWD_ABI_VERSION stays 4 (csrc/swd_circuit.hip).
+ * State per shot and qubit: two bits x, z (the Pauli frame against a noiseless run).  Ops in list order, op codes of circuit.py
+ * (R 0, RX 1, H 2, CX 3, M 4, MR 5, MRX 6, XERR 7, DEP1 8, DEP2 9, MX 12, ZERR 13; DETECTOR 10 and OBSERVABLE 11 are not ops of the
+ * program: they are the two maps); rnd = the op's randomisation bit, 0 when `randomize` is 0:
+ *     R q: x = 0, z = rnd            RX q: z = 0, x = rnd           H q: swap x, z          CX c,t: x[t] ^= x[c], z[c] ^= z[t]
+ *     M q,i: rec[i] = x, z = rnd     MR q,i: rec[i] = x, x = 0, z = rnd     MX q,i: rec[i] = z, x = rnd     MRX q,i: rec[i] = z, z = 0, x = rnd
+ *     XERR / ZERR q: flip x / z iff u < thr          DEP1 q: iff u < thr, Pauli 1 + (u 3) / thr on q (1 X, 2 Y, 3 Z; Y flips both)
+ *     DEP2 a,b: iff u < thr, k = 1 + (u 15) / thr, Pauli k >> 2 on a and k & 3 on b (0 = I); the products are 64-bit integers
+ * thr = min(floor(p 2^32 + 0.5), 2^32 - 1), the DEM sampler's rule, computed by the caller.  Streams: Philox4x32-10 keyed by `seed`;
+ * noise ops are numbered j = 0, 1, ... in list order and u is output word j % 4 of counter (shot lo, shot hi, j / 4, 2); the ops
+ * that take rnd (R, RX, M, MR, MX, MRX) are numbered r = 0, 1, ... in list order and rnd is bit r % 32 of output word (r / 32) % 4 of
+ * counter (shot lo, shot hi, r / 128, 3) -- counter words 3 = 0 and 1 are the DEM and the Pauli sampler's.  Shot b of a call is shot
+ * number first_shot + b: a result is a pure function of (program, seed, shot number), whatever the batch, the lanes or the rank.
+ *   create   one entry per op: kind, qa, qb (two-qubit ops), thr (noise ops), meas (record index of a measurement), noise_slot and
+ *            rand_slot (the op's number j or r; they must count up in list order); entries an op does not use are ignored.
+ *            det_map [num_det x num_meas], obs_map [num_obs x num_meas] (either nullable): CSR, row = the measurements a detector /
+ *            an observable is the parity of (channel_probs ignored).  SWD_ERR_VALUE: a code that is not executable, a qubit or a
+ *            measurement index out of range, a measurement written twice or never, slots out of order, a map that reads outside
+ *            the record.  SWD_ERR_CAPACITY: more than 4096 qubits (a wave keeps 16 bytes per qubit in 64 KB of LDS).
+ *   info     info[8] = { qubits, measurements, detectors, observables, noise slots, randomisation slots, device bytes, qubit bound }
+ *   measure_dev  meas [B][num_meas] bytes, or with packed != 0 [B][ceil(num_meas / 8)] with measurement i in bit i & 7 of byte
+ *            i >> 3 (the front end's packed layout); meas_stride = bytes between shots, 0 = dense; bytes past a row are not touched
+ *   sample_dev   det [B][num_det] bytes (det_stride as above), obs_flips [B] bit masks (nullable; SWD_ERR_CAPACITY when asked for
+ *            with more than 32 observables), meas (nullable) the unpacked record of the same shots
+ * Both are asynchronous on `stream` (two launches) and keep, per stream HANDLE they have been called on, ceil(B / 64) num_meas 8
+ * bytes of device memory between the launches (the largest B so far; released with the sampler, not before: a caller that keeps
+ * creating streams should call the sampler on a fixed set of them, or destroy it with them).  Calls on different streams may
+ * overlap.  Calls on ONE stream share that buffer and rely on the stream's order: two host threads must not call one sampler on the
+ * same stream at the same time (the handle is otherwise safe to share between threads).  measure / sample: the same with host
+ * pointers, dense, synchronous, on the null stream.  B = 0 does nothing. */
+typedef struct swd_circuit_sampler swd_circuit_sampler;
+swd_circuit_sampler *swd_circuit_sampler_create(int32_t num_ops, const int32_t *kind, const int32_t *qa, const int32_t *qb,
+                                                const uint32_t *thr, const int32_t *meas, const int32_t *noise_slot,
+                                                const int32_t *rand_slot, int32_t num_qubits, int32_t num_meas,
+                                                const swd_graph_desc *det_map, const swd_graph_desc *obs_map, int32_t randomize, int device);
+void swd_circuit_sampler_destroy(swd_circuit_sampler *s);
+int swd_circuit_sampler_info(const swd_circuit_sampler *s, int64_t *info);
+int swd_circuit_sampler_measure_dev(swd_circuit_sampler *s, int32_t B, uint64_t seed, uint64_t first_shot, uint8_t *meas,
+                                    int64_t meas_stride, int32_t packed, void *stream);
+int swd_circuit_sampler_sample_dev(swd_circuit_sampler *s, int32_t B, uint64_t seed, uint64_t first_shot, uint8_t *det,
+                                   int64_t det_stride, uint32_t *obs_flips, uint8_t *meas, int64_t meas_stride, void *stream);
+int swd_circuit_sampler_measure(swd_circuit_sampler *s, int32_t B, uint64_t seed, uint64_t first_shot, uint8_t *meas, int32_t packed);
+int swd_circuit_sampler_sample(swd_circuit_sampler *s, int32_t B, uint64_t seed, uint64_t first_shot, uint8_t *det,
+                               uint32_t *obs_flips, uint8_t *meas);
+
 /* ---- online sessions: the window loop driven by the arrival of detector rows --------------------
  * The (W, F) scheme exists so that corrections are committed while the experiment still runs; the loop of the reference harness
  * (/root/reference/osd.py:130-179) is causal -- window t reads only rows < row1 of det ^ chk @ total_e_hat.  A session owns the state

@@ -3,7 +3,7 @@
 Host-side problem construction (codes, circuit, windows) is pure numpy/scipy and importable
 anywhere; the decoder classes need libswd_hip.so and a gfx950 GPU and raise otherwise.
 """
-from .decoders import (CodeCapacityExperiment, CodeCapacityResult, DemSampler, MeasurementFrontEnd, MeasurementSession, RollingMeasurementSession, MemoryExperiment, MemoryResult, PauliSampler, RollingDemSampler, RollingMemoryExperiment, RollingMemoryResult, RollingSession, SlidingWindowDecoder, SlidingWindowSession, SlidingWindowStream, bp4_osd, bp_history_decoder, bpgd_decoder,  # noqa: F401
+from .decoders import (CircuitSampler, CodeCapacityExperiment, CodeCapacityResult, DemSampler, MeasurementFrontEnd, MeasurementSession, RollingMeasurementSession, MemoryExperiment, MemoryResult, PauliSampler, RollingDemSampler, RollingMemoryExperiment, RollingMemoryResult, RollingSession, SlidingWindowDecoder, SlidingWindowSession, SlidingWindowStream, bp4_osd, bp_history_decoder, bpgd_decoder,  # noqa: F401
                        bpgdg_decoder, group_account_device, osd_window, window_forms)
 from ._lib import CapacityError  # noqa: F401
 from .codes import CSSCode, create_surface_codes, hypergraph_product, rep_code  # noqa: F401
@@ -21,4 +21,4 @@ __all__ = ["osd_window", "bpgdg_decoder", "bpgd_decoder", "bp_history_decoder", 
            "CodeCapacityExperiment", "CodeCapacityResult", "MemoryExperiment", "MemoryResult", "RollingDemSampler", "RollingMemoryExperiment",
            "RollingMemoryResult", "group_account_device", "window_forms", "CSSCode", "rep_code", "hypergraph_product", "create_surface_codes",
            "phenomenological_dem", "css_phenomenological_dem", "MeasurementFrontEnd", "MeasurementSession", "RollingMeasurementSession",
-           "MeasurementMap", "measurement_map", "phenomenological_measurement_map", "CapacityError"]
+           "MeasurementMap", "measurement_map", "phenomenological_measurement_map", "CapacityError", "CircuitSampler"]

@@ -133,6 +133,13 @@ SYMBOLS = [
     ("swd_rolling_sampler_info", C.c_int, [_vp, C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     ("swd_rolling_sampler_rows_dev", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
     ("swd_rolling_sampler_rows", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    ("swd_circuit_sampler_create", _vp, [_i32] + [_vp] * 7 + [_i32, _i32, C.POINTER(GraphDesc), C.POINTER(GraphDesc), _i32, C.c_int]),
+    ("swd_circuit_sampler_destroy", None, [_vp]),
+    ("swd_circuit_sampler_info", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("swd_circuit_sampler_measure_dev", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _vp, _i64, _i32, _vp]),
+    ("swd_circuit_sampler_sample_dev", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _vp, _i64, _vp, _vp, _i64, _vp]),
+    ("swd_circuit_sampler_measure", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _vp, _i32]),
+    ("swd_circuit_sampler_sample", C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("swd_pauli_sampler_create", _vp, [C.POINTER(GraphDesc), C.POINTER(GraphDesc), _vp, _vp, _vp, C.c_int]),
     ("swd_pauli_sampler_destroy", None, [_vp]),
     ("swd_pauli_sampler_info", C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),

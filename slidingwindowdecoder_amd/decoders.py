@@ -1738,6 +1738,121 @@ class DemSampler(_Handle):
         return det[:shots], flips[:shots] if flips is not None else None
 
 
+class CircuitSampler(_Handle):
+    """Runs a memory circuit's op list (``circuit.bb_memory_ops``, ``shyps.shyps_memory_ops``) forwards on the device: a Pauli-frame
+    simulation (``frames.py`` states the rule, C ABI swd_circuit_sampler_*).  ``measure`` / ``measure_device`` give the raw
+    measurement record of every shot -- what ``MeasurementFrontEnd`` and the measurement sessions take; ``sample`` /
+    ``sample_device`` give detectors and true observable flips in ``DemSampler``'s form, drawn from the circuit itself.  Every
+    result is a pure function of (ops, seed, shot number).  ``randomize=False``: the record is the flips against the all-zero
+    noiseless record; detectors and observables do not depend on it.  ``mmap``: the circuit's ``MeasurementMap``
+    (``measurement_map(ops, n_half)``; ``n_half``, optional: the detector rows per round, which an op list does not mark and a
+    measurement session asks its map for -- ``code.N // 2`` for the BB circuits; the sampler itself does not use it)."""
+    _destroy = "swd_circuit_sampler_destroy"
+    close = _Handle._release
+
+    def __init__(self, ops, device=0, randomize=True, n_half=None):
+        from .frames import compile_ops
+        from .measurements import measurement_map
+        self.program = prog = compile_ops(ops)  # ValueError names what is wrong with the list
+        self.mmap = measurement_map(ops, n_half)
+        self.device, self.randomize = int(device), bool(randomize)
+        self.num_qubits, self.num_meas = prog.num_qubits, prog.num_meas
+        self.num_det, self.num_obs = int(self.mmap.det.shape[0]), int(self.mmap.obs.shape[0])
+        keep = []
+        dd, od = _template_desc(self.mmap.det, keep), _template_desc(self.mmap.obs, keep)
+        arrays = [np.ascontiguousarray(a) for a in (prog.kind, prog.qa, prog.qb, prog.thr, prog.meas, prog.noise_slot, prog.rand_slot)]
+        self._h = _lib.lib().swd_circuit_sampler_create(len(prog), *[a.ctypes.data for a in arrays], prog.num_qubits, prog.num_meas,
+                                                        C.byref(dd), C.byref(od), int(self.randomize), self.device)
+        if not self._h:
+            raise _lib.error("swd_circuit_sampler_create")
+
+    def info(self):
+        """dict: qubits, measurements, detectors, observables, noise_slots, random_slots, device_bytes, max_qubits"""
+        v = (C.c_int64 * 8)()
+        if _lib.lib().swd_circuit_sampler_info(self._h, v):
+            raise _lib.error("swd_circuit_sampler_info")
+        return dict(zip(("qubits", "measurements", "detectors", "observables", "noise_slots", "random_slots", "device_bytes", "max_qubits"), v))
+
+    def record_bytes(self, packed=False):
+        return (self.num_meas + 7) // 8 if packed else self.num_meas
+
+    def measure(self, shots, seed=20240318, first_shot=0, packed=False):
+        """-> the record uint8 [shots, num_meas] (host); ``packed``: [shots, ceil(num_meas / 8)], measurement i in bit ``i & 7`` of
+        byte ``i >> 3`` (``np.packbits(..., bitorder="little")``, the front end's packed layout)"""
+        meas = np.zeros((shots, self.record_bytes(packed)), np.uint8)
+        if _lib.lib().swd_circuit_sampler_measure(self._h, shots, int(seed), int(first_shot), meas.ctypes.data, int(bool(packed))):
+            raise _lib.error("swd_circuit_sampler_measure")
+        return meas
+
+    def sample(self, shots, seed=20240318, first_shot=0, return_measurements=False):
+        """-> det uint8 [shots, num_det], obs uint8 [shots, num_obs] (, the record uint8 [shots, num_meas]) on the host"""
+        det = np.zeros((shots, self.num_det), np.uint8)
+        flips = np.zeros(shots, np.uint32)
+        meas = np.zeros((shots, self.num_meas), np.uint8) if return_measurements else None
+        if self.num_obs > 32:
+            raise _lib.CapacityError(f"sample: observable masks carry at most 32 observables, the circuit has {self.num_obs}")
+        if _lib.lib().swd_circuit_sampler_sample(self._h, shots, int(seed), int(first_shot), det.ctypes.data, flips.ctypes.data,
+                                                 meas.ctypes.data if return_measurements else None):
+            raise _lib.error("swd_circuit_sampler_sample")
+        obs = ((flips[:, None] >> np.arange(self.num_obs, dtype=np.uint32)) & 1).astype(np.uint8)
+        return (det, obs, meas) if return_measurements else (det, obs)
+
+    def _check_out(self, t, shots, width, dtype, name):
+        """a caller's tensor: on this sampler's device, ``dtype``, at least ``shots`` rows, [.., >= width] with unit column stride"""
+        import torch
+        want = torch.device("cuda", self.device)
+        if not isinstance(t, torch.Tensor) or t.device != want:
+            raise ValueError(f"{name} lives on {getattr(t, 'device', type(t).__name__)}, the sampler on {want}")
+        ok = t.dtype == dtype and t.shape[0] >= shots
+        if width is None:
+            ok = ok and t.dim() == 1 and (t.shape[0] <= 1 or t.stride(0) == 1)
+        else:
+            ok = ok and t.dim() == 2 and t.shape[1] >= width and (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= width)
+        if not ok:
+            raise ValueError(f"{name} must be a {dtype} tensor [>= {shots}" + (f", >= {width}] with unit column stride" if width is not None else "], contiguous"))
+
+    def measure_device(self, shots, seed=20240318, first_shot=0, packed=False, out=None, stream=None):
+        """-> the record as a uint8 CUDA tensor [shots, ``record_bytes(packed)``]; asynchronous on the current (or given) torch stream.
+        ``out``: a uint8 CUDA tensor [>= shots, >= record bytes] with unit column stride to fill; bytes past a shot's record (a padded
+        buffer) are left as they are."""
+        import torch
+        dev, row = torch.device("cuda", self.device), self.record_bytes(packed)
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        if out is None:
+            with torch.cuda.stream(st):
+                out = torch.empty((shots, row), dtype=torch.uint8, device=dev)
+        else:
+            self._check_out(out, shots, row, torch.uint8, "out")
+        if shots and _lib.lib().swd_circuit_sampler_measure_dev(self._h, shots, int(seed), int(first_shot), out.data_ptr(),
+                                                                out.stride(0) if out.shape[0] > 1 else 0, int(bool(packed)), st.cuda_stream):
+            raise _lib.error("swd_circuit_sampler_measure_dev")
+        return out[:shots, :row]
+
+    def sample_device(self, shots, seed=20240318, first_shot=0, out=None, stream=None, meas=None):
+        """``DemSampler.sample_device``'s call: -> det uint8 [shots, num_det], observable-flip bit masks int32 [shots], CUDA tensors;
+        asynchronous on the current (or given) torch stream.  ``out`` = (det, flips) tensors to fill (``flips`` None: no masks);
+        ``meas``: uint8 [>= shots, >= num_meas], receives the record of the same shots."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        if out is None:
+            with torch.cuda.stream(st):
+                out = (torch.empty((shots, self.num_det), dtype=torch.uint8, device=dev), torch.empty((shots,), dtype=torch.int32, device=dev))
+        det, flips = out
+        self._check_out(det, shots, self.num_det, torch.uint8, "det")
+        if flips is not None:
+            self._check_out(flips, shots, None, torch.int32, "flips")
+        if meas is not None:
+            self._check_out(meas, shots, self.num_meas, torch.uint8, "meas")
+        if shots and _lib.lib().swd_circuit_sampler_sample_dev(self._h, shots, int(seed), int(first_shot), det.data_ptr(),
+                                                               det.stride(0) if det.shape[0] > 1 else 0,
+                                                               flips.data_ptr() if flips is not None else None,
+                                                               meas.data_ptr() if meas is not None else None,
+                                                               meas.stride(0) if meas is not None and meas.shape[0] > 1 else 0, st.cuda_stream):
+            raise _lib.error("swd_circuit_sampler_sample_dev")
+        return det[:shots, :self.num_det], flips[:shots] if flips is not None else None
+
+
 class PauliSampler(_Handle):
     """Samples Pauli errors of a CSS code and their syndromes on the device: what the first lines of the reference's data-noise
     cells compute with ``np.random.uniform`` and two dense products (/root/reference/Misc.ipynb cell 2:
@@ -2266,28 +2381,42 @@ class MemoryExperiment(_MemoryLaneExperiment):
     the predicted observable flips with the true ones and reduce the per-window records -- only counters come back to the host.
 
     ``plan``: a ``windows.WindowPlan`` with 1..32 observables that the one-launch pipeline takes; ``decoder`` and the keyword
-    arguments are those of ``SlidingWindowDecoder``.  With ``window_loop="device"`` any plan the single-window decoders take,
+    arguments are those of ``SlidingWindowDecoder``.  ``sampler``: None -- the ``DemSampler`` of the plan -- or an object with
+    ``DemSampler.sample_device``'s call that draws ``plan.chk.shape[0]`` detectors in the plan's row order (``CircuitSampler``).  With ``window_loop="device"`` any plan the single-window decoders take,
     the ones beyond the pipeline kernels included: the lanes of ``run`` are then torch streams that call ``decode_device`` of
     the one window-loop handle, whose decodes are ordered on the device (general-form windows also join their previous
     stream on the host when the stream changes), so two lanes overlap sampling and accounting with the loop, not two loops."""
 
     _device_loop = True
 
-    def __init__(self, plan, decoder="osd_window", device=0, **decoder_kwargs):
+    def __init__(self, plan, decoder="osd_window", device=0, sampler=None, **decoder_kwargs):
+        if sampler is not None:  # (before the window decoders are built)
+            if not callable(getattr(sampler, "sample_device", None)):
+                raise ValueError("sampler must be None (the DemSampler of the plan) or an object with DemSampler's sample_device")
+            if getattr(sampler, "num_det", None) != plan.chk.shape[0]:
+                raise ValueError(f"the sampler draws {getattr(sampler, 'num_det', None)} detectors, the plan has {plan.chk.shape[0]}")
+            if getattr(sampler, "device", int(device)) != int(device):
+                raise ValueError(f"the sampler lives on device {sampler.device}, the experiment on device {int(device)}")
         super().__init__(plan, decoder, device, decoder_kwargs)
-        self.sampler = DemSampler(plan.chk, plan.obs, plan.priors, device=self.device)
+        self.sampler = DemSampler(plan.chk, plan.obs, plan.priors, device=self.device) if sampler is None else sampler
         self.W = self.decoder.W
         self._stream = None
 
     @classmethod
-    def bb(cls, N, p, num_repeat, W, F, method=1, z_basis=True, decoder="osd_window", **kw):
-        """the plan as the notebooks build it: ``bb_code(N)``, ``bb_dem(code, A, B, p, num_repeat, z_basis)``, ``plan_windows``"""
-        from .circuit import bb_dem
+    def bb(cls, N, p, num_repeat, W, F, method=1, z_basis=True, decoder="osd_window", sampler=None, **kw):
+        """the plan as the notebooks build it: ``bb_code(N)``, ``bb_dem(code, A, B, p, num_repeat, z_basis)``, ``plan_windows``.
+        ``sampler="circuit"``: the shots are drawn from the circuit itself -- ``CircuitSampler(bb_memory_ops(...))``, whose
+        detectors are in the plan's row order (the plan permutes columns only) -- instead of from the detector error model."""
+        from .circuit import bb_dem, bb_memory_ops
         from .codes import bb_code
         from .windows import plan_windows
         code, A, B = bb_code(N)
         dem = bb_dem(code, A, B, p, num_repeat, z_basis=z_basis)
-        return cls(plan_windows(dem.chk, dem.obs, dem.priors, N // 2, W, F, method, z_basis), decoder=decoder, **kw)
+        if isinstance(sampler, str):
+            if sampler != "circuit":
+                raise ValueError(f"sampler: None, \"circuit\" or a sampler object, got {sampler!r}")
+            sampler = CircuitSampler(bb_memory_ops(code, A, B, p, num_repeat, z_basis), device=kw.get("device", 0), n_half=N // 2)
+        return cls(plan_windows(dem.chk, dem.obs, dem.priors, N // 2, W, F, method, z_basis), decoder=decoder, sampler=sampler, **kw)
 
     @classmethod
     def phenomenological(cls, code_or_matrices, p, num_repeat, W, F, q=None, basis="z", noise="bitflip", decoder="osd_window", **kw):
